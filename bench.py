@@ -24,6 +24,9 @@ which workload ran):
                                                kernel-only (`value`) and `end_to_end` (+ rank-order gather of the
                                                survivors into one pinned host buffer)
     --workload filter_agg [--scaling strong]   configs[4]: filter + SUM/COUNT, RCCL all-reduce of 16 bytes
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (a fixed seeded sample of a large result), so that
+two builds can be compared output for output on identical inputs.
 """
 import argparse
 import json
@@ -159,6 +162,90 @@ def sampled_window_check(buf, total_rows):
     return ok
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_ROWS = 1 << 20    # output rows --dump-outputs keeps per column; a larger result is sampled
+DUMP_SEED = 20261015          # fixed: the same output size gives the same sampled rows in every run and build
+DUMP_CHUNK_ROWS = 1 << 25     # device rows read back at a time while sampling
+
+
+def dump_positions(n):
+    """Rows of an n-row result that --dump-outputs keeps: all of them up to DUMP_SAMPLE_ROWS, else a fixed seeded sample (sorted)."""
+    import numpy as np
+    if n <= DUMP_SAMPLE_ROWS:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE_ROWS, replace=False)).astype(np.int64)
+
+
+def sample_columns(cols, positions, nullable):
+    """[(values float64, validity float32 0/1 or None)] of device columns at `positions` (sorted rows of the columns), read back
+    DUMP_CHUNK_ROWS rows at a time.  A nullable output without a bitmap (no null survived) reads as all valid."""
+    import numpy as np
+    out = []
+    for c in cols:
+        n = c.length
+        vals = np.zeros(len(positions), np.float64)
+        valid = np.ones(len(positions), np.float32) if nullable else None
+        for lo in range(0, n, DUMP_CHUNK_ROWS):
+            hi = min(n, lo + DUMP_CHUNK_ROWS)
+            a, b = np.searchsorted(positions, [lo, hi])
+            if a == b:
+                continue
+            part = c.slice(lo, hi - lo)
+            h = part.download()
+            part.free()
+            rel = positions[a:b] - lo
+            vals[a:b] = h.logical_values()[rel]
+            if nullable and h.validity is not None:
+                valid[a:b] = h.logical_valid()[rel]
+        out.append((vals, valid))
+    return out
+
+
+def output_names(workload):
+    """Names of the projected output columns of a filter + project workload, in projection order."""
+    return ["f", "x"] if workload == "and2_nulls" else ["x"]
+
+
+def sample_parts(parts, workload, total=None, start=0):
+    """--dump-outputs arrays of a filter + project result held as parts in row order (ranks, or windows): `parts` is a list of
+    (rows, [device columns]) that covers rows [start, ...) of a `total`-row result (default: the parts are all of it).  Rows are
+    sampled over the whole result; each part is read back only where a sampled row falls."""
+    import numpy as np
+    names, nullable = output_names(workload), workload == "and2_nulls"
+    total = sum(r for r, _ in parts) if total is None else total
+    pos = dump_positions(total)
+    lo, hi = np.searchsorted(pos, [start, start + sum(r for r, _ in parts)])
+    arrays = {"rows": np.array([total], np.float64), "index": pos[lo:hi].astype(np.float64)}
+    got = [[] for _ in names]
+    for rows, cols in parts:
+        a, b = np.searchsorted(pos, [start, start + rows])
+        for j, (v, m) in enumerate(sample_columns(cols, pos[a:b] - start, nullable)):
+            got[j].append((v, m))
+        start += rows
+    for j, name in enumerate(names):
+        arrays[name] = np.concatenate([v for v, _ in got[j]]) if got[j] else np.zeros(0, np.float64)
+        if nullable:
+            arrays[name + "_valid"] = np.concatenate([m for _, m in got[j]]) if got[j] else np.zeros(0, np.float32)
+    return arrays
+
+
+def write_dump(directory, arrays):
+    """DIR/<name>.npy for every array (float32 / float64, at most DUMP_MAX_BYTES in all).  The directory gets a .gitignore of its
+    own, so a dump inside a checkout leaves `git status` clean."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget")
+    os.makedirs(directory, exist_ok=True)
+    ign = os.path.join(directory, ".gitignore")
+    if not os.path.exists(ign):
+        with open(ign, "w") as f:
+            f.write("*\n")
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def traffic_for(kernel, workload, args):
     """PMC traffic of this kernel from profiles/traffic.json -- attached only when that file's entry was measured on the
     SAME kernel instantiation as the one this run launched, at the same size."""
@@ -279,7 +366,7 @@ def main_host_table(args):
             ctxs[bad].set_option("inject_failure", 1)
         for c in ctxs:
             c.synchronize()
-        steps = max(1, min(args.steps, 5))
+        steps = args.steps
         t0 = time.perf_counter()
         all_gbs = []
         for k in range(steps):
@@ -293,6 +380,11 @@ def main_host_table(args):
         got = res.column(0)
         ok = got.length == survivors and sampled_window_check(got.values, got.length) and survivors == int((xs > LITERAL).sum())
         res.free()
+        if args.dump_outputs:   # what the last timed step computed: the gathered survivors in host memory
+            prog.at("dump")
+            pos = dump_positions(got.length)
+            write_dump(args.dump_outputs, {"rows": np.array([float(got.length)]), "index": pos.astype(np.float64),
+                                           "x": got.logical_values()[pos].astype(np.float64)})
         prog.at("report")
         per_rank_gbs = [sum(g[r] for g in all_gbs) / len(all_gbs) for r in range(world)]
         for r in range(world):
@@ -387,21 +479,27 @@ def _main_group(args, prog):
             for c in ctxs:
                 c.synchronize()
 
-        def step(use_cols=None):
-            """One pass of the hot path on every rank at once; the outputs stay in HBM."""
+        def step(use_cols=None, keep=None):
+            """One pass of the hot path on every rank at once; the outputs stay in HBM (and are kept in `keep`, a list, when given)."""
             if args.workload == "filter_agg":
-                _, _, cnt = group.filter_agg(cols, pred, 0)   # per-rank partials, then the RCCL all-reduce of 16 bytes
+                s, _, cnt = group.filter_agg(cols, pred, 0)   # per-rank partials, then the RCCL all-reduce of 16 bytes
+                if keep is not None:
+                    keep[:] = [s, cnt]
                 return cnt
             res, rows = group.filter_project_resident(use_cols or cols, pred, proj)
+            if keep is not None:
+                keep[:] = [res, rows]
+                return rows
             res.free()
             return rows
 
-        def timed(use_cols, steps):
+        def timed(use_cols, steps, keep=None):
+            """`steps` steps; `keep` (a list) receives the last step's outputs"""
             sync_all()
             t0 = time.perf_counter()
             s = 0
-            for _ in range(steps):
-                s = step(use_cols)
+            for k in range(steps):
+                s = step(use_cols, keep if k + 1 == steps else None)
             sync_all()
             return time.perf_counter() - t0, s
 
@@ -416,7 +514,8 @@ def _main_group(args, prog):
             c.set_option("profile_kernels", 1)
             c.kernel_stats(reset=True)
         inject("timed")
-        elapsed, survivors = timed(None, args.steps)
+        kept = [] if args.dump_outputs else None
+        elapsed, survivors = timed(None, args.steps, kept)
         per_rank = [c.kernel_stats() for c in ctxs]
         for c in ctxs:
             c.set_option("profile_kernels", 0)
@@ -431,6 +530,17 @@ def _main_group(args, prog):
         if args.workload != "filter_agg" and not all(prog.ranks[r]["survivors_plausible"] for r in range(world)):
             prog.phase = "survivor check"
             raise RuntimeError("a rank's survivor count is not what the generator's distribution allows (6 sigma): see per_rank")
+
+        if args.dump_outputs:   # what the last timed step computed, as its caller receives it (ranks in row order)
+            import numpy as np
+            prog.at("dump")
+            if args.workload == "filter_agg":
+                write_dump(args.dump_outputs, {"sum": np.array([float(kept[0])]), "count": np.array([float(kept[1])])})
+            else:
+                res = kept[0]
+                parts = [(res.rank_rows[r], [res.column(r, j) for j in range(len(proj))]) for r in range(world)]
+                write_dump(args.dump_outputs, sample_parts(parts, args.workload))
+                res.free()
 
         # the BASELINE metric as worded ("1e9-row ... at 1/2/4/8 GPUs") read as STRONG scaling: ONE 1e9-row table cut into N row
         # ranges (1.25e8 rows per GPU at N = 8: launch-latency territory) -- a secondary figure next to the weak-scaling `value`
@@ -752,10 +862,11 @@ def main_ranks(args):
         outs, rows = prepared(keep=True)
         return outs, rows, None
 
-    def seam_steps(steps):
+    def seam_steps(steps, keep=None):
         """`steps` passes over the rank's rows through seam S1, as ONE stream of windows (a stream operator does not stop between two
         passes of a benchmark): window i + 1 is begun before window i is finished; the per-batch survivor counts land in the operator's
-        pinned arrays; every window's outputs are released at once.  Returns the survivors of the last pass."""
+        pinned arrays; every window's outputs are released at once -- except the last pass's when `keep` is a list: its windows'
+        (rows, outputs) are appended there, in row order.  Returns the survivors of the last pass."""
         q = S["seam"]
         nwin = len(q["tables"])
 
@@ -770,8 +881,11 @@ def main_ranks(args):
                 pending.append(begin(i + 1))
             outs, _, _, tot = pending.pop(0)(False)
             total += tot
-            for o in outs:
-                o.free()
+            if keep is not None and i >= (steps - 1) * nwin:
+                keep.append((tot, outs))
+            else:
+                for o in outs:
+                    o.free()
             if (i + 1) % nwin == 0:
                 last, total = total, 0
         return last
@@ -820,10 +934,13 @@ def main_ranks(args):
 
     def timed_loop(steps):
         if S["seam"] is not None:   # K passes as one stream of windows (two in flight throughout)
-            R["survivors"] = seam_steps(steps)
+            R["survivors"] = seam_steps(steps, R.setdefault("kept", []) if args.dump_outputs else None)
             return
-        for _ in range(steps):
+        for _ in range(steps - 1 if args.dump_outputs else steps):
             R["survivors"] = step()
+        if args.dump_outputs:   # the last step keeps its outputs for the dump: the same call with the release left for later
+            R["last"] = query()
+            R["survivors"] = R["last"][1]
 
     guard("timed", lambda: (ctx.set_option("profile_kernels", 1), ctx.kernel_stats(reset=True)))
     barrier()
@@ -870,6 +987,33 @@ def main_ranks(args):
     if dist is not None:
         per_rank = [None] * world
         dist.all_gather_object(per_rank, me)
+
+    # ---- --dump-outputs: what the last timed step computed, as its caller receives it (rank 0 writes the whole result's) ---------
+    if args.dump_outputs:
+        import numpy as np
+        prog.at("dump")
+        D = {}
+        if args.workload == "filter_agg":
+            _, count, total_sum = R["last"]   # after the all-reduce every rank holds the global pair
+            D["arrays"] = {"sum": np.array([float(total_sum)]), "count": np.array([float(count)])}
+        else:
+            parts = R.get("kept", []) if S["seam"] is not None else [(R["last"][1], R["last"][0])]
+            counts = [sum(r for r, _ in parts)]
+            if dist is not None:
+                counts = [None] * world
+                dist.all_gather_object(counts, sum(r for r, _ in parts))
+            guard("dump", lambda: D.update(arrays=sample_parts(parts, args.workload, total=sum(counts), start=sum(counts[:rank]))))
+            for _, outs in parts:
+                for o in outs:
+                    o.free()
+            agree()
+            if dist is not None:
+                pieces = [None] * world
+                dist.all_gather_object(pieces, D["arrays"])
+                D["arrays"] = {k: v if k == "rows" else np.concatenate([pc[k] for pc in pieces]) for k, v in pieces[0].items()}
+        if rank == 0:
+            guard("dump", write_dump, args.dump_outputs, D["arrays"])
+        agree()
 
     # ---- the BASELINE metric as worded ("1e9-row ... at 1/2/4/8 GPUs") read as STRONG scaling: ONE 1e9-row table cut into N
     #      row ranges (1.25e8 rows per GPU at N = 8: launch-latency territory), next to the weak-scaling `value` ------------------
@@ -1022,7 +1166,14 @@ def main():
     ap.add_argument("--workload", default="filter_project", choices=sorted(WORKLOADS),
                     help="filter_project = BASELINE configs[1] (default, the headline); and2_nulls = configs[2]; "
                          "filter_agg = configs[4] (SUM/COUNT + RCCL all-reduce of 16 bytes)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, at most 64 MB): "
+                         "rows = the result's row count, index = the result rows kept (all of them up to 2^20, else a fixed seeded "
+                         "sample), one array per projected column at those rows (x; f, x and their *_valid for and2_nulls), or sum and "
+                         "count for filter_agg.  The inputs are the same in every run, so two builds compare output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     # The launch mode is decided from the environment alone, before anything touches a GPU (and nothing is ever
     # re-executed): a launcher that set RANK / WORLD_SIZE gets one rank per process; `--gpus N` without one gets the
     # single-process driver.

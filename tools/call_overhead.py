@@ -1,5 +1,5 @@
 import sys, time, os
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from rivulus_amd import capi
 from rivulus_amd.capi import RV_INT64, Predicate, Term, synth_spec
 ctx = capi.Context(0)
