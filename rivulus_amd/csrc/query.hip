@@ -373,7 +373,9 @@ uint64_t filter_by_groups(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t n
         // (and up to 55 % of the rows surviving -- tools/wide_ab.py, nine columns of 2e8 rows, groups beyond the first: 2.47 against 2.88 ms
         // at 10 %, 3.71 / 3.83 at 50 %, 4.67 / 4.46 at 84 %: there the direct kernel's whole-line stores win; option groups_by_ranges = 1: always)
         const bool offsets_there = first_ranges && first_ranges->offsets && ctx->overflow_reruns == reruns_before && ctx->opt_groups_by_ranges >= 0 && sel && sel->length > 0;
-        const bool sparse_enough = ctx->opt_groups_by_ranges == 1 || (sel && rows * rvt::kRangesSparseDen <= sel->length * rvt::kRangesSparseNum);
+        // (a mask pass with outputs of an ASSUMED size: `rows` is their capacity, not a count -- they were sized for the compaction at
+        // the scan's offsets, so the late groups take it; a re-run with outputs of the exact size decides again from the count)
+        bool sparse_enough = ctx->opt_groups_by_ranges == 1 || rows_assumed || (sel && rows * rvt::kRangesSparseDen <= sel->length * rvt::kRangesSparseNum);
         // nullable columns among them: their validity bits by bits_compact_kernel at the same offsets, their null counts out of the
         // context's control block (eight counters per read-back) -- not next to a caller's own launches on that block (after_launch)
         struct LateNulls {
@@ -529,6 +531,7 @@ uint64_t filter_by_groups(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t n
                 }
             if (!fits) {
                 ctx->overflow_reruns += 1;
+                sparse_enough = ctx->opt_groups_by_ranges == 1 || rows * rvt::kRangesSparseDen <= sel->length * rvt::kRangesSparseNum;
                 late_groups();
             }
             ctx->remember_selectivity(predicate_signature(cols, ncols, terms, nterms, policy, ex), n_rows ? static_cast<double>(rows) / static_cast<double>(n_rows) : 0.0);

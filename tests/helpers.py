@@ -1,12 +1,14 @@
-"""Shared helpers: golden-case loading and column comparison."""
+"""Shared helpers: golden-case loading, column comparison, the constants of thresholds.hpp."""
 import json
 import os
+import re
 
 import numpy as np
 
 from rivulus_amd.capi import Column, Predicate, Term
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "cases.json")
+THRESHOLDS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "rivulus_amd", "csrc", "thresholds.hpp")
 _NP = {"i": np.int64, "f": np.float64, "b": np.bool_}
 
 
@@ -46,3 +48,14 @@ def assert_columns_equal(got, expected, what=""):
     for j, (g, e) in enumerate(zip(got, expected)):
         diff = g.same_as(e)
         assert diff is None, f"{what} column {j}: {diff}"
+
+
+def const(name):
+    """The value of constant `name` in rivulus_amd/csrc/thresholds.hpp (tests name a switch, never its value)."""
+    with open(THRESHOLDS) as f:
+        m = re.search(rf"\b{name} = ([^;,]+)[;,]", f.read())
+    v = m.group(1).strip()
+    if "<<" in v:
+        a, b = re.findall(r"\d+", v)[-2:]
+        return int(a) << int(b)
+    return float(v) if "." in v else int(v)

@@ -155,5 +155,6 @@ def test_every_threshold_of_the_table_is_read_by_the_launch_code():
     assert not unused, f"constants of thresholds.hpp that no unit reads: {unused}"
     paths = open(os.path.join(ROOT, "tests", "test_paths_gpu.py")).read()
     for n in ("kDirectFromOneColumn", "kDirectFromTwoProjected", "kDirectFromThreeProjected", "kDirectFromOneProjectedOfSeveral", "kDirectFromTwoProjectedNullable",
-              "kDeferPlainUpTo", "kMaskPathPlainUpTo", "kSampleFromRows", "kRangesFromRows"):
+              "kDeferPlainUpTo", "kMaskPathPlainUpTo", "kMaskPathAssumeUpTo", "kRangesSparseNum", "kDirectTallBelow", "kSampleFromRows",
+              "kRangesFromRows"):
         assert n in names and n in paths, n

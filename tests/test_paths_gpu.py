@@ -2,24 +2,13 @@
 measured crossovers (the files each row names); this test pins the MECHANISM -- the selectivity a predicate is known to have over these
 buffers (its last pass, or the first call's strided sample) picks the path, the same way on the first call of a big table as on the
 second of any -- so that a change of a constant, or of the code that reads it, shows up as a path that moved."""
-import re
-
 import numpy as np
 import pytest
 
+from helpers import const
 from rivulus_amd.capi import RV_BOOLEAN, RV_FLOAT64, RV_INT64, Predicate, Term, synth_spec
 
 pytestmark = pytest.mark.gpu
-HDR = open(__file__.replace("tests/test_paths_gpu.py", "rivulus_amd/csrc/thresholds.hpp")).read()
-
-
-def const(name):
-    m = re.search(rf"\b{name} = ([^;,]+)[;,]", HDR)
-    v = m.group(1).strip()
-    if "<<" in v:
-        a, b = re.findall(r"\d+", v)[-2:]
-        return int(a) << int(b)
-    return float(v) if "." in v else int(v)
 
 
 def kernel_after(ctx, cols, pred, proj, calls=2):
@@ -83,6 +72,16 @@ def test_filter_by_a_boolean_column_takes_the_mask_path_while_sparse(gpu_ctx, bi
     sparse, dense = big[3], big[4]  # 9.5 % / 70 % of the rows survive
     first, second = kernel_after(gpu_ctx, [sparse, big[0]], Predicate([Term(0, "is_true")]), [1])
     assert first.startswith("compact_ranges_kernel") and second.startswith("compact_ranges_kernel")
+    # up to kMaskPathAssumeUpTo the outputs are sized from the known selectivity (the sample's, on this table's first call); from ~44 %
+    # that capacity passes kRangesSparseNum / kRangesSparseDen of the rows, and the columns must still follow at the scan's offsets
+    assert 0.45 < 0.49 <= const("kMaskPathAssumeUpTo") < const("kRangesSparseNum") / const("kRangesSparseDen")
+    for pct in (45, 49):
+        mask = gpu_ctx.generate(synth_spec(RV_BOOLEAN, seed=50, length=big[0].length, true_percent=pct))
+        try:
+            first, second = kernel_after(gpu_ctx, [mask, big[0]], Predicate([Term(0, "is_true")]), [1], calls=2)
+            assert first.startswith("compact_ranges_kernel") and second.startswith("compact_ranges_kernel"), (pct, first, second)
+        finally:
+            mask.free()
     # a plain column of a selection denser than kMaskPathPlainUpTo: the direct kernel's pass -- from the first call on (the sample taken
     # to decide which columns the pass carries has told how dense the selection is)
     assert const("kMaskPathPlainUpTo") < 0.7
