@@ -352,6 +352,53 @@ rv_status rv_selection_indices(rv_ctx *ctx, const rv_dcolumn *selection, rv_dcol
 rv_status rv_concat(rv_ctx *ctx, const rv_dcolumn *const *parts, uint32_t nparts,
                     rv_dcolumn **out);
 
+/* ---- inner hash join (PhysicalPlan::HashJoin) ----------------------------- */
+/* PhysicalPlan::HashJoin with JoinType::Inner (src/physical_plan/plan.rs:174-284; planned by planner.rs:90-110, reached
+ * through LazyFrame::inner_join, builder.rs:85-95).  The left frame is the BUILD side, the right frame the PROBE side
+ * (planner.rs:102-108).
+ *
+ * Key equality is AnyValue's Hash + PartialEq (src/datatypes/series.rs:72-98), not SQL's:
+ *   - Null == Null: a null probe key matches every null build key; an RV_NULL key column is all nulls;
+ *   - Int64 and Boolean keys match on equal values;
+ *   - Float64 keys match when their bits are equal and the value is not NaN.  NaN never matches, not even the same bits
+ *     (PartialEq fails).  +0.0 and -0.0 do NOT match: they hash apart (to_bits), and the reference could pair them only
+ *     on a random SipHash bucket-and-tag collision;
+ *   - key columns of different dtypes (Int64 against Float64: is_comparable_with allows it, series.rs:144-156) match
+ *     null to null only: values of different AnyValue variants never compare equal;
+ *   - String keys are not supported on the device: RV_ERR_UNSUPPORTED (String PAYLOAD columns are).
+ * Pairs come in probe-row order and, within a probe row, in ascending build-row order -- the reference's result_pairs
+ * (plan.rs:196-204; the Vec push order of its HashMap<AnyValue, Vec<usize>>) -- identically on every run: output
+ * positions come from scans of match counts, never from the order atomics land in.
+ *
+ * A failed call leaves the context usable and creates no outputs. */
+typedef struct rv_join_table rv_join_table;  /* a build side hashed on the device; probed by any number of key columns */
+/* The reference's HashMap build (plan.rs:183-192) over one key column (a slice is fine).  Build sides of 2^32 rows or
+ * more: RV_ERR_UNSUPPORTED (32-bit build row ids inside).  Context option "join_hash_bits" = b (tests) hashes the
+ * keys of tables built afterwards to b low bits: long collision chains on small inputs. */
+rv_status rv_join_build(rv_ctx *ctx, const rv_dcolumn *build_key, rv_join_table **out);
+/* The probe loop (plan.rs:194-204): out_probe_idx / out_build_idx receive the `result_pairs` as two Int64 device
+ * arrays without nulls, row indices into the probe key column and the build key column as given (offsets of slices
+ * excluded) -- what rv_take_device takes as they are.  The pair count is known on the device before anything is
+ * allocated: a count whose two outputs the device cannot hold is RV_ERR_OOM, and the context still works.  A key
+ * column of another dtype than the table's matches null to null only (see above).  rv_ctx_last_kernel names the
+ * probe kernel that wrote the pairs: join_probe_emit<0> (every list one row: unique build keys),
+ * join_probe_emit<1> (lists written lane by lane), join_probe_emit<2> (lists longer than a lane takes, written by
+ * a whole workgroup); join_probe_count when no pair came out. */
+rv_status rv_join_probe(rv_ctx *ctx, const rv_join_table *table, const rv_dcolumn *probe_key,
+                        rv_dcolumn **out_probe_idx, rv_dcolumn **out_build_idx, uint64_t *out_rows);
+/* Build rows, hash slots and the longest match list of a table (any pointer may be NULL). */
+rv_status rv_join_table_info(const rv_join_table *table, uint64_t *build_rows, uint64_t *slots, uint64_t *longest_list);
+rv_status rv_join_table_free(rv_ctx *ctx, rv_join_table *table);
+/* The whole operator in one call: build + probe + gather (materialize_join_result, plan.rs:212-255).  out[] receives
+ * n_probe + n_build - 1 columns in the reference's order: every probe column, then every build column except
+ * build_cols[build_key] (names, and the `_right` suffix of a build column whose name the probe side also has, live in
+ * the caller).  Gathered cells keep their nulls; zero pairs give zero-row columns of the same dtypes
+ * (create_empty_join_result, plan.rs:257-284).  Errors: a key index out of range RV_ERR_INVALID_ARG, columns of one
+ * side of unequal length RV_ERR_LENGTH_MISMATCH, plus those of rv_join_build / rv_join_probe. */
+rv_status rv_hash_join(rv_ctx *ctx, const rv_dcolumn *const *build_cols, uint32_t n_build, uint32_t build_key,
+                       const rv_dcolumn *const *probe_cols, uint32_t n_probe, uint32_t probe_key,
+                       rv_dcolumn **out, uint64_t *out_rows);
+
 /* ---- fused filter + project (K1+K2, the hot path) ------------------------- */
 /* == SelectStream(FilterStream(input)) on one batch (stream.rs:136-158, :202-210) and
  * == PhysicalPlan::Filter followed by Select (plan.rs:97-150, :68-96): evaluate pred

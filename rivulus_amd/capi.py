@@ -126,6 +126,11 @@ PROTOTYPES = {
     "rv_take_device": (C.c_int, [_P, _PP, C.c_uint32, _P, _PP]),
     "rv_selection_indices": (C.c_int, [_P, _P, _PP]),
     "rv_concat": (C.c_int, [_P, _PP, C.c_uint32, _PP]),
+    "rv_join_build": (C.c_int, [_P, _P, _PP]),
+    "rv_join_probe": (C.c_int, [_P, _P, _P, _PP, _PP, _U64P]),
+    "rv_join_table_info": (C.c_int, [_P, _U64P, _U64P, _U64P]),
+    "rv_join_table_free": (C.c_int, [_P, _P]),
+    "rv_hash_join": (C.c_int, [_P, _PP, C.c_uint32, C.c_uint32, _PP, C.c_uint32, C.c_uint32, _PP, _U64P]),
     "rv_filter_project": (C.c_int, [_P, _PP, C.c_uint32, C.POINTER(RvPredicate), C.POINTER(C.c_uint32), C.c_uint32,
                                     _PP, _U64P, _PP]),
     "rv_download_string": (C.c_int, [_P, _P, _P, _P, _P, C.POINTER(C.c_int)]),
@@ -464,6 +469,36 @@ class DeviceColumn:
             pass
 
 
+class JoinTable:
+    """rv_join_table: a build side hashed on the device, probed by any number of key columns."""
+    def __init__(self, ctx: "Context", handle):
+        self.ctx, self.handle = ctx, handle
+
+    def probe(self, key: DeviceColumn):
+        """result_pairs (plan.rs:194-204): (probe_idx, build_idx) Int64 device columns and the pair count."""
+        pi, bi, rows = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        _check(load().rv_join_probe(self.ctx.handle, self.handle, key.handle, C.byref(pi), C.byref(bi), C.byref(rows)))
+        return DeviceColumn(self.ctx, pi), DeviceColumn(self.ctx, bi), rows.value
+
+    def info(self):
+        """(build rows, hash slots, longest match list)"""
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(load().rv_join_table_info(self.handle, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def free(self):
+        if self.handle is not None:
+            load().rv_join_table_free(self.ctx.handle, self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            if self.ctx.handle is not None:
+                self.free()
+        except Exception:
+            pass
+
+
 def _handles(cols: Sequence[DeviceColumn]):
     arr = (C.c_void_p * max(1, len(cols)))()
     for i, c in enumerate(cols):
@@ -607,6 +642,21 @@ class Context:
         out = C.c_void_p()
         _check(load().rv_concat(self.handle, _handles(parts), len(parts), C.byref(out)))
         return DeviceColumn(self, out)
+
+    def join_build(self, key: DeviceColumn) -> "JoinTable":
+        """PhysicalPlan::HashJoin's build side (plan.rs:183-192) hashed on the device."""
+        out = C.c_void_p()
+        _check(load().rv_join_build(self.handle, key.handle, C.byref(out)))
+        return JoinTable(self, out)
+
+    def hash_join(self, build_cols: Sequence[DeviceColumn], build_key: int, probe_cols: Sequence[DeviceColumn], probe_key: int):
+        """Inner hash join (plan.rs:174-284): (every probe column, then the build columns but the key), rows."""
+        n = len(probe_cols) + len(build_cols) - 1
+        out = (C.c_void_p * max(1, n))()
+        rows = C.c_uint64()
+        _check(load().rv_hash_join(self.handle, _handles(build_cols), len(build_cols), build_key, _handles(probe_cols), len(probe_cols),
+                                   probe_key, out, C.byref(rows)))
+        return [DeviceColumn(self, C.c_void_p(out[i])) for i in range(max(0, n))], rows.value
 
     def filter_project(self, cols: Sequence[DeviceColumn], pred: Predicate, proj: Sequence[int],
                        want_selection: bool = False):

@@ -1,0 +1,277 @@
+// Inner hash join on the device (reference PhysicalPlan::HashJoin, plan.rs:174-284): build table, probe, gather.
+// One unit of the backend library behind include/rivulus_gpu.h (gfx950 only; compiled with hipcc).  Shared helpers and the
+// functions the units call across each other are declared in launch.hpp (namespace rvl); the kernels are in join_kernel.hpp.
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include "join_kernel.hpp"
+#include "launch.hpp"
+
+using namespace rvh;
+using namespace rvl;
+
+// A build side hashed on the device (join_kernel.hpp has the layout).  Probed by any number of key columns.
+struct rv_join_table {
+    rv_dtype key_dtype = RV_NULL;
+    uint64_t n_build = 0;
+    uint64_t n_keyed = 0;   // rows in key groups (non-null, non-NaN)
+    uint64_t n_null = 0;    // null rows, behind them in `rows`
+    uint64_t max_group = 0; // longest key group
+    uint64_t nslots = 0;
+    uint64_t hash_mask = ~0ull;
+    DevBufRef slots, rows;
+    std::shared_ptr<rvh::Pool> pool;  // keeps the blocks' pool alive with the table
+};
+
+namespace rvl {
+namespace {
+
+rvk::JoinTableView table_view(const rv_join_table *t, rv_dtype probe_dtype) {
+    rvk::JoinTableView v{};
+    v.slots = static_cast<unsigned long long *>(t->slots->ptr);
+    v.rows = static_cast<const uint32_t *>(t->rows->ptr);
+    v.slot_mask = t->nslots - 1;
+    v.hash_mask = t->hash_mask;
+    v.null_start = static_cast<uint32_t>(t->n_keyed);
+    v.null_count = static_cast<uint32_t>(t->n_null);
+    // AnyValue's PartialEq (series.rs:85-97): values of different variants never compare equal; only Null meets Null
+    v.match_values = t->key_dtype == probe_dtype && t->key_dtype != RV_NULL;
+    return v;
+}
+
+void check_key(const rv_dcolumn *key, const char *what) {
+    require(key != nullptr, RV_ERR_INVALID_ARG, fmt("%s: NULL key column", what));
+    require(key->dtype != RV_STRING, RV_ERR_UNSUPPORTED,
+            fmt("%s: String join keys are not supported on the device (String payload columns are)", what));
+    require(key->dtype == RV_NULL || key->dtype == RV_BOOLEAN || is_value_type(key->dtype), RV_ERR_UNSUPPORTED,
+            fmt("%s: unsupported key dtype", what));
+}
+
+// a bitmap of n rows at offset 0 as the BooleanArray selection_prefix / selection_to_indices read
+DevBufRef ascending_rows(rv_ctx *ctx, const DevBufRef &bitmap, uint64_t n, uint64_t count) {
+    rv_dcolumn sel;
+    sel.dtype = RV_BOOLEAN;
+    sel.values = bitmap;
+    sel.length = n;
+    sel.null_count = 0;
+    DevBufRef excl = selection_prefix(ctx, &sel, count);
+    return selection_to_indices(ctx, &sel, count, excl);
+}
+
+std::unique_ptr<rv_join_table> build_table(rv_ctx *ctx, const rv_dcolumn *key) {
+    check_key(key, "rv_join_build");
+    const uint64_t n = key->length;
+    require(n < (uint64_t{1} << 32), RV_ERR_UNSUPPORTED, "rv_join_build: build sides of 2^32 rows or more are not supported (32-bit build row ids)");
+    auto t = std::make_unique<rv_join_table>();
+    t->key_dtype = key->dtype;
+    t->n_build = n;
+    t->pool = ctx->pool;
+    if (ctx->opt_join_hash_bits > 0 && ctx->opt_join_hash_bits < 64) t->hash_mask = (uint64_t{1} << ctx->opt_join_hash_bits) - 1;
+    const rvk::DevCol kv = dev_view(key);
+
+    // 1. which rows go into key groups, which into the null group
+    const uint64_t nwords = (n + 63) / 64;
+    DevBufRef keep = pool_alloc(ctx, nwords * 8 + 16), nulls = pool_alloc(ctx, nwords * 8 + 16);
+    if (n) {
+        Ctrl *ctrl = prepare_ctrl(ctx, 0);
+        const uint64_t waves = (nwords + rvk::kJoinClassWords - 1) / rvk::kJoinClassWords;
+        hipLaunchKernelGGL(rvk::join_classify, dim3(static_cast<uint32_t>((waves + 3) / 4)), dim3(256), 0, ctx->stream, kv, n,
+                           static_cast<uint64_t *>(keep->ptr), static_cast<uint64_t *>(nulls->ptr), &ctrl->pops[0]);
+        RV_HIP(hipGetLastError());
+        const Ctrl *h = fetch_ctrl(ctx);
+        t->n_keyed = h->pops[0];
+        t->n_null = h->pops[1];
+    }
+    uint64_t nslots = 16;
+    while (nslots < 2 * t->n_keyed) nslots *= 2;
+    t->nslots = nslots;
+    t->slots = pool_alloc(ctx, nslots * 16);
+    RV_HIP(hipMemsetAsync(t->slots->ptr, 0, nslots * 16, ctx->stream));
+    t->rows = pool_alloc(ctx, std::max<size_t>((t->n_keyed + t->n_null) * 4, 16));
+    uint32_t *rows = static_cast<uint32_t *>(t->rows->ptr);
+
+    // 2. key groups: (key bits, row) of the kept rows in row order, a stable radix sort, then one slot per distinct key
+    if (t->n_keyed) {
+        const uint64_t m = t->n_keyed;
+        DevBufRef idx = ascending_rows(ctx, keep, n, m);
+        DevBufRef keys_in = pool_alloc(ctx, m * 8), keys_out = pool_alloc(ctx, m * 8), rows_in = pool_alloc(ctx, m * 4 + 16);
+        const int grid = grid_for_words(ctx, m, 256);
+        hipLaunchKernelGGL(rvk::join_gather_keys, dim3(grid), dim3(256), 0, ctx->stream, kv, static_cast<const uint64_t *>(idx->ptr), m,
+                           static_cast<uint64_t *>(keys_in->ptr), static_cast<uint32_t *>(rows_in->ptr));
+        RV_HIP(hipGetLastError());
+        const unsigned end_bit = key->dtype == RV_BOOLEAN ? 1 : 64;
+        size_t temp_bytes = 0;
+        RV_HIP(rocprim::radix_sort_pairs(nullptr, temp_bytes, static_cast<const uint64_t *>(keys_in->ptr), static_cast<uint64_t *>(keys_out->ptr),
+                                         static_cast<const uint32_t *>(rows_in->ptr), rows, static_cast<size_t>(m), 0u, end_bit, ctx->stream));
+        DevBufRef temp = pool_alloc(ctx, std::max<size_t>(temp_bytes, 16));
+        RV_HIP(rocprim::radix_sort_pairs(temp->ptr, temp_bytes, static_cast<const uint64_t *>(keys_in->ptr), static_cast<uint64_t *>(keys_out->ptr),
+                                         static_cast<const uint32_t *>(rows_in->ptr), rows, static_cast<size_t>(m), 0u, end_bit, ctx->stream));
+        rvk::JoinTableView v = table_view(t.get(), key->dtype);
+        Ctrl *ctrl = prepare_ctrl(ctx, 0);
+        hipLaunchKernelGGL(rvk::join_insert_heads, dim3(grid), dim3(256), 0, ctx->stream, v, static_cast<const uint64_t *>(keys_out->ptr), m);
+        hipLaunchKernelGGL(rvk::join_insert_tails, dim3(grid), dim3(256), 0, ctx->stream, v, static_cast<const uint64_t *>(keys_out->ptr), m,
+                           &ctrl->pops[2]);
+        RV_HIP(hipGetLastError());
+        t->max_group = fetch_ctrl(ctx)->pops[2];  // (also: the scratch blocks above go back to the pool after their last reader)
+    }
+    // 3. the null group, ascending, behind the key groups
+    if (t->n_null) {
+        DevBufRef idx = ascending_rows(ctx, nulls, n, t->n_null);
+        hipLaunchKernelGGL(rvk::join_null_rows, dim3(grid_for_words(ctx, t->n_null, 256)), dim3(256), 0, ctx->stream,
+                           static_cast<const uint64_t *>(idx->ptr), t->n_null, rows + t->n_keyed);
+        RV_HIP(hipGetLastError());
+    }
+    RV_HIP(hipStreamSynchronize(ctx->stream));
+    return t;
+}
+
+rv_dcolumn *index_column(const DevBufRef &buf, uint64_t rows) {
+    auto o = std::make_unique<rv_dcolumn>();
+    o->dtype = RV_INT64;
+    o->length = rows;
+    o->null_count = 0;
+    o->values = buf;
+    return o.release();
+}
+
+// result_pairs of plan.rs:196-204 as two Int64 index buffers: count pass, scan of the tile counts, one read-back of the total,
+// the size check, then the emit pass
+uint64_t probe_table(rv_ctx *ctx, const rv_join_table *t, const rv_dcolumn *key, DevBufRef &out_probe, DevBufRef &out_build) {
+    check_key(key, "rv_join_probe");
+    const uint64_t n = key->length;
+    rvk::JoinProbeParams p{};
+    p.table = table_view(t, key->dtype);
+    p.key = dev_view(key);
+    p.n = n;
+    p.lane_most = rvt::kJoinLaneListMost;
+    // the longest list a probe row of this key column can meet
+    const uint64_t longest = std::max<uint64_t>(p.table.match_values ? t->max_group : 0, t->n_null);
+    uint64_t total = 0;
+    DevBufRef tiles;
+    const uint64_t ntiles = (n + rvk::kJoinTileRows - 1) / rvk::kJoinTileRows;
+    if (n && longest) {
+        tiles = pool_alloc(ctx, ntiles * 8 + 16);
+        p.tile_counts = static_cast<uint64_t *>(tiles->ptr);
+        Ctrl *ctrl = prepare_ctrl(ctx, 0);
+        hipLaunchKernelGGL(rvk::join_probe_count, dim3(static_cast<uint32_t>(ntiles)), dim3(rvk::kJoinThreads), 0, ctx->stream, p);
+        hipLaunchKernelGGL(rvk::scan_sums_inplace, dim3(1), dim3(1024), 0, ctx->stream, p.tile_counts, ntiles, &ctrl->pops[0]);
+        RV_HIP(hipGetLastError());
+        ctx->last_kernel = "join_probe_count";
+        total = fetch_ctrl(ctx)->pops[0];
+    }
+    // two 8-byte indices per pair: refuse what the device cannot hold before anything is allocated (n_probe x n_build pairs can
+    // exceed 2^64 bytes)
+    const uint64_t limit = static_cast<uint64_t>(ctx->props.totalGlobalMem) / 16;
+    require(total <= limit, RV_ERR_OOM,
+            fmt("rv_join_probe: %llu pairs need %llu x 16 bytes of output, more than the device's %llu bytes", static_cast<unsigned long long>(total),
+                static_cast<unsigned long long>(total), static_cast<unsigned long long>(ctx->props.totalGlobalMem)));
+    out_probe = pool_alloc(ctx, std::max<size_t>(total * 8, 16));
+    out_build = pool_alloc(ctx, std::max<size_t>(total * 8, 16));
+    if (total) {
+        p.out_probe = static_cast<int64_t *>(out_probe->ptr);
+        p.out_build = static_cast<int64_t *>(out_build->ptr);
+        const dim3 grid(static_cast<uint32_t>(ntiles)), block(rvk::kJoinThreads);
+        const int mode = longest <= 1 ? 0 : longest <= rvt::kJoinLaneListMost ? 1 : 2;
+        if (mode == 0) hipLaunchKernelGGL(rvk::join_probe_emit<0>, grid, block, 0, ctx->stream, p);
+        else if (mode == 1) hipLaunchKernelGGL(rvk::join_probe_emit<1>, grid, block, 0, ctx->stream, p);
+        else hipLaunchKernelGGL(rvk::join_probe_emit<2>, grid, block, 0, ctx->stream, p);
+        RV_HIP(hipGetLastError());
+        ctx->last_kernel = fmt("join_probe_emit<%d>", mode);
+    }
+    RV_HIP(hipStreamSynchronize(ctx->stream));  // `tiles` goes back to the pool
+    return total;
+}
+
+}  // namespace
+}  // namespace rvl
+
+extern "C" {
+
+rv_status rv_join_build(rv_ctx *ctx, const rv_dcolumn *build_key, rv_join_table **out) {
+    return guarded([&] {
+        require(ctx && build_key && out, RV_ERR_INVALID_ARG, "rv_join_build: NULL argument");
+        *out = nullptr;
+        set_device(ctx);
+        *out = build_table(ctx, build_key).release();
+    });
+}
+
+rv_status rv_join_probe(rv_ctx *ctx, const rv_join_table *table, const rv_dcolumn *probe_key, rv_dcolumn **out_probe_idx,
+                        rv_dcolumn **out_build_idx, uint64_t *out_rows) {
+    return guarded([&] {
+        require(ctx && table && probe_key && out_probe_idx && out_build_idx, RV_ERR_INVALID_ARG, "rv_join_probe: NULL argument");
+        *out_probe_idx = *out_build_idx = nullptr;
+        set_device(ctx);
+        DevBufRef pi, bi;
+        const uint64_t rows = probe_table(ctx, table, probe_key, pi, bi);
+        std::unique_ptr<rv_dcolumn> a(index_column(pi, rows)), b(index_column(bi, rows));
+        *out_probe_idx = a.release();
+        *out_build_idx = b.release();
+        if (out_rows) *out_rows = rows;
+    });
+}
+
+rv_status rv_join_table_free(rv_ctx *ctx, rv_join_table *table) {
+    return guarded([&] {
+        require(ctx, RV_ERR_INVALID_ARG, "rv_join_table_free: NULL context");
+        if (table) {
+            RV_HIP(hipStreamSynchronize(ctx->stream));
+            delete table;
+        }
+    });
+}
+
+rv_status rv_join_table_info(const rv_join_table *table, uint64_t *build_rows, uint64_t *slots, uint64_t *longest_list) {
+    return guarded([&] {
+        require(table, RV_ERR_INVALID_ARG, "rv_join_table_info: NULL table");
+        if (build_rows) *build_rows = table->n_build;
+        if (slots) *slots = table->nslots;
+        if (longest_list) *longest_list = std::max(table->max_group, table->n_null);
+    });
+}
+
+rv_status rv_hash_join(rv_ctx *ctx, const rv_dcolumn *const *build_cols, uint32_t n_build, uint32_t build_key,
+                       const rv_dcolumn *const *probe_cols, uint32_t n_probe, uint32_t probe_key, rv_dcolumn **out, uint64_t *out_rows) {
+    return guarded([&] {
+        require(ctx && build_cols && probe_cols && out, RV_ERR_INVALID_ARG, "rv_hash_join: NULL argument");
+        require(build_key < n_build, RV_ERR_INVALID_ARG, fmt("rv_hash_join: build key %u out of range for %u build columns", build_key, n_build));
+        require(probe_key < n_probe, RV_ERR_INVALID_ARG, fmt("rv_hash_join: probe key %u out of range for %u probe columns", probe_key, n_probe));
+        check_batch(build_cols, n_build);
+        check_batch(probe_cols, n_probe);
+        for (uint32_t c = 0; c < n_build; ++c) {
+            const rv_dtype d = build_cols[c]->dtype;
+            require(is_value_type(d) || d == RV_BOOLEAN || d == RV_STRING || d == RV_NULL, RV_ERR_UNSUPPORTED, "rv_hash_join: unsupported dtype");
+        }
+        for (uint32_t c = 0; c < n_probe; ++c) {
+            const rv_dtype d = probe_cols[c]->dtype;
+            require(is_value_type(d) || d == RV_BOOLEAN || d == RV_STRING || d == RV_NULL, RV_ERR_UNSUPPORTED, "rv_hash_join: unsupported dtype");
+        }
+        check_key(build_cols[build_key], "rv_hash_join");
+        check_key(probe_cols[probe_key], "rv_hash_join");
+        set_device(ctx);
+        const uint32_t nout = n_probe + n_build - 1;
+        for (uint32_t c = 0; c < nout; ++c) out[c] = nullptr;
+        std::unique_ptr<rv_join_table> t = build_table(ctx, build_cols[build_key]);
+        DevBufRef pi, bi;
+        const uint64_t rows = probe_table(ctx, t.get(), probe_cols[probe_key], pi, bi);
+        // materialize_join_result (plan.rs:212-255): every probe column by probe_idx, then every build column but the key by
+        // build_idx.  The indices come from the tables themselves: no bounds pre-pass.
+        std::vector<const rv_dcolumn *> build_rest;
+        for (uint32_t c = 0; c < n_build; ++c)
+            if (c != build_key) build_rest.push_back(build_cols[c]);
+        try {
+            take_on_device(ctx, probe_cols, n_probe, static_cast<const uint64_t *>(pi->ptr), rows, out, false);
+            take_on_device(ctx, build_rest.data(), static_cast<uint32_t>(build_rest.size()), static_cast<const uint64_t *>(bi->ptr), rows, out + n_probe, false);
+            RV_HIP(hipStreamSynchronize(ctx->stream));  // the index buffers go back to the pool
+        } catch (...) {
+            (void)hipStreamSynchronize(ctx->stream);
+            for (uint32_t c = 0; c < nout; ++c) {
+                delete out[c];
+                out[c] = nullptr;
+            }
+            throw;
+        }
+        if (out_rows) *out_rows = rows;
+    });
+}
+
+}  // extern "C"

@@ -1,0 +1,302 @@
+// Inner hash join (reference PhysicalPlan::HashJoin, plan.rs:174-284): the build-side table and the probe kernels.
+//
+// Layout of a build table (join.hip, build_table):
+//   rows   uint32 build row ids: the non-null, non-NaN rows grouped by key, each group ascending (a stable radix sort of
+//          (key bits, row)), followed by the null rows, ascending -- the Vec push order of the reference's
+//          HashMap<AnyValue, Vec<usize>>;
+//   slots  open addressing, a power of two >= 2 x the non-null rows, linear probing; one 16-byte slot per distinct key:
+//          x = the key's 64 bits (Int64 value, Float64 to_bits, Boolean 0 / 1), y = start into `rows` | count << 32;
+//          y == 0: empty.
+// A probe row's matches are rows[start, start + count): the key's group, the null group for a null probe key, nothing for a
+// miss or a NaN.  Output positions come from scans of match counts (no atomics): the pairs are in probe-row order and, within
+// a probe row, in ascending build-row order, identically on every run.
+#pragma once
+
+#include "device_common.hpp"
+
+namespace rvk {
+
+constexpr int kJoinThreads = 256;                             // one workgroup of the probe kernels
+constexpr int kJoinRowsPerThread = 16;                        // rows per lane of a probe tile, kJoinThreads apart
+constexpr int kJoinTileRows = kJoinThreads * kJoinRowsPerThread;  // 4096 probe rows per workgroup
+constexpr int kJoinClassWords = 16;                           // 64-row words per wave of join_classify
+constexpr uint64_t kJoinClaimed = 0xFFFFFFFF00000000ull;      // y of a slot whose head has claimed it and whose count is not set yet
+
+// key classes of a cell
+enum : uint32_t { JK_VALUE = 0, JK_NULL = 1, JK_NEVER = 2 };
+
+// class and 64 key bits of row i of a key column (AnyValue's Hash / PartialEq, series.rs:72-98): a null cell is JK_NULL (Null ==
+// Null), a NaN JK_NEVER (PartialEq fails even for the same bits); every other cell is its bits.  +0.0 and -0.0 differ in their
+// bits and so never match: the reference hashes them apart (to_bits) and could pair them only on a SipHash bucket-and-tag collision.
+__device__ __forceinline__ uint32_t join_key(const DevCol &c, uint64_t i, uint64_t &bits) {
+    bits = 0;
+    if (c.dtype == DT_NULL) return JK_NULL;
+    const uint64_t at = c.offset + i;
+    if (c.validity && !((c.validity[at >> 3] >> (at & 7)) & 1)) return JK_NULL;
+    if (c.dtype == DT_BOOLEAN) {
+        bits = (static_cast<const uint8_t *>(c.values)[at >> 3] >> (at & 7)) & 1;
+        return JK_VALUE;
+    }
+    bits = static_cast<const uint64_t *>(c.values)[at];
+    if (c.dtype == DT_FLOAT64 && (bits & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull) return JK_NEVER;
+    return JK_VALUE;
+}
+
+__device__ __forceinline__ uint64_t join_wave_max64(uint64_t v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint64_t y = (static_cast<uint64_t>(__shfl_xor(static_cast<uint32_t>(v >> 32), d, 64)) << 32) | __shfl_xor(static_cast<uint32_t>(v), d, 64);
+        v = y > v ? y : v;
+    }
+    return v;
+}
+
+// murmur3's 64-bit finaliser: every key bit reaches the low bits the slot index is taken from
+__device__ __forceinline__ uint64_t join_hash(uint64_t k) {
+    k ^= k >> 33;
+    k *= 0xff51afd7ed558ccdull;
+    k ^= k >> 33;
+    k *= 0xc4ceb9fe1a85ec53ull;
+    k ^= k >> 33;
+    return k;
+}
+
+struct JoinTableView {
+    unsigned long long *slots;  // 2 words per slot (x, y)
+    const uint32_t *rows;
+    uint64_t slot_mask;   // slots - 1
+    uint64_t hash_mask;   // ~0, or the low bits option "join_hash_bits" leaves (collision tests)
+    uint32_t null_start, null_count;
+    int32_t match_values;  // 0: the key dtypes differ (or one is Null): only null meets null
+    int32_t pad;
+};
+
+// (start, count) of the matches of one probe cell
+__device__ __forceinline__ uint32_t join_lookup(const JoinTableView &t, uint32_t cls, uint64_t bits, uint32_t &start) {
+    start = 0;
+    if (cls == JK_NULL) {
+        start = t.null_start;
+        return t.null_count;
+    }
+    if (cls != JK_VALUE || !t.match_values) return 0;
+    uint64_t s = join_hash(bits) & t.hash_mask & t.slot_mask;
+    for (;;) {
+        const ulonglong2 e = *reinterpret_cast<const ulonglong2 *>(&t.slots[2 * s]);
+        if (e.y == 0) return 0;
+        if (e.x == bits) {
+            start = static_cast<uint32_t>(e.y);
+            return static_cast<uint32_t>(e.y >> 32);
+        }
+        s = (s + 1) & t.slot_mask;
+    }
+}
+
+// ---- build ----------------------------------------------------------------------------------------------------------------------
+// Bitmaps (offset 0) of the rows whose key goes into the table (`keep`: valid, not NaN) and of the null rows; their popcounts
+// are added to counts[0] / counts[1] once per wave.
+static __global__ __launch_bounds__(256) void join_classify(DevCol key, uint64_t n, uint64_t *keep, uint64_t *nulls, unsigned long long *counts) {
+    const int lane = lane_id();
+    const uint64_t wave = (static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x) >> 6;
+    const uint64_t nwords = (n + 63) / 64;
+    unsigned long long nk = 0, nn = 0;
+    for (int w = 0; w < kJoinClassWords; ++w) {
+        const uint64_t word = wave * kJoinClassWords + w;
+        if (word >= nwords) break;  // wave-uniform
+        const uint64_t i = word * 64 + lane;
+        uint64_t bits;
+        const uint32_t cls = i < n ? join_key(key, i, bits) : JK_NEVER;
+        const uint64_t k = ballot64(cls == JK_VALUE), z = ballot64(cls == JK_NULL);
+        if (lane == 0) {
+            keep[word] = k;
+            nulls[word] = z;
+        }
+        nk += __popcll(k);
+        nn += __popcll(z);
+    }
+    if (lane == 0 && (nk | nn)) {
+        atomicAdd(&counts[0], nk);
+        atomicAdd(&counts[1], nn);
+    }
+}
+
+// (key bits, row) of the kept rows, in row order: the input of the stable sort
+static __global__ __launch_bounds__(256) void join_gather_keys(DevCol key, const uint64_t *idx, uint64_t n, uint64_t *keys, uint32_t *rows) {
+    for (uint64_t j = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; j < n; j += static_cast<uint64_t>(gridDim.x) * blockDim.x) {
+        const uint64_t r = idx[j];
+        uint64_t bits;
+        (void)join_key(key, r, bits);
+        keys[j] = bits;
+        rows[j] = static_cast<uint32_t>(r);
+    }
+}
+
+// the null rows (ascending) behind the key groups
+static __global__ __launch_bounds__(256) void join_null_rows(const uint64_t *idx, uint64_t n, uint32_t *rows) {
+    for (uint64_t j = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; j < n; j += static_cast<uint64_t>(gridDim.x) * blockDim.x)
+        rows[j] = static_cast<uint32_t>(idx[j]);
+}
+
+// The first row of every group of equal keys claims a free slot.  Each distinct key has exactly one head, so a head never meets
+// its own key on the way: it takes the first empty slot.
+static __global__ __launch_bounds__(256) void join_insert_heads(JoinTableView t, const uint64_t *keys, uint64_t n) {
+    for (uint64_t j = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; j < n; j += static_cast<uint64_t>(gridDim.x) * blockDim.x) {
+        const uint64_t k = keys[j];
+        if (j > 0 && keys[j - 1] == k) continue;
+        uint64_t s = join_hash(k) & t.hash_mask & t.slot_mask;
+        while (atomicCAS(&t.slots[2 * s + 1], 0ull, kJoinClaimed | j) != 0ull) s = (s + 1) & t.slot_mask;
+        t.slots[2 * s] = k;
+    }
+}
+
+// The last row of every group finds its key's slot (every head has been inserted: a launch earlier on the stream) and sets the
+// count; the largest count goes to *max_count.
+static __global__ __launch_bounds__(256) void join_insert_tails(JoinTableView t, const uint64_t *keys, uint64_t n, unsigned long long *max_count) {
+    unsigned long long most = 0;
+    for (uint64_t j = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; j < n; j += static_cast<uint64_t>(gridDim.x) * blockDim.x) {
+        const uint64_t k = keys[j];
+        if (j + 1 < n && keys[j + 1] == k) continue;
+        uint64_t s = join_hash(k) & t.hash_mask & t.slot_mask;
+        while (t.slots[2 * s] != k || t.slots[2 * s + 1] == 0) s = (s + 1) & t.slot_mask;
+        const uint64_t start = t.slots[2 * s + 1] & 0xFFFFFFFFull;
+        const uint64_t count = j + 1 - start;
+        t.slots[2 * s + 1] = start | (count << 32);
+        most = count > most ? count : most;
+    }
+    most = join_wave_max64(most);
+    if (lane_id() == 0 && most) atomicMax(max_count, most);
+}
+
+// ---- probe ----------------------------------------------------------------------------------------------------------------------
+struct JoinProbeParams {
+    JoinTableView table;
+    DevCol key;
+    uint64_t n;
+    uint64_t *tile_counts;  // count pass: matches per tile; emit pass: their exclusive prefixes
+    int64_t *out_probe, *out_build;
+    uint32_t lane_most;     // emit, mode 2: lists longer than this are written by the whole workgroup
+};
+
+// Pass 1: matches per tile of kJoinTileRows probe rows (64-bit: one row can match every build row).
+static __global__ __launch_bounds__(kJoinThreads) void join_probe_count(JoinProbeParams p) {
+    __shared__ uint64_t s_wave[kJoinThreads / 64];
+    const uint64_t base = static_cast<uint64_t>(blockIdx.x) * kJoinTileRows + threadIdx.x;
+    uint64_t mine = 0;
+#pragma unroll
+    for (int k = 0; k < kJoinRowsPerThread; ++k) {
+        const uint64_t i = base + static_cast<uint64_t>(k) * kJoinThreads;
+        if (i < p.n) {
+            uint64_t bits;
+            const uint32_t cls = join_key(p.key, i, bits);
+            uint32_t start;
+            mine += join_lookup(p.table, cls, bits, start);
+        }
+    }
+    mine = wave_sum64(mine);
+    if (lane_id() == 0) s_wave[threadIdx.x >> 6] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t t = 0;
+#pragma unroll
+        for (int w = 0; w < kJoinThreads / 64; ++w) t += s_wave[w];
+        p.tile_counts[blockIdx.x] = t;
+    }
+}
+
+// exclusive prefix of v over the workgroup, in thread order; *total = the workgroup's sum (every thread)
+__device__ __forceinline__ uint64_t join_block_scan(uint64_t v, uint64_t *s_wave, uint64_t &total) {
+    const int lane = lane_id(), wave = threadIdx.x >> 6;
+    uint64_t incl = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t y = (static_cast<uint64_t>(__shfl_up(static_cast<uint32_t>(incl >> 32), d, 64)) << 32) | __shfl_up(static_cast<uint32_t>(incl), d, 64);
+        if (lane >= d) incl += y;
+    }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    uint64_t before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < kJoinThreads / 64; ++w) {
+        before += w < wave ? s_wave[w] : 0;
+        all += s_wave[w];
+    }
+    __syncthreads();
+    total = all;
+    return before + incl - v;
+}
+
+// Pass 2: the pairs of a tile at its prefix, rows in order.  MODE 0: every list holds at most one row (unique build keys, the
+// foreign-key join): a stream compaction, positions from a ballot.  MODE 1: lists of at most lane_most rows, each written by its
+// lane.  MODE 2: longer lists as well -- queued in LDS and written by the whole workgroup, so that a key with thousands of build
+// rows does not serialise on one lane.
+template <int MODE>
+static __global__ __launch_bounds__(kJoinThreads) void join_probe_emit(JoinProbeParams p) {
+    __shared__ uint64_t s_wave[kJoinThreads / 64];
+    __shared__ uint64_t s_q_out[kJoinThreads], s_q_row[kJoinThreads];
+    __shared__ uint32_t s_q_start[kJoinThreads], s_q_count[kJoinThreads];
+    __shared__ uint32_t s_q_n;
+    const int lane = lane_id(), wave = threadIdx.x >> 6;
+    uint64_t out = p.tile_counts[blockIdx.x];
+    const uint64_t base = static_cast<uint64_t>(blockIdx.x) * kJoinTileRows + threadIdx.x;
+    if (MODE == 2 && threadIdx.x == 0) s_q_n = 0;
+    for (int k = 0; k < kJoinRowsPerThread; ++k) {
+        const uint64_t i = base + static_cast<uint64_t>(k) * kJoinThreads;
+        if (static_cast<uint64_t>(blockIdx.x) * kJoinTileRows + static_cast<uint64_t>(k) * kJoinThreads >= p.n) break;  // workgroup-uniform
+        uint32_t count = 0, start = 0;
+        if (i < p.n) {
+            uint64_t bits;
+            const uint32_t cls = join_key(p.key, i, bits);
+            count = join_lookup(p.table, cls, bits, start);
+        }
+        if (MODE == 0) {
+            const uint64_t m = ballot64(count != 0);
+            if (lane == 0) s_wave[wave] = __popcll(m);
+            __syncthreads();
+            uint64_t before = 0, all = 0;
+#pragma unroll
+            for (int w = 0; w < kJoinThreads / 64; ++w) {
+                before += w < wave ? s_wave[w] : 0;
+                all += s_wave[w];
+            }
+            if (count) {
+                const uint64_t o = out + before + __popcll(m & low_mask(lane));
+                p.out_probe[o] = static_cast<int64_t>(i);
+                p.out_build[o] = p.table.rows[start];
+            }
+            out += all;
+            __syncthreads();
+        } else {
+            uint64_t all;
+            const uint64_t o = out + join_block_scan(count, s_wave, all);
+            if (MODE == 2 && count > p.lane_most) {
+                const uint32_t q = atomicAdd(&s_q_n, 1u);
+                s_q_out[q] = o;
+                s_q_row[q] = i;
+                s_q_start[q] = start;
+                s_q_count[q] = count;
+            } else {
+                for (uint32_t j = 0; j < count; ++j) {
+                    p.out_probe[o + j] = static_cast<int64_t>(i);
+                    p.out_build[o + j] = p.table.rows[start + j];
+                }
+            }
+            out += all;
+            if (MODE == 2) {
+                __syncthreads();
+                const uint32_t nq = s_q_n;
+                for (uint32_t q = 0; q < nq; ++q) {
+                    const uint64_t qo = s_q_out[q], qr = s_q_row[q];
+                    const uint32_t qs = s_q_start[q], qc = s_q_count[q];
+                    for (uint32_t j = threadIdx.x; j < qc; j += kJoinThreads) {
+                        p.out_probe[qo + j] = static_cast<int64_t>(qr);
+                        p.out_build[qo + j] = p.table.rows[qs + j];
+                    }
+                }
+                __syncthreads();
+                if (threadIdx.x == 0) s_q_n = 0;
+                __syncthreads();
+            }
+        }
+    }
+}
+
+}  // namespace rvk

@@ -230,6 +230,11 @@ void normalize_predicate(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t nc
 void check_batch(const rv_dcolumn *const *cols, uint32_t ncols);
 void bool_op(rv_ctx *ctx, int kind, const rv_dcolumn *a, const rv_dcolumn *b, rv_dcolumn **out);
 
+// ---- take_concat.hip ---------------------------------------------------------------------------------------
+// RecordBatch::take with the index list in HBM (bounds pre-pass unless check_bounds is false), one gather per column
+void take_on_device(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, const uint64_t *d_idx, uint64_t n_indices, rv_dcolumn **out,
+                    bool check_bounds = true);
+
 // ---- query.hip ---------------------------------------------------------------------------------------------
 uint64_t filter_by_groups(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, const rv_term *terms, uint32_t nterms, rv_null_policy policy,
                           const uint32_t *proj, uint32_t nproj, rv_dcolumn **out, rv_dcolumn **out_selection, const ExprInfo *ex = nullptr,

@@ -248,6 +248,7 @@ struct rv_ctx {
     int64_t opt_inject_failure = 0; // fault injection: this many upcoming query calls fail with RV_ERR_DEVICE before launching
     bool undrained = false;         // a group's failed collective may still sit on this context's stream (group.hip, drop_comms): destroy waits
                                     // for it a bounded time and leaks the context's device memory rather than wait without end
+    int64_t opt_join_hash_bits = 0; // tests: join tables built from now on hash keys to this many low bits (long collision chains); 0: all 64
     int64_t opt_bools_in_pass = 0;  // 1: projected Boolean columns are compacted inside the fused pass (lane-form PEXT)
     unsigned long long last_stamps[32] = {};
     // per (kernel, dynamic LDS bytes): resident workgroups per CU; per kernel: largest LDS size enabled so far

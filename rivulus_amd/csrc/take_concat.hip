@@ -8,15 +8,16 @@ using namespace rvl;
 
 namespace rvl {
 // RecordBatch::take (record_batch.rs:108-178) with the index list in HBM: bounds pre-pass as a device reduction, then one
-// gather per column.  `d_idx` holds n_indices 8-byte indices.
-void take_on_device(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, const uint64_t *d_idx, uint64_t n_indices, rv_dcolumn **out) {
+// gather per column.  `d_idx` holds n_indices 8-byte indices; check_bounds false: the caller knows them to be in range.
+void take_on_device(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, const uint64_t *d_idx, uint64_t n_indices, rv_dcolumn **out,
+                    bool check_bounds) {
     const uint64_t rows = ncols ? cols[0]->length : 0;
     for (uint32_t c = 0; c < ncols; ++c) {
         require(is_value_type(cols[c]->dtype) || cols[c]->dtype == RV_BOOLEAN || cols[c]->dtype == RV_STRING || cols[c]->dtype == RV_NULL,
                 RV_ERR_UNSUPPORTED, "rv_take: unsupported dtype");
         out[c] = nullptr;
     }
-    if (n_indices) {  // record_batch.rs:109-116: the FIRST index that is out of bounds, with the reference's text
+    if (n_indices && check_bounds) {  // record_batch.rs:109-116: the FIRST index that is out of bounds, with the reference's text
         Ctrl *ctrl = prepare_ctrl(ctx, 0);
         RV_HIP(hipMemsetAsync(&ctrl->pops[0], 0xFF, 8, ctx->stream));
         hipLaunchKernelGGL(rvk::take_bounds_kernel, dim3(grid_for_words(ctx, n_indices, 256)), dim3(256), 0, ctx->stream, d_idx, n_indices, rows, &ctrl->pops[0]);

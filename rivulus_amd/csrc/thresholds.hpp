@@ -75,4 +75,11 @@ constexpr uint32_t kWalkThreads = 8;               // (16 measured slower: profi
 constexpr double kStrTilesFrom = 0.50;             // source-tile order instead of (start, length) lists            tools/str_sweep.py, profiles/r04c_*
 constexpr double kBoolCapFactor = 1.25;            // Boolean outputs sized for the expected survivors x this + kBoolCapSlack rows
 constexpr uint64_t kBoolCapSlack = 65536;
+
+// ---- inner hash join (join.hip, probe_table) -----------------------------------------------------------------------------------------
+// A probe row's match list of up to this many build rows is written by its own lane (join_probe_emit<1>); a table with longer lists
+// probes with join_probe_emit<2>, which hands those lists to the whole workgroup.  (A table whose lists all hold one row takes
+// join_probe_emit<0>, the plain compaction: no threshold.)  Set by reasoning -- a lane writing 32 pairs costs about what handing
+// them to the workgroup costs -- NOT by a sweep; profiles/r06_join_bench.jsonl times 8 rows per key on the lane path (tools/join_bench.py).
+constexpr uint32_t kJoinLaneListMost = 32;
 }  // namespace rvt

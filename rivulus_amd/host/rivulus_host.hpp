@@ -1632,11 +1632,13 @@ class PhysicalPlan;
 using PhysicalPlanPtr = std::shared_ptr<const PhysicalPlan>;
 class PhysicalPlan {
   public:
-    enum Kind { DataFrameSource, Select, Filter } kind = DataFrameSource;
+    enum Kind { DataFrameSource, Select, Filter, HashJoin } kind = DataFrameSource;
     DeviceFrame df;
     PhysicalPlanPtr input;
     std::vector<std::string> columns, final_names;
     CompareTerm term;  // Filter { column, value, op }
+    PhysicalPlanPtr build_side;          // HashJoin { build_side, probe_side = input, build_key, probe_key, Inner }
+    std::string build_key, probe_key;
 
     static PhysicalPlanPtr source(DeviceFrame f) {
         auto p = std::make_shared<PhysicalPlan>();
@@ -1656,6 +1658,16 @@ class PhysicalPlan {
         p->input = std::move(in);
         p->columns = std::move(cols);
         p->final_names = std::move(finals);
+        return p;
+    }
+    // planner.rs:102-108: the left frame is the build side, the right frame the probe side
+    static PhysicalPlanPtr hash_join(PhysicalPlanPtr build, PhysicalPlanPtr probe, std::string build_key, std::string probe_key) {
+        auto p = std::make_shared<PhysicalPlan>();
+        p->kind = HashJoin;
+        p->build_side = std::move(build);
+        p->input = std::move(probe);
+        p->build_key = std::move(build_key);
+        p->probe_key = std::move(probe_key);
         return p;
     }
     DeviceFrame execute() const {
@@ -1695,6 +1707,45 @@ class PhysicalPlan {
                 DeviceFrame res;
                 res.names = in.names;
                 for (auto *h : out) res.columns.push_back(execution::Array::adopt(ctx, h));
+                return res;
+            }
+            case HashJoin: {  // plan.rs:174-207 (JoinType::Inner), one rv_hash_join
+                DeviceFrame b = build_side->execute();
+                const execution::ArrayRef *bk = b.column(build_key);
+                if (!bk) throw Panic("called `Option::unwrap()` on a `None` value");  // plan.rs:184: build_df.column(..).unwrap()
+                DeviceFrame p = input->execute();
+                const execution::ArrayRef *pk = p.column(probe_key);
+                if (!pk) throw Panic("called `Option::unwrap()` on a `None` value");  // plan.rs:195
+                std::vector<const rv_dcolumn *> bcols, pcols;
+                uint32_t bki = 0, pki = 0;
+                for (size_t i = 0; i < b.columns.size(); ++i) {
+                    if (!b.columns[i]->on_device()) throw Error(RV_ERR_UNSUPPORTED, "columns off the device are outside the device path");
+                    if (&b.columns[i] == bk) bki = static_cast<uint32_t>(i);
+                    bcols.push_back(b.columns[i]->handle());
+                }
+                for (size_t i = 0; i < p.columns.size(); ++i) {
+                    if (!p.columns[i]->on_device()) throw Error(RV_ERR_UNSUPPORTED, "columns off the device are outside the device path");
+                    if (&p.columns[i] == pk) pki = static_cast<uint32_t>(i);
+                    pcols.push_back(p.columns[i]->handle());
+                }
+                std::vector<rv_dcolumn *> out(pcols.size() + bcols.size() - 1, nullptr);
+                uint64_t rows = 0;
+                const ContextRef ctx = (*pk)->context();
+                check(rv_hash_join(ctx->raw(), bcols.data(), static_cast<uint32_t>(bcols.size()), bki, pcols.data(), static_cast<uint32_t>(pcols.size()),
+                                   pki, out.data(), &rows));
+                // materialize_join_result (plan.rs:212-255): probe names, then the build names but the key, `_right` where the probe
+                // frame has the name too
+                DeviceFrame res;
+                size_t k = 0;
+                for (size_t i = 0; i < p.columns.size(); ++i, ++k) {
+                    res.names.push_back(p.names[i]);
+                    res.columns.push_back(execution::Array::adopt(ctx, out[k]));
+                }
+                for (size_t i = 0; i < b.columns.size(); ++i) {
+                    if (b.names[i] == build_key) continue;
+                    res.names.push_back(p.column(b.names[i]) ? b.names[i] + "_right" : b.names[i]);
+                    res.columns.push_back(execution::Array::adopt(ctx, out[k++]));
+                }
                 return res;
             }
         }
