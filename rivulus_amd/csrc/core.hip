@@ -33,6 +33,14 @@ DevBufRef pool_alloc(rv_ctx *ctx, size_t bytes) {
     b->id = next_id.fetch_add(1, std::memory_order_relaxed);
     return b;
 }
+std::unique_ptr<rv_dcolumn> new_value_column(rv_ctx *ctx, rv_dtype dtype, uint64_t rows) {
+    auto o = std::make_unique<rv_dcolumn>();
+    o->dtype = dtype;
+    o->length = rows;
+    o->null_count = 0;
+    o->values = pool_alloc(ctx, std::max<size_t>(elem_bytes(dtype, rows), 8));
+    return o;
+}
 
 void set_device(rv_ctx *ctx) { RV_HIP(hipSetDevice(ctx->device)); }
 // option "inject_failure": a query entry point fails before it launches anything (rv_group_* failure handling)

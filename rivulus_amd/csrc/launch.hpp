@@ -15,6 +15,10 @@
 #include "runtime.hpp"
 #include "thresholds.hpp"
 
+namespace rvk {
+struct RangesCompact;
+}
+
 namespace rvl {
 using namespace rvh;
 
@@ -56,6 +60,8 @@ bool is_value_type(rv_dtype t);
 void check_string_offsets(const int32_t *offsets, uint64_t first, uint64_t count, uint64_t data_bytes);
 rvk::DevTerm lower_term(const rv_term &t, rv_dtype col_type, rv_null_policy policy, uint32_t slot = 0);
 int grid_for_words(rv_ctx *ctx, uint64_t items, int block);
+// a value column of `rows` rows (values only, no nulls): the output of a compaction
+std::unique_ptr<rv_dcolumn> new_value_column(rv_ctx *ctx, rv_dtype dtype, uint64_t rows);
 
 // A predicate with OR / NOT, lowered for the kernels: `terms` handed along with it is the literal list of a
 // conjunctive normal form (a user term may appear several times); see normalize_predicate.
@@ -197,6 +203,7 @@ void str_sel_copy(rv_ctx *ctx, StrSelLaunch &L, uint64_t rows);
 rv_dcolumn *str_sel_result(StrSelLaunch &L, uint64_t rows, const Ctrl &fetched);
 void bool_compact_queue(rv_ctx *ctx, const rv_dcolumn *src, const rv_dcolumn *sel, const RangeOffsets &ranges, Ctrl *ctrl, int slot, BoolCompactLaunch &L);
 rv_dcolumn *bool_compact_result(BoolCompactLaunch &L, uint64_t rows, const Ctrl &fetched);
+void launch_bits_compact(rv_ctx *ctx, const rvk::BitsCompact &b);  // a workgroup per 256 selection words, at most 8 per CU
 rv_dcolumn *concat_strings(rv_ctx *ctx, const rv_dcolumn *const *parts, uint32_t nparts);
 rv_dcolumn *string_term_mask(rv_ctx *ctx, const rv_dcolumn *col, const rv_term &t, rv_null_policy policy);
 
@@ -238,7 +245,9 @@ void take_on_device(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, 
 // ---- query.hip ---------------------------------------------------------------------------------------------
 uint64_t filter_by_groups(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, const rv_term *terms, uint32_t nterms, rv_null_policy policy,
                           const uint32_t *proj, uint32_t nproj, rv_dcolumn **out, rv_dcolumn **out_selection, const ExprInfo *ex = nullptr,
-                          BatchReq *req = nullptr, const AfterLaunch *after_launch = nullptr, RangeOffsets *ranges = nullptr);
+                          BatchReq *req = nullptr);
+// compact_ranges_kernel<ncols, nullable> at the offsets in `q` (ranges_kernel.hpp); names itself in ctx->last_kernel
+void launch_compact_ranges(rv_ctx *ctx, const rvk::RangesCompact &q, int ncols, bool nullable);
 uint64_t filter_query(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, const rv_predicate *pred, const uint32_t *proj, uint32_t nproj,
                       rv_dcolumn **out, rv_dcolumn **out_selection, BatchReq *req = nullptr);
 

@@ -8,158 +8,129 @@ using namespace rvh;
 using namespace rvl;
 
 namespace rvl {
-// ---- RecordBatch kernels ---------------------------------------------------------------------------
-// Columns are compacted in groups that fit one single-pass launch (<= 4 eight-byte columns
-// and <= 4 bit streams each); every group re-reads the predicate bitmap only (1 bit/row).
-// `terms` is a normalised term list (normalize_predicate): no String columns, at most kMaxBoolCols Boolean ones.
-uint64_t filter_by_groups(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, const rv_term *terms, uint32_t nterms,
-                          rv_null_policy policy, const uint32_t *proj, uint32_t nproj, rv_dcolumn **out, rv_dcolumn **out_selection,
-                          const ExprInfo *ex, BatchReq *req, const AfterLaunch *after_launch, RangeOffsets *ranges) {
-    // String, Boolean and Null projections are produced AFTER the fused pass, from the selection bitmap it
-    // materialises: strings gathered by the surviving row indices, Boolean columns compacted bit-wise
-    // (bits_compact_kernel; as byte-staged streams inside the fused pass they made it ~2.4x slower), Null
-    // columns are just a length.  The 8-byte columns go through the fused pass.
-    // ... unless the launch runs in lane form (8-byte loads), where a Boolean column rides along as a bit stream: a software
-    // PEXT per 64-row word inside the pass (fused_kernel.hpp), up to kMaxBitStreams streams (values + validity each).
-    // Measured (profiles/README.md): the per-lane PEXT costs the issue-bound pass more than the separate bit-compaction
-    // kernel costs in traffic, so it is off by default (option "bools_in_pass" = 1 turns it on).
-    int bool_streams = 0;
-    bool bools_in_pass = ctx->opt_bools_in_pass != 0 && ctx->opt_vec != 2 && ex == nullptr;
-    {
-        std::vector<char> seen(ncols, 0);
-        for (uint32_t j = 0; j < nproj && bools_in_pass; ++j) {
-            const uint32_t c = proj[j];
-            if (c >= ncols) break;
-            if (cols[c]->dtype == RV_BOOLEAN) bool_streams += cols[c]->validity ? 2 : 1;
-            else if (cols[c]->dtype == RV_STRING || cols[c]->dtype == RV_NULL) bools_in_pass = false;  // a selection bitmap is made anyway
-        }
-        bools_in_pass = bools_in_pass && bool_streams > 0 && bool_streams <= rvk::kMaxBitStreams;
+// ---- the Boolean-mask path: mask_select_kernel + a scan of its counts per 1024 rows stand in for the chained pass, the value columns
+//      are compacted at the scan's offsets.  A call (filter_by_groups) and a window of RecordBatches in flight share these steps.
+struct MaskWindow {
+    rv_ctx::LaunchCtrl ctrl;  // a window's own control block: pops[0] <- the scan's total
+    bool launched = false;
+    std::unique_ptr<rv_dcolumn> sel;
+    DevBufRef counts;
+    RangeOffsets ranges;  // the scan's offsets, one per 1024 rows
+    std::vector<const rv_dcolumn *> src;  // the projected source columns (a window's caller keeps them alive until finish)
+    uint64_t n = 0, assumed = 0, signature = 0;
+};
+// Where the scan's total goes: waited for and returned, or left in pops[0] of the context's control block or of the window's own
+// (several windows may be in flight).
+enum class MaskTotal { kWait, kInContext, kInWindow };
+
+// `b is true` alone, RV_NULL_DROPS, over a Boolean column of a table of kRangesFromRows rows and more (any non-empty one with option
+// groups_by_ranges = 1, none with -1), in batches (if any) of whole 1024-row ranges.  Each caller adds its own conditions.
+static bool mask_shape(const rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, const rv_term *terms, uint32_t nterms, rv_null_policy policy,
+                       bool expr, uint64_t chunk_rows) {
+    const uint64_t n = ncols ? cols[0]->length : 0;
+    return ctx->opt_groups_by_ranges >= 0 && !expr && nterms == 1 && terms[0].op == RV_IS_TRUE && policy == RV_NULL_DROPS && terms[0].column < ncols &&
+           cols[terms[0].column]->dtype == RV_BOOLEAN && (n >= rvt::kRangesFromRows || (ctx->opt_groups_by_ranges == 1 && n > 0)) && chunk_rows % 1024 == 0;
+}
+// outputs sized before the survivor count is known, from what the predicate kept the last time it ran over these buffers: x 1.2 + 2 % of the rows
+static uint64_t assumed_rows(uint64_t n, double known) {
+    return std::min<uint64_t>(n, static_cast<uint64_t>(static_cast<double>(n) * (known * rvt::kOutSizingFactor + rvt::kOutSizingSlack)) + 4096);
+}
+// mask_select_kernel (the per-batch counts of a window of RecordBatches straight into the caller's array at 1024-row batches, through
+// batch_counts_from_waves at longer ones), then the scan of its counts.  Returns the survivor count with MaskTotal::kWait, else 0.
+static uint64_t mask_select_begin(rv_ctx *ctx, const rv_dcolumn *mask, BatchReq *req, MaskTotal total, MaskWindow &w) {
+    w.n = mask->length;
+    const uint64_t nwords = (w.n + 63) / 64, nranges = (w.n + 1023) / 1024;
+    w.sel = std::make_unique<rv_dcolumn>();
+    w.sel->dtype = RV_BOOLEAN;
+    w.sel->length = w.n;
+    w.sel->null_count = 0;
+    w.sel->values = pool_alloc(ctx, std::max<size_t>(bitmap_words_bytes(w.n) + 8, 16));
+    w.counts = pool_alloc(ctx, nranges * 4 + 16);
+    if (total == MaskTotal::kInWindow) {
+        w.ctrl = acquire_launch_ctrl(ctx, 0, 0);  // zeroed on the stream
+        w.launched = true;
+    } else if (ctx->opt_profile) {  // (option profile_kernels: a call's mask kernels -- selection, scan, compaction -- are its device time)
+        RV_HIP(hipEventRecord(ctx->evk0, ctx->stream));
     }
-    auto post_pass = [&](uint32_t c) {
-        return cols[c]->dtype == RV_STRING || cols[c]->dtype == RV_NULL || (cols[c]->dtype == RV_BOOLEAN && !bools_in_pass);
-    };
-    bool any_post = false;
-    for (uint32_t j = 0; j < nproj; ++j) {
-        require(proj[j] < ncols, RV_ERR_INVALID_ARG, fmt("projection %u references column %u of %u", j, proj[j], ncols));
-        any_post |= post_pass(proj[j]);
+    rvk::MaskSelect q{};
+    q.values = static_cast<const uint8_t *>(mask->values->ptr);
+    q.values_bytes = mask->values->bytes;
+    q.validity = mask->validity ? static_cast<const uint8_t *>(mask->validity->ptr) : nullptr;
+    q.validity_bytes = mask->validity ? mask->validity->bytes : 0;
+    q.offset = mask->offset;
+    q.n = w.n;
+    q.sel = static_cast<uint64_t *>(w.sel->values->ptr);
+    q.counts = static_cast<uint32_t *>(w.counts->ptr);
+    // the reference's 1024-row batches ARE the ranges: their counts go straight to the caller's (pinned) array, 8 bytes per batch
+    q.batch_counts = (req && req->counts && req->chunk_rows == 1024) ? req->counts : nullptr;
+    hipLaunchKernelGGL(rvk::mask_select_kernel, dim3(static_cast<uint32_t>((nwords + 255) / 256)), dim3(256), 0, ctx->stream, q);
+    RV_HIP(hipGetLastError());
+    if (req && req->counts && req->chunk_rows != 1024) {  // the survivors of every batch: sums of the counts per 1024 rows, written where the caller reads them
+        const uint64_t per_batch = req->chunk_rows / 1024;
+        const uint64_t threads = per_batch < 32 ? req->nb : (per_batch < 4096 ? req->nb * 64 : req->nb * 256);
+        const dim3 cgrid(static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>((threads + 255) / 256, static_cast<uint64_t>(ctx->props.multiProcessorCount) * 8))));
+        hipLaunchKernelGGL(rvk::batch_counts_from_waves, cgrid, dim3(256), 0, ctx->stream, static_cast<const uint32_t *>(q.counts), nranges, per_batch, req->nb, req->counts);
+        RV_HIP(hipGetLastError());
     }
-    if (any_post) {
-        std::vector<uint32_t> fixed, fixed_pos;
-        for (uint32_t j = 0; j < nproj; ++j)
-            if (!post_pass(proj[j])) {
-                fixed.push_back(proj[j]);
-                fixed_pos.push_back(j);
-            }
-        std::vector<rv_dcolumn *> fo(fixed.size() ? fixed.size() : 1, nullptr);
-        rv_dcolumn *sel = nullptr;
-        uint64_t rows = 0;
-        // String and Boolean columns are produced from the selection bitmap by launches queued right behind the fused pass,
-        // while it is still writing that bitmap, at the pass's wave offsets (no scan over the bitmap): the lengths pass of the
-        // first String column, bits_compact_kernel for up to 6 Boolean columns.  The host waits for the pass (it sizes the
-        // copy launches by the survivor count) while those run, and reads the shared control block once, at the end.
-        StrSelLaunch first_str;
-        int first_str_j = -1;
-        std::vector<uint32_t> bool_js;
-        // A Boolean column that the predicate itself requires to be true (`b is true` in a plain AND: the one filter form the
-        // reference's streaming planner accepts, streaming_planner.rs:139) is all true and never null among the survivors
-        // (record_batch.rs:237 keeps Some(true) only): its output is rows ones, nothing to read or compact.
-        std::vector<char> all_true(nproj, 0);
-        for (uint32_t j = 0; j < nproj; ++j) {
-            if (cols[proj[j]]->dtype == RV_STRING && first_str_j < 0) first_str_j = static_cast<int>(j);
-            if (cols[proj[j]]->dtype != RV_BOOLEAN) continue;
-            for (uint32_t t = 0; t < nterms && !ex; ++t)
-                if (terms[t].column == proj[j] && terms[t].op == RV_IS_TRUE) all_true[j] = 1;
-            if (!all_true[j]) bool_js.push_back(j);
-        }
-        RangeOffsets wave_ranges;
-        const bool want_bools = !bool_js.empty() && bool_js.size() <= 6;
-        const bool want_ranges = want_bools || first_str_j >= 0;
-        std::vector<BoolCompactLaunch> bool_launches(want_bools ? bool_js.size() : 0);
-        bool bools_queued = false;
-        const AfterLaunch queue_post = [&](const rv_dcolumn *s) {
-            if (!str_sel_eligible(s, wave_ranges)) return;  // an empty table, or a geometry whose ranges do not tile 4096 rows
-            Ctrl *ctrl = prepare_ctrl(ctx, 0);
-            if (first_str_j >= 0) str_sel_queue(ctx, cols[proj[first_str_j]], s, wave_ranges, ctrl, 0, first_str);
-            if (want_bools) {
-                for (size_t k = 0; k < bool_js.size(); ++k)
-                    bool_compact_queue(ctx, cols[proj[bool_js[k]]], s, wave_ranges, ctrl, 1 + static_cast<int>(k), bool_launches[k]);
-                bools_queued = true;
-            }
-        };
-        try {
-            if (req && (first_str_j >= 0 || !bool_js.empty())) req->sel_optional = false;  // columns produced from the selection bitmap
-            const uint64_t reruns_before = ctx->overflow_reruns;
-            // the selection bitmap: for the String / Boolean columns compacted by it (a NullArray or an all-true column is a length)
-            const bool need_sel = out_selection != nullptr || first_str_j >= 0 || !bool_js.empty();
-            rows = filter_by_groups(ctx, cols, ncols, terms, nterms, policy, fixed.data(), static_cast<uint32_t>(fixed.size()), fo.data(),
-                                    need_sel ? &sel : nullptr, ex, req, &queue_post, want_ranges ? &wave_ranges : nullptr);
-            for (size_t k = 0; k < fixed.size(); ++k) {
-                out[fixed_pos[k]] = fo[k];
-                fo[k] = nullptr;
-            }
-            if (first_str.queued || bools_queued) {
-                // outputs sized by a bound that the pass overflowed (it was re-run with exact sizes): what was queued with
-                // the same bound is dropped and the columns take the scan path below
-                const bool usable = ctx->overflow_reruns == reruns_before;
-                if (first_str.queued && usable) str_sel_copy(ctx, first_str, rows);
-                const Ctrl fetched = *fetch_ctrl(ctx);  // one read-back for everything queued behind the pass
-                if (first_str.queued && usable) out[first_str_j] = str_sel_result(first_str, rows, fetched);
-                if (bools_queued && usable)
-                    for (size_t k = 0; k < bool_js.size(); ++k) out[bool_js[k]] = bool_compact_result(bool_launches[k], rows, fetched);
-            }
-            DevBufRef excl;  // survivor prefix per selection word: the paths that could not be queued behind the pass
-            auto need_excl = [&]() -> const DevBufRef & {
-                if (!excl) excl = selection_prefix(ctx, sel, rows);
-                return excl;
-            };
-            for (uint32_t j = 0; j < nproj; ++j) {
-                const rv_dcolumn *src = cols[proj[j]];
-                if (out[j]) continue;  // fixed-width columns, and what was queued behind the pass
-                if (src->dtype == RV_STRING) {
-                    if (str_sel_eligible(sel, wave_ranges) && rows <= wave_ranges.out_capacity) {  // further String columns: the same launches, one after the other
-                        StrSelLaunch L;
-                        str_sel_queue(ctx, src, sel, wave_ranges, prepare_ctrl(ctx, 0), 0, L);
-                        str_sel_copy(ctx, L, rows);
-                        const Ctrl fetched = *fetch_ctrl(ctx);
-                        out[j] = str_sel_result(L, rows, fetched);
-                    } else {
-                        out[j] = gather_strings_selected(ctx, src, sel, rows, need_excl());
-                    }
-                } else if (src->dtype == RV_BOOLEAN && all_true[j]) {
-                    auto o = std::make_unique<rv_dcolumn>();
-                    o->dtype = RV_BOOLEAN;
-                    o->length = rows;
-                    o->null_count = 0;
-                    const size_t wb = zeroed_bitmap_bytes(rows);
-                    o->values = pool_alloc(ctx, wb);
-                    RV_HIP(hipMemsetAsync(o->values->ptr, 0, wb, ctx->stream));  // tail bits zero (bitmap.rs:178-188)
-                    if (rows / 8) RV_HIP(hipMemsetAsync(o->values->ptr, 0xFF, rows / 8, ctx->stream));
-                    if (rows % 8) RV_HIP(hipMemsetAsync(static_cast<char *>(o->values->ptr) + rows / 8, (1 << (rows % 8)) - 1, 1, ctx->stream));
-                    out[j] = o.release();
-                } else if (src->dtype == RV_BOOLEAN) {
-                    out[j] = compact_boolean(ctx, src, sel, rows, need_excl());
-                } else if (src->dtype == RV_NULL) {
-                    auto o = std::make_unique<rv_dcolumn>();
-                    o->dtype = RV_NULL;
-                    o->length = rows;
-                    o->null_count = static_cast<int64_t>(rows);
-                    out[j] = o.release();
-                }
-            }
-            RV_HIP(hipStreamSynchronize(ctx->stream));  // excl goes back to the pool
-        } catch (...) {
-            for (auto *d : fo) delete d;
-            for (uint32_t j = 0; j < nproj; ++j) {
-                delete out[j];
-                out[j] = nullptr;
-            }
-            delete sel;
-            throw;
-        }
-        if (out_selection) *out_selection = sel;
-        else delete sel;
-        return rows;
+    if (req && req->counts) {
+        req->counted = true;
+        ctx->batch_counts_in_pass += 1;
     }
+    w.ranges.range_rows = 1024;
+    unsigned long long *total_dst = total == MaskTotal::kInWindow ? &static_cast<Ctrl *>(w.ctrl.dev)->pops[0] : nullptr;
+    return device_exclusive_scan(ctx, w.counts->ptr, nranges, w.ranges.offsets, false, total == MaskTotal::kWait, total_dst);
+}
+// the plain columns `w.src` compacted at the scan's offsets into `outs`, sized for `cap` rows, in groups of kRangesMaxCols
+static void mask_compact(rv_ctx *ctx, const MaskWindow &w, uint64_t cap, rv_dcolumn *const *outs) {
+    rvk::RangesCompact q{};
+    q.sel = static_cast<const uint64_t *>(w.sel->values->ptr);
+    q.nwords = (w.n + 63) / 64;
+    q.n = w.n;
+    q.range_offsets = static_cast<const uint64_t *>(w.ranges.offsets->ptr);
+    q.range_rows = 1024;
+    q.out_capacity = cap;
+    for (size_t g0 = 0; g0 < w.src.size(); g0 += rvk::kRangesMaxCols) {
+        const size_t k = std::min<size_t>(rvk::kRangesMaxCols, w.src.size() - g0);
+        for (size_t c = 0; c < k; ++c) {
+            q.in[c] = static_cast<const char *>(w.src[g0 + c]->values->ptr) + w.src[g0 + c]->offset * 8;
+            q.out[c] = static_cast<uint64_t *>(outs[g0 + c]->values->ptr);
+        }
+        launch_compact_ranges(ctx, q, static_cast<int>(k), false);
+    }
+}
+
+void launch_compact_ranges(rv_ctx *ctx, const rvk::RangesCompact &q, int ncols, bool nullable) {
+    const dim3 grid(static_cast<uint32_t>((q.nwords + 63) / 64)), block(256);  // a wave per 16 words, four per workgroup
+    switch (ncols * 2 + (nullable ? 1 : 0)) {
+        case 2: hipLaunchKernelGGL((rvk::compact_ranges_kernel<1, false>), grid, block, 0, ctx->stream, q); break;
+        case 3: hipLaunchKernelGGL((rvk::compact_ranges_kernel<1, true>), grid, block, 0, ctx->stream, q); break;
+        case 4: hipLaunchKernelGGL((rvk::compact_ranges_kernel<2, false>), grid, block, 0, ctx->stream, q); break;
+        case 5: hipLaunchKernelGGL((rvk::compact_ranges_kernel<2, true>), grid, block, 0, ctx->stream, q); break;
+        case 6: hipLaunchKernelGGL((rvk::compact_ranges_kernel<3, false>), grid, block, 0, ctx->stream, q); break;
+        case 7: hipLaunchKernelGGL((rvk::compact_ranges_kernel<3, true>), grid, block, 0, ctx->stream, q); break;
+        case 8: hipLaunchKernelGGL((rvk::compact_ranges_kernel<4, false>), grid, block, 0, ctx->stream, q); break;
+        default: hipLaunchKernelGGL((rvk::compact_ranges_kernel<4, true>), grid, block, 0, ctx->stream, q); break;
+    }
+    RV_HIP(hipGetLastError());
+    ctx->last_kernel = fmt("compact_ranges_kernel<%d>", ncols);
+}
+
+// ---- the value columns: plan, then run -----------------------------------------------------------------------------
+// Columns are compacted in groups that fit one single-pass launch (<= 4 eight-byte columns and <= 4 bit streams each); every
+// group re-reads the predicate bitmap only (1 bit/row).  What is decided before anything is launched (host only -- but
+// expected_selectivity may take its sample on the way):
+struct GroupPlan {
+    uint64_t n_rows = 0;
+    bool mask_path = false;      // no chained pass: mask_select_kernel + a scan of its counts (MaskWindow)
+    uint64_t mask_assumed = 0;   // ... with the outputs sized before the survivor count is known, for this many rows (0: the scan is waited for)
+    uint64_t mask_signature = 0;
+    // groups[0]: the first pass's columns (empty on the mask path); the later groups are compacted at its offsets, or run passes of their own
+    std::vector<std::vector<uint32_t>> groups, group_pos;
+};
+static GroupPlan plan_groups(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, const rv_term *terms, uint32_t nterms, rv_null_policy policy,
+                             const uint32_t *proj, uint32_t nproj, const ExprInfo *ex, const BatchReq *req, const AfterLaunch *after_launch,
+                             const RangeOffsets *ranges) {
+    GroupPlan p;
     // how much of the budget do the predicate columns take?
     std::vector<char> pred_value(ncols, 0);
     int pred_vals = 0;
@@ -177,9 +148,6 @@ uint64_t filter_by_groups(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t n
                 pred_value[c] = 1;
                 ++pred_vals;
             }
-    // greedy grouping of the projection list
-    std::vector<std::vector<uint32_t>> groups(1);
-    std::vector<std::vector<uint32_t>> group_pos(1);
     auto cost_of = [&](const std::vector<uint32_t> &g, bool with_pred, int &vals, int &bits) {
         vals = with_pred ? pred_vals : 0;
         bits = 0;
@@ -201,10 +169,10 @@ uint64_t filter_by_groups(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t n
     // has no warm-up call); should the pass then keep more than 55 % of the rows, or its offsets be unusable, the deferred groups run
     // as passes of their own, as before.
     bool defer_plain = false;
-    const uint64_t n_rows = ncols ? cols[0]->length : 0;
+    p.n_rows = ncols ? cols[0]->length : 0;
     // (a window of RecordBatches -- `req` -- takes it as well since round 5: the pass still counts the survivors of every batch, the
     // null counts per output batch are taken from the compacted outputs whoever wrote them)
-    if (ctx->opt_groups_by_ranges >= 0 && n_rows >= rvt::kRangesFromRows && nterms >= 1 && nterms <= static_cast<uint32_t>(rvk::kMaxTerms)) {
+    if (ctx->opt_groups_by_ranges >= 0 && p.n_rows >= rvt::kRangesFromRows && nterms >= 1 && nterms <= static_cast<uint32_t>(rvk::kMaxTerms)) {
         const double kept = expected_selectivity(ctx, cols, ncols, terms, nterms, policy, ex);  // (a first call over a big table: the sample, now)
         defer_plain = kept >= 0.0 && kept <= rvt::kDeferPlainUpTo;  // (tools/wide_ab.py sweep: 10-15 % faster at 10 and 20 % kept, a wash from 30 % on)
     }
@@ -212,349 +180,451 @@ uint64_t filter_by_groups(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t n
     // NULLABLE columns the predicate does not read are left to it at every selectivity: the passes that carry columns with output
     // bitmaps are the weakest launches there are (direct kernel with bitmaps 3.5 TB/s; tools/wide_ab.py nullable always sweep, 2e8
     // rows, kept 30 / 50 / 84 %: three columns 1.59 / 1.77 / 2.05 -> 1.14 / 1.30 / 1.63 ms, nine 4.24 / 5.20 / 6.22 -> 3.71 / 4.33 / 5.08)
-    const bool defer_nullable_always = ctx->opt_groups_by_ranges >= 0 && !after_launch && n_rows >= rvt::kRangesFromRows;
+    const bool defer_nullable_always = ctx->opt_groups_by_ranges >= 0 && !after_launch && p.n_rows >= rvt::kRangesFromRows;
     // A predicate that is ONE Boolean column (`mask is true`: RecordBatch::filter, the reference's streaming filter) over a big table,
     // sparse or with nullable columns: no chained pass at all -- mask_select_kernel + a scan of its counts stand in for it.
     // A WINDOW of RecordBatches (`req`: rv_filter_project_chunked / _batches, the reference's streaming filter at its 1024-row batches,
     // stream.rs:136-158) takes it too when a batch is a whole number of 1024-row ranges: the counts mask_select_kernel leaves per 1024
     // rows ARE the per-batch survivor counts.  String / Boolean columns projected next to the value columns (`after_launch`, `ranges`)
     // are queued at the scan's offsets once the value columns are on their way.
-    bool mask_path = false;
-    if (ctx->opt_groups_by_ranges >= 0 && (!req || (req->counts && req->chunk_rows % 1024 == 0)) && !ex && nterms == 1 && terms[0].op == RV_IS_TRUE && policy == RV_NULL_DROPS &&
-        terms[0].column < ncols && cols[terms[0].column]->dtype == RV_BOOLEAN && (n_rows >= rvt::kRangesFromRows || (ctx->opt_groups_by_ranges == 1 && n_rows > 0)) &&
+    if (mask_shape(ctx, cols, ncols, terms, nterms, policy, ex != nullptr, req ? req->chunk_rows : 0) && (!req || req->counts) &&
         (nproj >= 1 || (after_launch && ranges))) {
-        mask_path = true;
-        bool any_plain = false;
-        for (uint32_t j = 0; j < nproj && mask_path; ++j) {
-            mask_path = proj[j] < ncols && is_value_type(cols[proj[j]]->dtype);
-            any_plain = any_plain || (mask_path && !cols[proj[j]]->validity);
+        p.mask_path = true;
+        bool any_plain = false, any_nullable = false;
+        for (uint32_t j = 0; j < nproj && p.mask_path; ++j) {
+            p.mask_path = is_value_type(cols[proj[j]]->dtype);
+            any_plain = any_plain || (p.mask_path && !cols[proj[j]]->validity);
+            any_nullable = any_nullable || cols[proj[j]]->validity;
         }
         // plain columns of a dense selection are better off in the direct kernel's pass (known from the predicate's last run only)
-        const double kept = ctx->seen_selectivity(predicate_signature(cols, ncols, terms, nterms, policy, ex));
-        if (mask_path && any_plain && kept > rvt::kMaskPathPlainUpTo && ctx->opt_groups_by_ranges != 1) mask_path = false;
-        if (mask_path) defer_plain = true;
+        p.mask_signature = predicate_signature(cols, ncols, terms, nterms, policy, ex);
+        const double kept = ctx->seen_selectivity(p.mask_signature);
+        if (p.mask_path && any_plain && kept > rvt::kMaskPathPlainUpTo && ctx->opt_groups_by_ranges != 1) p.mask_path = false;
+        if (p.mask_path) defer_plain = true;
+        // The outputs are sized by the survivor count, which the scan delivers -- a host round trip with the device idle (20-30 us of
+        // a 0.4 ms window).  A predicate the context has run over these buffers before (a stream's windows) sizes them from what it
+        // kept then, queues the columns' compaction right behind the scan, and reads the count at the end; more survivors than that:
+        // the late groups run again, decided from the exact count.  Plain columns only (a nullable one's null count shares the control
+        // block with the scan's total; String / Boolean columns are sized by the exact count).
+        if (p.mask_path && !after_launch && nproj >= 1 && !any_nullable && ctx->opt_out_sizing >= 0 && kept >= 0.0 && kept <= rvt::kMaskPathAssumeUpTo &&
+            p.n_rows >= rvt::kRangesFromRows)
+            p.mask_assumed = assumed_rows(p.n_rows, kept);
     }
+    // greedy grouping of the projection list
+    p.groups.resize(1);
+    p.group_pos.resize(1);
     std::vector<uint32_t> late, late_pos;
     for (uint32_t j = 0; j < nproj; ++j) {
-        require(proj[j] < ncols, RV_ERR_INVALID_ARG, fmt("projection %u references column %u of %u", j, proj[j], ncols));
         const rv_dcolumn *pc = cols[proj[j]];
-        if ((defer_plain || (defer_nullable_always && pc->validity)) && is_value_type(pc->dtype) && (!pc->validity || !after_launch || mask_path) && !pred_value[proj[j]]) {
+        if ((defer_plain || (defer_nullable_always && pc->validity)) && is_value_type(pc->dtype) && (!pc->validity || !after_launch || p.mask_path) && !pred_value[proj[j]]) {
             late.push_back(proj[j]);
             late_pos.push_back(j);
             continue;
         }
-        auto trial = groups.back();
+        auto trial = p.groups.back();
         trial.push_back(proj[j]);
         int vals, bits;
-        cost_of(trial, groups.size() == 1, vals, bits);
+        cost_of(trial, p.groups.size() == 1, vals, bits);
         if (vals > rvk::kMaxValueCols || bits > rvk::kMaxBitStreams) {
-            groups.emplace_back();
-            group_pos.emplace_back();
+            p.groups.emplace_back();
+            p.group_pos.emplace_back();
         }
-        groups.back().push_back(proj[j]);
-        group_pos.back().push_back(j);
+        p.groups.back().push_back(proj[j]);
+        p.group_pos.back().push_back(j);
     }
     // (the first group may be empty: the pass then only evaluates the predicate -- selection bitmap, wave offsets, survivor count -- as
     // rv_eval_predicate's does.  Not when the predicate reads no 8-byte column at all (RecordBatch::filter by a BooleanArray): a pass
     // over nothing but a bitmap still walks every tile through the chain, 0.60 ms per 5e8 rows -- as long as one that carries a
     // column; measured: b is true -> [x] 1.25 ms that way against 0.79)
-    if (pred_vals == 0 && !mask_path && groups.size() == 1 && groups[0].empty() && !late.empty()) {
-        groups[0].push_back(late.front());
-        group_pos[0].push_back(late_pos.front());
+    if (pred_vals == 0 && !p.mask_path && p.groups.size() == 1 && p.groups[0].empty() && !late.empty()) {
+        p.groups[0].push_back(late.front());
+        p.group_pos[0].push_back(late_pos.front());
         late.erase(late.begin());
         late_pos.erase(late_pos.begin());
     }
     for (size_t k = 0; k < late.size(); ++k) {
         if (k % rvk::kRangesMaxCols == 0) {
-            groups.emplace_back();
-            group_pos.emplace_back();
+            p.groups.emplace_back();
+            p.group_pos.emplace_back();
         }
-        groups.back().push_back(late[k]);
-        group_pos.back().push_back(late_pos[k]);
+        p.groups.back().push_back(late[k]);
+        p.group_pos.back().push_back(late_pos[k]);
     }
-    const bool multi = groups.size() > 1;
-    rv_dcolumn *sel = nullptr;
-    std::vector<rv_dcolumn *> tmp(nproj ? nproj : 1, nullptr);
+    return p;
+}
+
+// The plan run: the first pass (the mask select, or the segmented / fused pass), the late groups at its offsets or as passes of their own,
+// the null counts of late nullable columns.  `rows` is always the exact survivor count.
+struct GroupRun {
+    rv_ctx *ctx;
+    const rv_dcolumn *const *cols;
+    const GroupPlan &plan;
+    const AfterLaunch *after_launch;
+    std::vector<std::unique_ptr<rv_dcolumn>> outs{};  // one per projected column, handed to the caller at the end
+    std::unique_ptr<rv_dcolumn> sel{};
     uint64_t rows = 0;
-    try {
-        if (req && multi) req->sel_optional = false;  // later groups read the selection bitmap
-        RangeOffsets own_ranges;  // the first pass's wave offsets: the later groups are compacted at them (ranges_kernel.hpp)
-        RangeOffsets *first_ranges = ranges ? ranges : (multi ? &own_ranges : nullptr);
-        const uint64_t reruns_before = ctx->overflow_reruns;
-        // kernels queued behind the pass for the deferred groups: the call returns when they have run (a caller on another stream --
-        // rv_device_ptrs, rv_ctx_stream -- sees finished columns, a device fault surfaces in THIS call, and `sel` / the wave offsets go
-        // back to the pool behind their last reader); with option profile_kernels their device time counts as the call's
-        bool late_launched = false;
-        auto before_late_launch = [&] {
-            if (!late_launched && ctx->opt_profile) RV_HIP(hipEventRecord(ctx->evk0, ctx->stream));
-            late_launched = true;
-        };
-        auto after_late_launches = [&] {
-            if (!late_launched) return;
-            if (ctx->opt_profile) RV_HIP(hipEventRecord(ctx->evk1, ctx->stream));
-            RV_HIP(hipStreamSynchronize(ctx->stream));
-            if (ctx->opt_profile) {
-                float ms = 0.f;
-                RV_HIP(hipEventElapsedTime(&ms, ctx->evk0, ctx->evk1));
-                ctx->kernel_ms += ms;
-            }
-            late_launched = false;
-        };
-        bool mask_ran = false;
-        uint64_t rows_assumed = 0;  // the mask path's outputs were sized before its survivor count was known: for this many rows
-        if (mask_path && groups[0].empty()) {
-            const rv_dcolumn *mask = cols[terms[0].column];
-            const uint64_t nwords = (n_rows + 63) / 64, nranges = (n_rows + 1023) / 1024;
-            auto s = std::make_unique<rv_dcolumn>();
-            s->dtype = RV_BOOLEAN;
-            s->length = n_rows;
-            s->null_count = 0;
-            s->values = pool_alloc(ctx, std::max<size_t>(bitmap_words_bytes(n_rows) + 8, 16));
-            DevBufRef counts = pool_alloc(ctx, nranges * 4 + 16);
-            rvk::MaskSelect q{};
-            q.values = static_cast<const uint8_t *>(mask->values->ptr);
-            q.values_bytes = mask->values->bytes;
-            q.validity = mask->validity ? static_cast<const uint8_t *>(mask->validity->ptr) : nullptr;
-            q.validity_bytes = mask->validity ? mask->validity->bytes : 0;
-            q.offset = mask->offset;
-            q.n = n_rows;
-            q.sel = static_cast<uint64_t *>(s->values->ptr);
-            q.counts = static_cast<uint32_t *>(counts->ptr);
-            // the reference's 1024-row batches ARE the ranges: their counts go straight to the caller's (pinned) array, 8 bytes per batch
-            q.batch_counts = (req && req->counts && req->chunk_rows == 1024) ? req->counts : nullptr;
-            before_late_launch();  // (option profile_kernels: the mask path's kernels -- selection, scan, compaction -- are the call's device time)
-            hipLaunchKernelGGL(rvk::mask_select_kernel, dim3(static_cast<uint32_t>((nwords + 255) / 256)), dim3(256), 0, ctx->stream, q);
-            RV_HIP(hipGetLastError());
-            if (req && req->counts && req->chunk_rows != 1024) {  // the survivors of every batch: sums of the counts per 1024 rows, written where the caller reads them
-                const uint64_t per_batch = req->chunk_rows / 1024;
-                const uint64_t threads = per_batch < 32 ? req->nb : (per_batch < 4096 ? req->nb * 64 : req->nb * 256);
-                const dim3 cgrid(static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>((threads + 255) / 256, static_cast<uint64_t>(ctx->props.multiProcessorCount) * 8))));
-                hipLaunchKernelGGL(rvk::batch_counts_from_waves, cgrid, dim3(256), 0, ctx->stream, static_cast<const uint32_t *>(q.counts), nranges, per_batch, req->nb, req->counts);
-                RV_HIP(hipGetLastError());
-            }
-            if (req && req->counts) {
-                req->counted = true;
-                ctx->batch_counts_in_pass += 1;
-            }
-            own_ranges.range_rows = 1024;
-            // The outputs are sized by the survivor count, which the scan delivers -- a host round trip with the device idle (20-30 us of
-            // a 0.4 ms window).  A predicate the context has run over these buffers before (a stream's windows) sizes them from what it
-            // kept then (x 1.2 + 2 % of the rows), queues the columns' compaction right behind the scan, and reads the count at the end;
-            // more survivors than that: the compaction runs once more with outputs of the exact size.  Plain columns only (a nullable
-            // one's null count shares the control block with the scan's total; String / Boolean columns are sized by the exact count).
-            const double known = ctx->seen_selectivity(predicate_signature(cols, ncols, terms, nterms, policy, ex));
-            bool all_plain = !after_launch && groups.size() > 1 && ctx->opt_out_sizing >= 0;
-            for (size_t g = 1; g < groups.size(); ++g)
-                for (uint32_t c : groups[g]) all_plain = all_plain && is_value_type(cols[c]->dtype) && !cols[c]->validity;
-            if (all_plain && known >= 0.0 && known <= rvt::kMaskPathAssumeUpTo && n_rows >= rvt::kRangesFromRows) {
-                rows_assumed = std::min<uint64_t>(n_rows, static_cast<uint64_t>(static_cast<double>(n_rows) * (known * rvt::kOutSizingFactor + rvt::kOutSizingSlack)) + 4096);
-                device_exclusive_scan(ctx, counts->ptr, nranges, own_ranges.offsets, false, false);  // (queued; the total stays in the control block)
-                rows = rows_assumed;
-            } else {
-                rows = device_exclusive_scan(ctx, counts->ptr, nranges, own_ranges.offsets, false, true);  // (waits: the outputs are sized by it)
-            }
-            own_ranges.out_capacity = rows;
-            own_ranges.expected_selectivity = n_rows ? static_cast<double>(rows) / static_cast<double>(n_rows) : 0.0;
-            first_ranges = &own_ranges;
-            if (ranges) *ranges = own_ranges;  // the caller's String / Boolean columns are compacted at the same offsets
-            mask_ran = true;
-            sel = s.release();
-            if (!rows_assumed) ctx->remember_selectivity(predicate_signature(cols, ncols, terms, nterms, policy, ex), own_ranges.expected_selectivity);
-            ctx->last_kernel = "mask_select_kernel";
-        } else {
-            // (a table sorted on the predicate's column, a query of one plain pass: stretch by stretch, fused_launch.hip)
-            const bool simple = !multi && !out_selection && !req && !after_launch && !first_ranges && !groups[0].empty();
-            if (!simple || !run_segmented_pass(ctx, cols, ncols, terms, nterms, policy, groups[0].data(), static_cast<uint32_t>(groups[0].size()), tmp.data(), ex, &rows))
-            rows = run_fused_pass(ctx, cols, ncols, terms, nterms, policy, groups[0].data(), static_cast<uint32_t>(groups[0].size()),
-                                  tmp.data(), (multi || out_selection) ? &sel : nullptr, ex, req, after_launch, first_ranges);
+    RangeOffsets own_ranges{};  // the first pass's wave offsets: the later groups are compacted at them (ranges_kernel.hpp)
+    RangeOffsets *first_ranges = nullptr;
+    bool offsets_there = false;
+    // kernels queued behind the pass for the deferred groups: the call returns when they have run (a caller on another stream --
+    // rv_device_ptrs, rv_ctx_stream -- sees finished columns, a device fault surfaces in THIS call, and `sel` / the wave offsets go
+    // back to the pool behind their last reader); with option profile_kernels their device time counts as the call's
+    bool late_launched = false;
+    // nullable columns among them: their validity bits by bits_compact_kernel at the same offsets, their null counts out of the
+    // context's control block (eight counters per read-back) -- not next to a caller's own launches on that block (after_launch)
+    struct LateNull {
+        const rv_dcolumn *src;
+        rv_dcolumn *col;
+        int slot;
+    };
+    std::vector<LateNull> late_nulls{};
+    Ctrl *late_ctrl = nullptr;
+
+    void start_late() {
+        if (!late_launched && ctx->opt_profile) RV_HIP(hipEventRecord(ctx->evk0, ctx->stream));
+        late_launched = true;
+    }
+    void wait_late() {
+        if (!late_launched) return;
+        if (ctx->opt_profile) RV_HIP(hipEventRecord(ctx->evk1, ctx->stream));
+        RV_HIP(hipStreamSynchronize(ctx->stream));
+        if (ctx->opt_profile) {
+            float ms = 0.f;
+            RV_HIP(hipEventElapsedTime(&ms, ctx->evk0, ctx->evk1));
+            ctx->kernel_ms += ms;
         }
-        for (size_t k = 0; k < groups[0].size(); ++k) out[group_pos[0][k]] = tmp[k];
-        // (offsets of a pass that overflowed its outputs and was re-run are not the re-run's: those groups take the pass path)
-        // (and up to 55 % of the rows surviving -- tools/wide_ab.py, nine columns of 2e8 rows, groups beyond the first: 2.47 against 2.88 ms
-        // at 10 %, 3.71 / 3.83 at 50 %, 4.67 / 4.46 at 84 %: there the direct kernel's whole-line stores win; option groups_by_ranges = 1: always)
-        const bool offsets_there = first_ranges && first_ranges->offsets && ctx->overflow_reruns == reruns_before && ctx->opt_groups_by_ranges >= 0 && sel && sel->length > 0;
-        // (a mask pass with outputs of an ASSUMED size: `rows` is their capacity, not a count -- they were sized for the compaction at
-        // the scan's offsets, so the late groups take it; a re-run with outputs of the exact size decides again from the count)
-        bool sparse_enough = ctx->opt_groups_by_ranges == 1 || rows_assumed || (sel && rows * rvt::kRangesSparseDen <= sel->length * rvt::kRangesSparseNum);
-        // nullable columns among them: their validity bits by bits_compact_kernel at the same offsets, their null counts out of the
-        // context's control block (eight counters per read-back) -- not next to a caller's own launches on that block (after_launch)
-        struct LateNulls {
-            rv_dcolumn *col;
-            int slot;
-        };
-        std::vector<LateNulls> late_nulls;
-        Ctrl *late_ctrl = nullptr;
-        auto finish_late_nulls = [&]() {
-            if (late_nulls.empty()) return;
-            const Ctrl fetched = *fetch_ctrl(ctx);
-            for (const LateNulls &q : late_nulls) {
-                q.col->null_count = static_cast<int64_t>(rows - fetched.valid_pop[q.slot]);
-                if (q.col->null_count == 0) q.col->validity.reset();  // the builder drops the bitmap when no null survived (primitive.rs:185-197)
+        late_launched = false;
+    }
+    void finish_late_nulls() {
+        if (late_nulls.empty()) return;
+        const Ctrl fetched = *fetch_ctrl(ctx);
+        for (const LateNull &q : late_nulls) {
+            q.col->null_count = static_cast<int64_t>(rows - fetched.valid_pop[q.slot]);
+            if (q.col->null_count == 0) q.col->validity.reset();  // the builder drops the bitmap when no null survived (primitive.rs:185-197)
+        }
+        late_nulls.clear();
+        late_ctrl = nullptr;
+    }
+
+    // the first pass, chained: segmented (a table sorted on the predicate's column, a query of one plain pass: stretch by stretch,
+    // fused_launch.hip) or fused
+    void fused_first(const rv_term *terms, uint32_t nterms, rv_null_policy policy, uint32_t ncols, const ExprInfo *ex, BatchReq *req, bool want_sel,
+                     RangeOffsets *ranges) {
+        const bool multi = plan.groups.size() > 1;
+        const std::vector<uint32_t> &g0 = plan.groups[0];
+        first_ranges = ranges ? ranges : (multi ? &own_ranges : nullptr);
+        std::vector<rv_dcolumn *> tmp(g0.size() ? g0.size() : 1, nullptr);
+        rv_dcolumn *s = nullptr;
+        const bool simple = !multi && !want_sel && !req && !after_launch && !first_ranges && !g0.empty();
+        if (!simple || !run_segmented_pass(ctx, cols, ncols, terms, nterms, policy, g0.data(), static_cast<uint32_t>(g0.size()), tmp.data(), ex, &rows))
+            rows = run_fused_pass(ctx, cols, ncols, terms, nterms, policy, g0.data(), static_cast<uint32_t>(g0.size()), tmp.data(), (multi || want_sel) ? &s : nullptr,
+                                  ex, req, after_launch, first_ranges);
+        sel.reset(s);
+        for (size_t k = 0; k < g0.size(); ++k) outs[plan.group_pos[0][k]].reset(tmp[k]);
+    }
+    // the first pass, a mask select: its count waited for, or (plan.mask_assumed) the columns compacted into outputs of the assumed
+    // size right behind the scan, the count left in the context's control block (assumed_count)
+    void mask_first(const rv_dcolumn *mask, const uint32_t *proj, uint32_t nproj, BatchReq *req, RangeOffsets *ranges) {
+        MaskWindow w;
+        late_launched = true;  // mask_select_begin starts the clock (option profile_kernels)
+        if (plan.mask_assumed) {
+            w.assumed = plan.mask_assumed;
+            mask_select_begin(ctx, mask, req, MaskTotal::kInContext, w);
+            ctx->last_kernel = "mask_select_kernel";
+            std::vector<rv_dcolumn *> o(nproj);
+            for (uint32_t j = 0; j < nproj; ++j) {
+                outs[j] = new_value_column(ctx, cols[proj[j]]->dtype, w.assumed);
+                o[j] = outs[j].get();
+                w.src.push_back(cols[proj[j]]);
             }
-            late_nulls.clear();
-            late_ctrl = nullptr;
-        };
-        auto late_groups = [&] {
-        for (size_t g = 1; g < groups.size(); ++g) {
-            bool plain = offsets_there && groups[g].size() <= static_cast<size_t>(rvk::kRangesMaxCols);
+            mask_compact(ctx, w, w.assumed, o.data());
+        } else {
+            rows = mask_select_begin(ctx, mask, req, MaskTotal::kWait, w);
+            w.ranges.out_capacity = rows;
+            w.ranges.expected_selectivity = w.n ? static_cast<double>(rows) / static_cast<double>(w.n) : 0.0;
+            if (ranges) *ranges = w.ranges;  // the caller's String / Boolean columns are compacted at the same offsets
+            ctx->remember_selectivity(plan.mask_signature, w.ranges.expected_selectivity);
+            ctx->last_kernel = "mask_select_kernel";
+        }
+        own_ranges = w.ranges;
+        first_ranges = &own_ranges;
+        sel = std::move(w.sel);
+    }
+    // the count the scan left in the control block: fits what the outputs were sized for, or the late groups run again, decided from it
+    void assumed_count() {
+        wait_late();
+        rows = fetch_ctrl(ctx)->pops[0];
+        if (rows <= plan.mask_assumed) {
+            for (auto &o : outs) o->length = rows;
+        } else {
+            for (auto &o : outs) o.reset();
+            ctx->overflow_reruns += 1;
+            late_groups();
+        }
+        ctx->remember_selectivity(plan.mask_signature, plan.n_rows ? static_cast<double>(rows) / static_cast<double>(plan.n_rows) : 0.0);
+    }
+
+    void late_groups() {
+        // (up to 55 % of the rows surviving -- tools/wide_ab.py, nine columns of 2e8 rows, groups beyond the first: 2.47 against 2.88 ms
+        // at 10 %, 3.71 / 3.83 at 50 %, 4.67 / 4.46 at 84 %: there the direct kernel's whole-line stores win; option groups_by_ranges = 1: always)
+        const bool sparse_enough = ctx->opt_groups_by_ranges == 1 || (sel && rows * rvt::kRangesSparseDen <= sel->length * rvt::kRangesSparseNum);
+        for (size_t g = 1; g < plan.groups.size(); ++g) {
+            bool plain = offsets_there && plan.groups[g].size() <= static_cast<size_t>(rvk::kRangesMaxCols);
             bool any_nulls = false;
-            for (uint32_t c : groups[g]) {
-                plain = plain && is_value_type(cols[c]->dtype) && (!cols[c]->validity || mask_ran || !after_launch);
+            for (uint32_t c : plan.groups[g]) {
+                plain = plain && is_value_type(cols[c]->dtype) && (!cols[c]->validity || plan.mask_path || !after_launch);
                 any_nulls = any_nulls || cols[c]->validity != nullptr;
             }
             // a dense selection: plain columns go through the direct kernel (5 % ahead); NULLABLE ones stay here -- the pass by a
             // Boolean predicate has no dense geometry for columns that keep nulls, and fell back to the default one + fused_redo_tiles
             // (nine nullable columns of 2e8 rows at 84 %: 18.4 ms)
-            if (plain && (sparse_enough || any_nulls)) {
-                rvk::RangesCompact q{};
-                q.sel = static_cast<const uint64_t *>(sel->values->ptr);
-                q.nwords = (sel->length + 63) / 64;
-                q.n = sel->length;
-                q.range_offsets = static_cast<const uint64_t *>(first_ranges->offsets->ptr);
-                q.range_rows = first_ranges->range_rows;
-                q.out_capacity = rows;
-                struct GroupNull {
-                    const rv_dcolumn *src;
-                    rv_dcolumn *col;
-                    int slot;
-                };
-                std::vector<GroupNull> group_nulls;
-                // (a group's nullable columns share one read-back of the control block: make room for all of them first)
-                size_t group_nullable = 0;
-                for (uint32_t c : groups[g]) group_nullable += cols[c]->validity && rows ? 1 : 0;
-                if (late_nulls.size() + group_nullable > 8) finish_late_nulls();
-                before_late_launch();
-                for (size_t k = 0; k < groups[g].size(); ++k) {
-                    const rv_dcolumn *src = cols[groups[g][k]];
-                    auto o = std::make_unique<rv_dcolumn>();
-                    o->dtype = src->dtype;
-                    o->length = rows;
-                    o->null_count = 0;
-                    o->values = pool_alloc(ctx, std::max<size_t>(elem_bytes(src->dtype, rows), 8));
-                    q.in[k] = static_cast<const char *>(src->values->ptr) + src->offset * 8;
-                    q.out[k] = static_cast<uint64_t *>(o->values->ptr);
-                    if (src->validity && rows) {
-                        q.validity[k] = static_cast<const uint8_t *>(src->validity->ptr);
-                        q.validity_bytes[k] = src->validity->bytes;
-                        q.bit_offset[k] = src->offset;
-                        if (!late_ctrl) late_ctrl = prepare_ctrl(ctx, 0);
-                        const int slot = static_cast<int>(late_nulls.size());
-                        const size_t wb = zeroed_bitmap_bytes(rows);
-                        o->validity = pool_alloc(ctx, wb);
-                        RV_HIP(hipMemsetAsync(o->validity->ptr, 0, wb, ctx->stream));
-                        group_nulls.push_back(GroupNull{src, o.get(), slot});
-                        late_nulls.push_back(LateNulls{o.get(), slot});
-                    }
-                    out[group_pos[g][k]] = o.release();
-                }
-                // the validity bits of the group's nullable columns, two columns per launch where they share their bit offset
-                for (size_t a = 0; a < group_nulls.size();) {
-                    const GroupNull &x0 = group_nulls[a];
-                    const bool two = a + 1 < group_nulls.size() && group_nulls[a + 1].src->offset == x0.src->offset;
-                    rvk::BitsCompact b{};
-                    b.sel = q.sel;
-                    b.nwords = q.nwords;
-                    b.offset = x0.src->offset;
-                    b.range_offsets = q.range_offsets;
-                    b.range_rows = q.range_rows;
-                    b.out_capacity = rows;
-                    b.src = static_cast<const uint8_t *>(x0.src->validity->ptr);
-                    b.src_bytes = x0.src->validity->bytes;
-                    b.out = static_cast<uint64_t *>(x0.col->validity->ptr);
-                    b.pop = striped(ctx, &late_ctrl->valid_pop[x0.slot]);
-                    if (two) {
-                        const GroupNull &x1 = group_nulls[a + 1];
-                        b.src2 = static_cast<const uint8_t *>(x1.src->validity->ptr);
-                        b.src2_bytes = x1.src->validity->bytes;
-                        b.out2 = static_cast<uint64_t *>(x1.col->validity->ptr);
-                        b.pop2 = striped(ctx, &late_ctrl->valid_pop[x1.slot]);
-                    }
-                    const dim3 bgrid(static_cast<uint32_t>(std::min<uint64_t>((q.nwords + 255) / 256, static_cast<uint64_t>(ctx->props.multiProcessorCount) * 8)));
-                    hipLaunchKernelGGL(rvk::bits_compact_kernel, bgrid, dim3(256), 0, ctx->stream, b);
-                    RV_HIP(hipGetLastError());
-                    a += two ? 2 : 1;
-                }
-                if (rows) {
-                    const dim3 grid(static_cast<uint32_t>((q.nwords + 63) / 64)), block(256);  // a wave per 16 words, four per workgroup
-                    const int pick = static_cast<int>(groups[g].size()) * 2 + (any_nulls ? 1 : 0);
-                    switch (pick) {
-                        case 2: hipLaunchKernelGGL((rvk::compact_ranges_kernel<1, false>), grid, block, 0, ctx->stream, q); break;
-                        case 3: hipLaunchKernelGGL((rvk::compact_ranges_kernel<1, true>), grid, block, 0, ctx->stream, q); break;
-                        case 4: hipLaunchKernelGGL((rvk::compact_ranges_kernel<2, false>), grid, block, 0, ctx->stream, q); break;
-                        case 5: hipLaunchKernelGGL((rvk::compact_ranges_kernel<2, true>), grid, block, 0, ctx->stream, q); break;
-                        case 6: hipLaunchKernelGGL((rvk::compact_ranges_kernel<3, false>), grid, block, 0, ctx->stream, q); break;
-                        case 7: hipLaunchKernelGGL((rvk::compact_ranges_kernel<3, true>), grid, block, 0, ctx->stream, q); break;
-                        case 8: hipLaunchKernelGGL((rvk::compact_ranges_kernel<4, false>), grid, block, 0, ctx->stream, q); break;
-                        default: hipLaunchKernelGGL((rvk::compact_ranges_kernel<4, true>), grid, block, 0, ctx->stream, q); break;
-                    }
-                    RV_HIP(hipGetLastError());
-                    ctx->last_kernel = fmt("compact_ranges_kernel<%d>", static_cast<int>(groups[g].size()));
-                }
-                continue;
-            }
-            // later groups: predicate == the materialised selection bitmap
-            after_late_launches();
-            finish_late_nulls();
-            std::vector<const rv_dcolumn *> gc;
-            std::vector<uint32_t> gp;
-            for (uint32_t c : groups[g]) {
-                gp.push_back(static_cast<uint32_t>(gc.size()));
-                gc.push_back(cols[c]);
-            }
-            rv_term st{};
-            st.column = static_cast<uint32_t>(gc.size());
-            st.op = RV_IS_TRUE;
-            gc.push_back(sel);
-            std::vector<rv_dcolumn *> gout(gp.size(), nullptr);
-            const uint64_t r2 = run_fused_pass(ctx, gc.data(), static_cast<uint32_t>(gc.size()), &st, 1, RV_NULL_DROPS, gp.data(),
-                                               static_cast<uint32_t>(gp.size()), gout.data(), nullptr);
-            for (size_t k = 0; k < gout.size(); ++k) out[group_pos[g][k]] = gout[k];
-            require(r2 == rows, RV_ERR_INTERNAL, "group passes disagree on the number of surviving rows");
+            if (plain && (sparse_enough || any_nulls)) compact_late_group(g, any_nulls);
+            else late_group_pass(g);
         }
-        };
-        late_groups();
-        if (rows_assumed) {  // the count the scan left in the control block: fits what the outputs were sized for, or the compaction runs again
-            after_late_launches();
-            const uint64_t counted = fetch_ctrl(ctx)->pops[0];
-            const bool fits = counted <= rows_assumed;
-            rows = counted;
-            own_ranges.out_capacity = rows;
-            for (size_t g = 1; g < groups.size(); ++g)
-                for (size_t k = 0; k < groups[g].size(); ++k) {
-                    rv_dcolumn *&o = out[group_pos[g][k]];
-                    if (fits) {
-                        if (o) o->length = rows;
-                    } else {
-                        delete o;
-                        o = nullptr;
-                    }
-                }
-            if (!fits) {
-                ctx->overflow_reruns += 1;
-                sparse_enough = ctx->opt_groups_by_ranges == 1 || rows * rvt::kRangesSparseDen <= sel->length * rvt::kRangesSparseNum;
-                late_groups();
-            }
-            ctx->remember_selectivity(predicate_signature(cols, ncols, terms, nterms, policy, ex), n_rows ? static_cast<double>(rows) / static_cast<double>(n_rows) : 0.0);
-        }
-        {
-            const bool waits = late_launched;
-            after_late_launches();
-            if (mask_ran && req && req->counted && !waits) RV_HIP(hipStreamSynchronize(ctx->stream));  // the per-batch counts are the caller's to read on return
-        }
-        finish_late_nulls();
-        // the caller's launches behind "the pass" (String / Boolean columns at the scan's offsets): the value columns' null counts
-        // have been read, so the context's one control block is theirs now
-        if (mask_ran && after_launch && *after_launch) (*after_launch)(sel);
-    } catch (...) {
-        for (uint32_t j = 0; j < nproj; ++j) {
-            delete out[j];
-            out[j] = nullptr;
-        }
-        delete sel;
-        throw;
     }
-    if (out_selection) *out_selection = sel;
-    else delete sel;
+    void compact_late_group(size_t g, bool any_nulls) {
+        const std::vector<uint32_t> &group = plan.groups[g];
+        rvk::RangesCompact q{};
+        q.sel = static_cast<const uint64_t *>(sel->values->ptr);
+        q.nwords = (sel->length + 63) / 64;
+        q.n = sel->length;
+        q.range_offsets = static_cast<const uint64_t *>(first_ranges->offsets->ptr);
+        q.range_rows = first_ranges->range_rows;
+        q.out_capacity = rows;
+        // (a group's nullable columns share one read-back of the control block: make room for all of them first)
+        size_t group_nullable = 0;
+        for (uint32_t c : group) group_nullable += cols[c]->validity && rows ? 1 : 0;
+        if (late_nulls.size() + group_nullable > 8) finish_late_nulls();
+        const size_t first_null = late_nulls.size();  // the group's own: late_nulls[first_null ..)
+        start_late();
+        for (size_t k = 0; k < group.size(); ++k) {
+            const rv_dcolumn *src = cols[group[k]];
+            std::unique_ptr<rv_dcolumn> &o = outs[plan.group_pos[g][k]];
+            o = new_value_column(ctx, src->dtype, rows);
+            q.in[k] = static_cast<const char *>(src->values->ptr) + src->offset * 8;
+            q.out[k] = static_cast<uint64_t *>(o->values->ptr);
+            if (src->validity && rows) {
+                q.validity[k] = static_cast<const uint8_t *>(src->validity->ptr);
+                q.validity_bytes[k] = src->validity->bytes;
+                q.bit_offset[k] = src->offset;
+                if (!late_ctrl) late_ctrl = prepare_ctrl(ctx, 0);
+                const int slot = static_cast<int>(late_nulls.size());
+                const size_t wb = zeroed_bitmap_bytes(rows);
+                o->validity = pool_alloc(ctx, wb);
+                RV_HIP(hipMemsetAsync(o->validity->ptr, 0, wb, ctx->stream));
+                late_nulls.push_back(LateNull{src, o.get(), slot});
+            }
+        }
+        // the validity bits of the group's nullable columns, two columns per launch where they share their bit offset
+        for (size_t a = first_null; a < late_nulls.size();) {
+            const LateNull &x0 = late_nulls[a];
+            const bool two = a + 1 < late_nulls.size() && late_nulls[a + 1].src->offset == x0.src->offset;
+            rvk::BitsCompact b{};
+            b.sel = q.sel;
+            b.nwords = q.nwords;
+            b.offset = x0.src->offset;
+            b.range_offsets = q.range_offsets;
+            b.range_rows = q.range_rows;
+            b.out_capacity = rows;
+            b.src = static_cast<const uint8_t *>(x0.src->validity->ptr);
+            b.src_bytes = x0.src->validity->bytes;
+            b.out = static_cast<uint64_t *>(x0.col->validity->ptr);
+            b.pop = striped(ctx, &late_ctrl->valid_pop[x0.slot]);
+            if (two) {
+                const LateNull &x1 = late_nulls[a + 1];
+                b.src2 = static_cast<const uint8_t *>(x1.src->validity->ptr);
+                b.src2_bytes = x1.src->validity->bytes;
+                b.out2 = static_cast<uint64_t *>(x1.col->validity->ptr);
+                b.pop2 = striped(ctx, &late_ctrl->valid_pop[x1.slot]);
+            }
+            launch_bits_compact(ctx, b);
+            a += two ? 2 : 1;
+        }
+        if (rows) launch_compact_ranges(ctx, q, static_cast<int>(group.size()), any_nulls);
+    }
+    // a later group as a pass of its own: predicate == the materialised selection bitmap
+    void late_group_pass(size_t g) {
+        wait_late();
+        finish_late_nulls();
+        std::vector<const rv_dcolumn *> gc;
+        std::vector<uint32_t> gp;
+        for (uint32_t c : plan.groups[g]) {
+            gp.push_back(static_cast<uint32_t>(gc.size()));
+            gc.push_back(cols[c]);
+        }
+        rv_term st{};
+        st.column = static_cast<uint32_t>(gc.size());
+        st.op = RV_IS_TRUE;
+        gc.push_back(sel.get());
+        std::vector<rv_dcolumn *> gout(gp.size(), nullptr);
+        const uint64_t r2 = run_fused_pass(ctx, gc.data(), static_cast<uint32_t>(gc.size()), &st, 1, RV_NULL_DROPS, gp.data(),
+                                           static_cast<uint32_t>(gp.size()), gout.data(), nullptr);
+        for (size_t k = 0; k < gout.size(); ++k) outs[plan.group_pos[g][k]].reset(gout[k]);
+        require(r2 == rows, RV_ERR_INTERNAL, "group passes disagree on the number of surviving rows");
+    }
+};
+
+// The fixed-width (and, in lane form, Boolean) columns of a filter.  `after_launch` / `ranges`: the String / Boolean columns that
+// filter_by_groups produces from the selection bitmap, queued behind the pass at its offsets.
+static uint64_t filter_value_columns(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, const rv_term *terms, uint32_t nterms, rv_null_policy policy,
+                                     const uint32_t *proj, uint32_t nproj, rv_dcolumn **out, rv_dcolumn **out_selection, const ExprInfo *ex, BatchReq *req,
+                                     const AfterLaunch *after_launch, RangeOffsets *ranges) {
+    const GroupPlan plan = plan_groups(ctx, cols, ncols, terms, nterms, policy, proj, nproj, ex, req, after_launch, ranges);
+    GroupRun run{ctx, cols, plan, after_launch};
+    run.outs.resize(nproj);
+    if (req && plan.groups.size() > 1) req->sel_optional = false;  // later groups read the selection bitmap
+    const uint64_t reruns_before = ctx->overflow_reruns;
+    if (plan.mask_path) run.mask_first(cols[terms[0].column], proj, nproj, req, ranges);
+    else run.fused_first(terms, nterms, policy, ncols, ex, req, out_selection != nullptr, ranges);
+    // (offsets of a pass that overflowed its outputs and was re-run are not the re-run's: those groups take the pass path)
+    run.offsets_there = run.first_ranges && run.first_ranges->offsets && ctx->overflow_reruns == reruns_before && ctx->opt_groups_by_ranges >= 0 && run.sel &&
+                        run.sel->length > 0;
+    if (plan.mask_assumed) run.assumed_count();
+    else run.late_groups();
+    const bool waits = run.late_launched;
+    run.wait_late();
+    if (plan.mask_path && req && req->counted && !waits) RV_HIP(hipStreamSynchronize(ctx->stream));  // the per-batch counts are the caller's to read on return
+    run.finish_late_nulls();
+    // the caller's launches behind "the pass" (String / Boolean columns at the scan's offsets): the value columns' null counts
+    // have been read, so the context's one control block is theirs now
+    if (plan.mask_path && after_launch && *after_launch) (*after_launch)(run.sel.get());
+    for (uint32_t j = 0; j < nproj; ++j) out[j] = run.outs[j].release();
+    if (out_selection) *out_selection = run.sel.release();
+    return run.rows;
+}
+
+// ---- RecordBatch::filter / project --------------------------------------------------------------------------------
+// `terms` is a normalised term list (normalize_predicate): no String columns, at most kMaxBoolCols Boolean ones.
+uint64_t filter_by_groups(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, const rv_term *terms, uint32_t nterms,
+                          rv_null_policy policy, const uint32_t *proj, uint32_t nproj, rv_dcolumn **out, rv_dcolumn **out_selection,
+                          const ExprInfo *ex, BatchReq *req) {
+    // String, Boolean and Null projections are produced AFTER the fused pass, from the selection bitmap it
+    // materialises: strings gathered by the surviving row indices, Boolean columns compacted bit-wise
+    // (bits_compact_kernel; as byte-staged streams inside the fused pass they made it ~2.4x slower), Null
+    // columns are just a length.  The 8-byte columns go through the fused pass.
+    // ... unless the launch runs in lane form (8-byte loads), where a Boolean column rides along as a bit stream: a software
+    // PEXT per 64-row word inside the pass (fused_kernel.hpp), up to kMaxBitStreams streams (values + validity each).
+    // Measured (profiles/README.md): the per-lane PEXT costs the issue-bound pass more than the separate bit-compaction
+    // kernel costs in traffic, so it is off by default (option "bools_in_pass" = 1 turns it on).
+    int bool_streams = 0;
+    bool bools_in_pass = ctx->opt_bools_in_pass != 0 && ctx->opt_vec != 2 && ex == nullptr;
+    for (uint32_t j = 0; j < nproj && bools_in_pass; ++j) {
+        const uint32_t c = proj[j];
+        if (c >= ncols) break;
+        if (cols[c]->dtype == RV_BOOLEAN) bool_streams += cols[c]->validity ? 2 : 1;
+        else if (cols[c]->dtype == RV_STRING || cols[c]->dtype == RV_NULL) bools_in_pass = false;  // a selection bitmap is made anyway
+    }
+    bools_in_pass = bools_in_pass && bool_streams > 0 && bool_streams <= rvk::kMaxBitStreams;
+    auto post_pass = [&](uint32_t c) {
+        return cols[c]->dtype == RV_STRING || cols[c]->dtype == RV_NULL || (cols[c]->dtype == RV_BOOLEAN && !bools_in_pass);
+    };
+    bool any_post = false;
+    for (uint32_t j = 0; j < nproj; ++j) {
+        require(proj[j] < ncols, RV_ERR_INVALID_ARG, fmt("projection %u references column %u of %u", j, proj[j], ncols));
+        any_post |= post_pass(proj[j]);
+    }
+    if (!any_post) return filter_value_columns(ctx, cols, ncols, terms, nterms, policy, proj, nproj, out, out_selection, ex, req, nullptr, nullptr);
+    std::vector<uint32_t> fixed, fixed_pos;
+    for (uint32_t j = 0; j < nproj; ++j)
+        if (!post_pass(proj[j])) {
+            fixed.push_back(proj[j]);
+            fixed_pos.push_back(j);
+        }
+    // String and Boolean columns are produced from the selection bitmap by launches queued right behind the fused pass,
+    // while it is still writing that bitmap, at the pass's wave offsets (no scan over the bitmap): the lengths pass of the
+    // first String column, bits_compact_kernel for up to 6 Boolean columns.  The host waits for the pass (it sizes the
+    // copy launches by the survivor count) while those run, and reads the shared control block once, at the end.
+    StrSelLaunch first_str;
+    int first_str_j = -1;
+    std::vector<uint32_t> bool_js;
+    // A Boolean column that the predicate itself requires to be true (`b is true` in a plain AND: the one filter form the
+    // reference's streaming planner accepts, streaming_planner.rs:139) is all true and never null among the survivors
+    // (record_batch.rs:237 keeps Some(true) only): its output is rows ones, nothing to read or compact.
+    std::vector<char> all_true(nproj, 0);
+    for (uint32_t j = 0; j < nproj; ++j) {
+        if (cols[proj[j]]->dtype == RV_STRING && first_str_j < 0) first_str_j = static_cast<int>(j);
+        if (cols[proj[j]]->dtype != RV_BOOLEAN) continue;
+        for (uint32_t t = 0; t < nterms && !ex; ++t)
+            if (terms[t].column == proj[j] && terms[t].op == RV_IS_TRUE) all_true[j] = 1;
+        if (!all_true[j]) bool_js.push_back(j);
+    }
+    RangeOffsets wave_ranges;
+    const bool want_bools = !bool_js.empty() && bool_js.size() <= 6;
+    const bool want_ranges = want_bools || first_str_j >= 0;
+    std::vector<BoolCompactLaunch> bool_launches(want_bools ? bool_js.size() : 0);
+    bool bools_queued = false;
+    const AfterLaunch queue_post = [&](const rv_dcolumn *s) {
+        if (!str_sel_eligible(s, wave_ranges)) return;  // an empty table, or a geometry whose ranges do not tile 4096 rows
+        Ctrl *ctrl = prepare_ctrl(ctx, 0);
+        if (first_str_j >= 0) str_sel_queue(ctx, cols[proj[first_str_j]], s, wave_ranges, ctrl, 0, first_str);
+        if (want_bools) {
+            for (size_t k = 0; k < bool_js.size(); ++k)
+                bool_compact_queue(ctx, cols[proj[bool_js[k]]], s, wave_ranges, ctrl, 1 + static_cast<int>(k), bool_launches[k]);
+            bools_queued = true;
+        }
+    };
+    if (req && (first_str_j >= 0 || !bool_js.empty())) req->sel_optional = false;  // columns produced from the selection bitmap
+    const uint64_t reruns_before = ctx->overflow_reruns;
+    // the selection bitmap: for the String / Boolean columns compacted by it (a NullArray or an all-true column is a length)
+    const bool need_sel = out_selection != nullptr || first_str_j >= 0 || !bool_js.empty();
+    std::vector<rv_dcolumn *> fo(fixed.size() ? fixed.size() : 1, nullptr);
+    rv_dcolumn *s = nullptr;
+    const uint64_t rows = filter_value_columns(ctx, cols, ncols, terms, nterms, policy, fixed.data(), static_cast<uint32_t>(fixed.size()), fo.data(),
+                                               need_sel ? &s : nullptr, ex, req, &queue_post, want_ranges ? &wave_ranges : nullptr);
+    std::unique_ptr<rv_dcolumn> sel(s);
+    std::vector<std::unique_ptr<rv_dcolumn>> outs(nproj);  // handed to the caller at the end
+    for (size_t k = 0; k < fixed.size(); ++k) outs[fixed_pos[k]].reset(fo[k]);
+    if (first_str.queued || bools_queued) {
+        // outputs sized by a bound that the pass overflowed (it was re-run with exact sizes): what was queued with
+        // the same bound is dropped and the columns take the scan path below
+        const bool usable = ctx->overflow_reruns == reruns_before;
+        if (first_str.queued && usable) str_sel_copy(ctx, first_str, rows);
+        const Ctrl fetched = *fetch_ctrl(ctx);  // one read-back for everything queued behind the pass
+        if (first_str.queued && usable) outs[first_str_j].reset(str_sel_result(first_str, rows, fetched));
+        if (bools_queued && usable)
+            for (size_t k = 0; k < bool_js.size(); ++k) outs[bool_js[k]].reset(bool_compact_result(bool_launches[k], rows, fetched));
+    }
+    DevBufRef excl;  // survivor prefix per selection word: the paths that could not be queued behind the pass
+    auto need_excl = [&]() -> const DevBufRef & {
+        if (!excl) excl = selection_prefix(ctx, sel.get(), rows);
+        return excl;
+    };
+    for (uint32_t j = 0; j < nproj; ++j) {
+        const rv_dcolumn *src = cols[proj[j]];
+        if (outs[j]) continue;  // fixed-width columns, and what was queued behind the pass
+        if (src->dtype == RV_STRING) {
+            if (str_sel_eligible(sel.get(), wave_ranges) && rows <= wave_ranges.out_capacity) {  // further String columns: the same launches, one after the other
+                StrSelLaunch L;
+                str_sel_queue(ctx, src, sel.get(), wave_ranges, prepare_ctrl(ctx, 0), 0, L);
+                str_sel_copy(ctx, L, rows);
+                const Ctrl fetched = *fetch_ctrl(ctx);
+                outs[j].reset(str_sel_result(L, rows, fetched));
+            } else {
+                outs[j].reset(gather_strings_selected(ctx, src, sel.get(), rows, need_excl()));
+            }
+        } else if (src->dtype == RV_BOOLEAN && all_true[j]) {
+            auto o = std::make_unique<rv_dcolumn>();
+            o->dtype = RV_BOOLEAN;
+            o->length = rows;
+            o->null_count = 0;
+            const size_t wb = zeroed_bitmap_bytes(rows);
+            o->values = pool_alloc(ctx, wb);
+            RV_HIP(hipMemsetAsync(o->values->ptr, 0, wb, ctx->stream));  // tail bits zero (bitmap.rs:178-188)
+            if (rows / 8) RV_HIP(hipMemsetAsync(o->values->ptr, 0xFF, rows / 8, ctx->stream));
+            if (rows % 8) RV_HIP(hipMemsetAsync(static_cast<char *>(o->values->ptr) + rows / 8, (1 << (rows % 8)) - 1, 1, ctx->stream));
+            outs[j] = std::move(o);
+        } else if (src->dtype == RV_BOOLEAN) {
+            outs[j].reset(compact_boolean(ctx, src, sel.get(), rows, need_excl()));
+        } else if (src->dtype == RV_NULL) {
+            outs[j] = std::make_unique<rv_dcolumn>();
+            outs[j]->dtype = RV_NULL;
+            outs[j]->length = rows;
+            outs[j]->null_count = static_cast<int64_t>(rows);
+        }
+    }
+    RV_HIP(hipStreamSynchronize(ctx->stream));  // excl goes back to the pool
+    for (uint32_t j = 0; j < nproj; ++j) out[j] = outs[j].release();
+    if (out_selection) *out_selection = sel.release();
     return rows;
 }
 
@@ -589,7 +659,6 @@ rv_status rv_filter_project(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t
 
 namespace rvl {
 struct BatchWalk;
-struct MaskWindow;
 }
 struct rv_pending {
     FusedLaunch launch;                 // valid when !done
@@ -838,6 +907,29 @@ void batch_counts(rv_ctx *ctx, const rv_dcolumn *sel, uint64_t rows, const std::
         }
         segment_counts(static_cast<const uint64_t *>(o->validity->ptr), obounds, valid.data());
         for (size_t b = 0; b < nb; ++b) out_nulls[b * nproj + j] = static_cast<int64_t>(out_rows[b] - valid[b]);
+    }
+}
+// The results of a window of RecordBatches filtered in one call (rv_filter_project_chunked / _batches): the total, the survivors per
+// batch (counted in the pass, or now from `sel`) and the null counts per output batch.  The outputs are freed on an error.
+static void batch_results(rv_ctx *ctx, const BatchReq &req, const rv_dcolumn *sel, uint64_t rows, const std::vector<uint64_t> &bounds, uint64_t uniform,
+                          uint64_t nb, rv_dcolumn **out, uint32_t nproj, uint64_t *out_rows, int64_t *out_nulls, uint64_t *out_total) {
+    try {
+        if (out_total) *out_total = rows;
+        if (nb == 1) {
+            out_rows[0] = rows;
+            if (out_nulls)
+                for (uint32_t j = 0; j < nproj; ++j) out_nulls[j] = out[j]->dtype == RV_NULL ? static_cast<int64_t>(rows) : std::max<int64_t>(0, out[j]->null_count);
+        } else if (nb > 1) {
+            require(req.counted || sel != nullptr, RV_ERR_INTERNAL, "per-batch counts: neither counted in the pass nor a selection bitmap to count");
+            if (req.counted) finish_batch_req(req, out_rows);
+            batch_counts(ctx, req.counted ? nullptr : sel, rows, bounds, uniform, static_cast<size_t>(nb), out, nproj, out_rows, out_nulls);
+        }
+    } catch (...) {
+        for (uint32_t j = 0; j < nproj; ++j) {
+            delete out[j];
+            out[j] = nullptr;
+        }
+        throw;
     }
 }
 }  // namespace rvl
@@ -1124,24 +1216,7 @@ void filter_project_batches_sync(rv_ctx *ctx, const rv_dcolumn *const *cols, uin
                 if (on) fprintf(stderr, "[batches] walk %.2f ms | pass %.2f ms | counts %.2f ms\n", b - a, c - b, d - c);
             }
         } tr{trace, tt0, tt1, tt2};
-        try {
-            if (out_total) *out_total = rows;
-            if (nbatches == 1) {
-                out_rows[0] = rows;
-                if (out_nulls)
-                    for (uint32_t j = 0; j < nproj; ++j) out_nulls[j] = out[j]->dtype == RV_NULL ? static_cast<int64_t>(rows) : std::max<int64_t>(0, out[j]->null_count);
-                return;
-            }
-            require(req.counted || sel != nullptr, RV_ERR_INTERNAL, "per-batch counts: neither counted in the pass nor a selection bitmap to count");
-                if (req.counted) finish_batch_req(req, out_rows);
-            batch_counts(ctx, req.counted ? nullptr : sel, rows, bounds, uniform, nbatches, out, nproj, out_rows, out_nulls);
-        } catch (...) {
-            for (uint32_t j = 0; j < nproj; ++j) {
-                delete out[j];
-                out[j] = nullptr;
-            }
-            throw;
-        }
+        batch_results(ctx, req, sel, rows, bounds, uniform, nbatches, out, nproj, out_rows, out_nulls, out_total);
 }
 }  // namespace rvl
 
@@ -1173,24 +1248,7 @@ rv_status rv_filter_project_chunked(rv_ctx *ctx, const rv_dcolumn *const *cols, 
         BatchReq req = make_batch_req(ctx, chunk_rows, nb, out_rows);
         const uint64_t rows = filter_query(ctx, cols, ncols, pred, proj, nproj, out, nb > 1 ? &sel : nullptr, nb > 1 ? &req : nullptr);
         std::unique_ptr<rv_dcolumn> sel_owner(sel);
-        try {
-            if (out_total) *out_total = rows;
-            if (nb == 1) {
-                out_rows[0] = rows;
-                if (out_nulls)
-                    for (uint32_t j = 0; j < nproj; ++j) out_nulls[j] = out[j]->dtype == RV_NULL ? static_cast<int64_t>(rows) : std::max<int64_t>(0, out[j]->null_count);
-            } else if (nb > 1) {
-                require(req.counted || sel != nullptr, RV_ERR_INTERNAL, "per-batch counts: neither counted in the pass nor a selection bitmap to count");
-                if (req.counted) finish_batch_req(req, out_rows);
-                batch_counts(ctx, req.counted ? nullptr : sel, rows, {}, chunk_rows, static_cast<size_t>(nb), out, nproj, out_rows, out_nulls);
-            }
-        } catch (...) {
-            for (uint32_t j = 0; j < nproj; ++j) {
-                delete out[j];
-                out[j] = nullptr;
-            }
-            throw;
-        }
+        batch_results(ctx, req, sel, rows, {}, chunk_rows, nb, out, nproj, out_rows, out_nulls, out_total);
     });
 }
 
@@ -1198,51 +1256,13 @@ rv_status rv_filter_project_chunked(rv_ctx *ctx, const rv_dcolumn *const *cols, 
 
 namespace rvl {
 // A window of 1024-row-multiple RecordBatches filtered by a BOOLEAN column (the reference's streaming filter, stream.rs:136-158) with its
-// whole work QUEUED: mask_select_kernel (selection words, counts per 1024 rows -- the per-batch counts, written where the caller reads
-// them), the scan of the counts (offsets; the total into the window's own control block) and the compaction of the plain value columns
-// at those offsets into outputs sized from what the predicate kept the last time.  finish reads the total: it fits, or the
-// compaction runs once more with outputs of the exact size.  (filter_by_groups' mask path is the same work with the host waiting for
-// the scan's total in the middle; this is its form for a stream operator that keeps two windows in flight.)
-struct MaskWindow {
-    rv_ctx::LaunchCtrl ctrl;  // pops[0] <- the scan's total
-    bool launched = false;
-    std::unique_ptr<rv_dcolumn> sel;
-    DevBufRef counts, offsets;
-    std::vector<const rv_dcolumn *> src;  // the projected source columns (the caller keeps them alive until finish)
-    uint64_t n = 0, assumed = 0, signature = 0;
-};
-static void mask_window_compact(rv_ctx *ctx, const MaskWindow &w, uint64_t cap, rv_dcolumn *const *outs) {
-    rvk::RangesCompact q{};
-    q.sel = static_cast<const uint64_t *>(w.sel->values->ptr);
-    q.nwords = (w.n + 63) / 64;
-    q.n = w.n;
-    q.range_offsets = static_cast<const uint64_t *>(w.offsets->ptr);
-    q.range_rows = 1024;
-    q.out_capacity = cap;
-    const dim3 grid(static_cast<uint32_t>((q.nwords + 63) / 64)), block(256);
-    for (size_t g0 = 0; g0 < w.src.size(); g0 += rvk::kRangesMaxCols) {
-        const size_t k = std::min<size_t>(rvk::kRangesMaxCols, w.src.size() - g0);
-        for (size_t c = 0; c < k; ++c) {
-            q.in[c] = static_cast<const char *>(w.src[g0 + c]->values->ptr) + w.src[g0 + c]->offset * 8;
-            q.out[c] = static_cast<uint64_t *>(outs[g0 + c]->values->ptr);
-        }
-        switch (k) {
-            case 1: hipLaunchKernelGGL((rvk::compact_ranges_kernel<1, false>), grid, block, 0, ctx->stream, q); break;
-            case 2: hipLaunchKernelGGL((rvk::compact_ranges_kernel<2, false>), grid, block, 0, ctx->stream, q); break;
-            case 3: hipLaunchKernelGGL((rvk::compact_ranges_kernel<3, false>), grid, block, 0, ctx->stream, q); break;
-            default: hipLaunchKernelGGL((rvk::compact_ranges_kernel<4, false>), grid, block, 0, ctx->stream, q); break;
-        }
-        RV_HIP(hipGetLastError());
-    }
-    ctx->last_kernel = fmt("compact_ranges_kernel<%d>", static_cast<int>(std::min<size_t>(rvk::kRangesMaxCols, w.src.size())));
-}
-// eligible: `b is true` alone over a Boolean column, RV_NULL_DROPS, plain value columns projected, a window of kRangesFromRows rows and
-// more in batches of a multiple of 1024 rows, counts the device can write, and a selectivity the context remembers for these buffers
+// whole mask path QUEUED, into outputs sized from what the predicate kept the last time: finish reads the total from the window's own
+// control block, and it fits, or the compaction runs once more with outputs of the exact size.
+// eligible: the mask shape, plain value columns projected, counts the device can write, and a selectivity the context remembers for these buffers
 static bool mask_window_eligible(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, const rv_predicate *pred, const uint32_t *proj, uint32_t nproj,
                                  uint64_t chunk_rows, const BatchReq &req, double &known, uint64_t &signature) {
-    if (pred->expr || pred->n_terms != 1 || pred->terms[0].op != RV_IS_TRUE || pred->nulls != RV_NULL_DROPS || pred->terms[0].column >= ncols) return false;
-    if (cols[pred->terms[0].column]->dtype != RV_BOOLEAN || (cols[0]->length < rvt::kRangesFromRows && ctx->opt_groups_by_ranges != 1) || chunk_rows % 1024 != 0 || nproj == 0) return false;
-    if (ctx->opt_groups_by_ranges < 0 || ctx->opt_out_sizing < 0 || !req.counts || static_cast<const void *>(req.counts) == ctx->h_stage) return false;
+    if (!mask_shape(ctx, cols, ncols, pred->terms, pred->n_terms, pred->nulls, pred->expr != nullptr, chunk_rows) || nproj == 0) return false;
+    if (ctx->opt_out_sizing < 0 || !req.counts || static_cast<const void *>(req.counts) == ctx->h_stage) return false;
     for (uint32_t j = 0; j < nproj; ++j)
         if (proj[j] >= ncols || !is_value_type(cols[proj[j]]->dtype) || cols[proj[j]]->validity) return false;
     rv_term t = pred->terms[0];
@@ -1251,53 +1271,20 @@ static bool mask_window_eligible(rv_ctx *ctx, const rv_dcolumn *const *cols, uin
     known = ctx->seen_selectivity(signature);
     return known >= 0.0 && known <= rvt::kMaskPathAssumeUpTo;
 }
+// (the window reports the compaction of its first group of columns)
+static void mask_window_compact(rv_ctx *ctx, const MaskWindow &w, uint64_t cap, rv_dcolumn *const *outs) {
+    mask_compact(ctx, w, cap, outs);
+    ctx->last_kernel = fmt("compact_ranges_kernel<%d>", static_cast<int>(std::min<size_t>(rvk::kRangesMaxCols, w.src.size())));
+}
 static void mask_window_begin(rv_ctx *ctx, const rv_dcolumn *const *cols, const rv_predicate *pred, const uint32_t *proj, uint32_t nproj, BatchReq &req,
                               double known, uint64_t signature, MaskWindow &w, rv_dcolumn **outs) {
     const rv_dcolumn *mask = cols[pred->terms[0].column];
-    w.n = mask->length;
     w.signature = signature;
-    w.assumed = std::min<uint64_t>(w.n, static_cast<uint64_t>(static_cast<double>(w.n) * (known * rvt::kOutSizingFactor + rvt::kOutSizingSlack)) + 4096);
-    const uint64_t nwords = (w.n + 63) / 64, nranges = (w.n + 1023) / 1024;
-    w.sel = std::make_unique<rv_dcolumn>();
-    w.sel->dtype = RV_BOOLEAN;
-    w.sel->length = w.n;
-    w.sel->null_count = 0;
-    w.sel->values = pool_alloc(ctx, std::max<size_t>(bitmap_words_bytes(w.n) + 8, 16));
-    w.counts = pool_alloc(ctx, nranges * 4 + 16);
-    w.ctrl = acquire_launch_ctrl(ctx, 0, 0);  // zeroed on the stream
-    w.launched = true;
-    rvk::MaskSelect q{};
-    q.values = static_cast<const uint8_t *>(mask->values->ptr);
-    q.values_bytes = mask->values->bytes;
-    q.validity = mask->validity ? static_cast<const uint8_t *>(mask->validity->ptr) : nullptr;
-    q.validity_bytes = mask->validity ? mask->validity->bytes : 0;
-    q.offset = mask->offset;
-    q.n = w.n;
-    q.sel = static_cast<uint64_t *>(w.sel->values->ptr);
-    q.counts = static_cast<uint32_t *>(w.counts->ptr);
-    q.batch_counts = req.chunk_rows == 1024 ? req.counts : nullptr;
-    hipLaunchKernelGGL(rvk::mask_select_kernel, dim3(static_cast<uint32_t>((nwords + 255) / 256)), dim3(256), 0, ctx->stream, q);
-    RV_HIP(hipGetLastError());
-    if (req.chunk_rows != 1024) {
-        const uint64_t per_batch = req.chunk_rows / 1024;
-        const uint64_t threads = per_batch < 32 ? req.nb : (per_batch < 4096 ? req.nb * 64 : req.nb * 256);
-        const dim3 cgrid(static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>((threads + 255) / 256, static_cast<uint64_t>(ctx->props.multiProcessorCount) * 8))));
-        hipLaunchKernelGGL(rvk::batch_counts_from_waves, cgrid, dim3(256), 0, ctx->stream, static_cast<const uint32_t *>(q.counts), nranges, per_batch, req.nb, req.counts);
-        RV_HIP(hipGetLastError());
-    }
-    req.counted = true;
-    ctx->batch_counts_in_pass += 1;
-    device_exclusive_scan(ctx, w.counts->ptr, nranges, w.offsets, false, false, &static_cast<Ctrl *>(w.ctrl.dev)->pops[0]);
-    w.src.clear();
+    w.assumed = assumed_rows(mask->length, known);
+    mask_select_begin(ctx, mask, &req, MaskTotal::kInWindow, w);
     for (uint32_t j = 0; j < nproj; ++j) {
-        const rv_dcolumn *src = cols[proj[j]];
-        auto o = std::make_unique<rv_dcolumn>();
-        o->dtype = src->dtype;
-        o->length = w.assumed;
-        o->null_count = 0;
-        o->values = pool_alloc(ctx, std::max<size_t>(elem_bytes(src->dtype, w.assumed), 8));
-        outs[j] = o.release();
-        w.src.push_back(src);
+        outs[j] = new_value_column(ctx, cols[proj[j]]->dtype, w.assumed).release();
+        w.src.push_back(cols[proj[j]]);
     }
     mask_window_compact(ctx, w, w.assumed, outs);
     RV_HIP(hipMemcpyAsync(w.ctrl.host, w.ctrl.dev, kCtrlBytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -1348,10 +1335,7 @@ static bool window_can_be_queued(rv_ctx *ctx, const rv_dcolumn *const *cols, uin
                                  uint64_t nb, uint64_t chunk_rows, const BatchReq &req) {
     if (nb < 2 || pred->expr || !single_pass_shape(cols, ncols, pred->terms, pred->n_terms, proj, nproj)) return false;
     if (!req.counts || static_cast<const void *>(req.counts) == ctx->h_stage) return false;  // counts through the shared staging block: one window at a time
-    const bool mask_shape = pred->n_terms == 1 && pred->terms[0].op == RV_IS_TRUE && pred->nulls == RV_NULL_DROPS && pred->terms[0].column < ncols &&
-                            cols[pred->terms[0].column]->dtype == RV_BOOLEAN && (cols[0]->length >= rvt::kRangesFromRows || ctx->opt_groups_by_ranges == 1) && chunk_rows % 1024 == 0 &&
-                            ctx->opt_groups_by_ranges >= 0;
-    return !mask_shape;
+    return !mask_shape(ctx, cols, ncols, pred->terms, pred->n_terms, pred->nulls, false, chunk_rows);
 }
 // the window's null counts per output batch (and, where the pass did not count them, its survivors per batch): finish's half
 static void window_counts(rv_ctx *ctx, rv_pending &pend, int64_t *out_nulls) {

@@ -52,6 +52,11 @@ DevBufRef selection_to_indices(rv_ctx *ctx, const rv_dcolumn *sel, uint64_t rows
     RV_HIP(hipGetLastError());
     return indices;
 }
+void launch_bits_compact(rv_ctx *ctx, const rvk::BitsCompact &b) {
+    const dim3 grid(static_cast<uint32_t>(std::min<uint64_t>((b.nwords + 255) / 256, static_cast<uint64_t>(ctx->props.multiProcessorCount) * 8)));
+    hipLaunchKernelGGL(rvk::bits_compact_kernel, grid, dim3(256), 0, ctx->stream, b);
+    RV_HIP(hipGetLastError());
+}
 // ... -> a Boolean column compacted by it (values under their validity, and the validity itself)
 rv_dcolumn *compact_boolean(rv_ctx *ctx, const rv_dcolumn *src, const rv_dcolumn *sel, uint64_t rows, const DevBufRef &excl) {
     auto o = std::make_unique<rv_dcolumn>();
@@ -76,7 +81,6 @@ rv_dcolumn *compact_boolean(rv_ctx *ctx, const rv_dcolumn *src, const rv_dcolumn
     b.nwords = nwords;
     b.offset = src->offset;
     b.excl = static_cast<const uint64_t *>(excl->ptr);
-    const dim3 grid(static_cast<uint32_t>(std::min<uint64_t>((nwords + 255) / 256, static_cast<uint64_t>(ctx->props.multiProcessorCount) * 8)));
     // values: false under a null (BooleanArray::new, boolean.rs:29-32); the validity rides in the same launch
     b.src = static_cast<const uint8_t *>(src->values->ptr);
     b.src_bytes = src->values->bytes;
@@ -90,8 +94,7 @@ rv_dcolumn *compact_boolean(rv_ctx *ctx, const rv_dcolumn *src, const rv_dcolumn
         b.out2 = static_cast<uint64_t *>(o->validity->ptr);
         b.pop2 = striped(ctx, &ctrl->pops[1]);
     }
-    hipLaunchKernelGGL(rvk::bits_compact_kernel, grid, dim3(256), 0, ctx->stream, b);
-    RV_HIP(hipGetLastError());
+    launch_bits_compact(ctx, b);
     const Ctrl *h = fetch_ctrl(ctx);
     o->null_count = src->validity ? static_cast<int64_t>(rows - h->pops[1]) : 0;
     if (o->null_count == 0) o->validity.reset();  // BooleanArrayBuilder::finish (boolean.rs:282-286)
@@ -198,8 +201,7 @@ rv_dcolumn *gather_strings_selected(rv_ctx *ctx, const rv_dcolumn *src, const rv
         b.src_bytes = src->validity->bytes;
         b.out = static_cast<uint64_t *>(o->validity->ptr);
         b.pop = striped(ctx, &ctrl->valid_pop[0]);
-        const dim3 grid(static_cast<uint32_t>(std::min<uint64_t>((nwords + 255) / 256, static_cast<uint64_t>(ctx->props.multiProcessorCount) * 8)));
-        hipLaunchKernelGGL(rvk::bits_compact_kernel, grid, dim3(256), 0, ctx->stream, b);
+        launch_bits_compact(ctx, b);
     }
     rvk::SelStr q{};
     q.sel = static_cast<const uint64_t *>(sel->values->ptr);
@@ -254,9 +256,7 @@ void str_sel_queue(rv_ctx *ctx, const rv_dcolumn *src, const rv_dcolumn *sel, co
         b.src_bytes = src->validity->bytes;
         b.out = static_cast<uint64_t *>(o->validity->ptr);
         b.pop = striped(ctx, &ctrl->valid_pop[slot]);
-        const dim3 grid(static_cast<uint32_t>(std::min<uint64_t>((nwords + 255) / 256, static_cast<uint64_t>(ctx->props.multiProcessorCount) * 8)));
-        hipLaunchKernelGGL(rvk::bits_compact_kernel, grid, dim3(256), 0, ctx->stream, b);
-        RV_HIP(hipGetLastError());
+        launch_bits_compact(ctx, b);
     }
     if (L.tiles) {  // the whole String side in source-tile order, queued here: nothing of it is sized by the survivor count
         const uint64_t ntiles = (nwords + 7) / 8, ngroups = (ntiles + rvk::kStrGroup - 1) / rvk::kStrGroup;
@@ -415,9 +415,7 @@ void bool_compact_queue(rv_ctx *ctx, const rv_dcolumn *src, const rv_dcolumn *se
             b.out2 = static_cast<uint64_t *>(o->validity->ptr);
             b.pop2 = striped(ctx, &ctrl->valid_pop[slot]);
         }
-        const dim3 grid(static_cast<uint32_t>(std::min<uint64_t>((nwords + 255) / 256, static_cast<uint64_t>(ctx->props.multiProcessorCount) * 8)));
-        hipLaunchKernelGGL(rvk::bits_compact_kernel, grid, dim3(256), 0, ctx->stream, b);
-        RV_HIP(hipGetLastError());
+        launch_bits_compact(ctx, b);
         L.launched = true;
     }
     L.col = std::move(o);
