@@ -398,6 +398,31 @@ rv_status rv_join_table_free(rv_ctx *ctx, rv_join_table *table);
 rv_status rv_hash_join(rv_ctx *ctx, const rv_dcolumn *const *build_cols, uint32_t n_build, uint32_t build_key,
                        const rv_dcolumn *const *probe_cols, uint32_t n_probe, uint32_t probe_key,
                        rv_dcolumn **out, uint64_t *out_rows);
+/* The streaming inner join's probe over one WINDOW of a resident probe frame (StreamingPhysicalPlan::HashJoin, which the
+ * reference leaves todo!(), streaming.rs:128-131, defined by the eager join): the probe frame is cut into BATCHES the way
+ * rv_filter_project_chunked cuts a table -- batch k is probe rows [k * chunk_rows, min((k + 1) * chunk_rows, length)), there
+ * are K = ceil(length / chunk_rows) of them, none for an empty frame -- and output batch k == rv_hash_join of the whole build
+ * side against probe batch k alone (same key rules, same names, same row order).  `table` is rv_join_build over
+ * build_cols[build_key]; build_cols are the columns it gathers from.
+ *   - out[n_probe + n_build - 1] hold the output batches back to back, in the column order of rv_hash_join; output batch k
+ *     is rows [sum(out_rows[0..k)), + out_rows[k]) of every out[j] -- rv_slice_known cuts it out without copying;
+ *   - out_rows[K] (capacity `nchunks`): the pairs of EVERY batch, all K, from one count pass and one read-back;
+ *   - out_nulls[K x nout] (may be NULL): null count of every materialised output batch and column;
+ *   - *out_total (may be NULL): the pairs materialised, sum(out_rows[0 .. *out_batches)).
+ * `max_pairs` bounds the window's output: only the longest prefix of batches whose pairs fit max_pairs AND what the device
+ * holds (16 bytes of indices per pair, as rv_join_probe) is materialised, and *out_batches reports its batch count.  At least
+ * one batch is always taken; only a single batch the device cannot hold is RV_ERR_OOM, with nothing allocated.  max_pairs = 0:
+ * the device limit only.  The caller continues with the probe rows from *out_batches x chunk_rows on.
+ * Errors: chunk_rows 0, nchunks below K, a key index out of range: RV_ERR_INVALID_ARG; a build column whose length differs
+ * from the table's build rows, or unequal columns on one side: RV_ERR_LENGTH_MISMATCH; anything else as rv_hash_join.  A failed
+ * call leaves the context usable and creates no outputs.  rv_ctx_last_kernel names the emit kernel as rv_join_probe does, or
+ * join_probe_count_batched when no pair came out. */
+rv_status rv_hash_join_chunked(rv_ctx *ctx, const rv_join_table *table,
+                               const rv_dcolumn *const *build_cols, uint32_t n_build, uint32_t build_key,
+                               const rv_dcolumn *const *probe_cols, uint32_t n_probe, uint32_t probe_key,
+                               uint64_t chunk_rows, uint64_t max_pairs,
+                               rv_dcolumn **out, uint64_t *out_rows, uint64_t nchunks, int64_t *out_nulls,
+                               uint64_t *out_total, uint64_t *out_batches);
 
 /* ---- fused filter + project (K1+K2, the hot path) ------------------------- */
 /* == SelectStream(FilterStream(input)) on one batch (stream.rs:136-158, :202-210) and

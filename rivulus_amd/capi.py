@@ -131,6 +131,8 @@ PROTOTYPES = {
     "rv_join_table_info": (C.c_int, [_P, _U64P, _U64P, _U64P]),
     "rv_join_table_free": (C.c_int, [_P, _P]),
     "rv_hash_join": (C.c_int, [_P, _PP, C.c_uint32, C.c_uint32, _PP, C.c_uint32, C.c_uint32, _PP, _U64P]),
+    "rv_hash_join_chunked": (C.c_int, [_P, _P, _PP, C.c_uint32, C.c_uint32, _PP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
+                                       _PP, _U64P, C.c_uint64, C.POINTER(C.c_int64), _U64P, _U64P]),
     "rv_filter_project": (C.c_int, [_P, _PP, C.c_uint32, C.POINTER(RvPredicate), C.POINTER(C.c_uint32), C.c_uint32,
                                     _PP, _U64P, _PP]),
     "rv_download_string": (C.c_int, [_P, _P, _P, _P, _P, C.POINTER(C.c_int)]),
@@ -657,6 +659,25 @@ class Context:
         _check(load().rv_hash_join(self.handle, _handles(build_cols), len(build_cols), build_key, _handles(probe_cols), len(probe_cols),
                                    probe_key, out, C.byref(rows)))
         return [DeviceColumn(self, C.c_void_p(out[i])) for i in range(max(0, n))], rows.value
+
+    def hash_join_chunked(self, table: "JoinTable", build_cols: Sequence[DeviceColumn], build_key: int, probe_cols: Sequence[DeviceColumn],
+                          probe_key: int, chunk_rows: int, max_pairs: int = 0, want_nulls: bool = True, nchunks: Optional[int] = None):
+        """rv_hash_join_chunked: the probe frame cut into chunk_rows-row batches, every batch joined against the whole build side
+        in one call.  Returns (outs, rows_per_batch[K], nulls[batches taken, nout] or None, total, batches taken)."""
+        n = probe_cols[0].length if probe_cols else 0
+        k = (n + chunk_rows - 1) // chunk_rows if chunk_rows > 0 else 0  # 0: the library reports the argument
+        cap = k if nchunks is None else nchunks
+        nout = len(probe_cols) + len(build_cols) - 1
+        out = (C.c_void_p * max(1, nout))()
+        rows = np.zeros(max(1, k, cap), dtype=np.uint64)
+        nulls = np.zeros(max(1, k) * max(1, nout), dtype=np.int64) if want_nulls else None
+        total, taken = C.c_uint64(), C.c_uint64()
+        _check(load().rv_hash_join_chunked(self.handle, table.handle, _handles(build_cols), len(build_cols), build_key, _handles(probe_cols),
+                                           len(probe_cols), probe_key, chunk_rows, max_pairs, out, rows.ctypes.data_as(_U64P), cap,
+                                           nulls.ctypes.data_as(C.POINTER(C.c_int64)) if want_nulls else None, C.byref(total), C.byref(taken)))
+        outs = [DeviceColumn(self, C.c_void_p(out[i])) for i in range(max(0, nout))]
+        b = taken.value
+        return outs, rows[:k], (nulls.reshape(max(1, k), max(1, nout))[:b] if want_nulls else None), total.value, b
 
     def filter_project(self, cols: Sequence[DeviceColumn], pred: Predicate, proj: Sequence[int],
                        want_selection: bool = False):

@@ -181,6 +181,159 @@ uint64_t probe_table(rv_ctx *ctx, const rv_join_table *t, const rv_dcolumn *key,
     return total;
 }
 
+static_assert(rvt::kJoinFastBatchRows * 4 == static_cast<uint64_t>(rvk::kJoinTileRows), "the fast count pass takes four batches per tile");
+
+// The probe of a window cut into batches of chunk_rows rows (rv_hash_join_chunked): ONE count pass that also counts every batch,
+// the tile scan, ONE read-back of the total and the K batch counts (into batch_rows[K]), the size check, then the emit pass over
+// the longest prefix of batches whose pairs fit `max_pairs` (0: no cap of the caller's) and the device -- at least one batch.
+// Returns the pairs of the prefix; *taken = its batches.
+uint64_t probe_table_batched(rv_ctx *ctx, const rv_join_table *t, const rv_dcolumn *key, uint64_t chunk_rows, uint64_t max_pairs,
+                             uint64_t *batch_rows, uint64_t &taken, DevBufRef &out_probe, DevBufRef &out_build) {
+    check_key(key, "rv_hash_join_chunked");
+    const uint64_t n = key->length;
+    const uint64_t nb = (n + chunk_rows - 1) / chunk_rows;
+    rvk::JoinProbeParams p{};
+    p.table = table_view(t, key->dtype);
+    p.key = dev_view(key);
+    p.n = n;
+    p.lane_most = rvt::kJoinLaneListMost;
+    const uint64_t longest = std::max<uint64_t>(p.table.match_values ? t->max_group : 0, t->n_null);
+    uint64_t total = 0;
+    DevBufRef tiles;
+    ctx->last_kernel = "join_probe_count_batched";
+    if (n) {
+        const uint64_t ntiles = (n + rvk::kJoinTileRows - 1) / rvk::kJoinTileRows;
+        tiles = pool_alloc(ctx, ntiles * 8 + 16);
+        DevBufRef counts = pool_alloc(ctx, nb * 8 + 16);
+        p.tile_counts = static_cast<uint64_t *>(tiles->ptr);
+        rvk::JoinBatchParams b{chunk_rows, nb, static_cast<unsigned long long *>(counts->ptr)};
+        const bool fast = chunk_rows == rvt::kJoinFastBatchRows;
+        if (!fast) RV_HIP(hipMemsetAsync(counts->ptr, 0, nb * 8, ctx->stream));
+        Ctrl *ctrl = prepare_ctrl(ctx, 0);
+        const dim3 grid(static_cast<uint32_t>(ntiles)), block(rvk::kJoinThreads);
+        if (fast) hipLaunchKernelGGL(rvk::join_probe_count_batched<true>, grid, block, 0, ctx->stream, p, b);
+        else hipLaunchKernelGGL(rvk::join_probe_count_batched<false>, grid, block, 0, ctx->stream, p, b);
+        hipLaunchKernelGGL(rvk::scan_sums_inplace, dim3(1), dim3(1024), 0, ctx->stream, p.tile_counts, ntiles, &ctrl->pops[0]);
+        RV_HIP(hipGetLastError());
+        void *hs = ctx->stage(nb * 8);
+        RV_HIP(hipMemcpyAsync(hs, counts->ptr, nb * 8, hipMemcpyDeviceToHost, ctx->stream));
+        total = fetch_ctrl(ctx)->pops[0];  // the one wait: the total and the batch counts together
+        std::memcpy(batch_rows, hs, nb * 8);
+        uint64_t sum = 0;
+        for (uint64_t k = 0; k < nb; ++k) sum += batch_rows[k];
+        require(sum == total, RV_ERR_INTERNAL, "rv_hash_join_chunked: per-batch pair counts do not add up");
+    }
+    // the longest prefix that fits; one batch the device cannot hold on its own is RV_ERR_OOM before anything is allocated
+    const uint64_t device_most = static_cast<uint64_t>(ctx->props.totalGlobalMem) / 16;
+    const uint64_t cap = max_pairs ? std::min(max_pairs, device_most) : device_most;
+    require(nb == 0 || batch_rows[0] <= device_most, RV_ERR_OOM,
+            fmt("rv_hash_join_chunked: batch 0 has %llu pairs, more than the device's %llu bytes hold at 16 bytes each",
+                static_cast<unsigned long long>(nb ? batch_rows[0] : 0), static_cast<unsigned long long>(ctx->props.totalGlobalMem)));
+    uint64_t pairs = 0;
+    taken = 0;
+    while (taken < nb && (taken == 0 || (pairs <= cap && batch_rows[taken] <= cap - pairs))) pairs += batch_rows[taken++];
+    out_probe = pool_alloc(ctx, std::max<size_t>(pairs * 8, 16));
+    out_build = pool_alloc(ctx, std::max<size_t>(pairs * 8, 16));
+    if (pairs) {
+        p.n = std::min(n, taken * chunk_rows);  // the prefix's rows: its tiles' prefixes are those of the whole window
+        p.out_probe = static_cast<int64_t *>(out_probe->ptr);
+        p.out_build = static_cast<int64_t *>(out_build->ptr);
+        const dim3 grid(static_cast<uint32_t>((p.n + rvk::kJoinTileRows - 1) / rvk::kJoinTileRows)), block(rvk::kJoinThreads);
+        const int mode = longest <= 1 ? 0 : longest <= rvt::kJoinLaneListMost ? 1 : 2;
+        if (mode == 0) hipLaunchKernelGGL(rvk::join_probe_emit<0>, grid, block, 0, ctx->stream, p);
+        else if (mode == 1) hipLaunchKernelGGL(rvk::join_probe_emit<1>, grid, block, 0, ctx->stream, p);
+        else hipLaunchKernelGGL(rvk::join_probe_emit<2>, grid, block, 0, ctx->stream, p);
+        RV_HIP(hipGetLastError());
+        ctx->last_kernel = fmt("join_probe_emit<%d>", mode);
+    }
+    // no wait here: `tiles` goes back to the pool, and its next user runs behind the emit pass on the stream
+    return pairs;
+}
+
+// null count of every output batch and column: set bits of each output validity inside the batches' pair ranges
+// (segment_popcount_kernel), one launch per column with a bitmap, every column's counts read back together
+void window_null_counts(rv_ctx *ctx, rv_dcolumn *const *out, uint32_t nout, const uint64_t *batch_rows, uint64_t nb, int64_t *out_nulls) {
+    std::vector<uint64_t> bounds(nb + 1, 0);
+    for (uint64_t k = 0; k < nb; ++k) bounds[k + 1] = bounds[k] + batch_rows[k];
+    std::vector<uint32_t> counted;  // columns with a bitmap
+    for (uint32_t j = 0; j < nout; ++j) {
+        for (uint64_t k = 0; k < nb; ++k) out_nulls[k * nout + j] = out[j]->dtype == RV_NULL ? static_cast<int64_t>(batch_rows[k]) : 0;
+        if (out[j]->dtype != RV_NULL && out[j]->validity) counted.push_back(j);
+    }
+    if (counted.empty() || nb == 0) return;
+    std::vector<rvk::SegItem> items;
+    uint64_t all_words = 0;
+    for (uint64_t k = 0; k < nb; ++k)
+        if (bounds[k + 1] > bounds[k]) all_words += ((bounds[k + 1] - 1) >> 6) - (bounds[k] >> 6) + 1;
+    const uint64_t chunk_words = std::max<uint64_t>(rvk::kSegChunkWords, (all_words / (static_cast<uint64_t>(ctx->props.multiProcessorCount) * 8) + 63) & ~63ull);
+    for (uint64_t k = 0; k < nb; ++k) {
+        if (bounds[k + 1] <= bounds[k]) continue;
+        const uint64_t nwords = ((bounds[k + 1] - 1) >> 6) - (bounds[k] >> 6) + 1;
+        for (uint64_t c = 0; c * chunk_words < nwords; ++c) items.push_back(rvk::SegItem{static_cast<uint32_t>(k), static_cast<uint32_t>(c)});
+    }
+    require(nb < (uint64_t{1} << 32), RV_ERR_UNSUPPORTED, "rv_hash_join_chunked: 2^32 batches or more in one window");
+    const size_t bb = (nb + 1) * 8, ib = items.size() * sizeof(rvk::SegItem), cb = counted.size() * nb * 8;
+    DevBufRef d_tables = pool_alloc(ctx, bb + ib + 16), d_counts = pool_alloc(ctx, cb + 16);
+    char *hs = static_cast<char *>(ctx->stage(std::max(bb + ib, cb)));
+    std::memcpy(hs, bounds.data(), bb);
+    std::memcpy(hs + bb, items.data(), ib);
+    RV_HIP(hipMemcpyAsync(d_tables->ptr, hs, bb + ib, hipMemcpyHostToDevice, ctx->stream));
+    RV_HIP(hipMemsetAsync(d_counts->ptr, 0, cb, ctx->stream));
+    const uint64_t *d_bounds = static_cast<const uint64_t *>(d_tables->ptr);
+    const auto *d_items = reinterpret_cast<const rvk::SegItem *>(static_cast<const char *>(d_tables->ptr) + bb);
+    const dim3 grid(static_cast<uint32_t>(std::min<uint64_t>((items.size() + 3) / 4, static_cast<uint64_t>(ctx->props.multiProcessorCount) * 16)));
+    for (size_t c = 0; c < counted.size() && !items.empty(); ++c)
+        hipLaunchKernelGGL(rvk::segment_popcount_kernel, grid, dim3(256), 0, ctx->stream, static_cast<const uint64_t *>(out[counted[c]]->validity->ptr),
+                           d_bounds, d_items, static_cast<uint64_t>(items.size()), chunk_words, static_cast<unsigned long long *>(d_counts->ptr) + c * nb);
+    RV_HIP(hipGetLastError());
+    RV_HIP(hipMemcpyAsync(hs, d_counts->ptr, cb, hipMemcpyDeviceToHost, ctx->stream));  // stream order: after the upload read hs
+    RV_HIP(hipStreamSynchronize(ctx->stream));
+    const uint64_t *valid = reinterpret_cast<const uint64_t *>(hs);
+    for (size_t c = 0; c < counted.size(); ++c)
+        for (uint64_t k = 0; k < nb; ++k) out_nulls[k * nout + counted[c]] = static_cast<int64_t>(batch_rows[k] - valid[c * nb + k]);
+}
+
+// the checks of rv_hash_join, shared by the chunked form
+void check_join_sides(const char *what, const rv_dcolumn *const *build_cols, uint32_t n_build, uint32_t build_key, const rv_dcolumn *const *probe_cols,
+                      uint32_t n_probe, uint32_t probe_key) {
+    require(build_key < n_build, RV_ERR_INVALID_ARG, fmt("%s: build key %u out of range for %u build columns", what, build_key, n_build));
+    require(probe_key < n_probe, RV_ERR_INVALID_ARG, fmt("%s: probe key %u out of range for %u probe columns", what, probe_key, n_probe));
+    check_batch(build_cols, n_build);
+    check_batch(probe_cols, n_probe);
+    for (uint32_t c = 0; c < n_build; ++c) {
+        const rv_dtype d = build_cols[c]->dtype;
+        require(is_value_type(d) || d == RV_BOOLEAN || d == RV_STRING || d == RV_NULL, RV_ERR_UNSUPPORTED, fmt("%s: unsupported dtype", what));
+    }
+    for (uint32_t c = 0; c < n_probe; ++c) {
+        const rv_dtype d = probe_cols[c]->dtype;
+        require(is_value_type(d) || d == RV_BOOLEAN || d == RV_STRING || d == RV_NULL, RV_ERR_UNSUPPORTED, fmt("%s: unsupported dtype", what));
+    }
+    check_key(build_cols[build_key], what);
+    check_key(probe_cols[probe_key], what);
+}
+
+// materialize_join_result (plan.rs:212-255): every probe column by probe_idx, then every build column but the key by build_idx.
+// The indices come from the tables themselves: no bounds pre-pass.  The outputs are freed on an error.
+void gather_pairs(rv_ctx *ctx, const rv_dcolumn *const *build_cols, uint32_t n_build, uint32_t build_key, const rv_dcolumn *const *probe_cols,
+                  uint32_t n_probe, const DevBufRef &pi, const DevBufRef &bi, uint64_t rows, rv_dcolumn **out) {
+    const uint32_t nout = n_probe + n_build - 1;
+    std::vector<const rv_dcolumn *> build_rest;
+    for (uint32_t c = 0; c < n_build; ++c)
+        if (c != build_key) build_rest.push_back(build_cols[c]);
+    try {
+        take_on_device(ctx, probe_cols, n_probe, static_cast<const uint64_t *>(pi->ptr), rows, out, false);
+        take_on_device(ctx, build_rest.data(), static_cast<uint32_t>(build_rest.size()), static_cast<const uint64_t *>(bi->ptr), rows, out + n_probe, false);
+        RV_HIP(hipStreamSynchronize(ctx->stream));  // the index buffers go back to the pool
+    } catch (...) {
+        (void)hipStreamSynchronize(ctx->stream);
+        for (uint32_t c = 0; c < nout; ++c) {
+            delete out[c];
+            out[c] = nullptr;
+        }
+        throw;
+    }
+}
+
 }  // namespace
 }  // namespace rvl
 
@@ -233,44 +386,54 @@ rv_status rv_hash_join(rv_ctx *ctx, const rv_dcolumn *const *build_cols, uint32_
                        const rv_dcolumn *const *probe_cols, uint32_t n_probe, uint32_t probe_key, rv_dcolumn **out, uint64_t *out_rows) {
     return guarded([&] {
         require(ctx && build_cols && probe_cols && out, RV_ERR_INVALID_ARG, "rv_hash_join: NULL argument");
-        require(build_key < n_build, RV_ERR_INVALID_ARG, fmt("rv_hash_join: build key %u out of range for %u build columns", build_key, n_build));
-        require(probe_key < n_probe, RV_ERR_INVALID_ARG, fmt("rv_hash_join: probe key %u out of range for %u probe columns", probe_key, n_probe));
-        check_batch(build_cols, n_build);
-        check_batch(probe_cols, n_probe);
-        for (uint32_t c = 0; c < n_build; ++c) {
-            const rv_dtype d = build_cols[c]->dtype;
-            require(is_value_type(d) || d == RV_BOOLEAN || d == RV_STRING || d == RV_NULL, RV_ERR_UNSUPPORTED, "rv_hash_join: unsupported dtype");
-        }
-        for (uint32_t c = 0; c < n_probe; ++c) {
-            const rv_dtype d = probe_cols[c]->dtype;
-            require(is_value_type(d) || d == RV_BOOLEAN || d == RV_STRING || d == RV_NULL, RV_ERR_UNSUPPORTED, "rv_hash_join: unsupported dtype");
-        }
-        check_key(build_cols[build_key], "rv_hash_join");
-        check_key(probe_cols[probe_key], "rv_hash_join");
+        check_join_sides("rv_hash_join", build_cols, n_build, build_key, probe_cols, n_probe, probe_key);
         set_device(ctx);
         const uint32_t nout = n_probe + n_build - 1;
         for (uint32_t c = 0; c < nout; ++c) out[c] = nullptr;
         std::unique_ptr<rv_join_table> t = build_table(ctx, build_cols[build_key]);
         DevBufRef pi, bi;
         const uint64_t rows = probe_table(ctx, t.get(), probe_cols[probe_key], pi, bi);
-        // materialize_join_result (plan.rs:212-255): every probe column by probe_idx, then every build column but the key by
-        // build_idx.  The indices come from the tables themselves: no bounds pre-pass.
-        std::vector<const rv_dcolumn *> build_rest;
-        for (uint32_t c = 0; c < n_build; ++c)
-            if (c != build_key) build_rest.push_back(build_cols[c]);
+        gather_pairs(ctx, build_cols, n_build, build_key, probe_cols, n_probe, pi, bi, rows, out);
+        if (out_rows) *out_rows = rows;
+    });
+}
+
+rv_status rv_hash_join_chunked(rv_ctx *ctx, const rv_join_table *table, const rv_dcolumn *const *build_cols, uint32_t n_build, uint32_t build_key,
+                               const rv_dcolumn *const *probe_cols, uint32_t n_probe, uint32_t probe_key, uint64_t chunk_rows, uint64_t max_pairs,
+                               rv_dcolumn **out, uint64_t *out_rows, uint64_t nchunks, int64_t *out_nulls, uint64_t *out_total, uint64_t *out_batches) {
+    return guarded([&] {
+        require(ctx && table && build_cols && probe_cols && out && out_batches, RV_ERR_INVALID_ARG, "rv_hash_join_chunked: NULL argument");
+        require(chunk_rows >= 1, RV_ERR_INVALID_ARG, "rv_hash_join_chunked: chunk_rows is 0");
+        check_join_sides("rv_hash_join_chunked", build_cols, n_build, build_key, probe_cols, n_probe, probe_key);
+        require(build_cols[build_key]->length == table->n_build, RV_ERR_LENGTH_MISMATCH,
+                fmt("rv_hash_join_chunked: build columns of %llu rows, the table was built from %llu", static_cast<unsigned long long>(build_cols[build_key]->length),
+                    static_cast<unsigned long long>(table->n_build)));
+        const uint64_t n = probe_cols[0]->length;
+        // dataframe_to_batches: ceil(n / chunk_rows) batches, none for an empty frame (streaming.rs:135-233)
+        const uint64_t nb = (n + chunk_rows - 1) / chunk_rows;
+        require(nb <= nchunks && (out_rows || nb == 0), RV_ERR_INVALID_ARG,
+                fmt("rv_hash_join_chunked: %llu batches, room for %llu", static_cast<unsigned long long>(nb), static_cast<unsigned long long>(nchunks)));
+        set_device(ctx);
+        const uint32_t nout = n_probe + n_build - 1;
+        for (uint32_t c = 0; c < nout; ++c) out[c] = nullptr;
+        *out_batches = 0;
+        std::vector<uint64_t> counts(nb);
+        uint64_t taken = 0;
+        DevBufRef pi, bi;
+        const uint64_t rows = probe_table_batched(ctx, table, probe_cols[probe_key], chunk_rows, max_pairs, counts.data(), taken, pi, bi);
+        gather_pairs(ctx, build_cols, n_build, build_key, probe_cols, n_probe, pi, bi, rows, out);
         try {
-            take_on_device(ctx, probe_cols, n_probe, static_cast<const uint64_t *>(pi->ptr), rows, out, false);
-            take_on_device(ctx, build_rest.data(), static_cast<uint32_t>(build_rest.size()), static_cast<const uint64_t *>(bi->ptr), rows, out + n_probe, false);
-            RV_HIP(hipStreamSynchronize(ctx->stream));  // the index buffers go back to the pool
+            if (out_nulls) window_null_counts(ctx, out, nout, counts.data(), taken, out_nulls);
         } catch (...) {
-            (void)hipStreamSynchronize(ctx->stream);
             for (uint32_t c = 0; c < nout; ++c) {
                 delete out[c];
                 out[c] = nullptr;
             }
             throw;
         }
-        if (out_rows) *out_rows = rows;
+        if (nb) std::memcpy(out_rows, counts.data(), nb * 8);
+        if (out_total) *out_total = rows;
+        *out_batches = taken;
     });
 }
 

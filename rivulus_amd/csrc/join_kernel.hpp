@@ -202,6 +202,123 @@ static __global__ __launch_bounds__(kJoinThreads) void join_probe_count(JoinProb
     }
 }
 
+// Pass 1 of a probe cut into batches of chunk_rows rows (rv_hash_join_chunked): the tile counts of join_probe_count and, in the
+// same pass, the pairs of every batch -- batch b is probe rows [b * chunk_rows, min((b + 1) * chunk_rows, n)).
+//   FAST (chunk_rows == rvt::kJoinFastBatchRows == kJoinTileRows / 4): a tile holds exactly four batches, and batch q of the tile is
+//        rows k = 4q .. 4q + 3 of every lane (256 apart).  Four per-lane partial sums, four block reductions, four plain stores.
+//   general: at every step k a wave holds 64 consecutive rows; a wave scan of their counts gives the sum of each batch's run, which
+//        the run's last lane adds to the batch's LDS counter (the tile's first kJoinTileBatchSlots batches) or straight to
+//        batch_counts.  One thread per LDS counter then stores it (a batch inside the tile) or adds it (a batch that spans tiles).
+//        batch_counts is zeroed by the caller.
+// Integer sums: the counts are the same on every run, whatever order the atomics land in.
+constexpr int kJoinTileBatchSlots = 256;
+struct JoinBatchParams {
+    uint64_t chunk_rows;
+    uint64_t nbatches;
+    unsigned long long *batch_counts;  // [nbatches]
+};
+
+template <bool FAST>
+static __global__ __launch_bounds__(kJoinThreads) void join_probe_count_batched(JoinProbeParams p, JoinBatchParams b) {
+    __shared__ uint64_t s_wave[4][kJoinThreads / 64];
+    __shared__ unsigned long long s_batch[FAST ? 1 : kJoinTileBatchSlots];
+    const int lane = lane_id(), wave = threadIdx.x >> 6;
+    const uint64_t tile0 = static_cast<uint64_t>(blockIdx.x) * kJoinTileRows;
+    if (FAST) {
+        uint64_t part[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int k = 0; k < kJoinRowsPerThread; ++k) {
+            const uint64_t i = tile0 + threadIdx.x + static_cast<uint64_t>(k) * kJoinThreads;
+            if (i < p.n) {
+                uint64_t bits;
+                const uint32_t cls = join_key(p.key, i, bits);
+                uint32_t start;
+                part[k >> 2] += join_lookup(p.table, cls, bits, start);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const uint64_t v = wave_sum64(part[q]);
+            if (lane == 0) s_wave[q][wave] = v;
+        }
+        __syncthreads();
+        if (threadIdx.x < 4) {
+            const int q = threadIdx.x;
+            uint64_t t = 0;
+#pragma unroll
+            for (int w = 0; w < kJoinThreads / 64; ++w) t += s_wave[q][w];
+            const uint64_t bi = static_cast<uint64_t>(blockIdx.x) * 4 + q;
+            if (bi < b.nbatches) b.batch_counts[bi] = t;
+        }
+        if (threadIdx.x == 0) {
+            uint64_t t = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int w = 0; w < kJoinThreads / 64; ++w) t += s_wave[q][w];
+            p.tile_counts[blockIdx.x] = t;
+        }
+        return;
+    }
+    const uint64_t chunk = b.chunk_rows;
+    const uint64_t tile_end = tile0 + kJoinTileRows < p.n ? tile0 + kJoinTileRows : p.n;
+    const uint64_t b0 = tile0 / chunk, b1 = (tile_end - 1) / chunk;
+    const uint64_t nslots = b1 - b0 + 1 < static_cast<uint64_t>(kJoinTileBatchSlots) ? b1 - b0 + 1 : kJoinTileBatchSlots;
+    for (int t = threadIdx.x; t < kJoinTileBatchSlots; t += kJoinThreads) s_batch[t] = 0;
+    __syncthreads();
+    uint64_t mine = 0;
+    for (int k = 0; k < kJoinRowsPerThread; ++k) {
+        const uint64_t row0 = tile0 + static_cast<uint64_t>(k) * kJoinThreads + static_cast<uint64_t>(wave) * 64;
+        if (row0 >= p.n) break;  // wave-uniform; no barrier inside the loop
+        const uint64_t i = row0 + lane;
+        uint64_t c = 0;
+        if (i < p.n) {
+            uint64_t bits;
+            const uint32_t cls = join_key(p.key, i, bits);
+            uint32_t start;
+            c = join_lookup(p.table, cls, bits, start);
+        }
+        mine += c;
+        uint64_t incl = c;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint64_t y = (static_cast<uint64_t>(__shfl_up(static_cast<uint32_t>(incl >> 32), d, 64)) << 32) | __shfl_up(static_cast<uint32_t>(incl), d, 64);
+            if (lane >= d) incl += y;
+        }
+        // the run of batch bi in this step starts at lane `first`; its sum is incl(last lane) - incl(first - 1)
+        const uint64_t bi = i / chunk;
+        const uint64_t bstart = bi * chunk;
+        const int first = bstart > row0 ? static_cast<int>(bstart - row0) : 0;
+        const int src = first > 0 ? first - 1 : 0;
+        const uint64_t at_src = (static_cast<uint64_t>(__shfl(static_cast<uint32_t>(incl >> 32), src, 64)) << 32) | __shfl(static_cast<uint32_t>(incl), src, 64);
+        const uint64_t before = first > 0 ? at_src : 0;
+        const bool last = lane == 63 || i + 1 >= p.n || i + 1 == bstart + chunk;
+        if (i < p.n && last) {
+            const unsigned long long sum = incl - before;
+            if (sum) {
+                const uint64_t slot = bi - b0;
+                if (slot < static_cast<uint64_t>(kJoinTileBatchSlots)) atomicAdd(&s_batch[slot], sum);
+                else atomicAdd(&b.batch_counts[bi], sum);
+            }
+        }
+    }
+    mine = wave_sum64(mine);
+    if (lane == 0) s_wave[0][wave] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t t = 0;
+#pragma unroll
+        for (int w = 0; w < kJoinThreads / 64; ++w) t += s_wave[0][w];
+        p.tile_counts[blockIdx.x] = t;
+    }
+    for (uint64_t t = threadIdx.x; t < nslots; t += kJoinThreads) {
+        const uint64_t bi = b0 + t;
+        const uint64_t lo = bi * chunk, hi = lo + chunk < p.n ? lo + chunk : p.n;
+        if (lo >= tile0 && hi <= tile0 + kJoinTileRows) b.batch_counts[bi] = s_batch[t];  // the batch lies inside this tile
+        else if (s_batch[t]) atomicAdd(&b.batch_counts[bi], s_batch[t]);
+    }
+}
+
 // exclusive prefix of v over the workgroup, in thread order; *total = the workgroup's sum (every thread)
 __device__ __forceinline__ uint64_t join_block_scan(uint64_t v, uint64_t *s_wave, uint64_t &total) {
     const int lane = lane_id(), wave = threadIdx.x >> 6;

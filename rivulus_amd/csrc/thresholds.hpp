@@ -82,4 +82,9 @@ constexpr uint64_t kBoolCapSlack = 65536;
 // join_probe_emit<0>, the plain compaction: no threshold.)  Set by reasoning -- a lane writing 32 pairs costs about what handing
 // them to the workgroup costs -- NOT by a sweep; profiles/r06_join_bench.jsonl times 8 rows per key on the lane path (tools/join_bench.py).
 constexpr uint32_t kJoinLaneListMost = 32;
+// rv_hash_join_chunked's count pass: batches of exactly this many probe rows (the reference's 1024, streaming_planner.rs:32; a quarter of
+// a 4096-row probe tile) are counted from per-lane partial sums (join_probe_count_batched<true>: no atomics, no LDS counters); every
+// other batch size takes the general pass (join_probe_count_batched<false>: a wave scan per step, LDS counters, integer atomics for
+// batches that span tiles).  Not a crossover: the fast form exists for this one size only.   tests/test_stream_join_gpu.py
+constexpr uint64_t kJoinFastBatchRows = 1024;
 }  // namespace rvt

@@ -9,6 +9,7 @@
 //   execution::{DataStream, MemoryStream, FilterStream,
 //               SelectStream, LimitStream}                   src/execution/stream.rs:25-213, streaming.rs:246-288
 //   execution::GpuFilterProjectStream                        the operator the new backend adds at seam S1
+//   execution::GpuHashJoinStream                             StreamingPhysicalPlan::HashJoin (todo!() in the reference, streaming.rs:128-131)
 //   expressions::{Expr, BinaryOperator}                      src/expressions/expr.rs:3-139
 //   physical_plan::{convert_filter_predicate, convert_select_expr,
 //                   extract_boolean_predicate_column,
@@ -1271,6 +1272,202 @@ class GpuChunkedFilterProjectStream : public DataStream {
     Ahead ahead_;
 };
 
+// One side of a streaming join: a stream, or a resident frame (a DataFrameSource: its columns after dataframe_to_batches' null
+// fill, cut into batch_size-row batches).
+struct JoinSide {
+    DataStreamRef stream;
+    std::vector<std::string> names;
+    std::vector<ArrayRef> columns;
+    size_t batch_size = 0;
+    SchemaRef schema() const {
+        if (stream) return stream->schema();
+        std::vector<Field> f;
+        for (size_t c = 0; c < columns.size(); ++c) f.push_back(Field{names[c], columns[c]->data_type(), true});
+        return std::make_shared<const Schema>(f);
+    }
+};
+
+// GpuHashJoinStream -- StreamingPhysicalPlan::HashJoin, inner (the reference's arm is todo!(), streaming.rs:128-131), defined by
+// the eager join: the build side is drained once (one batch as it is, several joined by RecordBatch::concat) and hashed
+// (rv_join_build); then EXACTLY one output batch per probe batch, empty ones included, in probe order, each == rv_hash_join of
+// the whole build side against that probe batch alone -- names, `_right` suffixes, row order and key rules of the eager join.
+//   - a resident probe frame: one rv_hash_join_chunked per WINDOW of window_rows rows (2^28 by default, as the filter streams: one
+//     window for most tables, and a launch plus a read-back per window is noise at that size); the output batches are
+//     rv_slice_known views of the window's outputs.  max_pairs (2^28 by default: 4 GiB of pair indices plus the gathered columns)
+//     bounds what one window materialises: a join larger than HBM streams through windows cut short at their out_batches, each
+//     window starting at the first batch the one before did not take;
+//   - any other probe stream (CSV, MemoryStream, a filter): one rv_hash_join_chunked per pulled batch against the same table.
+//     Correct, but launch-bound like every per-batch device call (about five launches, a read-back and a wait per batch).
+// Under a limit (limit_hint) windows are sized by LimitWindow with the pairs counted as its survivors: limit(10) probes a few
+// thousand rows, not the table.
+class GpuHashJoinStream : public DataStream {
+  public:
+    GpuHashJoinStream(JoinSide build, JoinSide probe, std::string build_key, std::string probe_key, size_t window_rows = size_t(1) << 28,
+                      uint64_t max_pairs = uint64_t(1) << 28)
+        : build_(std::move(build)), probe_(std::move(probe)), build_key_(std::move(build_key)), probe_key_(std::move(probe_key)),
+          window_rows_(std::max<size_t>(1, window_rows)), max_pairs_(max_pairs) {
+        build_schema_ = build_.schema();
+        probe_schema_ = probe_.schema();
+        auto bk = build_schema_->index_of(build_key_);
+        if (!bk) throw StreamError::execution("Column '" + build_key_ + "' not found in schema");
+        auto pk = probe_schema_->index_of(probe_key_);
+        if (!pk) throw StreamError::execution("Column '" + probe_key_ + "' not found in schema");
+        bki_ = static_cast<uint32_t>(*bk);
+        pki_ = static_cast<uint32_t>(*pk);
+        // materialize_join_result (plan.rs:212-255): every probe column, then every build column but the key, `_right` on a name the
+        // probe side has too
+        std::vector<Field> f = probe_schema_->fields();
+        for (size_t i = 0; i < build_schema_->num_fields(); ++i) {
+            const Field &b = build_schema_->field(i);
+            if (i == bki_) continue;
+            f.push_back(Field{probe_schema_->field_by_name(b.name()) ? b.name() + "_right" : b.name(), b.data_type(), b.is_nullable()});
+        }
+        output_schema_ = std::make_shared<const Schema>(f);
+        probe_rows_ = probe_.stream ? 0 : (probe_.columns.empty() ? 0 : probe_.columns[0]->len());
+    }
+    ~GpuHashJoinStream() override {
+        if (table_) rv_join_table_free(table_ctx_->raw(), table_);
+    }
+    SchemaRef schema() const override { return output_schema_; }
+    void limit_hint(size_t rows) override { limit_.hint(rows); }  // counted in pairs: not passed on to the probe side
+    size_t rows_scanned() const { return limit_.scanned(); }
+
+    std::optional<RecordBatch> next_batch() override {
+        if (probe_.stream) return next_pulled();
+        if (next_in_window_ == window_rows_out_.size()) {
+            if (next_row_ >= probe_rows_) return std::nullopt;
+            refill();
+        }
+        const size_t b = next_in_window_++, nout = joined_.size();
+        const ContextRef &ctx = probe_.columns[0]->context();
+        std::vector<ArrayRef> arrays;
+        for (size_t j = 0; j < nout; ++j) {
+            rv_dcolumn *piece = nullptr;
+            check_stream(rv_slice_known(ctx->raw(), joined_[j]->handle(), at_, window_rows_out_[b], window_nulls_[b * nout + j], &piece));
+            arrays.push_back(Array::adopt(ctx, piece));
+        }
+        at_ += window_rows_out_[b];
+        return RecordBatch::new_unchecked(output_schema_, std::move(arrays), window_rows_out_[b]);
+    }
+
+  private:
+    static void check_stream(rv_status st) {
+        try {
+            check(st);
+        } catch (const Error &e) {
+            throw StreamError::execution(e.what());
+        }
+    }
+    // the build side drained and hashed, once (ctx: the probe side's, for a build side that yields no batch)
+    void ensure_built(const ContextRef &ctx) {
+        if (table_) return;
+        try {
+            if (build_.stream) {
+                std::vector<RecordBatch> parts = build_.stream->collect();
+                RecordBatch whole = parts.empty() ? RecordBatch::empty(ctx, build_schema_) : parts.size() == 1 ? std::move(parts[0]) : RecordBatch::concat(parts);
+                build_.columns = whole.columns();
+            } else if (build_.columns.empty()) {
+                build_.columns = RecordBatch::empty(ctx, build_schema_).columns();
+            }
+            for (auto &c : build_.columns) build_handles_.push_back(c->handle());
+            table_ctx_ = build_.columns[bki_]->context();
+            check(rv_join_build(table_ctx_->raw(), build_.columns[bki_]->handle(), &table_));
+        } catch (const Error &e) {
+            throw StreamError::execution(e.what());
+        }
+    }
+    // rv_hash_join_chunked over the n rows of `probe` in batches of `chunk`, into out / rows / nulls; returns the batches taken
+    uint64_t join_window(const ContextRef &ctx, const std::vector<const rv_dcolumn *> &probe, uint64_t n, uint64_t chunk, std::vector<ArrayRef> &out,
+                         std::vector<uint64_t> &rows, std::vector<int64_t> &nulls, uint64_t &pairs) {
+        const size_t nout = output_schema_->num_fields();
+        const uint64_t nb = (n + chunk - 1) / chunk;
+        std::vector<rv_dcolumn *> raw(nout, nullptr);
+        rows.assign(std::max<uint64_t>(nb, 1), 0);
+        nulls.assign(std::max<uint64_t>(nb, 1) * nout, 0);
+        uint64_t taken = 0;
+        check_stream(rv_hash_join_chunked(ctx->raw(), table_, build_handles_.data(), static_cast<uint32_t>(build_handles_.size()), bki_, probe.data(),
+                                          static_cast<uint32_t>(probe.size()), pki_, chunk, max_pairs_, raw.data(), rows.data(), nb, nulls.data(), &pairs, &taken));
+        out.clear();
+        for (auto *h : raw) out.push_back(Array::adopt(ctx, h));
+        rows.resize(taken);
+        return taken;
+    }
+    void refill() {  // the next window of the resident probe frame
+        const ContextRef ctx = probe_.columns[0]->context();
+        ensure_built(ctx);
+        const size_t batch = probe_.batch_size;
+        const size_t want = limit_.next(ctx, window_rows_);
+        const size_t want_batches = std::max<size_t>(1, (want + batch - 1) / batch);
+        const size_t cap_batches = std::max<size_t>(1, window_rows_ / batch);
+        const size_t len = std::min(probe_rows_ - next_row_, std::min(cap_batches, want_batches) * batch);
+        std::vector<ArrayRef> views;
+        std::vector<const rv_dcolumn *> cols;
+        for (auto &c : probe_.columns) {
+            views.push_back(c->slice(next_row_, len));
+            cols.push_back(views.back()->handle());
+        }
+        std::vector<ArrayRef> out;
+        std::vector<uint64_t> rows;
+        std::vector<int64_t> nulls;
+        uint64_t pairs = 0;
+        const uint64_t taken = join_window(ctx, cols, len, batch, out, rows, nulls, pairs);
+        const size_t probed = std::min<size_t>(len, taken * batch);
+        joined_ = std::move(out);
+        window_rows_out_ = std::move(rows);
+        window_nulls_ = std::move(nulls);
+        next_in_window_ = 0;
+        at_ = 0;
+        next_row_ += probed;
+        limit_.record(probed, pairs);
+    }
+    std::optional<RecordBatch> next_pulled() {  // one probe batch pulled, one call
+        auto batch = probe_.stream->next_batch();
+        if (!batch) return std::nullopt;
+        const ContextRef ctx = batch_ctx(*batch);
+        ensure_built(ctx);
+        std::vector<const rv_dcolumn *> cols;
+        for (auto &c : batch->columns()) cols.push_back(c->handle());
+        std::vector<ArrayRef> out;
+        std::vector<uint64_t> rows;
+        std::vector<int64_t> nulls;
+        uint64_t pairs = 0;
+        join_window(ctx, cols, batch->num_rows(), std::max<size_t>(1, batch->num_rows()), out, rows, nulls, pairs);
+        limit_.record(batch->num_rows(), pairs);
+        if (rows.empty()) return RecordBatch::new_unchecked(output_schema_, std::move(out), 0);  // a zero-row probe batch
+        std::vector<ArrayRef> arrays;
+        for (size_t j = 0; j < out.size(); ++j) {
+            rv_dcolumn *piece = nullptr;
+            check_stream(rv_slice_known(ctx->raw(), out[j]->handle(), 0, rows[0], nulls[j], &piece));
+            arrays.push_back(Array::adopt(ctx, piece));
+        }
+        return RecordBatch::new_unchecked(output_schema_, std::move(arrays), rows[0]);
+    }
+    static ContextRef batch_ctx(const RecordBatch &b) {
+        try {
+            return b.ctx();
+        } catch (const Error &e) {
+            throw StreamError::execution(e.what());
+        }
+    }
+
+    JoinSide build_, probe_;
+    std::string build_key_, probe_key_;
+    size_t window_rows_;
+    uint64_t max_pairs_;
+    SchemaRef build_schema_, probe_schema_, output_schema_;
+    uint32_t bki_ = 0, pki_ = 0;
+    rv_join_table *table_ = nullptr;
+    ContextRef table_ctx_;
+    std::vector<const rv_dcolumn *> build_handles_;
+    size_t probe_rows_ = 0, next_row_ = 0;
+    std::vector<ArrayRef> joined_;  // the current window's outputs, all its batches back to back
+    std::vector<uint64_t> window_rows_out_;
+    std::vector<int64_t> window_nulls_;
+    size_t next_in_window_ = 0;
+    uint64_t at_ = 0;
+    LimitWindow limit_;
+};
+
 }  // namespace execution
 
 // ---------------------------------------------------------------------------------------
@@ -1483,7 +1680,7 @@ class StreamingPhysicalPlan;
 using StreamingPlanPtr = std::shared_ptr<const StreamingPhysicalPlan>;
 class StreamingPhysicalPlan {
   public:
-    enum Kind { MemorySource, DataFrameSource, CsvFileSource, Filter, GpuFilterProject, Select, Limit } kind = MemorySource;
+    enum Kind { MemorySource, DataFrameSource, CsvFileSource, Filter, GpuFilterProject, Select, Limit, HashJoin } kind = MemorySource;
     // DataFrameSource (streaming.rs:85-94)
     DeviceFrame df;
     size_t df_batch_size = 0;
@@ -1500,6 +1697,8 @@ class StreamingPhysicalPlan {
     execution::LoweredPredicate predicate;
     std::vector<std::string> columns;
     size_t n = 0;
+    StreamingPlanPtr build_side;  // HashJoin { build_side, probe_side = input, build_key, probe_key }, inner
+    std::string build_key, probe_key;
 
     static StreamingPlanPtr memory_source(std::vector<execution::RecordBatch> b) {
         auto p = std::make_shared<StreamingPhysicalPlan>();
@@ -1557,6 +1756,18 @@ class StreamingPhysicalPlan {
         return p;
     }
 
+    // streaming.rs:128-131 (todo!() in the reference), defined by the eager join: the left plan is the build side, the right the
+    // probe side (planner.rs:102-108); one output batch per probe batch
+    static StreamingPlanPtr hash_join(StreamingPlanPtr build, StreamingPlanPtr probe, std::string build_key, std::string probe_key) {
+        auto p = std::make_shared<StreamingPhysicalPlan>();
+        p->kind = HashJoin;
+        p->build_side = std::move(build);
+        p->input = std::move(probe);
+        p->build_key = std::move(build_key);
+        p->probe_key = std::move(probe_key);
+        return p;
+    }
+
     execution::DataStreamRef execute() const {  // streaming.rs:71-133
         using namespace execution;
         try {
@@ -1578,23 +1789,42 @@ class StreamingPhysicalPlan {
                 case Filter: return std::make_unique<FilterStream>(input->execute(), predicate_column);
                 case GpuFilterProject:
                     // over a resident frame the chunker and the operator fuse: no per-batch handles (rv_filter_project_chunked)
-                    if (input->kind == DataFrameSource && !input->df.columns.empty() && input->df.height() > 0 && input->df_batch_size > 0) {
-                        std::vector<ArrayRef> filled;
-                        for (auto &col : input->df.columns) {  // dataframe_to_batches' null fill, once per column instead of once per batch
-                            rv_dcolumn *f = nullptr;
-                            check(rv_fill_nulls(col->context()->raw(), col->handle(), &f));
-                            filled.push_back(Array::adopt(col->context(), f));
-                        }
-                        return std::make_unique<GpuChunkedFilterProjectStream>(input->df.names, std::move(filled), input->df_batch_size, predicate, columns);
-                    }
+                    if (input->kind == DataFrameSource && !input->df.columns.empty() && input->df.height() > 0 && input->df_batch_size > 0)
+                        return std::make_unique<GpuChunkedFilterProjectStream>(input->df.names, input->filled_columns(), input->df_batch_size, predicate, columns);
                     return std::make_unique<GpuFilterProjectStream>(input->execute(), predicate, columns);
                 case Select: return std::make_unique<SelectStream>(input->execute(), columns);
                 case Limit: return std::make_unique<LimitStream>(input->execute(), n);
+                case HashJoin: {
+                    // a resident frame is taken whole, after the null fill: windows of the probe frame, the build frame as it is (an
+                    // empty frame too: it still has its columns' names and dtypes)
+                    auto side = [](const StreamingPhysicalPlan &p) {
+                        JoinSide s;
+                        if (p.kind == DataFrameSource && !p.df.columns.empty() && p.df_batch_size > 0) {
+                            s.names = p.df.names;
+                            s.columns = p.filled_columns();
+                            s.batch_size = p.df_batch_size;
+                        } else {
+                            s.stream = p.execute();
+                        }
+                        return s;
+                    };
+                    return std::make_unique<GpuHashJoinStream>(side(*build_side), side(*input), build_key, probe_key);
+                }
             }
         } catch (const StreamError &e) {
             throw StreamingExecutionError(std::string("Stream error: ") + e.what());
         }
         throw Panic("unreachable");
+    }
+    // dataframe_to_batches' null fill, once per column instead of once per batch (a DataFrameSource)
+    std::vector<execution::ArrayRef> filled_columns() const {
+        std::vector<execution::ArrayRef> filled;
+        for (auto &col : df.columns) {
+            rv_dcolumn *f = nullptr;
+            check(rv_fill_nulls(col->context()->raw(), col->handle(), &f));
+            filled.push_back(execution::Array::adopt(col->context(), f));
+        }
+        return filled;
     }
     std::vector<execution::RecordBatch> collect_batches() const {
         auto s = execute();
