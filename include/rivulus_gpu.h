@@ -44,7 +44,8 @@ typedef enum rv_status {
     RV_ERR_UNSUPPORTED = 5,
     RV_ERR_DEVICE = 6,
     RV_ERR_OOM = 7,
-    RV_ERR_INTERNAL = 8
+    RV_ERR_INTERNAL = 8,
+    RV_ERR_PARSE = 9            /* file_stream.rs:43-122: a CSV cell or line the schema does not accept */
 } rv_status;
 
 /* execution::schema::DataType, src/execution/schema.rs:1-8 */
@@ -187,6 +188,7 @@ typedef struct rv_ctx rv_ctx;         /* one device + one stream + scratch arena
 typedef struct rv_dcolumn rv_dcolumn; /* device-resident array (values + validity)   */
 typedef struct rv_comm rv_comm;       /* RCCL communicator, one rank per process     */
 typedef struct rv_pending rv_pending; /* a fused launch queued by rv_filter_project_begin */
+typedef struct rv_csv_reader rv_csv_reader; /* a CSV file parsed on the device, batch by batch */
 
 /* ---- library / context ------------------------------------------------- */
 uint32_t rv_abi_version(void);
@@ -248,7 +250,10 @@ rv_status rv_ctx_device_info(rv_ctx *ctx, int *compute_units, uint64_t *hbm_byte
  * "inject_failure" = k: the next k query calls on this context (rv_filter_project*, rv_filter_agg) return RV_ERR_DEVICE
  * before anything is launched -- fault injection for the failure handling of rv_group_* (tests/test_group_gpu.py).
  * "bool_cap" = k > 0: Boolean columns compacted behind the pass get output bitmaps of at most k rows (they are sized for the expected
- * survivors + 25 %; more survivors than that and the column takes the scan path after the pass: this forces that fallback in tests). */
+ * survivors + 25 %; more survivors than that and the column takes the scan path after the pass: this forces that fallback in tests).
+ * "csv_slow_cap" = k > 0: a CSV chunk's first list of Float64 cells left to the exact slow kernel holds at most k cells (default:
+ * rows x Float64 columns, at most 2^20); more such cells and the chunk is parsed again with a list of the exact size (forces
+ * that path in tests). */
 rv_status rv_ctx_set_option(rv_ctx *ctx, const char *key, int64_t value);
 /* current value of an option, or of the read-only counters "overflow_reruns" (launches re-run because speculatively sized
  * outputs were too small), "last_selectivity_ppm" (survivors per million rows of the last fused launch, -1: none yet),
@@ -258,7 +263,9 @@ rv_status rv_ctx_set_option(rv_ctx *ctx, const char *key, int64_t value);
  * filter launch of the context so far: what a pushed-down Limit keeps small), "samples_taken" (selectivity samples so far),
  * "speculative_batch_passes", "last_rows_in" / "last_rows_out" (rows / survivors of the last fused pass), "hbm_free_bytes"
  * (what the device reports free right now), "segmented_passes" (queries that ran stretch by stretch, option "segments") and
- * "segment_fallbacks" (... that started so and ran as one pass after all: more survivors than the sample's profile promised). */
+ * "segment_fallbacks" (... that started so and ran as one pass after all: more survivors than the sample's profile promised),
+ * "csv_slow_cells" (Float64 cells of CSV scans on this context that only the exact slow kernel could round) and
+ * "csv_slow_reparses" (CSV chunks parsed a second time because those cells outgrew the first list). */
 rv_status rv_ctx_get_option(rv_ctx *ctx, const char *key, int64_t *value);
 
 /* Device time of the hot-path kernel launches (fused filter+compact, filter+aggregate)
@@ -626,6 +633,27 @@ rv_status rv_group_filter_agg(rv_group *group, const rv_dcolumn *const *shards, 
  * "allreduce_calls", "comm_aborts", "distinct_devices" (0 / 1), "last_agg_filter_us", "last_allreduce_us" (wall time of
  * the two phases of the last rv_group_filter_agg). */
 rv_status rv_group_stat(rv_group *group, const char *key, int64_t *value);
+
+/* ---- CSV scan on the device (CsvFileStream, file_stream.rs:10-368) -------------------------------------------------
+ * The file goes to HBM in pinned chunks (the read of the next chunk overlaps the parse of this one) and gfx950 kernels
+ * split and parse it.  rv_csv_next returns the batches CsvFileStream::next_batch returns, call by call: the header (line
+ * 1) is skipped, blank lines are skipped but counted, a trailing '\r' is stripped, cells are trimmed and "" / "null" is a
+ * null.  batch_rows 0: calculate_adaptive_batch_size.  Int64 / Float64 columns carry a bitmap only in a batch that holds
+ * a null; RV_CSV_NULLS_AS_REFERENCE inverts it as the reference does (file_stream.rs:213-249).
+ * A bad line returns RV_ERR_PARSE with the reference's text in rv_last_error() ("Line 3, field 0: Cannot parse 'x2' as
+ * Int64", "Line 2: Expected 4 fields, found 3"); the rows of that batch before it are dropped and the next call starts
+ * at the line after it.  chunk_bytes 0: 64 MiB; a line longer than a chunk makes the chunk grow.
+ * delimiter: one byte (0 .. 255).
+ * rv_csv_next: out[0 .. ncols) receives device columns (zero-copy slices of the parsed chunk, released with rv_free);
+ * *out_rows == 0: the end of the stream, nothing written to out. */
+#define RV_CSV_NULLS_AS_REFERENCE 1u
+rv_status rv_csv_open(rv_ctx *ctx, const char *path, const rv_dtype *dtypes, uint32_t ncols, uint32_t delimiter,
+                      uint64_t batch_rows, uint32_t flags, uint64_t chunk_bytes, rv_csv_reader **out);
+rv_status rv_csv_next(rv_csv_reader *reader, rv_dcolumn **out, uint64_t *out_rows);
+/* batch_rows: the rows of a full batch; lines: file lines parsed so far (the header and blank lines included);
+ * bytes_read: file bytes read so far */
+rv_status rv_csv_reader_info(const rv_csv_reader *reader, uint64_t *batch_rows, uint64_t *lines, uint64_t *bytes_read);
+rv_status rv_csv_close(rv_csv_reader *reader);
 
 /* Pin caller-owned host memory (e.g. a shared-memory segment several one-GPU processes gather into) so that
  * rv_download / rv_upload move it by DMA. */

@@ -25,7 +25,9 @@ RV_NULL_DROPS, RV_NULL_IS_LEAST = 0, 1
 RV_COMM_ID_BYTES = 128
 OPS = {"==": RV_EQ, "!=": RV_NE, "<": RV_LT, ">": RV_GT, "<=": RV_LE, ">=": RV_GE, "is_true": RV_IS_TRUE}
 STATUS_NAMES = ["RV_OK", "RV_ERR_INVALID_ARG", "RV_ERR_LENGTH_MISMATCH", "RV_ERR_TYPE_MISMATCH",
-                "RV_ERR_OUT_OF_BOUNDS", "RV_ERR_UNSUPPORTED", "RV_ERR_DEVICE", "RV_ERR_OOM", "RV_ERR_INTERNAL"]
+                "RV_ERR_OUT_OF_BOUNDS", "RV_ERR_UNSUPPORTED", "RV_ERR_DEVICE", "RV_ERR_OOM", "RV_ERR_INTERNAL", "RV_ERR_PARSE"]
+RV_ERR_INVALID_ARG, RV_ERR_UNSUPPORTED, RV_ERR_PARSE = 1, 5, 9
+RV_CSV_NULLS_AS_REFERENCE = 1
 
 
 class RvColumn(C.Structure):
@@ -179,6 +181,10 @@ PROTOTYPES = {
     "rv_group_stat": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int64)]),
     "rv_host_register": (C.c_int, [_P, _P, C.c_size_t]),
     "rv_host_unregister": (C.c_int, [_P, _P]),
+    "rv_csv_open": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int), C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, _PP]),
+    "rv_csv_next": (C.c_int, [_P, _PP, _U64P]),
+    "rv_csv_reader_info": (C.c_int, [_P, _U64P, _U64P, _U64P]),
+    "rv_csv_close": (C.c_int, [_P]),
 }
 
 _lib = None
@@ -508,6 +514,51 @@ def _handles(cols: Sequence[DeviceColumn]):
     return arr
 
 
+class CsvReader:
+    """rv_csv_reader: a CSV file parsed on the device.  Iterating yields one list of DeviceColumn per batch, the batches
+    CsvFileStream::next_batch returns; a bad line raises RvError(RV_ERR_PARSE) and the next call goes on after it."""
+    def __init__(self, ctx: "Context", handle, ncols: int):
+        self.ctx, self.handle, self.ncols = ctx, handle, ncols
+
+    def next_batch(self) -> Optional[List[DeviceColumn]]:
+        out = (C.c_void_p * max(1, self.ncols))()
+        rows = C.c_uint64()
+        _check(load().rv_csv_next(self.handle, out, C.byref(rows)))
+        if rows.value == 0:
+            return None
+        return [DeviceColumn(self.ctx, C.c_void_p(out[i])) for i in range(self.ncols)]
+
+    def __iter__(self):
+        while True:
+            b = self.next_batch()
+            if b is None:
+                return
+            yield b
+
+    def info(self):
+        """(rows of a full batch, file lines parsed so far, file bytes read so far)"""
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(load().rv_csv_reader_info(self.handle, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def close(self):
+        if self.handle is not None:
+            load().rv_csv_close(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Context:
     def __init__(self, device: int = 0):
         self.handle = None
@@ -644,6 +695,19 @@ class Context:
         out = C.c_void_p()
         _check(load().rv_concat(self.handle, _handles(parts), len(parts), C.byref(out)))
         return DeviceColumn(self, out)
+
+    def csv_open(self, path: str, dtypes: Sequence[int], delimiter: str = ",", batch_rows: int = 0, nulls_as_reference: bool = True,
+                 chunk_bytes: int = 0) -> CsvReader:
+        """rv_csv_open: CsvFileStream over `path` with the column types `dtypes`, parsed on the device (batch_rows 0: adaptive,
+        chunk_bytes 0: the default chunk)."""
+        d = delimiter.encode() if isinstance(delimiter, str) else bytes([delimiter])
+        if len(d) != 1:
+            raise ValueError("the delimiter is one byte")
+        arr = (C.c_int * max(1, len(dtypes)))(*dtypes)
+        out = C.c_void_p()
+        _check(load().rv_csv_open(self.handle, os.fsencode(path), arr, len(dtypes), d[0], batch_rows,
+                                  RV_CSV_NULLS_AS_REFERENCE if nulls_as_reference else 0, chunk_bytes, C.byref(out)))
+        return CsvReader(self, out, len(dtypes))
 
     def join_build(self, key: DeviceColumn) -> "JoinTable":
         """PhysicalPlan::HashJoin's build side (plan.rs:183-192) hashed on the device."""

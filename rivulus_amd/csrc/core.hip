@@ -243,6 +243,7 @@ const char *rv_status_name(rv_status s) {
         case RV_ERR_DEVICE: return "RV_ERR_DEVICE";
         case RV_ERR_OOM: return "RV_ERR_OOM";
         case RV_ERR_INTERNAL: return "RV_ERR_INTERNAL";
+        case RV_ERR_PARSE: return "RV_ERR_PARSE";
     }
     return "RV_ERR_?";
 }
@@ -391,6 +392,10 @@ rv_status rv_ctx_set_option(rv_ctx *ctx, const char *key, int64_t value) {
         else if (k == "agg_grid") ctx->opt_agg_grid = value;
         else if (k == "bools_in_pass") ctx->opt_bools_in_pass = value;
         else if (k == "inject_failure") ctx->opt_inject_failure = value;
+        else if (k == "csv_slow_cap") {
+            require(value >= 0 && value < (int64_t(1) << 31), RV_ERR_INVALID_ARG, "csv_slow_cap must be in [0, 2^31)");
+            ctx->opt_csv_slow_cap = value;
+        }
         else if (k == "join_hash_bits") {
             require(value >= 0 && value < 64, RV_ERR_INVALID_ARG, "join_hash_bits must be in [0, 64)");
             ctx->opt_join_hash_bits = value;
@@ -437,6 +442,9 @@ rv_status rv_ctx_get_option(rv_ctx *ctx, const char *key, int64_t *value) {
         else if (k == "spin_limit") *value = ctx->opt_spin_limit;
         else if (k == "agg_grid") *value = ctx->opt_agg_grid;
         else if (k == "bools_in_pass") *value = ctx->opt_bools_in_pass;
+        else if (k == "csv_slow_cap") *value = ctx->opt_csv_slow_cap;
+        else if (k == "csv_slow_cells") *value = static_cast<int64_t>(ctx->csv_slow_cells);
+        else if (k == "csv_slow_reparses") *value = static_cast<int64_t>(ctx->csv_slow_reparses);
         else if (k == "inject_failure") *value = ctx->opt_inject_failure;
         else if (k == "join_hash_bits") *value = ctx->opt_join_hash_bits;
         else if (k == "out_sizing") *value = ctx->opt_out_sizing;

@@ -250,6 +250,9 @@ struct rv_ctx {
                                     // for it a bounded time and leaks the context's device memory rather than wait without end
     int64_t opt_join_hash_bits = 0; // tests: join tables built from now on hash keys to this many low bits (long collision chains); 0: all 64
     int64_t opt_bools_in_pass = 0;  // 1: projected Boolean columns are compacted inside the fused pass (lane-form PEXT)
+    int64_t opt_csv_slow_cap = 0;   // tests: k > 0 caps a CSV chunk's first list of undecided Float64 cells at k (forces the re-parse)
+    uint64_t csv_slow_cells = 0;    // Float64 cells the CSV scan's exact slow kernel decided (csv_f64_slow), context total
+    uint64_t csv_slow_reparses = 0; // CSV chunks parsed twice because their undecided cells outgrew the first list
     unsigned long long last_stamps[32] = {};
     // per (kernel, dynamic LDS bytes): resident workgroups per CU; per kernel: largest LDS size enabled so far
     std::map<std::pair<const void *, size_t>, int> occupancy;

@@ -707,6 +707,10 @@ using Literal = std::variant<std::monostate, int64_t, double, bool, std::string>
 // bit, its defect included -- reproduces that; CsvNulls::AsIntended marks the null cells as null and must be asked
 // for ("CSV nulls").  String and Boolean columns are right in the reference.
 enum class CsvNulls { AsIntended, AsReference };
+// Where the cells are parsed.  Host: one host core reads and parses every line, then each batch is uploaded.  Device: the
+// file goes to HBM in pinned chunks and gfx950 kernels split and parse it (rv_csv_open / rv_csv_next): the same batches and
+// the same errors, call by call.
+enum class CsvScan { Host, Device };
 
 inline size_t calculate_adaptive_batch_size(const Schema &schema) {  // file_stream.rs:345-368
     size_t row_bytes = 0;
@@ -727,17 +731,31 @@ class CsvFileStream : public DataStream {
   public:
     // Err(String) of CsvFileStream::new (file_stream.rs:21-41) -> Error(RV_ERR_INVALID_ARG, same text)
     CsvFileStream(ContextRef ctx, const std::string &path, SchemaRef schema, std::optional<size_t> batch_size = std::nullopt,
-                  std::optional<char> delimiter = std::nullopt, CsvNulls nulls = CsvNulls::AsReference)
-        : ctx_(std::move(ctx)), file_(path), schema_(std::move(schema)), batch_size_(batch_size ? *batch_size : calculate_adaptive_batch_size(*schema_)),
+                  std::optional<char> delimiter = std::nullopt, CsvNulls nulls = CsvNulls::AsReference, CsvScan scan = CsvScan::Host)
+        : ctx_(std::move(ctx)), schema_(std::move(schema)), batch_size_(batch_size ? *batch_size : calculate_adaptive_batch_size(*schema_)),
           delimiter_(delimiter.value_or(',')), nulls_(nulls) {
+        if (scan == CsvScan::Device) {  // rv_csv_open gives the same two errors, in the same order
+            std::vector<rv_dtype> types;
+            for (auto &f : schema_->fields()) types.push_back(to_rv(f.data_type()));
+            check(rv_csv_open(ctx_->raw(), path.c_str(), types.data(), static_cast<uint32_t>(types.size()), static_cast<unsigned char>(delimiter_),
+                              batch_size_, nulls_ == CsvNulls::AsReference ? RV_CSV_NULLS_AS_REFERENCE : 0u, 0, &reader_));
+            return;
+        }
+        file_.open(path);
         if (!file_) throw Error(RV_ERR_INVALID_ARG, "Failed to open file: " + std::string(std::strerror(errno)));
         for (auto &f : schema_->fields())
             if (f.data_type() == DataType::Null) throw Error(RV_ERR_UNSUPPORTED, "Null columns are outside the device path");
     }
+    ~CsvFileStream() override {
+        if (reader_) rv_csv_close(reader_);
+    }
+    CsvFileStream(const CsvFileStream &) = delete;
+    CsvFileStream &operator=(const CsvFileStream &) = delete;
     SchemaRef schema() const override { return schema_; }
     size_t batch_size() const { return batch_size_; }
 
     std::optional<RecordBatch> next_batch() override {  // read_batch, file_stream.rs:124-197
+        if (reader_) return next_device_batch();
         if (finished_) return std::nullopt;
         const size_t ncols = schema_->num_fields();
         std::vector<std::vector<int64_t>> ints(ncols);
@@ -790,6 +808,24 @@ class CsvFileStream : public DataStream {
     }
 
   private:
+    std::optional<RecordBatch> next_device_batch() {
+        // batch size 0: read_batch gathers no row and every call is the end (rv_csv_open would take 0 for "adaptive")
+        if (batch_size_ == 0) return std::nullopt;
+        const size_t ncols = schema_->num_fields();
+        std::vector<rv_dcolumn *> out(std::max<size_t>(ncols, 1), nullptr);
+        uint64_t rows = 0;
+        const rv_status s = rv_csv_next(reader_, out.data(), &rows);
+        if (s == RV_ERR_PARSE) fail(rv_last_error());
+        check(s);
+        if (rows == 0) return std::nullopt;
+        std::vector<ArrayRef> cols;
+        for (size_t c = 0; c < ncols; ++c) cols.push_back(Array::adopt(ctx_, out[c]));
+        try {
+            return RecordBatch::try_new(schema_, std::move(cols));
+        } catch (const Error &e) {
+            throw StreamError::execution(std::string("Failed to create RecordBatch: ") + e.what());
+        }
+    }
     static std::string trim(const std::string &s) {
         size_t b = 0, e = s.size();
         while (b < e && std::isspace(static_cast<unsigned char>(s[b]))) ++b;
@@ -877,6 +913,7 @@ class CsvFileStream : public DataStream {
     CsvNulls nulls_;
     size_t current_line_ = 0;
     bool finished_ = false;
+    rv_csv_reader *reader_ = nullptr;  // CsvScan::Device
 };
 
 struct CompareTerm {
@@ -1691,6 +1728,7 @@ class StreamingPhysicalPlan {
     std::optional<size_t> csv_batch_size;
     std::optional<char> csv_delimiter;
     execution::CsvNulls csv_nulls = execution::CsvNulls::AsReference;
+    execution::CsvScan csv_scan = execution::CsvScan::Host;
     std::vector<execution::RecordBatch> batches;
     StreamingPlanPtr input;
     std::string predicate_column;
@@ -1714,7 +1752,8 @@ class StreamingPhysicalPlan {
         return p;
     }
     static StreamingPlanPtr csv_file_source(ContextRef ctx, std::string path, execution::SchemaRef schema, std::optional<size_t> batch_size = std::nullopt,
-                                            std::optional<char> delimiter = std::nullopt, execution::CsvNulls nulls = execution::CsvNulls::AsReference) {
+                                            std::optional<char> delimiter = std::nullopt, execution::CsvNulls nulls = execution::CsvNulls::AsReference,
+                                            execution::CsvScan scan = execution::CsvScan::Host) {
         auto p = std::make_shared<StreamingPhysicalPlan>();
         p->kind = CsvFileSource;
         p->csv_ctx = std::move(ctx);
@@ -1723,6 +1762,7 @@ class StreamingPhysicalPlan {
         p->csv_batch_size = batch_size;
         p->csv_delimiter = delimiter;
         p->csv_nulls = nulls;
+        p->csv_scan = scan;
         return p;
     }
     static StreamingPlanPtr filter(StreamingPlanPtr in, std::string predicate_column) {
@@ -1782,7 +1822,7 @@ class StreamingPhysicalPlan {
                 }
                 case CsvFileSource:
                     try {
-                        return std::make_unique<CsvFileStream>(csv_ctx, csv_path, csv_schema, csv_batch_size, csv_delimiter, csv_nulls);
+                        return std::make_unique<CsvFileStream>(csv_ctx, csv_path, csv_schema, csv_batch_size, csv_delimiter, csv_nulls, csv_scan);
                     } catch (const Error &e) {
                         throw StreamingExecutionError(std::string("Invalid operation: ") + e.what());  // streaming.rs:102-103
                     }
