@@ -191,256 +191,393 @@ static void launch_redo(rv_ctx *ctx, FusedLaunch &L) {
     RV_HIP(hipGetLastError());
 }
 
-// One single-pass launch: predicate over `cols`, compaction of the columns in proj; queued on the context's
-// stream, not waited for.  out[] / sel_out receive the output handles at once (their length is set by
-// fused_finish).
-void fused_begin(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, const rv_term *terms,
-                 uint32_t nterms, rv_null_policy policy, const uint32_t *proj, uint32_t nproj,
-                 rv_dcolumn **out, rv_dcolumn **sel_out, FusedLaunch &L, const ExprInfo *ex, BatchReq *req,
-                 RangeOffsets *ranges) {
+struct Bound {
+    const rv_dcolumn *const *cols;
+    rvk::ScanInputs *in;
+    std::vector<int> value_slot, bool_slot;  // per batch column: its slot, or -1
+    std::vector<char> never_null;            // per batch column: no null among the survivors (its output needs no bitmap)
+    int nvals = 0, nbools = 0, npred = 0;  // value slots [0, npred): the 8-byte columns the terms read (the direct kernel loads them first)
+
+    int add_value(const rv_dcolumn *col) {  // a slot of its own
+        require(nvals < rvk::kMaxValueCols, RV_ERR_UNSUPPORTED, "too many 8-byte columns for one pass");
+        in->cols[nvals] = dev_view(col);
+        return nvals++;
+    }
+    int value_of(uint32_t c) {
+        if (value_slot[c] < 0) value_slot[c] = add_value(cols[c]);
+        return value_slot[c];
+    }
+    int bool_of(uint32_t c) {
+        if (bool_slot[c] < 0) {
+            require(nbools < rvk::kMaxBoolCols, RV_ERR_UNSUPPORTED, "too many Boolean predicate columns for one pass");
+            bool_slot[c] = nbools;
+            in->bcols[nbools++] = dev_view(cols[c]);
+        }
+        return bool_slot[c];
+    }
+};
+
+// The predicate's columns bound to slots of `in` and its terms lowered there.
+static Bound bind_inputs(const rv_dcolumn *const *cols, uint32_t ncols, const rv_term *terms, uint32_t nterms, rv_null_policy policy,
+                         const ExprInfo *ex, rvk::ScanInputs &in) {
     require(nterms >= 1 && nterms <= static_cast<uint32_t>(rvk::kMaxTerms), RV_ERR_UNSUPPORTED,
             fmt("predicate needs 1..%d terms, got %u", rvk::kMaxTerms, nterms));
-    const uint64_t n = ncols ? cols[0]->length : 0;
-    const uint64_t signature = predicate_signature(cols, ncols, terms, nterms, policy, ex);
-    L.signature = signature;
-    double seen = L.place ? L.place_selectivity : ctx->seen_selectivity(signature);  // (a segment: its own density, out of the profile)
-    bool sampled_now = false;  // `seen` comes from a sample taken by this call: its histogram is in ctx->last_sample_hist
-
-    rvk::FusedParams &p = L.p;
-    p = rvk::FusedParams{};
-    p.in.n = n;
-    p.in.nterms = static_cast<int32_t>(nterms);
-    std::vector<int> value_slot(ncols, -1), bool_slot(ncols, -1);
-    int nvals = 0, nbools = 0;
-    auto slot_of_value = [&](uint32_t c) {
-        if (value_slot[c] < 0) {
-            require(nvals < rvk::kMaxValueCols, RV_ERR_UNSUPPORTED, "too many 8-byte columns for one pass");
-            value_slot[c] = nvals;
-            p.in.cols[nvals++] = dev_view(cols[c]);
-        }
-        return value_slot[c];
-    };
+    Bound b{cols, &in, std::vector<int>(ncols, -1), std::vector<int>(ncols, -1), std::vector<char>(ncols, 0)};
+    in.n = ncols ? cols[0]->length : 0;
+    in.nterms = static_cast<int32_t>(nterms);
     for (uint32_t t = 0; t < nterms; ++t) {
         const uint32_t c = terms[t].column;
         require(c < ncols, RV_ERR_INVALID_ARG, fmt("term %u references column %u of %u", t, c, ncols));
         const rv_dtype ct = cols[c]->dtype;
         require(is_value_type(ct) || ct == RV_BOOLEAN, RV_ERR_UNSUPPORTED,
                 "predicate columns must be Int64, Float64 or Boolean on the device path");
-        uint32_t slot;
-        if (ct == RV_BOOLEAN) {
-            if (bool_slot[c] < 0) {
-                require(nbools < rvk::kMaxBoolCols, RV_ERR_UNSUPPORTED, "too many Boolean predicate columns for one pass");
-                bool_slot[c] = nbools;
-                p.in.bcols[nbools++] = dev_view(cols[c]);
-            }
-            slot = static_cast<uint32_t>(bool_slot[c]);
-        } else {
-            slot = static_cast<uint32_t>(slot_of_value(c));
-        }
-        p.in.terms[t] = lower_term(terms[t], ct, policy, slot);
-        if (ex) p.in.terms[t].set_literal(ex->negate[t] != 0, ex->group_end[t] != 0);
+        const int slot = ct == RV_BOOLEAN ? b.bool_of(c) : b.value_of(c);
+        in.terms[t] = lower_term(terms[t], ct, policy, static_cast<uint32_t>(slot));
+        if (ex) in.terms[t].set_literal(ex->negate[t] != 0, ex->group_end[t] != 0);
     }
-    const int npred = nvals;  // value slots [0, npred): the 8-byte columns the terms read (the direct kernel loads them first)
+    b.npred = b.nvals;
 
     // a nullable column tested by a term that drops its null rows has no null among the survivors: its output
     // needs no bitmap (and the builder would drop it anyway, primitive.rs:179-185)
-    std::vector<char> never_null(ncols, 0);
     if (!ex) {
         for (uint32_t t = 0; t < nterms; ++t)
-            if (is_value_type(cols[terms[t].column]->dtype) && !p.in.terms[t].null_v()) never_null[terms[t].column] = 1;
+            if (is_value_type(cols[terms[t].column]->dtype) && !in.terms[t].null_v()) b.never_null[terms[t].column] = 1;
     } else {
         // OR / NOT: only strict propagation (RV_NULL_DROPS) guarantees it, and then for every column the expression reads
-        p.in.expr_mode = 1;
-        p.in.negate_result = ex->negate_result ? 1 : 0;
+        in.expr_mode = 1;
+        in.negate_result = ex->negate_result ? 1 : 0;
         if (ex->strict) {
             for (uint32_t c : ex->strict_cols) {
                 require(c < ncols, RV_ERR_INTERNAL, "strict column out of range");
                 if (is_value_type(cols[c]->dtype)) {
-                    never_null[c] = 1;
-                    if (cols[c]->validity) p.in.strict_values |= 1u << slot_of_value(c);
+                    b.never_null[c] = 1;
+                    if (cols[c]->validity) in.strict_values |= 1u << b.value_of(c);
                 } else if (cols[c]->dtype == RV_BOOLEAN && cols[c]->validity) {
-                    if (bool_slot[c] < 0) {  // its literals were simplified away: still read for its nulls
-                        require(nbools < rvk::kMaxBoolCols, RV_ERR_UNSUPPORTED, "too many Boolean predicate columns for one pass");
-                        bool_slot[c] = nbools;
-                        p.in.bcols[nbools++] = dev_view(cols[c]);
-                    }
-                    p.in.strict_bools |= 1u << bool_slot[c];
+                    in.strict_bools |= 1u << b.bool_of(c);  // (its literals may have been simplified away: still read for its nulls)
                 }
             }
         }
     }
+    return b;
+}
 
-    // A predicate this context has not run over this data: its selectivity from a strided sample (agg_kernel.hpp,
-    // sample_count_kernel; ~10 us of device time, one launch, the host spins on a pinned word), so that the FIRST launch is already
-    // sized for it -- the reference's operators have no warm-up call (stream.rs:136-158), and a one-shot collect() is always
-    // the first call.  Not for small tables: below 2^25 rows a pass is a few tens of microseconds, and a mis-sized one costs less
-    // than the sample.
-    if (seen < 0.0 && !L.place && ctx->opt_sample >= 0 && n >= (ctx->opt_sample > 0 ? static_cast<uint64_t>(ctx->opt_sample) : rvt::kSampleFromRows)) {
-        const double s = sample_selectivity(ctx, p.in, nvals);
-        if (s >= 0.0) {
-            seen = s;
-            sampled_now = true;
-        }
-    }
-    if (L.sample_only) {  // expected_selectivity(): the caller wanted what this launch would have been sized by, nothing more
-        L.sampled = seen;
-        if (seen >= 0.0 && ctx->seen_selectivity(signature) < 0.0) {  // (the pass itself will not sample again)
-            rv_ctx::SeenPredicate *q = ctx->remember_selectivity(signature, seen);
-            if (sampled_now) keep_sample(ctx, q);
-        }
-        return;
-    }
+// A predicate this context has not run over this data: its selectivity from a strided sample (agg_kernel.hpp,
+// sample_count_kernel; ~10 us of device time, one launch, the host spins on a pinned word), so that the FIRST launch is already
+// sized for it -- the reference's operators have no warm-up call (stream.rs:136-158), and a one-shot collect() is always
+// the first call.  Not for small tables: below 2^25 rows a pass is a few tens of microseconds, and a mis-sized one costs less
+// than the sample.  The sample's histogram and profile travel with the predicate's memory (the pass will store its true selectivity).
+// < 0: no sample taken.
+static double first_call_sample(rv_ctx *ctx, const rvk::ScanInputs &in, int nvals, uint64_t signature) {
+    if (ctx->opt_sample < 0 || in.n < (ctx->opt_sample > 0 ? static_cast<uint64_t>(ctx->opt_sample) : rvt::kSampleFromRows)) return -1.0;
+    const double s = sample_selectivity(ctx, in, nvals);
+    if (s >= 0.0) keep_sample(ctx, ctx->remember_selectivity(signature, s));
+    return s;
+}
 
-    if (sampled_now) {  // the sample's histogram travels with the predicate's memory (the pass will store its true selectivity)
-        keep_sample(ctx, ctx->remember_selectivity(signature, seen));
-    }
-
-    // Output capacity (output_capacity above).  Option "out_sizing": 0 = sized from the predicate's known selectivity for big tables,
-    // for every row otherwise; -1 = always for every row (no second pass, 2x the input in HBM); 1 = the context's last observed
-    // selectivity x 1.5 + 1 % (a stream of similar batches), k >= 2 = a caller-given bound of k rows per million.  A launch that
-    // overflows its outputs still counts exactly; fused_finish then re-runs it with buffers of the exact size
-    // (record_batch.rs:131-178 never over-allocates either: the builders grow).
-    // (a stretch appends at row place_base of the caller's buffers: pointers rounded down to a 128-byte line, the rest enters the
-    // chain as the output row of its first survivor -- FusedParams::out_bias -- and every buffer and capacity below counts from there)
-    const uint32_t bias = L.place ? static_cast<uint32_t>(L.place_base & 15) : 0u;
-    const uint64_t cap_out = L.place ? (L.place_capacity > L.place_base ? L.place_capacity - L.place_base : 0) + bias : output_capacity(ctx, n, seen);
-    p.out_capacity = cap_out;
-    p.out_bias = bias;
-    L.out_bias = bias;
-    ctx->fused_rows_scanned += n;
-    L.n = n;
-    L.out_dtypes.clear();
-    // outputs
-    std::vector<OutCol> &outs = L.outs;
-    outs.assign(nproj, OutCol{});
-    size_t stage_row_bytes = 0;
+// Every projected column bound to a value slot or to bit streams, its output handle created (in out[] at once: the callers free it on
+// an error); alloc_outputs gives it buffers.  Returns the bytes a row of the outputs takes in an LDS slot.
+static size_t bind_outputs(Bound &b, uint32_t ncols, const uint32_t *proj, uint32_t nproj, rv_dcolumn **out, FusedLaunch &L) {
+    rvk::FusedParams &p = L.p;
+    L.outs.assign(nproj, OutCol{});
+    size_t row_bytes = 0;
+    uint32_t projected = 0;  // value slots an output already writes
     int nxs = 0;
     for (uint32_t j = 0; j < nproj; ++j) {
         const uint32_t c = proj[j];
         require(c < ncols, RV_ERR_INVALID_ARG, fmt("projection %u references column %u of %u", j, c, ncols));
-        const rv_dcolumn *src = cols[c];
-        auto *o = new rv_dcolumn();
-        outs[j].col = o;
-        out[j] = o;
-        o->dtype = src->dtype;
+        const rv_dcolumn *src = b.cols[c];
+        OutCol &o = L.outs[j];
+        o.col = out[j] = new rv_dcolumn();
+        o.col->dtype = src->dtype;
         if (is_value_type(src->dtype)) {
             // the same source column projected twice shares nothing: give it its own slot view
-            int slot = value_slot[c];
-            if (slot >= 0 && p.out_values[slot]) {  // already projected once: duplicate slot
-                require(nvals < rvk::kMaxValueCols, RV_ERR_UNSUPPORTED, "too many 8-byte columns for one pass");
-                slot = nvals;
-                p.in.cols[nvals++] = dev_view(src);
-            } else {
-                slot = slot_of_value(c);
-            }
-            outs[j].value_slot = slot;
-            if (L.place) {  // the caller's buffer, from row place_base on
-                o->values = (*L.place)[j];
-                p.out_values[slot] = static_cast<uint64_t *>(o->values->ptr) + (L.place_base - bias);
-            } else {
-                o->values = pool_alloc(ctx, std::max<size_t>(elem_bytes(src->dtype, cap_out), 8));
-                p.out_values[slot] = static_cast<uint64_t *>(o->values->ptr);
-            }
-            stage_row_bytes += 8;
-            if (src->validity && !never_null[c]) {
-                o->validity = pool_alloc(ctx, zeroed_bitmap_bytes(cap_out));
-                RV_HIP(hipMemsetAsync(o->validity->ptr, 0, zeroed_bitmap_bytes(cap_out), ctx->stream));
-                p.out_validity[slot] = static_cast<uint64_t *>(o->validity->ptr);
-                stage_row_bytes += 1;
-            }
+            const int slot = b.value_slot[c];
+            o.value_slot = slot >= 0 && (projected >> slot & 1u) ? b.add_value(src) : b.value_of(c);
+            projected |= 1u << o.value_slot;
+            o.validity = src->validity && !b.never_null[c];
+            row_bytes += o.validity ? 9 : 8;
         } else if (src->dtype == RV_BOOLEAN) {
             require(nxs + (src->validity ? 2 : 1) <= rvk::kMaxBitStreams, RV_ERR_UNSUPPORTED,
                     "too many Boolean columns for one pass");
-            const size_t wb = zeroed_bitmap_bytes(cap_out);
-            o->values = pool_alloc(ctx, wb);
-            RV_HIP(hipMemsetAsync(o->values->ptr, 0, wb, ctx->stream));
-            rvk::BitStream bs{};
+            rvk::BitStream &bs = p.xs[nxs];
             bs.src = static_cast<const uint8_t *>(src->values->ptr);
             bs.src_bytes = src->values->bytes;
             bs.mask = src->validity ? static_cast<const uint8_t *>(src->validity->ptr) : nullptr;
             bs.mask_bytes = src->validity ? src->validity->bytes : 0;
             bs.offset = src->offset;
-            bs.out = static_cast<uint64_t *>(o->values->ptr);
-            outs[j].xs_values = nxs;
-            p.xs[nxs++] = bs;
-            stage_row_bytes += 1;
+            o.xs_values = nxs++;
+            row_bytes += src->validity ? 2 : 1;
             if (src->validity) {
-                o->validity = pool_alloc(ctx, wb);
-                RV_HIP(hipMemsetAsync(o->validity->ptr, 0, wb, ctx->stream));
-                rvk::BitStream vs{};
+                rvk::BitStream &vs = p.xs[nxs];
                 vs.src = static_cast<const uint8_t *>(src->validity->ptr);
                 vs.src_bytes = src->validity->bytes;
                 vs.offset = src->offset;
-                vs.out = static_cast<uint64_t *>(o->validity->ptr);
-                outs[j].xs_valid = nxs;
-                p.xs[nxs++] = vs;
-                stage_row_bytes += 1;
+                o.xs_valid = nxs++;
             }
         } else {
             throw Error(RV_ERR_UNSUPPORTED, "only Int64, Float64 and Boolean columns are compacted on the device path");
         }
     }
     p.nxs = nxs;
+    return row_bytes;
+}
 
-    rv_dcolumn *sel = nullptr;
-    auto make_selection = [&] {
-        sel = new rv_dcolumn();
-        *sel_out = sel;
-        sel->dtype = RV_BOOLEAN;
-        sel->length = n;
-        sel->null_count = 0;
-        sel->values = pool_alloc(ctx, std::max<size_t>(bitmap_words_bytes(n), 8));
-        p.out_selection = static_cast<uint64_t *>(sel->values->ptr);
+// Buffers of every output of L for `cap` rows, bitmaps zeroed on the stream (kernels OR their edge words into them).  A stretch's
+// values land in the caller's buffers from row place_base on (out_bias rows before it: the pointers are rounded down to a 128-byte line).
+// The pass's outputs (fused_begin) and those of its re-run after an output overflow (fused_finish).
+static void alloc_outputs(rv_ctx *ctx, FusedLaunch &L, uint64_t cap) {
+    rvk::FusedParams &p = L.p;
+    p.out_capacity = cap;
+    const size_t wb = zeroed_bitmap_bytes(cap);
+    auto zeroed_bitmap = [&](DevBufRef &buf) {
+        buf = pool_alloc(ctx, wb);
+        RV_HIP(hipMemsetAsync(buf->ptr, 0, wb, ctx->stream));
+        return static_cast<uint64_t *>(buf->ptr);
     };
-    // a selection bitmap wanted only for per-batch counts is decided below, once the geometry is known
-    const bool sel_deferred = sel_out && req && req->sel_optional && n > 0;
-    if (sel_out && !sel_deferred) make_selection();
-    if (sel_deferred) *sel_out = nullptr;
-    if (n == 0) {
-        for (auto &o : outs) {
-            o.col->length = 0;
-            o.col->null_count = 0;
-            o.col->validity.reset();
+    for (size_t j = 0; j < L.outs.size(); ++j) {
+        const OutCol &o = L.outs[j];
+        if (o.value_slot >= 0) {
+            if (L.place) {
+                o.col->values = (*L.place)[j];
+                p.out_values[o.value_slot] = static_cast<uint64_t *>(o.col->values->ptr) + (L.place_base - L.out_bias);
+            } else {
+                o.col->values = pool_alloc(ctx, std::max<size_t>(elem_bytes(o.col->dtype, cap), 8));
+                p.out_values[o.value_slot] = static_cast<uint64_t *>(o.col->values->ptr);
+            }
+            if (o.validity) p.out_validity[o.value_slot] = zeroed_bitmap(o.col->validity);
+        } else {
+            p.xs[o.xs_values].out = zeroed_bitmap(o.col->values);
+            if (o.xs_valid >= 0) p.xs[o.xs_valid].out = zeroed_bitmap(o.col->validity);
         }
-        L.launched = false;
-        return;
     }
+}
 
+// The selection bitmap of L's pass, in *sel_out at once.
+static void make_selection(rv_ctx *ctx, FusedLaunch &L, rv_dcolumn **sel_out) {
+    auto *sel = new rv_dcolumn();
+    *sel_out = sel;
+    sel->dtype = RV_BOOLEAN;
+    sel->length = L.p.in.n;
+    sel->null_count = 0;
+    sel->values = pool_alloc(ctx, std::max<size_t>(bitmap_words_bytes(L.p.in.n), 8));
+    L.p.out_selection = static_cast<uint64_t *>(sel->values->ptr);
+}
+
+// What the launch will be.  Decided before anything is allocated or queued for it.
+struct LaunchChoice {
+    const rvk::FusedEntry *staged = nullptr;   // the staged pass's instantiation, last tried
+    const rvk::DirectEntry *direct = nullptr;  // the direct kernel's (runs instead when set)
+    int r = 0, vec = 1, waves = 0, flags = 0;  // of the kernel that runs
+    void (*fn)(const rvk::FusedParams) = nullptr;
+    int need = 0;
+    size_t stages = 3, lds = 0, stage_row_bytes = 0;
+    uint32_t cap = 0, ntiles = 0;
+    uint64_t tile_rows = 0;
+    bool make_selection = false;  // the selection bitmap deferred for per-batch counts is wanted after all (the pass cannot count them)
+    double redo_expected = 0.0;   // share of the staged pass's wave ranges expected to outgrow their slots
+};
+
+// per-batch counts out of the pass: a batch must be a whole number of the geometry's wave ranges (64 x rows per lane)
+static bool counts_in_pass(const BatchReq *req, int r) { return req && req->counts && req->chunk_rows % (64u * static_cast<uint64_t>(r)) == 0; }
+
+// The direct instantiation for this launch's columns and features, or none.
+static const rvk::DirectEntry *find_direct(rv_ctx *ctx, const Bound &b, int nv_out, double seen, const BatchReq *req, const RangeOffsets *ranges) {
+    const rvk::DirectEntry *found = nullptr;
+    const int npred = b.npred, nvals = b.nvals;
+    int dflags = b.nbools ? (rvk::FF_VALIDITY | rvk::FF_BOOL) : 0;
+    if (ctx->opt_stamp) dflags |= rvk::FF_STAMP;  // diagnostic instantiations (phase cycle sums), a few geometries only
+    for (int s = 0; s < npred; ++s)
+        if (b.in->cols[s].validity) dflags |= rvk::FF_VALIDITY;
+    if (nv_out) dflags |= rvk::FF_VALIDITY | rvk::FF_OUTVALID;
+    // the first listed instantiation that covers the inputs' features (listed leanest first) -- among those whose wave
+    // ranges serve the caller's side outputs, when it asks for any: wave offsets need a range that tiles 4096 rows, per-batch
+    // counts a batch that is a whole number of ranges
+    const rvk::DirectEntry *fallback = nullptr;
+    bool tall_tried = false;
+    // (columns with an output bitmap: a validity byte per row each in the LDS slot)
+    auto direct_lds = [&](const rvk::DirectEntry &g) { return static_cast<size_t>(g.waves) * 64 * g.r * (8 * static_cast<size_t>(nvals) + nv_out); };
+    constexpr size_t kDirectLdsBudget = (160 * 1024) / 2 - 512;
+    for (int t = 0; t < 2 && !found; ++t) {
+        size_t cnt = 0;
+        const rvk::DirectEntry *tab = t ? rvk::direct_entries_b(&cnt) : rvk::direct_entries_a(&cnt);
+        for (size_t i = 0; i < cnt && !found; ++i) {
+            const rvk::DirectEntry &g = tab[i];
+            if (g.np != npred || g.nq != nvals - npred || (g.flags & dflags) != dflags || ((g.flags ^ dflags) & rvk::FF_STAMP) != 0) continue;
+            if (ctx->opt_direct_r > 0 || ctx->opt_direct_waves > 0) {  // diagnostic: a named geometry or none
+                if ((ctx->opt_direct_r <= 0 || g.r == ctx->opt_direct_r) && (ctx->opt_direct_waves <= 0 || g.waves == ctx->opt_direct_waves)) found = &g;
+                continue;
+            }
+            if (g.waves != 8 || direct_lds(g) > kDirectLdsBudget) continue;  // two workgroups per CU have to fit
+            const bool serves = (!ranges || 4096u % (64u * static_cast<uint32_t>(g.r)) == 0) && (!(req && req->counts) || counts_in_pass(req, g.r));
+            // one loaded column while fewer than kDirectTallBelow survive (a table of runs at 30-50 %, a selection just past
+            // kDirectFromOneColumn): the 16-row geometry -- what the launch keeps in registers and LDS behind a tile's aggregate
+            // covers the chain's latency only at the rate that storage / latency gives, and below ~70 % that, not HBM, is the bound
+            if (serves && npred == 1 && nvals == 1 && !nv_out && seen >= 0.0 && seen < rvt::kDirectTallBelow && g.r != 16 && !tall_tried) {
+                tall_tried = true;
+                for (size_t k = i + 1; k < cnt; ++k)
+                    if (tab[k].np == 1 && tab[k].nq == 0 && tab[k].r == 16 && tab[k].waves == 8 && tab[k].flags == g.flags && direct_lds(tab[k]) <= kDirectLdsBudget &&
+                        (!(req && req->counts) || counts_in_pass(req, 16))) {
+                        found = &tab[k];
+                        break;
+                    }
+                if (found) break;
+            }
+            if (serves) found = &g;
+            else if (!fallback) fallback = &g;
+        }
+    }
+    if (!found && ctx->opt_direct_r <= 0 && ctx->opt_direct_waves <= 0) found = fallback;
+    return found;
+}
+
+// The direct kernel for the launch, when an instantiation serves it (find_direct), with its tiles and LDS: one slot per wave, its rows of
+// every loaded column (+ a validity byte per row and column when nulls can survive).  A staged geometry's cap and stage_row_bytes stay.
+static bool use_direct(rv_ctx *ctx, LaunchChoice &c, const Bound &b, int nv_out, double seen, const BatchReq *req, const RangeOffsets *ranges,
+                       bool sel_deferred) {
+    const rvk::DirectEntry *d = find_direct(ctx, b, nv_out, seen, req, ranges);
+    if (!d) return false;
+    c.direct = d;
+    // per-batch counts out of the pass need a batch to be a whole number of the geometry's wave ranges: else the caller counts
+    // the selection bitmap, which the kernel writes on the way
+    if (sel_deferred && !counts_in_pass(req, d->r)) c.make_selection = true;
+    c.tile_rows = static_cast<uint64_t>(d->waves) * 64 * d->r;
+    const uint64_t ntiles64 = (b.in->n + c.tile_rows - 1) / c.tile_rows;
+    require(ntiles64 < (1ull << 31) - 1, RV_ERR_UNSUPPORTED, "batch too large for one launch");
+    c.ntiles = static_cast<uint32_t>(ntiles64);
+    c.stages = 2;
+    c.lds = static_cast<size_t>(d->waves) * 64 * d->r * (8 * static_cast<size_t>(b.nvals) + nv_out);
+    return true;
+}
+
+// The staged instantiation e's tiles, stages, LDS slot capacity and LDS bytes.  `row_bytes`: what a row of the outputs takes in a slot.
+static void size_staged(rv_ctx *ctx, LaunchChoice &c, const rvk::FusedEntry &e, uint64_t n, int nvals, int nxs, size_t row_bytes, bool dense_sizing) {
+    c.stage_row_bytes = row_bytes;
+    if (e.flags & rvk::FF_PROJALL)  // the kernel stages a validity byte for every column when any has a bitmap
+        c.stage_row_bytes = static_cast<size_t>(nvals) * (((e.flags & rvk::FF_VALIDITY) && !(e.flags & rvk::FF_NONULL)) ? 9 : 8) + static_cast<size_t>(nxs);
+    c.tile_rows = static_cast<uint64_t>(e.waves) * 64 * e.r;
+    const uint64_t ntiles64 = (n + c.tile_rows - 1) / c.tile_rows;
+    require(ntiles64 < (1ull << 31), RV_ERR_UNSUPPORTED, "batch too large for one launch");
+    c.ntiles = static_cast<uint32_t>(ntiles64);
+
+    // LDS: every wave owns two slots (double buffered for the deferred look-back) of cap rows.
+    // One 1024-thread workgroup per CU may use most of the 160 KiB; 512-thread variants keep to
+    // half so that two workgroups fit.
+    const uint32_t rows_per_wave = 64u * static_cast<uint32_t>(e.r);
+    // 16 waves x 4 per SIMD is one workgroup per CU (128 VGPRs each): it may use most of the LDS; smaller workgroups run
+    // two per CU -- unless sized for a dense selection: one workgroup per CU whatever its size, two stages
+    const bool roomy = dense_sizing || ctx->opt_roomy != 0;
+    const size_t budget = (roomy || e.waves >= 16) ? 144 * 1024 : 72 * 1024;
+    // Three stages (write-out two iterations after the aggregate went out, so the scanner's prefix is
+    // there when it is needed) when a slot still holds 3/16 of a wave's rows; two otherwise.
+    auto cap_for = [&](size_t st) -> uint32_t {
+        if (!c.stage_row_bytes) return rows_per_wave;
+        return static_cast<uint32_t>(std::min<uint64_t>(rows_per_wave, (budget / (st * e.waves * c.stage_row_bytes)) & ~size_t(63)));
+    };
+    c.stages = 3;
+    if (ctx->opt_depth == 1 || (ctx->opt_depth == 0 && (roomy || cap_for(3) * 16 < rows_per_wave * 3))) c.stages = 2;
+    c.cap = cap_for(c.stages);
+    if (ctx->opt_cap_rows > 0) c.cap = static_cast<uint32_t>(std::min<int64_t>(c.cap, std::max<int64_t>(64, ctx->opt_cap_rows & ~int64_t(63))));
+    c.cap = std::max<uint32_t>(c.cap, 64u * static_cast<uint32_t>(e.vec));  // a slot holds at least one chunk
+    require(c.cap >= 64, RV_ERR_INTERNAL, "LDS stage too small");
+    // bit streams of a lane-form launch are staged as R + 1 words of bits, whatever the slot's row capacity
+    auto lds_for = [&](size_t st, uint32_t rows) {
+        const size_t xs_words = (e.vec == 1 && rows < (static_cast<uint32_t>(e.r) + 2) * 8u) ? static_cast<size_t>(nxs) * ((e.r + 2) * 8 - rows) : 0;
+        const size_t slot = (static_cast<size_t>(rows) * c.stage_row_bytes + xs_words + 15) & ~size_t(15);
+        return rvk::kLdsHeader + st * e.waves * slot + static_cast<size_t>(e.waves) * rvk::kLdsDumpBytes;
+    };
+    // the minimum slot of a wide row (several columns with validity bytes) times three stages can pass the CU's 160 KiB
+    // (a forced "depth" = 2 on such a shape): two stages then
+    constexpr size_t kLdsPerCu = 160 * 1024;
+    if (c.stages == 3 && lds_for(3, c.cap) > kLdsPerCu) c.stages = 2;
+    require(lds_for(c.stages, c.cap) <= kLdsPerCu, RV_ERR_UNSUPPORTED,
+            fmt("fused pass: %zu bytes of LDS for %d columns at %u rows per slot", lds_for(c.stages, c.cap), nvals, c.cap));
+    c.lds = lds_for(c.stages, c.cap);
+}
+
+// Survivors that come in RUNS (a table sorted or clustered on the predicate's column: ids, timestamps): a wave of the staged
+// pass whose 64 R rows hold more of them than its LDS slot leaves its range to the redo kernel (fused_kernel.hpp,
+// fused_redo_waves) -- cheap while few ranges do, but past a point the direct kernel, whose rows wait in registers whatever
+// survives, is ahead.  The share of ranges to expect: what the last staged pass of this predicate over these buffers left
+// to the redo kernel, or -- on a first call -- the share of the sample's 1024-row blocks denser than the slot.
+static double redo_estimate(rv_ctx *ctx, const FusedLaunch &L, double seen, bool sampled_now, uint32_t cap_rows, uint32_t rows_per_wave) {
+    const rv_ctx::SeenPredicate *q = L.place ? nullptr : ctx->seen_entry(L.signature);
+    if (cap_rows >= rows_per_wave) return 0.0;
+    const double ratio = static_cast<double>(cap_rows) / rows_per_wave, width = 1.0 / rvk::kSampleBuckets;
+    // measured by a staged pass whose slots held at least this share of a wave's rows (roomier slots than it had: unknown -- independent
+    // rows stop outgrowing them, runs do not)
+    if (q && q->redo_fraction >= 0.0 && std::fabs(q->redo_at - seen) < rvt::kRedoMemorySelectivityBand && ratio <= q->redo_ratio + rvt::kRedoMemorySlotBand) return q->redo_fraction;
+    const float *hist = sampled_now ? ctx->last_sample_hist : ((q && q->have_hist) ? q->hist : nullptr);
+    if (!hist) return 0.0;
+    double f = 0.0;
+    for (int b = 0; b < rvk::kSampleBuckets; ++b) {
+        const double lo = b * width, hi = lo + width;
+        if (lo >= ratio) f += hist[b];
+        else if (hi > ratio) f += hist[b] * (hi - ratio) / width;
+    }
+    return f;
+}
+
+// The kernel and geometry of L's pass: the project's policy, read from the bound shape, the selectivity the pass is sized by (`seen`;
+// `sampled_now`: out of a sample this call took), the caller's side outputs and the context's options and predicate memory.  Allocates
+// nothing, queues nothing, writes nothing of the context.  `row_bytes`: what a row of the outputs takes in an LDS slot (bind_outputs).
+static LaunchChoice choose_launch(rv_ctx *ctx, const FusedLaunch &L, const Bound &b, size_t row_bytes, bool expr, bool sel_deferred, double seen,
+                                  bool sampled_now, const BatchReq *req, const RangeOffsets *ranges) {
+    const rvk::FusedParams &p = L.p;
+    const int nvals = b.nvals, npred = b.npred, nxs = p.nxs;
+    const uint64_t n = p.in.n;
+    LaunchChoice c;
     // 16-byte loads need every loaded 8-byte column to start 16-byte aligned
     int vec = ctx->opt_vec == 1 ? 1 : (ctx->opt_vec == 2 ? 2 : (nvals <= 3 ? 2 : 1));
     for (int s = 0; s < nvals; ++s) {
         const uintptr_t a = reinterpret_cast<uintptr_t>(p.in.cols[s].values) + p.in.cols[s].offset * 8;
         if (a & 15) vec = 1;
     }
-    int need = 0;
     for (int s = 0; s < nvals; ++s)
-        if (p.in.cols[s].validity) need |= rvk::FF_VALIDITY;
-    if (nbools) need |= rvk::FF_BOOL;
+        if (p.in.cols[s].validity) c.need |= rvk::FF_VALIDITY;
+    if (b.nbools) c.need |= rvk::FF_BOOL;
     // shapes that read bit buffers (null bitmaps, Boolean columns) or evaluate an expression run in lane form with 8-byte
     // loads: measured faster than 16-byte loads + per-slot mask arrays on every such shape (profiles/README.md)
-    if (ctx->opt_vec == 0 && (need || ex)) vec = 1;
-    if (nxs) need |= rvk::FF_XS;
-    if (p.out_selection) need |= rvk::FF_SEL;
-    if (ex) need |= rvk::FF_EXPR;
+    if (ctx->opt_vec == 0 && (c.need || expr)) vec = 1;
+    if (nxs) c.need |= rvk::FF_XS;
+    if (p.out_selection) c.need |= rvk::FF_SEL;
+    if (expr) c.need |= rvk::FF_EXPR;
     // predicate shape: one compare term on the only loaded column, no nulls -> single-pass fast path
-    if (!ex && (need & ~rvk::FF_SEL) == 0 && nvals == 1 && nterms == 1 && !p.in.terms[0].is_bool() && p.in.terms[0].code() != rvk::TC_CONST)
-        need |= p.in.terms[0].is_float() ? rvk::FF_ONE_F64 : rvk::FF_ONE_I64;
+    if (!expr && (c.need & ~rvk::FF_SEL) == 0 && nvals == 1 && p.in.nterms == 1 && !p.in.terms[0].is_bool() && p.in.terms[0].code() != rvk::TC_CONST)
+        c.need |= p.in.terms[0].is_float() ? rvk::FF_ONE_F64 : rvk::FF_ONE_I64;
     // diagnostics (per-phase stamps, ablations) exist in the FF_STAMP instantiations only; "debug" implies them
-    if ((ctx->opt_stamp || ctx->opt_debug) && (need == rvk::FF_ONE_I64 || (nvals == 2 && need == rvk::FF_VALIDITY))) need |= rvk::FF_STAMP;
+    if ((ctx->opt_stamp || ctx->opt_debug) && (c.need == rvk::FF_ONE_I64 || (nvals == 2 && c.need == rvk::FF_VALIDITY))) c.need |= rvk::FF_STAMP;
     // every loaded column projected, output bitmap exactly where there is an input bitmap?
     // ... or no output bitmap at all (FF_NONULL: every nullable column is tested by a null-dropping term)
-    bool all_proj = nvals > 0 && !(need & (rvk::FF_ONE_I64 | rvk::FF_ONE_F64));
-    for (int s = 0; s < nvals; ++s) all_proj = all_proj && p.out_values[s];
-    bool mirror = all_proj, none = all_proj;
+    int projected = 0, nv_out = 0;  // loaded columns projected; ... whose output keeps a bitmap
     for (int s = 0; s < nvals; ++s) {
-        mirror = mirror && ((p.out_validity[s] != nullptr) == (p.in.cols[s].validity != nullptr));
-        none = none && p.out_validity[s] == nullptr;
+        projected += p.out_values[s] != nullptr;
+        nv_out += p.out_validity[s] != nullptr;
     }
+    const bool all_proj = nvals > 0 && !(c.need & (rvk::FF_ONE_I64 | rvk::FF_ONE_F64)) && projected == nvals;
+    bool mirror = all_proj;
+    for (int s = 0; s < nvals; ++s) mirror = mirror && ((p.out_validity[s] != nullptr) == (p.in.cols[s].validity != nullptr));
+    const bool none = all_proj && nv_out == 0;
     // not every loaded column projected, but no output bitmap anywhere: the staging needs no validity select either
-    bool no_out_validity = nvals > 0 && (need & rvk::FF_VALIDITY) && !(need & (rvk::FF_ONE_I64 | rvk::FF_ONE_F64));
-    for (int s2 = 0; s2 < nvals; ++s2) no_out_validity = no_out_validity && p.out_validity[s2] == nullptr;
+    const bool no_out_validity = nvals > 0 && (c.need & rvk::FF_VALIDITY) && !(c.need & (rvk::FF_ONE_I64 | rvk::FF_ONE_F64)) && nv_out == 0;
     const int prefer = mirror ? rvk::FF_PROJALL
-                              : ((none && (need & rvk::FF_VALIDITY)) ? (rvk::FF_PROJALL | rvk::FF_NONULL) : ((no_out_validity && !all_proj) ? rvk::FF_NONULL : 0));
+                              : ((none && (c.need & rvk::FF_VALIDITY)) ? (rvk::FF_PROJALL | rvk::FF_NONULL) : ((no_out_validity && !all_proj) ? rvk::FF_NONULL : 0));
+    c.stage_row_bytes = row_bytes;
+
+    // Most rows survive and the outputs are plain value columns: the direct kernel (direct_kernel.hpp), which keeps a tile's rows
+    // in registers until its output offset is known
+    bool plain = nvals >= 1 && nxs == 0 && ctx->opt_rows_per_lane <= 0 &&
+                 ctx->opt_cap_rows == 0 && (ctx->opt_debug & ~int64_t(4)) == 0 && (p.in.strict_values >> npred) == 0;
+    for (int s = npred; s < nvals; ++s) plain = plain && p.out_values[s] != nullptr;
+    // measured crossovers against the staged geometries (tools/dense_sweep.py, profiles/r04_dense_sweep.txt): one loaded column
+    // from 55 %; one column projected of several loaded from 60 % (the staged pass holds every survivor in its slots there);
+    // two projected columns from 22 %, three or four from 15 % (their staged rows crowd the LDS slots early)
+    // (columns that keep nulls carry a validity byte per row through the LDS slot: later, tools/dense_nullable.py -- two projected
+    // columns from 35 %, three from 22 %)
+    double dense_from = nvals == 1 ? rvt::kDirectFromOneColumn
+                                   : (projected <= 1 ? rvt::kDirectFromOneProjectedOfSeveral : (projected == 2 ? rvt::kDirectFromTwoProjected : rvt::kDirectFromThreeProjected));
+    if (nv_out && nvals > 1) dense_from = std::max(dense_from, projected <= 2 ? rvt::kDirectFromTwoProjectedNullable : rvt::kDirectFromThreeProjectedNullable);
+    if (plain && (ctx->opt_direct > 0 || (ctx->opt_direct == 0 && seen >= dense_from))) use_direct(ctx, c, b, nv_out, seen, req, ranges, sel_deferred);
+
     // Geometry: the instantiation, then the LDS slots (rows a wave can stage per tile).  A wave with more survivors than its
     // slot holds leaves its range to the redo kernel, which re-reads it -- so a selectivity the default geometry's slots would
     // not hold (the context's last pass WITH THIS PREDICATE says so) walks down:
@@ -452,126 +589,11 @@ void fused_begin(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, con
     // on the share of redone tiles did: the dense geometry redoes none).  x > lit -> [x, y, fn], 5e8 rows, ms per call at
     // 10 / 20 / 30 / 50 / 90 %: default geometry + redo kernel 2.4 / 8.1 / 8.7 / 9.8 / 12.4; walked down 2.4 / 3.7 / 3.8 / 6.5 / 6.9
     // (tools/roomy_ab.py; one column: tools/dense_one.py).
-    const size_t stage_row_bytes_in = stage_row_bytes;
-    const rvk::FusedEntry *chosen = nullptr;
-    uint64_t tile_rows = 0;
-    uint32_t cap = 0;
-    size_t stages = 3, lds = 0;
-    auto counts_here = [&](int rows_per_lane) { return req && req->counts && req->chunk_rows % (64u * static_cast<uint64_t>(rows_per_lane)) == 0; };
     int min_r = 0, below_r = 1 << 30;  // pick_fused's `roomy` level (0 default, 1 walk down the 16-wave geometries, 2 fewest waves)
     bool dense_sizing = false;
-    // Most rows survive and the outputs are plain value columns: the direct kernel (direct_kernel.hpp), which keeps a tile's rows
-    // in registers until its output offset is known
-    const rvk::DirectEntry *direct = nullptr;
-    bool plain = nvals >= 1 && nxs == 0 && ctx->opt_rows_per_lane <= 0 &&
-                 ctx->opt_cap_rows == 0 && (ctx->opt_debug & ~int64_t(4)) == 0 && (p.in.strict_values >> npred) == 0;
-    bool out_validity = false;  // a projected column keeps nulls among the survivors: the FF_OUTVALID instantiations
-    for (int s = 0; s < nvals; ++s) out_validity = out_validity || p.out_validity[s] != nullptr;
-    for (int s = npred; s < nvals; ++s) plain = plain && p.out_values[s] != nullptr;
-    // the direct instantiation for this launch's columns and features, or none
-    auto direct_candidate = [&]() -> const rvk::DirectEntry * {
-        const rvk::DirectEntry *found = nullptr;
-        int dflags = nbools ? (rvk::FF_VALIDITY | rvk::FF_BOOL) : 0;
-        if (ctx->opt_stamp) dflags |= rvk::FF_STAMP;  // diagnostic instantiations (phase cycle sums), a few geometries only
-        for (int s = 0; s < npred; ++s)
-            if (p.in.cols[s].validity) dflags |= rvk::FF_VALIDITY;
-        if (out_validity) dflags |= rvk::FF_VALIDITY | rvk::FF_OUTVALID;
-        // the first listed instantiation that covers the inputs' features (listed leanest first) -- among those whose wave
-        // ranges serve the caller's side outputs, when it asks for any: wave offsets need a range that tiles 4096 rows, per-batch
-        // counts a batch that is a whole number of ranges
-        const rvk::DirectEntry *fallback = nullptr;
-        bool tall_tried = false;
-        int nv_out = 0;  // columns with an output bitmap: a validity byte per row each in the LDS slot
-        for (int s = 0; s < nvals; ++s) nv_out += p.out_validity[s] != nullptr;
-        auto direct_lds = [&](const rvk::DirectEntry &g) { return static_cast<size_t>(g.waves) * 64 * g.r * (8 * static_cast<size_t>(nvals) + nv_out); };
-        constexpr size_t kDirectLdsBudget = (160 * 1024) / 2 - 512;
-        for (int t = 0; t < 2 && !found; ++t) {
-            size_t cnt = 0;
-            const rvk::DirectEntry *tab = t ? rvk::direct_entries_b(&cnt) : rvk::direct_entries_a(&cnt);
-            for (size_t i = 0; i < cnt && !found; ++i) {
-                const rvk::DirectEntry &g = tab[i];
-                if (g.np != npred || g.nq != nvals - npred || (g.flags & dflags) != dflags || ((g.flags ^ dflags) & rvk::FF_STAMP) != 0) continue;
-                if (ctx->opt_direct_r > 0 || ctx->opt_direct_waves > 0) {  // diagnostic: a named geometry or none
-                    if ((ctx->opt_direct_r <= 0 || g.r == ctx->opt_direct_r) && (ctx->opt_direct_waves <= 0 || g.waves == ctx->opt_direct_waves)) found = &g;
-                    continue;
-                }
-                if (g.waves != 8 || direct_lds(g) > kDirectLdsBudget) continue;  // two workgroups per CU have to fit
-                const bool serves = (!ranges || 4096u % (64u * static_cast<uint32_t>(g.r)) == 0) && (!(req && req->counts) || counts_here(g.r));
-                // one loaded column while fewer than kDirectTallBelow survive (a table of runs at 30-50 %, a selection just past
-                // kDirectFromOneColumn): the 16-row geometry -- what the launch keeps in registers and LDS behind a tile's aggregate
-                // covers the chain's latency only at the rate that storage / latency gives, and below ~70 % that, not HBM, is the bound
-                if (serves && npred == 1 && nvals == 1 && !out_validity && seen >= 0.0 && seen < rvt::kDirectTallBelow && g.r != 16 && !tall_tried) {
-                    tall_tried = true;
-                    for (size_t k = i + 1; k < cnt; ++k)
-                        if (tab[k].np == 1 && tab[k].nq == 0 && tab[k].r == 16 && tab[k].waves == 8 && tab[k].flags == g.flags && direct_lds(tab[k]) <= kDirectLdsBudget &&
-                            (!(req && req->counts) || counts_here(16))) {
-                            found = &tab[k];
-                            break;
-                        }
-                    if (found) break;
-                }
-                if (serves) found = &g;
-                else if (!fallback) fallback = &g;
-            }
-        }
-        if (!found && ctx->opt_direct_r <= 0 && ctx->opt_direct_waves <= 0) found = fallback;
-        return found;
-    };
-    {
-        int projected = 0;
-        for (int s = 0; s < nvals; ++s) projected += p.out_values[s] != nullptr;
-        // measured crossovers against the staged geometries (tools/dense_sweep.py, profiles/r04_dense_sweep.txt): one loaded column
-        // from 55 %; one column projected of several loaded from 60 % (the staged pass holds every survivor in its slots there);
-        // two projected columns from 22 %, three or four from 15 % (their staged rows crowd the LDS slots early)
-        // (columns that keep nulls carry a validity byte per row through the LDS slot: later, tools/dense_nullable.py -- two projected
-        // columns from 35 %, three from 22 %)
-        double dense_from = nvals == 1 ? rvt::kDirectFromOneColumn
-                                       : (projected <= 1 ? rvt::kDirectFromOneProjectedOfSeveral : (projected == 2 ? rvt::kDirectFromTwoProjected : rvt::kDirectFromThreeProjected));
-        if (out_validity && nvals > 1) dense_from = std::max(dense_from, projected <= 2 ? rvt::kDirectFromTwoProjectedNullable : rvt::kDirectFromThreeProjectedNullable);
-        const bool dense = seen >= dense_from;
-        if (plain && (ctx->opt_direct > 0 || (ctx->opt_direct == 0 && dense))) direct = direct_candidate();
-    }
-    auto size_direct = [&] {
-        // per-batch counts out of the pass need a batch to be a whole number of the geometry's wave ranges: else the caller counts
-        // the selection bitmap, which the kernel writes on the way
-        if (sel_deferred && !sel && !counts_here(direct->r)) make_selection();
-        tile_rows = static_cast<uint64_t>(direct->waves) * 64 * direct->r;
-        const uint64_t ntiles64 = (n + tile_rows - 1) / tile_rows;
-        require(ntiles64 < (1ull << 31) - 1, RV_ERR_UNSUPPORTED, "batch too large for one launch");
-        p.ntiles = static_cast<uint32_t>(ntiles64);
-        stages = 2;
-        // one slot per wave: its rows of every loaded column (+ a validity byte per row and column when nulls can survive)
-        int nv_out = 0;
-        for (int s = 0; s < nvals; ++s) nv_out += p.out_validity[s] != nullptr;
-        lds = static_cast<size_t>(direct->waves) * 64 * direct->r * (8 * static_cast<size_t>(nvals) + nv_out);
-    };
-    if (direct) size_direct();
-    // Survivors that come in RUNS (a table sorted or clustered on the predicate's column: ids, timestamps): a wave of the staged
-    // pass whose 64 R rows hold more of them than its LDS slot leaves its range to the redo kernel (fused_kernel.hpp,
-    // fused_redo_waves) -- cheap while few ranges do, but past a point the direct kernel, whose rows wait in registers whatever
-    // survives, is ahead.  The share of ranges to expect: what the last staged pass of this predicate over these buffers left
-    // to the redo kernel, or -- on a first call -- the share of the sample's 1024-row blocks denser than the slot.
-    auto redo_estimate = [&](uint32_t cap_rows, uint32_t rows_per_wave) -> double {
-        const rv_ctx::SeenPredicate *q = L.place ? nullptr : ctx->seen_entry(signature);
-        if (cap_rows >= rows_per_wave) return 0.0;
-        const double ratio = static_cast<double>(cap_rows) / rows_per_wave, width = 1.0 / rvk::kSampleBuckets;
-        // measured by a staged pass whose slots held at least this share of a wave's rows (roomier slots than it had: unknown -- independent
-        // rows stop outgrowing them, runs do not)
-        if (q && q->redo_fraction >= 0.0 && std::fabs(q->redo_at - seen) < rvt::kRedoMemorySelectivityBand && ratio <= q->redo_ratio + rvt::kRedoMemorySlotBand) return q->redo_fraction;
-        const float *hist = sampled_now ? ctx->last_sample_hist : ((q && q->have_hist) ? q->hist : nullptr);
-        if (!hist) return 0.0;
-        double f = 0.0;
-        for (int b = 0; b < rvk::kSampleBuckets; ++b) {
-            const double lo = b * width, hi = lo + width;
-            if (lo >= ratio) f += hist[b];
-            else if (hi > ratio) f += hist[b] * (hi - ratio) / width;
-        }
-        return f;
-    };
-    double redo_expected = 0.0;
-    while (!direct) {
-        chosen = &pick_fused(ctx, nvals, vec, need, prefer, min_r, below_r);
-        if (min_r == 1 && (chosen->waves != 16 || chosen->r >= below_r)) {  // no 16-wave geometry below that many rows per lane left
+    while (!c.direct) {
+        c.staged = &pick_fused(ctx, nvals, vec, c.need, prefer, min_r, below_r);
+        if (min_r == 1 && (c.staged->waves != 16 || c.staged->r >= below_r)) {  // no 16-wave geometry below that many rows per lane left
             if (!dense_sizing) {  // the walk again, sized for a dense selection
                 dense_sizing = true;
                 below_r = 1 << 30;
@@ -580,90 +602,50 @@ void fused_begin(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, con
             }
             continue;
         }
-        // per-batch counts out of the pass: a batch must be a whole number of the geometry's wave ranges
-        if (sel_deferred && !sel && !counts_here(chosen->r)) {  // the caller will count the selection bitmap instead: materialise it after all
-            make_selection();
-            need |= rvk::FF_SEL;
-            chosen = &pick_fused(ctx, nvals, vec, need, prefer, min_r, below_r);
+        if (sel_deferred && !c.make_selection && !counts_in_pass(req, c.staged->r)) {  // the caller will count the selection bitmap instead
+            c.make_selection = true;
+            c.need |= rvk::FF_SEL;
+            c.staged = &pick_fused(ctx, nvals, vec, c.need, prefer, min_r, below_r);
         }
-        const rvk::FusedEntry &e = *chosen;
-        stage_row_bytes = stage_row_bytes_in;
-        if (e.flags & rvk::FF_PROJALL)  // the kernel stages a validity byte for every column when any has a bitmap
-            stage_row_bytes = static_cast<size_t>(nvals) * (((e.flags & rvk::FF_VALIDITY) && !(e.flags & rvk::FF_NONULL)) ? 9 : 8) + static_cast<size_t>(nxs);
-        tile_rows = static_cast<uint64_t>(e.waves) * 64 * e.r;
-        const uint64_t ntiles64 = (n + tile_rows - 1) / tile_rows;
-        require(ntiles64 < (1ull << 31), RV_ERR_UNSUPPORTED, "batch too large for one launch");
-        p.ntiles = static_cast<uint32_t>(ntiles64);
-
-        // LDS: every wave owns two slots (double buffered for the deferred look-back) of cap rows.
-        // One 1024-thread workgroup per CU may use most of the 160 KiB; 512-thread variants keep to
-        // half so that two workgroups fit.
-        const uint32_t rows_per_wave = 64u * static_cast<uint32_t>(e.r);
-        // 16 waves x 4 per SIMD is one workgroup per CU (128 VGPRs each): it may use most of the LDS; smaller workgroups run
-        // two per CU -- unless sized for a dense selection: one workgroup per CU whatever its size, two stages
-        const bool roomy = dense_sizing || ctx->opt_roomy != 0;
-        const size_t budget = (roomy || e.waves >= 16) ? 144 * 1024 : 72 * 1024;
-        // Three stages (write-out two iterations after the aggregate went out, so the scanner's prefix is
-        // there when it is needed) when a slot still holds 3/16 of a wave's rows; two otherwise.
-        auto cap_for = [&](size_t st) -> uint32_t {
-            if (!stage_row_bytes) return rows_per_wave;
-            return static_cast<uint32_t>(std::min<uint64_t>(rows_per_wave, (budget / (st * e.waves * stage_row_bytes)) & ~size_t(63)));
-        };
-        stages = 3;
-        if (ctx->opt_depth == 1 || (ctx->opt_depth == 0 && (roomy || cap_for(3) * 16 < rows_per_wave * 3))) stages = 2;
-        cap = cap_for(stages);
-        if (ctx->opt_cap_rows > 0) cap = static_cast<uint32_t>(std::min<int64_t>(cap, std::max<int64_t>(64, ctx->opt_cap_rows & ~int64_t(63))));
-        cap = std::max<uint32_t>(cap, 64u * static_cast<uint32_t>(e.vec));  // a slot holds at least one chunk
-        require(cap >= 64, RV_ERR_INTERNAL, "LDS stage too small");
-        // bit streams of a lane-form launch are staged as R + 1 words of bits, whatever the slot's row capacity
-        auto lds_for = [&](size_t st, uint32_t rows) {
-            const size_t xs_words = (e.vec == 1 && rows < (static_cast<uint32_t>(e.r) + 2) * 8u) ? static_cast<size_t>(nxs) * ((e.r + 2) * 8 - rows) : 0;
-            const size_t slot = (static_cast<size_t>(rows) * stage_row_bytes + xs_words + 15) & ~size_t(15);
-            return rvk::kLdsHeader + st * e.waves * slot + static_cast<size_t>(e.waves) * rvk::kLdsDumpBytes;
-        };
-        // the minimum slot of a wide row (several columns with validity bytes) times three stages can pass the CU's 160 KiB
-        // (a forced "depth" = 2 on such a shape): two stages then
-        constexpr size_t kLdsPerCu = 160 * 1024;
-        if (stages == 3 && lds_for(3, cap) > kLdsPerCu) stages = 2;
-        require(lds_for(stages, cap) <= kLdsPerCu, RV_ERR_UNSUPPORTED,
-                fmt("fused pass: %zu bytes of LDS for %d columns at %u rows per slot", lds_for(stages, cap), nvals, cap));
-        lds = lds_for(stages, cap);
+        size_staged(ctx, c, *c.staged, n, nvals, nxs, row_bytes, dense_sizing);
         // expected survivors of a wave (+ 10 % and three standard deviations of a binomial) against the slot
+        const uint32_t rows_per_wave = 64u * static_cast<uint32_t>(c.staged->r);
         const double expect = seen * rows_per_wave;
-        const bool crowded = min_r < 2 && ctx->opt_rows_per_lane <= 0 && nvals >= 1 && stage_row_bytes && cap < rows_per_wave &&
-                             seen > 0.0 && expect * rvt::kCrowdedMargin + rvt::kCrowdedSigmas * std::sqrt(expect) > static_cast<double>(cap);
+        const bool crowded = min_r < 2 && ctx->opt_rows_per_lane <= 0 && nvals >= 1 && c.stage_row_bytes && c.cap < rows_per_wave &&
+                             seen > 0.0 && expect * rvt::kCrowdedMargin + rvt::kCrowdedSigmas * std::sqrt(expect) > static_cast<double>(c.cap);
         if (!crowded) break;
-        below_r = e.r;  // the next 16-wave geometry with fewer rows per lane
+        below_r = c.staged->r;  // the next 16-wave geometry with fewer rows per lane
         min_r = 1;
     }
-    if (!direct && chosen && seen >= 0.0 && stage_row_bytes) {
-        redo_expected = redo_estimate(cap, 64u * static_cast<uint32_t>(chosen->r));
+    if (!c.direct && seen >= 0.0 && c.stage_row_bytes) {
+        c.redo_expected = redo_estimate(ctx, L, seen, sampled_now, c.cap, 64u * static_cast<uint32_t>(c.staged->r));
         // Per 1e9 rows of one column the redo kernel costs ~3.5 ms x the share of ranges it re-reads (tools/skew_sweep.py: sorted
         // 10 % 1.37 -> 1.68 ms, sorted 50 % 1.98 -> 3.95 ms); the direct kernel costs 0.8 ms more than the staged pass at 10 %
         // selectivity, 0.4 at 30 %, 0.25 at 50 % (profiles/r04_dense_sweep.txt).
         if (plain && ctx->opt_direct == 0 && ctx->opt_skew >= 0 &&
-            redo_expected * rvt::kRedoMsPerShare > std::max(rvt::kDirectPenaltyFloor, rvt::kDirectPenaltyAt0 - rvt::kDirectPenaltySlope * seen)) {
-            direct = direct_candidate();
-            if (direct) {
-                size_direct();
-                redo_expected = 0.0;
-            }
-        }
+            c.redo_expected * rvt::kRedoMsPerShare > std::max(rvt::kDirectPenaltyFloor, rvt::kDirectPenaltyAt0 - rvt::kDirectPenaltySlope * seen) &&
+            use_direct(ctx, c, b, nv_out, seen, req, ranges, sel_deferred))
+            c.redo_expected = 0.0;
     }
-    // the launch geometry, whichever kernel was chosen
-    struct Geometry {
-        int ncols, r, vec, waves, flags;
-        void (*fn)(const rvk::FusedParams);
-    };
-    const Geometry e = direct ? Geometry{nvals, direct->r, 1, direct->waves, direct->flags, direct->fn}
-                              : Geometry{chosen->ncols, chosen->r, chosen->vec, chosen->waves, chosen->flags, chosen->fn};
-    p.cap_rows = cap;
-    p.depth = static_cast<int32_t>(stages) - 1;
+    if (c.direct) c.r = c.direct->r, c.vec = 1, c.waves = c.direct->waves, c.flags = c.direct->flags, c.fn = c.direct->fn;
+    else c.r = c.staged->r, c.vec = c.staged->vec, c.waves = c.staged->waves, c.flags = c.staged->flags, c.fn = c.staged->fn;
+    return c;
+}
+
+// The rest of the pass's parameters, a control block, and the pass queued on the stream -- with the redo kernel behind it when ranges
+// are expected to outgrow their slots, and the per-batch counts.  Fills what fused_finish reads.
+static void launch_pass(rv_ctx *ctx, FusedLaunch &L, const LaunchChoice &c, int nvals, rv_dcolumn **sel_out, BatchReq *req, RangeOffsets *ranges,
+                        double seen) {
+    rvk::FusedParams &p = L.p;
+    if (c.make_selection) make_selection(ctx, L, sel_out);
+    p.ntiles = c.ntiles;
+    p.cap_rows = c.cap;
+    p.depth = static_cast<int32_t>(c.stages) - 1;
 
     // the staged pass lists the wave ranges whose survivors outgrew their LDS slot (fused_kernel.hpp, fused_redo_waves): one
     // word per range behind the descriptors, zeroed with them; the direct kernel's rows never leave their registers: no list
-    L.range_rows = 64u * static_cast<uint32_t>(e.r);
-    L.nranges = direct ? 0 : static_cast<uint64_t>(p.ntiles) * e.waves;
+    L.range_rows = 64u * static_cast<uint32_t>(c.r);
+    L.nranges = c.direct ? 0 : static_cast<uint64_t>(p.ntiles) * c.waves;
     L.ctrl = acquire_launch_ctrl(ctx, p.ntiles, L.nranges);
     Ctrl *ctrl = static_cast<Ctrl *>(L.ctrl.dev);
     p.state = reinterpret_cast<uint64_t *>(static_cast<unsigned char *>(L.ctrl.dev) + kCtrlBytes);
@@ -678,19 +660,19 @@ void fused_begin(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, con
     p.redo = L.nranges ? reinterpret_cast<unsigned long long *>(static_cast<unsigned char *>(L.ctrl.dev) + kCtrlBytes + static_cast<size_t>(p.ntiles) * 8) : nullptr;
 
     // both calls cost several microseconds: once per (kernel, LDS size) and context
-    const void *fn = reinterpret_cast<const void *>(e.fn);
+    const void *fn = reinterpret_cast<const void *>(c.fn);
     size_t &enabled = ctx->lds_enabled[fn];
-    if (lds > enabled) {
-        RV_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-        enabled = lds;
+    if (c.lds > enabled) {
+        RV_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(c.lds)));
+        enabled = c.lds;
     }
     // persistent grid: as many workgroups as the device keeps resident (tiles are handed out
     // by the ticket counter, so residency is a speed matter only, never correctness)
-    auto occ = ctx->occupancy.find({fn, lds});
+    auto occ = ctx->occupancy.find({fn, c.lds});
     if (occ == ctx->occupancy.end()) {
         int q = 0;
-        RV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, fn, e.waves * 64, lds));
-        occ = ctx->occupancy.emplace(std::make_pair(fn, lds), std::max(1, q)).first;
+        RV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, fn, c.waves * 64, c.lds));
+        occ = ctx->occupancy.emplace(std::make_pair(fn, c.lds), std::max(1, q)).first;
     }
     int per_cu = occ->second;
     if (ctx->opt_wgs_per_cu > 0) per_cu = static_cast<int>(ctx->opt_wgs_per_cu);
@@ -698,16 +680,16 @@ void fused_begin(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, con
     const uint32_t grid = 1 + static_cast<uint32_t>(std::min<uint64_t>(p.ntiles, static_cast<uint64_t>(ctx->props.multiProcessorCount) * per_cu - 1));
     p.overflow = &ctrl->overflow;
     if (ranges) {
-        ranges->range_rows = 64u * static_cast<uint32_t>(e.r);
-        ranges->out_capacity = cap_out;
+        ranges->range_rows = 64u * static_cast<uint32_t>(c.r);
+        ranges->out_capacity = p.out_capacity;
         ranges->expected_selectivity = seen;
         if (4096u % ranges->range_rows == 0) {
-            ranges->offsets = pool_alloc(ctx, static_cast<size_t>(p.ntiles) * e.waves * 8 + 16);
+            ranges->offsets = pool_alloc(ctx, static_cast<size_t>(p.ntiles) * c.waves * 8 + 16);
             p.wave_offsets = static_cast<uint64_t *>(ranges->offsets->ptr);
         }
     }
-    if (counts_here(e.r)) {
-        if (req->chunk_rows == 64u * static_cast<uint64_t>(e.r)) {
+    if (counts_in_pass(req, c.r)) {
+        if (req->chunk_rows == 64u * static_cast<uint64_t>(c.r)) {
             // a batch IS a wave range (the reference's 1024-row batches at 16 rows per lane): the pass writes every batch's survivor
             // count where the caller reads it -- 128 bytes per tile over PCIe, spread over the whole pass; no scratch, no second kernel
             // (which took 39 us per 2^28-row window, serialised behind the pass whatever stream it ran on: profiles/r05_seam_*)
@@ -716,20 +698,24 @@ void fused_begin(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, con
             req->counted = true;
             ctx->batch_counts_in_pass += 1;
         } else {
-            L.wave_counts = pool_alloc(ctx, static_cast<size_t>(p.ntiles) * e.waves * 4 + 16);
+            L.wave_counts = pool_alloc(ctx, static_cast<size_t>(p.ntiles) * c.waves * 4 + 16);
             p.wave_counts = static_cast<uint32_t *>(L.wave_counts->ptr);
         }
     }
-    L.direct_stamp = direct && (direct->flags & rvk::FF_STAMP);
-    L.fn = e.fn;
+    L.direct_stamp = c.direct && (c.flags & rvk::FF_STAMP);
+    L.fn = c.fn;
     L.grid = grid;
-    L.block = static_cast<uint32_t>(e.waves * 64);
-    L.lds = lds;
+    L.block = static_cast<uint32_t>(c.waves * 64);
+    L.lds = c.lds;
     L.timed = ctx->opt_profile != 0;
-    ctx->last_kernel = direct ? fmt("fused_direct_compact<%d,%d,%d,%d,%d>", direct->np, direct->nq, e.r, e.waves, e.flags) : fmt("fused_filter_compact<%d,%d,%d,%d,%d>", e.ncols, e.r, e.vec, e.waves, e.flags);
+    L.need = c.need;
+    L.nvals = nvals;
+    L.stage_row_bytes = c.stage_row_bytes;
+    ctx->last_kernel = c.direct ? fmt("fused_direct_compact<%d,%d,%d,%d,%d>", c.direct->np, c.direct->nq, c.r, c.waves, c.flags)
+                                : fmt("fused_filter_compact<%d,%d,%d,%d,%d>", nvals, c.r, c.vec, c.waves, c.flags);
     // a free control block for this pass to zero while it runs (big launches: the zeroing hides in the pass), for a later launch
     int zero_at = -1;
-    if (n >= rvt::kRangesFromRows && e.waves >= 2) {
+    if (p.in.n >= rvt::kRangesFromRows && c.waves >= 2) {
         zero_at = block_to_zero(ctx, L.ctrl);
         if (zero_at >= 0) {
             const rv_ctx::LaunchCtrl &z = ctx->ctrl_free[static_cast<size_t>(zero_at)];
@@ -744,27 +730,23 @@ void fused_begin(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, con
         }
         RV_HIP(hipEventRecord(L.ctrl.tk0, ctx->stream));
     }
-    hipLaunchKernelGGL(e.fn, dim3(grid), dim3(e.waves * 64), lds, ctx->stream, p);
+    hipLaunchKernelGGL(c.fn, dim3(grid), dim3(c.waves * 64), c.lds, ctx->stream, p);
     RV_HIP(hipGetLastError());
     if (zero_at >= 0) {  // queued: whatever follows on this stream finds the block zero
         rv_ctx::LaunchCtrl &z = ctx->ctrl_free[static_cast<size_t>(zero_at)];
         z.clean = std::min(z.dirty, z.bytes);
     }
-    L.p.zero_ptr = nullptr;  // (a re-run after an output overflow zeroes nothing: the block may be in use by then)
-    L.p.zero_n16 = 0;
-    L.nvals = nvals;
-    L.redo_queued = false;
-    if (L.nranges && (redo_expected > 0.0 || L.place_edge) && (stage_row_bytes || nxs)) {
-        // ranges are expected to outgrow their slots (they did the last time): the redo kernel follows the pass on the stream at
-        // once instead of waiting for the host to read the count
-        launch_redo(ctx, L);
-        L.redo_queued = true;
-    }
+    p.zero_ptr = nullptr;  // (a re-run after an output overflow zeroes nothing: the block may be in use by then)
+    p.zero_n16 = 0;
+    // ranges are expected to outgrow their slots (they did the last time): the redo kernel follows the pass on the stream at
+    // once instead of waiting for the host to read the count
+    L.redo_queued = L.nranges && (c.redo_expected > 0.0 || L.place_edge) && (c.stage_row_bytes || p.nxs);
+    if (L.redo_queued) launch_redo(ctx, L);
     if (L.timed) RV_HIP(hipEventRecord(L.ctrl.tk1, ctx->stream));
     if (p.wave_counts) {
         // wave counts -> the caller's per-batch array (pinned host memory, written by the device: no read-back to queue); the scratch is
         // kept until the launch is finished
-        const uint64_t per_batch = req->chunk_rows / (64u * static_cast<uint64_t>(e.r)), nwaves = static_cast<uint64_t>(p.ntiles) * e.waves;
+        const uint64_t per_batch = req->chunk_rows / (64u * static_cast<uint64_t>(c.r)), nwaves = static_cast<uint64_t>(p.ntiles) * c.waves;
         const uint64_t threads = per_batch < 32 ? req->nb : (per_batch < 4096 ? req->nb * 64 : req->nb * 256);
         const dim3 cgrid(static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>((threads + 255) / 256, static_cast<uint64_t>(ctx->props.multiProcessorCount) * 8))));
         hipLaunchKernelGGL(rvk::batch_counts_from_waves, cgrid, dim3(256), 0, ctx->stream, static_cast<const uint32_t *>(p.wave_counts), nwaves, per_batch, req->nb, req->counts);
@@ -773,37 +755,80 @@ void fused_begin(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, con
         ctx->batch_counts_in_pass += 1;
         p.wave_counts = nullptr;  // a re-run after an output overflow does not count again (the first pass's counts are exact)
     }
-    L.p.batch_counts = nullptr;  // (likewise)
+    p.batch_counts = nullptr;  // (likewise)
     RV_HIP(hipMemcpyAsync(L.ctrl.host, L.ctrl.dev, kCtrlBytes, hipMemcpyDeviceToHost, ctx->stream));
     RV_HIP(hipEventRecord(L.ctrl.ev, ctx->stream));
     L.launched = true;
-    L.need = need;
-    L.nvals = nvals;
-    L.nxs = nxs;
-    L.stage_row_bytes = stage_row_bytes;
-    L.tile_rows = tile_rows;
 }
 
-// Waits for the launch, runs the redo kernel when wave ranges outgrew their slots (unless it was queued behind the pass), fixes the output lengths / null counts.
+// One single-pass launch: predicate over `cols`, compaction of the columns in proj; queued on the context's
+// stream, not waited for.  out[] / sel_out receive the output handles at once (their length is set by
+// fused_finish).
+void fused_begin(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, const rv_term *terms,
+                 uint32_t nterms, rv_null_policy policy, const uint32_t *proj, uint32_t nproj,
+                 rv_dcolumn **out, rv_dcolumn **sel_out, FusedLaunch &L, const ExprInfo *ex, BatchReq *req,
+                 RangeOffsets *ranges) {
+    rvk::FusedParams &p = L.p;
+    p = rvk::FusedParams{};
+    Bound b = bind_inputs(cols, ncols, terms, nterms, policy, ex, p.in);
+    const uint64_t n = p.in.n;
+    L.signature = predicate_signature(cols, ncols, terms, nterms, policy, ex);
+    double seen = L.place ? L.place_selectivity : ctx->seen_selectivity(L.signature);  // (a segment: its own density, out of the profile)
+    bool sampled_now = false;  // `seen` comes from a sample taken by this call: its histogram is in ctx->last_sample_hist
+    if (seen < 0.0 && !L.place) {
+        seen = first_call_sample(ctx, p.in, b.nvals, L.signature);
+        sampled_now = seen >= 0.0;
+    }
+
+    // Output capacity (output_capacity above).  Option "out_sizing": 0 = sized from the predicate's known selectivity for big tables,
+    // for every row otherwise; -1 = always for every row (no second pass, 2x the input in HBM); 1 = the context's last observed
+    // selectivity x 1.5 + 1 % (a stream of similar batches), k >= 2 = a caller-given bound of k rows per million.  A launch that
+    // overflows its outputs still counts exactly; fused_finish then re-runs it with buffers of the exact size
+    // (record_batch.rs:131-178 never over-allocates either: the builders grow).
+    // (a stretch appends at row place_base of the caller's buffers: pointers rounded down to a 128-byte line, the rest enters the
+    // chain as the output row of its first survivor -- FusedParams::out_bias -- and every buffer and capacity below counts from there)
+    L.out_bias = L.place ? static_cast<uint32_t>(L.place_base & 15) : 0u;
+    p.out_bias = L.out_bias;
+    const uint64_t cap_out = L.place ? (L.place_capacity > L.place_base ? L.place_capacity - L.place_base : 0) + L.out_bias : output_capacity(ctx, n, seen);
+    ctx->fused_rows_scanned += n;
+    L.n = n;
+    const size_t row_bytes = bind_outputs(b, ncols, proj, nproj, out, L);
+    alloc_outputs(ctx, L, cap_out);
+    // a selection bitmap wanted only for per-batch counts is decided with the geometry
+    const bool sel_deferred = sel_out && req && req->sel_optional && n > 0;
+    if (sel_deferred) *sel_out = nullptr;
+    else if (sel_out) make_selection(ctx, L, sel_out);
+    if (n == 0) {
+        for (auto &o : L.outs) {
+            o.col->length = 0;
+            o.col->null_count = 0;
+            o.col->validity.reset();
+        }
+        L.launched = false;
+        return;
+    }
+    const LaunchChoice c = choose_launch(ctx, L, b, row_bytes, ex != nullptr, sel_deferred, seen, sampled_now, req, ranges);
+    launch_pass(ctx, L, c, b.nvals, sel_out, req, ranges, seen);
+}
+
 // What a pass over this predicate would be sized by: the selectivity it had the last time it ran over these buffers, or -- a predicate
 // the context has not seen, over a big table -- the strided sample its first launch would take (taken here instead, once); < 0: unknown.
 // For decisions that precede the launch (which columns the pass should carry at all: query.hip, filter_by_groups).
 double expected_selectivity(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, const rv_term *terms, uint32_t nterms, rv_null_policy policy,
                             const ExprInfo *ex) {
-    const double known = ctx->seen_selectivity(predicate_signature(cols, ncols, terms, nterms, policy, ex));
+    const uint64_t signature = predicate_signature(cols, ncols, terms, nterms, policy, ex);
+    const double known = ctx->seen_selectivity(signature);
     if (known >= 0.0) return known;
-    FusedLaunch L;
-    L.sample_only = true;
-    fused_begin(ctx, cols, ncols, terms, nterms, policy, nullptr, 0, nullptr, nullptr, L, ex, nullptr, nullptr);
-    return L.sampled;
+    rvk::ScanInputs in{};
+    const Bound b = bind_inputs(cols, ncols, terms, nterms, policy, ex, in);  // (the errors a pass would raise before its sample)
+    return first_call_sample(ctx, in, b.nvals, signature);
 }
 
+// Waits for the launch, runs the redo kernel when wave ranges outgrew their slots (unless it was queued behind the pass), fixes the output lengths / null counts.
 uint64_t fused_finish(rv_ctx *ctx, FusedLaunch &L) {
     if (!L.launched) return 0;
     rvk::FusedParams &p = L.p;
     std::vector<OutCol> &outs = L.outs;
-    const int need = L.need, nxs = L.nxs;
-    const size_t stage_row_bytes = L.stage_row_bytes;
     struct Release {
         rv_ctx *ctx;
         FusedLaunch &L;
@@ -836,30 +861,7 @@ uint64_t fused_finish(rv_ctx *ctx, FusedLaunch &L) {
         // speculative output sizing guessed too low: the count is exact, so give every output exactly that many rows
         // and run the pass once more (same kernel, same geometry, fresh descriptors)
         const uint64_t exact = h->out_count;
-        p.out_capacity = exact;
-        for (auto &o : outs) {
-            if (o.value_slot >= 0) {
-                o.col->values = pool_alloc(ctx, std::max<size_t>(exact * 8, 8));
-                p.out_values[o.value_slot] = static_cast<uint64_t *>(o.col->values->ptr);
-                if (o.col->validity) {
-                    const size_t wb = zeroed_bitmap_bytes(exact);
-                    o.col->validity = pool_alloc(ctx, wb);
-                    RV_HIP(hipMemsetAsync(o.col->validity->ptr, 0, wb, ctx->stream));
-                    p.out_validity[o.value_slot] = static_cast<uint64_t *>(o.col->validity->ptr);
-                }
-            }
-            if (o.xs_values >= 0) {
-                const size_t wb = zeroed_bitmap_bytes(exact);
-                o.col->values = pool_alloc(ctx, wb);
-                RV_HIP(hipMemsetAsync(o.col->values->ptr, 0, wb, ctx->stream));
-                p.xs[o.xs_values].out = static_cast<uint64_t *>(o.col->values->ptr);
-                if (o.xs_valid >= 0) {
-                    o.col->validity = pool_alloc(ctx, wb);
-                    RV_HIP(hipMemsetAsync(o.col->validity->ptr, 0, wb, ctx->stream));
-                    p.xs[o.xs_valid].out = static_cast<uint64_t *>(o.col->validity->ptr);
-                }
-            }
-        }
+        alloc_outputs(ctx, L, exact);
         const size_t zeroed = kCtrlBytes + (static_cast<size_t>(p.ntiles) + L.nranges) * 8;
         RV_HIP(hipMemsetAsync(L.ctrl.dev, 0, (zeroed + 15) & ~size_t(15), ctx->stream));
         hipLaunchKernelGGL(L.fn, dim3(L.grid), dim3(L.block), L.lds, ctx->stream, p);
@@ -876,7 +878,7 @@ uint64_t fused_finish(rv_ctx *ctx, FusedLaunch &L) {
             q->redo_ratio = L.range_rows ? static_cast<double>(p.cap_rows) / L.range_rows : 1.0;
         }
     }
-    if (h->redo_count > 0 && (stage_row_bytes || nxs) && !(L.redo_queued && !rerun)) {
+    if (h->redo_count > 0 && (L.stage_row_bytes || p.nxs) && !(L.redo_queued && !rerun)) {
         if (L.timed) RV_HIP(hipEventRecord(ctx->evk0, ctx->stream));
         launch_redo(ctx, L);
         if (L.timed) RV_HIP(hipEventRecord(ctx->evk1, ctx->stream));
@@ -902,7 +904,7 @@ uint64_t fused_finish(rv_ctx *ctx, FusedLaunch &L) {
         fprintf(stderr, "[stamp direct] cycles/tile (s_memtime, wave 1): load wait %.0f | predicate+count %.0f | barrier 1 %.0f | publish..offset (wave 0: %.0f) %.0f | barrier 2 %.0f | stores %.0f | barrier 3 %.0f | moves+load issue %.0f\n",
                 q[0] / t, q[1] / t, q[2] / t, q[8] / t, q[3] / t, q[4] / t, q[5] / t, q[6] / t, q[7] / t);
     }
-    if ((need & rvk::FF_STAMP) && ctx->opt_stamp) {
+    if ((L.need & rvk::FF_STAMP) && ctx->opt_stamp) {
         std::memcpy(ctx->last_stamps, h->stamps, sizeof(h->stamps));
         for (int w = 0; w < 2; ++w) {
             const unsigned long long *q = h->stamps + 8 * w;

@@ -75,6 +75,7 @@ struct ExprInfo {
 struct OutCol {
     rv_dcolumn *col = nullptr;
     int value_slot = -1;           // value column slot, or -1
+    bool validity = false;         // the value column's output keeps a bitmap
     int xs_values = -1, xs_valid = -1;  // bit stream indices (Boolean columns)
 };
 
@@ -103,16 +104,13 @@ struct FusedLaunch {
     rvk::FusedParams p{};
     std::vector<OutCol> outs;
     rv_ctx::LaunchCtrl ctrl;
-    int need = 0, nvals = 0, nxs = 0;
+    int need = 0, nvals = 0;
     size_t stage_row_bytes = 0;
-    uint64_t tile_rows = 0;
     uint32_t range_rows = 0;  // rows of a wave range (64 x rows per lane); nranges: ranges of the launch's redo list (0: no list)
     uint64_t nranges = 0;
     bool launched = false;  // false: empty input, nothing to wait for
     DevBufRef wave_counts;      // scratch of the per-batch counts kernel queued behind the pass, kept until the launch is finished
     bool redo_queued = false;  // the redo kernel was queued right behind the pass (ranges were expected to outgrow their slots)
-    bool sample_only = false;  // fused_begin stops behind the selectivity it would size the launch by (expected_selectivity)
-    double sampled = -1.0;
     bool timed = false;     // kernel events recorded (option profile_kernels)
     bool direct_stamp = false;  // a diagnostic instantiation of the direct kernel ran: print its phase sums
     // for a re-run after an output overflow (speculative sizing)
@@ -121,7 +119,6 @@ struct FusedLaunch {
     size_t lds = 0;
     uint64_t n = 0;
     uint64_t signature = 0;  // of the predicate (rv_ctx::seen)
-    std::vector<rv_dtype> out_dtypes;  // dtype of every projected source column
     // ---- a SEGMENT of a table filtered piece by piece (run_segmented_pass): the pass writes into buffers the caller owns, from row
     //      `place_base` on; it is sized by `place_selectivity` (the segment's own, out of the sample's profile) instead of the
     //      predicate's memory, leaves that memory alone, and an overflow of the shared outputs is the caller's to handle (`overflowed`)
