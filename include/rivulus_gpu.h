@@ -372,7 +372,9 @@ rv_status rv_concat(rv_ctx *ctx, const rv_dcolumn *const *parts, uint32_t nparts
  *     on a random SipHash bucket-and-tag collision;
  *   - key columns of different dtypes (Int64 against Float64: is_comparable_with allows it, series.rs:144-156) match
  *     null to null only: values of different AnyValue variants never compare equal;
- *   - String keys are not supported on the device: RV_ERR_UNSUPPORTED (String PAYLOAD columns are).
+ *   - String keys go through the string dictionary (below): rv_string_dict_build / _encode reduce them to Int64 ids
+ *     first.  A raw String key column handed to the calls of this section is RV_ERR_UNSUPPORTED (String PAYLOAD
+ *     columns are fine).
  * Pairs come in probe-row order and, within a probe row, in ascending build-row order -- the reference's result_pairs
  * (plan.rs:196-204; the Vec push order of its HashMap<AnyValue, Vec<usize>>) -- identically on every run: output
  * positions come from scans of match counts, never from the order atomics land in.
@@ -430,6 +432,43 @@ rv_status rv_hash_join_chunked(rv_ctx *ctx, const rv_join_table *table,
                                uint64_t chunk_rows, uint64_t max_pairs,
                                rv_dcolumn **out, uint64_t *out_rows, uint64_t nchunks, int64_t *out_nulls,
                                uint64_t *out_total, uint64_t *out_batches);
+
+/* ---- string dictionary (String join keys) --------------------------------- */
+/* The join kernels take 64 key bits per cell.  A String key column gets there through a DICTIONARY: the distinct
+ * non-null strings of one column, each named by an Int64 id, built once on the device; any number of String columns
+ * are then ENCODED against it into Int64 id columns, and the Int64 join runs on the ids unchanged.
+ *
+ * The id of a string is the row index (slice offset excluded) of its FIRST occurrence in the column the dictionary
+ * was built from.  An ids column is an RV_INT64 column of the length of `col`, offset 0:
+ *   - a null cell is null: the validity is re-based to bit 0, absent when `col` has no nulls, null_count is known;
+ *   - a valid cell whose bytes occur in the dictionary gets that string's id;
+ *   - a valid cell whose bytes do not occur gets -1.
+ * Equality is byte equality of the cell (AnyValue::String's PartialEq / Hash, src/datatypes/series.rs:72-98): "" is
+ * a value and not null, embedded NUL bytes count, nothing is normalised.  The result is EXACT -- a hash decides where
+ * to look, never whether two strings are equal: every hit is confirmed against the bytes -- and identical on every
+ * run: an id is the minimum row, whatever order the atomics land in.
+ *
+ * Join property (the reason for the id convention): for String key columns B (build) and P (probe), with ids_B from
+ * rv_string_dict_build(B) and ids_P = rv_string_dict_encode(dict, P), rv_join_build(ids_B) + rv_join_probe(ids_P)
+ * yield exactly the reference's result_pairs for B and P: equal strings meet, null meets null, and an absent string
+ * meets nothing because every build id is >= 0.
+ *
+ * An RV_NULL column is accepted by both calls: all-null ids, an empty dictionary.  Errors leave the context usable
+ * and create nothing: a column of any other dtype RV_ERR_TYPE_MISMATCH, NULL arguments RV_ERR_INVALID_ARG, columns
+ * of 2^32 rows or more RV_ERR_UNSUPPORTED (the join's own limit).  Context option "string_hash_bits" = b (tests; 0 =
+ * all 64) truncates the string hash of dictionaries built afterwards to b low bits: long collision chains on small
+ * inputs, the twin of "join_hash_bits". */
+typedef struct rv_string_dict rv_string_dict;  /* the distinct strings of a column; encodes any number of columns */
+/* Distinct non-null strings of a String column (a slice is fine).  The dictionary shares the column's buffers the way
+ * rv_slice does and keeps them alive: freeing the column handle after the build is allowed.  out_ids (may be NULL)
+ * receives rv_string_dict_encode(dict, col).  rv_ctx_last_kernel: str_dict_insert, or str_dict_encode with out_ids. */
+rv_status rv_string_dict_build(rv_ctx *ctx, const rv_dcolumn *col, rv_string_dict **out, rv_dcolumn **out_ids);
+/* The ids of a String (or RV_NULL) column against a dictionary, as described above. */
+rv_status rv_string_dict_encode(rv_ctx *ctx, const rv_string_dict *dict, const rv_dcolumn *col, rv_dcolumn **out_ids);
+/* Rows of the source column, distinct strings, and hash slots (a power of two, at least twice the non-null rows) of a
+ * dictionary (any pointer may be NULL). */
+rv_status rv_string_dict_info(const rv_string_dict *dict, uint64_t *rows, uint64_t *distinct, uint64_t *slots);
+rv_status rv_string_dict_free(rv_ctx *ctx, rv_string_dict *dict);
 
 /* ---- fused filter + project (K1+K2, the hot path) ------------------------- */
 /* == SelectStream(FilterStream(input)) on one batch (stream.rs:136-158, :202-210) and

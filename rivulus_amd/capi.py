@@ -132,6 +132,10 @@ PROTOTYPES = {
     "rv_join_probe": (C.c_int, [_P, _P, _P, _PP, _PP, _U64P]),
     "rv_join_table_info": (C.c_int, [_P, _U64P, _U64P, _U64P]),
     "rv_join_table_free": (C.c_int, [_P, _P]),
+    "rv_string_dict_build": (C.c_int, [_P, _P, _PP, _PP]),
+    "rv_string_dict_encode": (C.c_int, [_P, _P, _P, _PP]),
+    "rv_string_dict_info": (C.c_int, [_P, _U64P, _U64P, _U64P]),
+    "rv_string_dict_free": (C.c_int, [_P, _P]),
     "rv_hash_join": (C.c_int, [_P, _PP, C.c_uint32, C.c_uint32, _PP, C.c_uint32, C.c_uint32, _PP, _U64P]),
     "rv_hash_join_chunked": (C.c_int, [_P, _P, _PP, C.c_uint32, C.c_uint32, _PP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
                                        _PP, _U64P, C.c_uint64, C.POINTER(C.c_int64), _U64P, _U64P]),
@@ -507,6 +511,36 @@ class JoinTable:
             pass
 
 
+class StringDict:
+    """rv_string_dict: the distinct non-null strings of a String column, each named by the row of its first occurrence."""
+    def __init__(self, ctx: "Context", handle):
+        self.ctx, self.handle = ctx, handle
+
+    def encode(self, col: DeviceColumn) -> DeviceColumn:
+        """Int64 ids of a String (or Null) column: the string's id, -1 for an absent string, null under a null."""
+        out = C.c_void_p()
+        _check(load().rv_string_dict_encode(self.ctx.handle, self.handle, col.handle, C.byref(out)))
+        return DeviceColumn(self.ctx, out)
+
+    def info(self):
+        """(rows of the source column, distinct strings, hash slots)"""
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(load().rv_string_dict_info(self.handle, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def free(self):
+        if self.handle is not None:
+            load().rv_string_dict_free(self.ctx.handle, self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            if self.ctx.handle is not None:
+                self.free()
+        except Exception:
+            pass
+
+
 def _handles(cols: Sequence[DeviceColumn]):
     arr = (C.c_void_p * max(1, len(cols)))()
     for i, c in enumerate(cols):
@@ -714,6 +748,12 @@ class Context:
         out = C.c_void_p()
         _check(load().rv_join_build(self.handle, key.handle, C.byref(out)))
         return JoinTable(self, out)
+
+    def string_dict_build(self, col: DeviceColumn, want_ids: bool = True):
+        """rv_string_dict_build: (dictionary, ids of `col` or None)."""
+        out, ids = C.c_void_p(), C.c_void_p()
+        _check(load().rv_string_dict_build(self.handle, col.handle, C.byref(out), C.byref(ids) if want_ids else None))
+        return StringDict(self, out), (DeviceColumn(self, ids) if want_ids else None)
 
     def hash_join(self, build_cols: Sequence[DeviceColumn], build_key: int, probe_cols: Sequence[DeviceColumn], probe_key: int):
         """Inner hash join (plan.rs:174-284): (every probe column, then the build columns but the key), rows."""

@@ -87,4 +87,10 @@ constexpr uint32_t kJoinLaneListMost = 32;
 // other batch size takes the general pass (join_probe_count_batched<false>: a wave scan per step, LDS counters, integer atomics for
 // batches that span tiles).  Not a crossover: the fast form exists for this one size only.   tests/test_stream_join_gpu.py
 constexpr uint64_t kJoinFastBatchRows = 1024;
+
+// ---- string dictionary (string_dict.hip, rv_string_dict_build) ----------------------------------------------------------------------
+// Slots per non-null row of the source column, rounded up to a power of two: 2 keeps the table at most half full, the load the join's
+// table has (join.hip).  Not a crossover and not swept: with linear probing the expected chain at 50 % is 1.5 slots for a hit and 2.5
+// for a miss, and every slot is one 8-byte word -- 16 bytes per row at most, next to the strings themselves.   tools/string_key_bench.py
+constexpr uint64_t kStrDictSlotsPerRow = 2;
 }  // namespace rvt

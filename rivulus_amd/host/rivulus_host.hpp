@@ -1309,6 +1309,79 @@ class GpuChunkedFilterProjectStream : public DataStream {
     Ahead ahead_;
 };
 
+// String join keys.  The join kernels take 64 key bits per cell, so a String key column is reduced to an Int64 ids column by the
+// device string dictionary (rv_string_dict_build / rv_string_dict_encode) and the Int64 join runs on the ids, unchanged:
+//   - both keys String: the dictionary is built ONCE over the build key, whose ids stand in for it (the build key never reaches
+//     the output); every probe frame / window / batch has its key encoded against the dictionary into a HELPER column that rides
+//     along as one more probe column and is the key -- the caller drops that one output column afterwards.  Equal strings meet,
+//     null meets null, an absent string (-1) meets nothing;
+//   - one key String, the other not: the reference pairs null to null only (values of different AnyValue variants never compare
+//     equal, series.rs:85-97).  The String side is encoded against an EMPTY dictionary -- its nulls stay nulls -- and handed to
+//     the join under a dtype that differs from the other side's (re-wrapped as Float64 when that is Int64), so only the nulls meet;
+//   - neither key String: inactive, the join runs as it always did.
+class StringKeyEncoder {
+  public:
+    StringKeyEncoder(DataType build, DataType probe) : build_(build), probe_(probe) {}
+    ~StringKeyEncoder() {
+        if (dict_) rv_string_dict_free(dict_ctx_->raw(), dict_);
+    }
+    StringKeyEncoder(const StringKeyEncoder &) = delete;
+    StringKeyEncoder &operator=(const StringKeyEncoder &) = delete;
+    bool active() const { return build_ == DataType::String || probe_ == DataType::String; }
+    bool probe_helper() const { return probe_ == DataType::String; }  // the probe side gets a helper column, which is its key
+
+    // what the join hashes in place of the build key (call once, before any probe_key); nullptr: the build key itself
+    ArrayRef build_key(const ArrayRef &key) {
+        if (build_ != DataType::String) return nullptr;
+        const ContextRef &ctx = key->context();
+        if (probe_ != DataType::String) return differing(ctx, encode(ctx, key), probe_);
+        rv_dcolumn *ids = nullptr;
+        check(rv_string_dict_build(ctx->raw(), key->handle(), &dict_, &ids));
+        dict_ctx_ = ctx;
+        return Array::adopt(ctx, ids);
+    }
+    // the helper column of one probe frame / window / batch; nullptr: the probe key itself
+    ArrayRef probe_key(const ContextRef &ctx, const ArrayRef &key) {
+        if (probe_ != DataType::String) return nullptr;
+        ArrayRef ids = encode(ctx, key);
+        return build_ == DataType::String ? ids : differing(ctx, ids, build_);
+    }
+
+  private:
+    // the ids of `key` against the dictionary (an empty one when only one side is String: built on first use)
+    ArrayRef encode(const ContextRef &ctx, const ArrayRef &key) {
+        if (!dict_) {
+            ArrayRef none = NullArray::create(ctx, 0);
+            check(rv_string_dict_build(ctx->raw(), none->handle(), &dict_, nullptr));
+            dict_ctx_ = ctx;
+        }
+        rv_dcolumn *ids = nullptr;
+        check(rv_string_dict_encode(ctx->raw(), dict_, key->handle(), &ids));
+        return Array::adopt(ctx, ids);
+    }
+    // an ids column whose buffers are read as Float64: a view that keeps the ids alive
+    class Float64View : public Array {
+      public:
+        Float64View(ContextRef ctx, rv_dcolumn *h, ArrayRef owner) : Array(std::move(ctx), h), owner_(std::move(owner)) {}
+
+      private:
+        ArrayRef owner_;
+    };
+    // `ids` (Int64) under a dtype other than `other`
+    static ArrayRef differing(const ContextRef &ctx, ArrayRef ids, DataType other) {
+        if (other != DataType::Int64) return ids;
+        rv_column c{};
+        check(rv_device_ptrs(ctx->raw(), ids->handle(), &c));
+        c.dtype = RV_FLOAT64;
+        rv_dcolumn *h = nullptr;
+        check(rv_wrap(ctx->raw(), &c, &h));
+        return std::make_shared<const Float64View>(ctx, h, std::move(ids));
+    }
+    DataType build_, probe_;
+    rv_string_dict *dict_ = nullptr;
+    ContextRef dict_ctx_;
+};
+
 // One side of a streaming join: a stream, or a resident frame (a DataFrameSource: its columns after dataframe_to_batches' null
 // fill, cut into batch_size-row batches).
 struct JoinSide {
@@ -1360,6 +1433,7 @@ class GpuHashJoinStream : public DataStream {
             f.push_back(Field{probe_schema_->field_by_name(b.name()) ? b.name() + "_right" : b.name(), b.data_type(), b.is_nullable()});
         }
         output_schema_ = std::make_shared<const Schema>(f);
+        string_keys_ = std::make_unique<StringKeyEncoder>(build_schema_->field(bki_).data_type(), probe_schema_->field(pki_).data_type());
         probe_rows_ = probe_.stream ? 0 : (probe_.columns.empty() ? 0 : probe_.columns[0]->len());
     }
     ~GpuHashJoinStream() override {
@@ -1408,25 +1482,47 @@ class GpuHashJoinStream : public DataStream {
             }
             for (auto &c : build_.columns) build_handles_.push_back(c->handle());
             table_ctx_ = build_.columns[bki_]->context();
-            check(rv_join_build(table_ctx_->raw(), build_.columns[bki_]->handle(), &table_));
+            // a String build key: its ids stand in for it, in the table and among the columns (the key is never gathered)
+            if ((build_key_ids_ = string_keys_->build_key(build_.columns[bki_]))) build_handles_[bki_] = build_key_ids_->handle();
+            check(rv_join_build(table_ctx_->raw(), build_handles_[bki_], &table_));
         } catch (const Error &e) {
             throw StreamError::execution(e.what());
         }
     }
-    // rv_hash_join_chunked over the n rows of `probe` in batches of `chunk`, into out / rows / nulls; returns the batches taken
-    uint64_t join_window(const ContextRef &ctx, const std::vector<const rv_dcolumn *> &probe, uint64_t n, uint64_t chunk, std::vector<ArrayRef> &out,
-                         std::vector<uint64_t> &rows, std::vector<int64_t> &nulls, uint64_t &pairs) {
-        const size_t nout = output_schema_->num_fields();
+    // rv_hash_join_chunked over the n rows of `probe` (columns `arrays`) in batches of `chunk`, into out / rows / nulls; returns the
+    // batches taken.  A String probe key is encoded first: its ids ride along as one more probe column, which is the key, and that
+    // column leaves the outputs and the null counts again.
+    uint64_t join_window(const ContextRef &ctx, std::vector<const rv_dcolumn *> probe, const std::vector<ArrayRef> &arrays, uint64_t n, uint64_t chunk,
+                         std::vector<ArrayRef> &out, std::vector<uint64_t> &rows, std::vector<int64_t> &nulls, uint64_t &pairs) {
+        ArrayRef helper;
+        uint32_t pki = pki_;
+        try {
+            helper = string_keys_->probe_key(ctx, arrays[pki_]);
+        } catch (const Error &e) {
+            throw StreamError::execution(e.what());
+        }
+        const size_t helper_at = probe.size();
+        if (helper) {
+            probe.push_back(helper->handle());
+            pki = static_cast<uint32_t>(helper_at);
+        }
+        const size_t nout = output_schema_->num_fields() + (helper ? 1 : 0);
         const uint64_t nb = (n + chunk - 1) / chunk;
         std::vector<rv_dcolumn *> raw(nout, nullptr);
         rows.assign(std::max<uint64_t>(nb, 1), 0);
         nulls.assign(std::max<uint64_t>(nb, 1) * nout, 0);
         uint64_t taken = 0;
         check_stream(rv_hash_join_chunked(ctx->raw(), table_, build_handles_.data(), static_cast<uint32_t>(build_handles_.size()), bki_, probe.data(),
-                                          static_cast<uint32_t>(probe.size()), pki_, chunk, max_pairs_, raw.data(), rows.data(), nb, nulls.data(), &pairs, &taken));
+                                          static_cast<uint32_t>(probe.size()), pki, chunk, max_pairs_, raw.data(), rows.data(), nb, nulls.data(), &pairs, &taken));
         out.clear();
         for (auto *h : raw) out.push_back(Array::adopt(ctx, h));
         rows.resize(taken);
+        if (helper) {
+            out.erase(out.begin() + static_cast<long>(helper_at));
+            for (uint64_t k = 0; k < taken; ++k)  // row k of the null counts: nout entries, the helper's at helper_at
+                for (size_t j = 0, w = 0; j < nout; ++j)
+                    if (j != helper_at) nulls[k * (nout - 1) + w++] = nulls[k * nout + j];
+        }
         return taken;
     }
     void refill() {  // the next window of the resident probe frame
@@ -1447,7 +1543,7 @@ class GpuHashJoinStream : public DataStream {
         std::vector<uint64_t> rows;
         std::vector<int64_t> nulls;
         uint64_t pairs = 0;
-        const uint64_t taken = join_window(ctx, cols, len, batch, out, rows, nulls, pairs);
+        const uint64_t taken = join_window(ctx, cols, views, len, batch, out, rows, nulls, pairs);
         const size_t probed = std::min<size_t>(len, taken * batch);
         joined_ = std::move(out);
         window_rows_out_ = std::move(rows);
@@ -1468,7 +1564,7 @@ class GpuHashJoinStream : public DataStream {
         std::vector<uint64_t> rows;
         std::vector<int64_t> nulls;
         uint64_t pairs = 0;
-        join_window(ctx, cols, batch->num_rows(), std::max<size_t>(1, batch->num_rows()), out, rows, nulls, pairs);
+        join_window(ctx, cols, batch->columns(), batch->num_rows(), std::max<size_t>(1, batch->num_rows()), out, rows, nulls, pairs);
         limit_.record(batch->num_rows(), pairs);
         if (rows.empty()) return RecordBatch::new_unchecked(output_schema_, std::move(out), 0);  // a zero-row probe batch
         std::vector<ArrayRef> arrays;
@@ -1496,6 +1592,8 @@ class GpuHashJoinStream : public DataStream {
     rv_join_table *table_ = nullptr;
     ContextRef table_ctx_;
     std::vector<const rv_dcolumn *> build_handles_;
+    std::unique_ptr<StringKeyEncoder> string_keys_;  // String keys go through the string dictionary
+    ArrayRef build_key_ids_;                         // ... the ids that stand in for a String build key
     size_t probe_rows_ = 0, next_row_ = 0;
     std::vector<ArrayRef> joined_;  // the current window's outputs, all its batches back to back
     std::vector<uint64_t> window_rows_out_;
@@ -1998,9 +2096,17 @@ class PhysicalPlan {
                     if (&p.columns[i] == pk) pki = static_cast<uint32_t>(i);
                     pcols.push_back(p.columns[i]->handle());
                 }
+                // String keys go through the string dictionary: ids in place of the build key, a helper column as the probe key
+                const ContextRef ctx = (*pk)->context();
+                execution::StringKeyEncoder string_keys((*bk)->data_type(), (*pk)->data_type());
+                const execution::ArrayRef build_ids = string_keys.build_key(*bk), helper = string_keys.probe_key(ctx, *pk);
+                if (build_ids) bcols[bki] = build_ids->handle();
+                if (helper) {
+                    pki = static_cast<uint32_t>(pcols.size());
+                    pcols.push_back(helper->handle());
+                }
                 std::vector<rv_dcolumn *> out(pcols.size() + bcols.size() - 1, nullptr);
                 uint64_t rows = 0;
-                const ContextRef ctx = (*pk)->context();
                 check(rv_hash_join(ctx->raw(), bcols.data(), static_cast<uint32_t>(bcols.size()), bki, pcols.data(), static_cast<uint32_t>(pcols.size()),
                                    pki, out.data(), &rows));
                 // materialize_join_result (plan.rs:212-255): probe names, then the build names but the key, `_right` where the probe
@@ -2011,6 +2117,7 @@ class PhysicalPlan {
                     res.names.push_back(p.names[i]);
                     res.columns.push_back(execution::Array::adopt(ctx, out[k]));
                 }
+                if (helper) rv_free(ctx->raw(), out[k++]);  // the helper column's pairs: not part of the frame
                 for (size_t i = 0; i < b.columns.size(); ++i) {
                     if (b.names[i] == build_key) continue;
                     res.names.push_back(p.column(b.names[i]) ? b.names[i] + "_right" : b.names[i]);
