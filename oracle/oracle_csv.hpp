@@ -14,6 +14,7 @@
 // a CSV field can hold.
 #pragma once
 
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <fstream>

@@ -311,6 +311,52 @@ rv_status rv_download(rv_ctx *ctx, const rv_dcolumn *col, void *values, uint8_t 
 
 }  // extern "C"
 namespace rvl {
+// ---- set bits per range (launch.hpp) ---------------------------------------------------------------
+void segment_bit_counts(rv_ctx *ctx, const char *what, const uint64_t *const *words, size_t m, const uint64_t *bounds, uint64_t nb, uint64_t *counts) {
+    const uint64_t cus = static_cast<uint64_t>(ctx->props.multiProcessorCount);
+    std::vector<rvk::SegItem> items;
+    uint64_t chunk_words = 0;
+    const rv_status st = rvk::segment_items(bounds, nb, cus, items, chunk_words);
+    require(st == RV_OK, st, fmt("%s: 2^32 batches or more in one window", what));
+    std::fill(counts, counts + m * nb, uint64_t{0});
+    if (m == 0 || items.empty()) return;
+    // the tables go through pinned staging: [bounds | items] in, [counts] out
+    const size_t bb = (nb + 1) * 8, ib = items.size() * sizeof(rvk::SegItem), cb = m * nb * 8;
+    DevBufRef d_tables = pool_alloc(ctx, bb + ib + 16), d_counts = pool_alloc(ctx, cb + 16);
+    char *hs = static_cast<char *>(ctx->stage(std::max(bb + ib, cb)));
+    std::memcpy(hs, bounds, bb);
+    std::memcpy(hs + bb, items.data(), ib);
+    RV_HIP(hipMemcpyAsync(d_tables->ptr, hs, bb + ib, hipMemcpyHostToDevice, ctx->stream));
+    RV_HIP(hipMemsetAsync(d_counts->ptr, 0, cb, ctx->stream));
+    const uint64_t *d_bounds = static_cast<const uint64_t *>(d_tables->ptr);
+    const auto *d_items = reinterpret_cast<const rvk::SegItem *>(static_cast<const char *>(d_tables->ptr) + bb);
+    const dim3 grid(static_cast<uint32_t>(std::min<uint64_t>((items.size() + 3) / 4, cus * 16)));
+    for (size_t c = 0; c < m; ++c)
+        hipLaunchKernelGGL(rvk::segment_popcount_kernel, grid, dim3(256), 0, ctx->stream, words[c], d_bounds, d_items, static_cast<uint64_t>(items.size()),
+                           chunk_words, static_cast<unsigned long long *>(d_counts->ptr) + c * nb);
+    RV_HIP(hipGetLastError());
+    RV_HIP(hipMemcpyAsync(hs, d_counts->ptr, cb, hipMemcpyDeviceToHost, ctx->stream));  // stream order: after the upload read hs
+    RV_HIP(hipStreamSynchronize(ctx->stream));
+    std::memcpy(counts, hs, cb);
+}
+
+void batch_null_counts(rv_ctx *ctx, const char *what, const rv_dcolumn *const *out, uint32_t nout, const uint64_t *batch_rows, uint64_t nb, int64_t *out_nulls) {
+    std::vector<uint32_t> counted;  // columns with a bitmap
+    std::vector<const uint64_t *> words;
+    for (uint32_t j = 0; j < nout; ++j) {
+        for (uint64_t k = 0; k < nb; ++k) out_nulls[k * nout + j] = out[j]->dtype == RV_NULL ? static_cast<int64_t>(batch_rows[k]) : 0;
+        if (out[j]->dtype == RV_NULL || !out[j]->validity) continue;
+        counted.push_back(j);
+        words.push_back(static_cast<const uint64_t *>(out[j]->validity->ptr));
+    }
+    if (counted.empty() || nb == 0) return;
+    std::vector<uint64_t> bounds(nb + 1, 0), valid(counted.size() * nb);
+    for (uint64_t k = 0; k < nb; ++k) bounds[k + 1] = bounds[k] + batch_rows[k];
+    segment_bit_counts(ctx, what, words.data(), words.size(), bounds.data(), nb, valid.data());
+    for (size_t c = 0; c < counted.size(); ++c)
+        for (uint64_t k = 0; k < nb; ++k) out_nulls[k * nout + counted[c]] = static_cast<int64_t>(batch_rows[k] - valid[c * nb + k]);
+}
+
 // ---- predicate ---------------------------------------------------------------------------------
 void check_batch(const rv_dcolumn *const *cols, uint32_t ncols) {
     require(cols != nullptr || ncols == 0, RV_ERR_INVALID_ARG, "cols is NULL");

@@ -5,6 +5,7 @@
 #pragma once
 
 #include "device_common.hpp"
+#include "segment_items.hpp"  // SegItem, kSegChunkWords: shared with the host
 
 namespace rvk {
 
@@ -189,10 +190,6 @@ static __global__ __launch_bounds__(64) void fold_stripes_kernel(unsigned long l
 // wave per chunk, one atomic per chunk: a million 1024-row ranges and four 64 Mi-row ranges both fill the device.
 // Survivor count of every input batch out of the selection bitmap of a coalesced launch, null count of every
 // output batch out of the compacted validity (rv_filter_project_batches).
-constexpr uint64_t kSegChunkWords = 4096;
-struct SegItem {
-    uint32_t segment, chunk;
-};
 static __global__ __launch_bounds__(256) void segment_popcount_kernel(const uint64_t *words, const uint64_t *bounds, const SegItem *items,
                                                                uint64_t nitems, uint64_t chunk_words, unsigned long long *counts) {
     const int lane = lane_id();

@@ -142,10 +142,7 @@ rv_status rv_filter_project_host(rv_ctx *ctx, const rv_column *host_cols, uint32
         } catch (...) {
             (void)hipStreamSynchronize(ctx->copy_stream);
             drop_parts();
-            for (uint32_t j = 0; j < nproj; ++j) {
-                delete out[j];
-                out[j] = nullptr;
-            }
+            drop_outputs(out, nproj);
             throw;
         }
         if (out_rows) *out_rows = total;

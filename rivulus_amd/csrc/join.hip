@@ -133,22 +133,48 @@ rv_dcolumn *index_column(const DevBufRef &buf, uint64_t rows) {
     return o.release();
 }
 
+// JoinProbeParams of `key` against `t`, without the tile counts and the outputs; longest = the longest list a probe row of this key
+// column can meet
+rvk::JoinProbeParams probe_params(const rv_join_table *t, const rv_dcolumn *key, uint64_t &longest) {
+    rvk::JoinProbeParams p{};
+    p.table = table_view(t, key->dtype);
+    p.key = dev_view(key);
+    p.n = key->length;
+    p.lane_most = rvt::kJoinLaneListMost;
+    longest = std::max<uint64_t>(p.table.match_values ? t->max_group : 0, t->n_null);
+    return p;
+}
+
+// pairs the device can hold: two 8-byte indices each
+uint64_t device_pair_cap(const rv_ctx *ctx) { return static_cast<uint64_t>(ctx->props.totalGlobalMem) / 16; }
+
+// the emit pass over the first p.n rows, into fresh index buffers of `pairs` pairs: by lists of at most one row, of at most a lane's
+// share, or longer
+void emit_pairs(rv_ctx *ctx, rvk::JoinProbeParams &p, uint64_t longest, uint64_t pairs, DevBufRef &out_probe, DevBufRef &out_build) {
+    out_probe = pool_alloc(ctx, std::max<size_t>(pairs * 8, 16));
+    out_build = pool_alloc(ctx, std::max<size_t>(pairs * 8, 16));
+    if (!pairs) return;
+    p.out_probe = static_cast<int64_t *>(out_probe->ptr);
+    p.out_build = static_cast<int64_t *>(out_build->ptr);
+    const dim3 grid(static_cast<uint32_t>((p.n + rvk::kJoinTileRows - 1) / rvk::kJoinTileRows)), block(rvk::kJoinThreads);
+    const int mode = longest <= 1 ? 0 : longest <= rvt::kJoinLaneListMost ? 1 : 2;
+    if (mode == 0) hipLaunchKernelGGL(rvk::join_probe_emit<0>, grid, block, 0, ctx->stream, p);
+    else if (mode == 1) hipLaunchKernelGGL(rvk::join_probe_emit<1>, grid, block, 0, ctx->stream, p);
+    else hipLaunchKernelGGL(rvk::join_probe_emit<2>, grid, block, 0, ctx->stream, p);
+    RV_HIP(hipGetLastError());
+    ctx->last_kernel = fmt("join_probe_emit<%d>", mode);
+}
+
 // result_pairs of plan.rs:196-204 as two Int64 index buffers: count pass, scan of the tile counts, one read-back of the total,
 // the size check, then the emit pass
 uint64_t probe_table(rv_ctx *ctx, const rv_join_table *t, const rv_dcolumn *key, DevBufRef &out_probe, DevBufRef &out_build) {
     check_key(key, "rv_join_probe");
-    const uint64_t n = key->length;
-    rvk::JoinProbeParams p{};
-    p.table = table_view(t, key->dtype);
-    p.key = dev_view(key);
-    p.n = n;
-    p.lane_most = rvt::kJoinLaneListMost;
-    // the longest list a probe row of this key column can meet
-    const uint64_t longest = std::max<uint64_t>(p.table.match_values ? t->max_group : 0, t->n_null);
+    uint64_t longest = 0;
+    rvk::JoinProbeParams p = probe_params(t, key, longest);
     uint64_t total = 0;
     DevBufRef tiles;
-    const uint64_t ntiles = (n + rvk::kJoinTileRows - 1) / rvk::kJoinTileRows;
-    if (n && longest) {
+    const uint64_t ntiles = (p.n + rvk::kJoinTileRows - 1) / rvk::kJoinTileRows;
+    if (p.n && longest) {
         tiles = pool_alloc(ctx, ntiles * 8 + 16);
         p.tile_counts = static_cast<uint64_t *>(tiles->ptr);
         Ctrl *ctrl = prepare_ctrl(ctx, 0);
@@ -158,25 +184,11 @@ uint64_t probe_table(rv_ctx *ctx, const rv_join_table *t, const rv_dcolumn *key,
         ctx->last_kernel = "join_probe_count";
         total = fetch_ctrl(ctx)->pops[0];
     }
-    // two 8-byte indices per pair: refuse what the device cannot hold before anything is allocated (n_probe x n_build pairs can
-    // exceed 2^64 bytes)
-    const uint64_t limit = static_cast<uint64_t>(ctx->props.totalGlobalMem) / 16;
-    require(total <= limit, RV_ERR_OOM,
+    // refuse what the device cannot hold before anything is allocated (n_probe x n_build pairs can exceed 2^64 bytes)
+    require(total <= device_pair_cap(ctx), RV_ERR_OOM,
             fmt("rv_join_probe: %llu pairs need %llu x 16 bytes of output, more than the device's %llu bytes", static_cast<unsigned long long>(total),
                 static_cast<unsigned long long>(total), static_cast<unsigned long long>(ctx->props.totalGlobalMem)));
-    out_probe = pool_alloc(ctx, std::max<size_t>(total * 8, 16));
-    out_build = pool_alloc(ctx, std::max<size_t>(total * 8, 16));
-    if (total) {
-        p.out_probe = static_cast<int64_t *>(out_probe->ptr);
-        p.out_build = static_cast<int64_t *>(out_build->ptr);
-        const dim3 grid(static_cast<uint32_t>(ntiles)), block(rvk::kJoinThreads);
-        const int mode = longest <= 1 ? 0 : longest <= rvt::kJoinLaneListMost ? 1 : 2;
-        if (mode == 0) hipLaunchKernelGGL(rvk::join_probe_emit<0>, grid, block, 0, ctx->stream, p);
-        else if (mode == 1) hipLaunchKernelGGL(rvk::join_probe_emit<1>, grid, block, 0, ctx->stream, p);
-        else hipLaunchKernelGGL(rvk::join_probe_emit<2>, grid, block, 0, ctx->stream, p);
-        RV_HIP(hipGetLastError());
-        ctx->last_kernel = fmt("join_probe_emit<%d>", mode);
-    }
+    emit_pairs(ctx, p, longest, total, out_probe, out_build);
     RV_HIP(hipStreamSynchronize(ctx->stream));  // `tiles` goes back to the pool
     return total;
 }
@@ -192,12 +204,8 @@ uint64_t probe_table_batched(rv_ctx *ctx, const rv_join_table *t, const rv_dcolu
     check_key(key, "rv_hash_join_chunked");
     const uint64_t n = key->length;
     const uint64_t nb = (n + chunk_rows - 1) / chunk_rows;
-    rvk::JoinProbeParams p{};
-    p.table = table_view(t, key->dtype);
-    p.key = dev_view(key);
-    p.n = n;
-    p.lane_most = rvt::kJoinLaneListMost;
-    const uint64_t longest = std::max<uint64_t>(p.table.match_values ? t->max_group : 0, t->n_null);
+    uint64_t longest = 0;
+    rvk::JoinProbeParams p = probe_params(t, key, longest);
     uint64_t total = 0;
     DevBufRef tiles;
     ctx->last_kernel = "join_probe_count_batched";
@@ -224,7 +232,7 @@ uint64_t probe_table_batched(rv_ctx *ctx, const rv_join_table *t, const rv_dcolu
         require(sum == total, RV_ERR_INTERNAL, "rv_hash_join_chunked: per-batch pair counts do not add up");
     }
     // the longest prefix that fits; one batch the device cannot hold on its own is RV_ERR_OOM before anything is allocated
-    const uint64_t device_most = static_cast<uint64_t>(ctx->props.totalGlobalMem) / 16;
+    const uint64_t device_most = device_pair_cap(ctx);
     const uint64_t cap = max_pairs ? std::min(max_pairs, device_most) : device_most;
     require(nb == 0 || batch_rows[0] <= device_most, RV_ERR_OOM,
             fmt("rv_hash_join_chunked: batch 0 has %llu pairs, more than the device's %llu bytes hold at 16 bytes each",
@@ -232,65 +240,10 @@ uint64_t probe_table_batched(rv_ctx *ctx, const rv_join_table *t, const rv_dcolu
     uint64_t pairs = 0;
     taken = 0;
     while (taken < nb && (taken == 0 || (pairs <= cap && batch_rows[taken] <= cap - pairs))) pairs += batch_rows[taken++];
-    out_probe = pool_alloc(ctx, std::max<size_t>(pairs * 8, 16));
-    out_build = pool_alloc(ctx, std::max<size_t>(pairs * 8, 16));
-    if (pairs) {
-        p.n = std::min(n, taken * chunk_rows);  // the prefix's rows: its tiles' prefixes are those of the whole window
-        p.out_probe = static_cast<int64_t *>(out_probe->ptr);
-        p.out_build = static_cast<int64_t *>(out_build->ptr);
-        const dim3 grid(static_cast<uint32_t>((p.n + rvk::kJoinTileRows - 1) / rvk::kJoinTileRows)), block(rvk::kJoinThreads);
-        const int mode = longest <= 1 ? 0 : longest <= rvt::kJoinLaneListMost ? 1 : 2;
-        if (mode == 0) hipLaunchKernelGGL(rvk::join_probe_emit<0>, grid, block, 0, ctx->stream, p);
-        else if (mode == 1) hipLaunchKernelGGL(rvk::join_probe_emit<1>, grid, block, 0, ctx->stream, p);
-        else hipLaunchKernelGGL(rvk::join_probe_emit<2>, grid, block, 0, ctx->stream, p);
-        RV_HIP(hipGetLastError());
-        ctx->last_kernel = fmt("join_probe_emit<%d>", mode);
-    }
+    p.n = std::min(n, taken * chunk_rows);  // the prefix's rows: its tiles' prefixes are those of the whole window
+    emit_pairs(ctx, p, longest, pairs, out_probe, out_build);
     // no wait here: `tiles` goes back to the pool, and its next user runs behind the emit pass on the stream
     return pairs;
-}
-
-// null count of every output batch and column: set bits of each output validity inside the batches' pair ranges
-// (segment_popcount_kernel), one launch per column with a bitmap, every column's counts read back together
-void window_null_counts(rv_ctx *ctx, rv_dcolumn *const *out, uint32_t nout, const uint64_t *batch_rows, uint64_t nb, int64_t *out_nulls) {
-    std::vector<uint64_t> bounds(nb + 1, 0);
-    for (uint64_t k = 0; k < nb; ++k) bounds[k + 1] = bounds[k] + batch_rows[k];
-    std::vector<uint32_t> counted;  // columns with a bitmap
-    for (uint32_t j = 0; j < nout; ++j) {
-        for (uint64_t k = 0; k < nb; ++k) out_nulls[k * nout + j] = out[j]->dtype == RV_NULL ? static_cast<int64_t>(batch_rows[k]) : 0;
-        if (out[j]->dtype != RV_NULL && out[j]->validity) counted.push_back(j);
-    }
-    if (counted.empty() || nb == 0) return;
-    std::vector<rvk::SegItem> items;
-    uint64_t all_words = 0;
-    for (uint64_t k = 0; k < nb; ++k)
-        if (bounds[k + 1] > bounds[k]) all_words += ((bounds[k + 1] - 1) >> 6) - (bounds[k] >> 6) + 1;
-    const uint64_t chunk_words = std::max<uint64_t>(rvk::kSegChunkWords, (all_words / (static_cast<uint64_t>(ctx->props.multiProcessorCount) * 8) + 63) & ~63ull);
-    for (uint64_t k = 0; k < nb; ++k) {
-        if (bounds[k + 1] <= bounds[k]) continue;
-        const uint64_t nwords = ((bounds[k + 1] - 1) >> 6) - (bounds[k] >> 6) + 1;
-        for (uint64_t c = 0; c * chunk_words < nwords; ++c) items.push_back(rvk::SegItem{static_cast<uint32_t>(k), static_cast<uint32_t>(c)});
-    }
-    require(nb < (uint64_t{1} << 32), RV_ERR_UNSUPPORTED, "rv_hash_join_chunked: 2^32 batches or more in one window");
-    const size_t bb = (nb + 1) * 8, ib = items.size() * sizeof(rvk::SegItem), cb = counted.size() * nb * 8;
-    DevBufRef d_tables = pool_alloc(ctx, bb + ib + 16), d_counts = pool_alloc(ctx, cb + 16);
-    char *hs = static_cast<char *>(ctx->stage(std::max(bb + ib, cb)));
-    std::memcpy(hs, bounds.data(), bb);
-    std::memcpy(hs + bb, items.data(), ib);
-    RV_HIP(hipMemcpyAsync(d_tables->ptr, hs, bb + ib, hipMemcpyHostToDevice, ctx->stream));
-    RV_HIP(hipMemsetAsync(d_counts->ptr, 0, cb, ctx->stream));
-    const uint64_t *d_bounds = static_cast<const uint64_t *>(d_tables->ptr);
-    const auto *d_items = reinterpret_cast<const rvk::SegItem *>(static_cast<const char *>(d_tables->ptr) + bb);
-    const dim3 grid(static_cast<uint32_t>(std::min<uint64_t>((items.size() + 3) / 4, static_cast<uint64_t>(ctx->props.multiProcessorCount) * 16)));
-    for (size_t c = 0; c < counted.size() && !items.empty(); ++c)
-        hipLaunchKernelGGL(rvk::segment_popcount_kernel, grid, dim3(256), 0, ctx->stream, static_cast<const uint64_t *>(out[counted[c]]->validity->ptr),
-                           d_bounds, d_items, static_cast<uint64_t>(items.size()), chunk_words, static_cast<unsigned long long *>(d_counts->ptr) + c * nb);
-    RV_HIP(hipGetLastError());
-    RV_HIP(hipMemcpyAsync(hs, d_counts->ptr, cb, hipMemcpyDeviceToHost, ctx->stream));  // stream order: after the upload read hs
-    RV_HIP(hipStreamSynchronize(ctx->stream));
-    const uint64_t *valid = reinterpret_cast<const uint64_t *>(hs);
-    for (size_t c = 0; c < counted.size(); ++c)
-        for (uint64_t k = 0; k < nb; ++k) out_nulls[k * nout + counted[c]] = static_cast<int64_t>(batch_rows[k] - valid[c * nb + k]);
 }
 
 // the checks of rv_hash_join, shared by the chunked form
@@ -300,14 +253,11 @@ void check_join_sides(const char *what, const rv_dcolumn *const *build_cols, uin
     require(probe_key < n_probe, RV_ERR_INVALID_ARG, fmt("%s: probe key %u out of range for %u probe columns", what, probe_key, n_probe));
     check_batch(build_cols, n_build);
     check_batch(probe_cols, n_probe);
-    for (uint32_t c = 0; c < n_build; ++c) {
-        const rv_dtype d = build_cols[c]->dtype;
-        require(is_value_type(d) || d == RV_BOOLEAN || d == RV_STRING || d == RV_NULL, RV_ERR_UNSUPPORTED, fmt("%s: unsupported dtype", what));
-    }
-    for (uint32_t c = 0; c < n_probe; ++c) {
-        const rv_dtype d = probe_cols[c]->dtype;
-        require(is_value_type(d) || d == RV_BOOLEAN || d == RV_STRING || d == RV_NULL, RV_ERR_UNSUPPORTED, fmt("%s: unsupported dtype", what));
-    }
+    for (const auto &[cols, n] : {std::pair{build_cols, n_build}, std::pair{probe_cols, n_probe}})
+        for (uint32_t c = 0; c < n; ++c) {
+            const rv_dtype d = cols[c]->dtype;
+            require(is_value_type(d) || d == RV_BOOLEAN || d == RV_STRING || d == RV_NULL, RV_ERR_UNSUPPORTED, fmt("%s: unsupported dtype", what));
+        }
     check_key(build_cols[build_key], what);
     check_key(probe_cols[probe_key], what);
 }
@@ -326,10 +276,7 @@ void gather_pairs(rv_ctx *ctx, const rv_dcolumn *const *build_cols, uint32_t n_b
         RV_HIP(hipStreamSynchronize(ctx->stream));  // the index buffers go back to the pool
     } catch (...) {
         (void)hipStreamSynchronize(ctx->stream);
-        for (uint32_t c = 0; c < nout; ++c) {
-            delete out[c];
-            out[c] = nullptr;
-        }
+        drop_outputs(out, nout);
         throw;
     }
 }
@@ -423,12 +370,9 @@ rv_status rv_hash_join_chunked(rv_ctx *ctx, const rv_join_table *table, const rv
         const uint64_t rows = probe_table_batched(ctx, table, probe_cols[probe_key], chunk_rows, max_pairs, counts.data(), taken, pi, bi);
         gather_pairs(ctx, build_cols, n_build, build_key, probe_cols, n_probe, pi, bi, rows, out);
         try {
-            if (out_nulls) window_null_counts(ctx, out, nout, counts.data(), taken, out_nulls);
+            if (out_nulls) batch_null_counts(ctx, "rv_hash_join_chunked", out, nout, counts.data(), taken, out_nulls);
         } catch (...) {
-            for (uint32_t c = 0; c < nout; ++c) {
-                delete out[c];
-                out[c] = nullptr;
-            }
+            drop_outputs(out, nout);
             throw;
         }
         if (nb) std::memcpy(out_rows, counts.data(), nb * 8);

@@ -1,6 +1,6 @@
 // Internal interface between the translation units of librivulus_gpu.so (core / fused_launch / strings / predicate / arrays /
-// query / take_concat / host_table / aggregate .hip): the control block, the request / launch records that travel with a
-// fused pass, and the functions the units call across each other.  Nothing here is part of the C ABI.
+// query / take_concat / host_table / aggregate / join / string_dict / csv / group .hip): the control block, the request / launch
+// records that travel with a fused pass, and the functions the units call across each other.  Nothing here is part of the C ABI.
 #pragma once
 
 #include <algorithm>
@@ -233,6 +233,21 @@ void normalize_predicate(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t nc
 // ---- arrays.hip --------------------------------------------------------------------------------------------
 void check_batch(const rv_dcolumn *const *cols, uint32_t ncols);
 void bool_op(rv_ctx *ctx, int kind, const rv_dcolumn *a, const rv_dcolumn *b, rv_dcolumn **out);
+// counts[c * nb + k] (host) = set bits of the LSB-first bitmap words[c] inside the bit range [bounds[k], bounds[k + 1]), for m
+// bitmaps and nb ranges (segment_items.hpp, segment_popcount_kernel): the tables uploaded once, one launch per bitmap, one
+// read-back, one wait.  Nothing is launched when m == 0 or no range holds a bit.  `what` names the caller in the refusal of
+// 2^32 ranges or more.
+void segment_bit_counts(rv_ctx *ctx, const char *what, const uint64_t *const *words, size_t m, const uint64_t *bounds, uint64_t nb, uint64_t *counts);
+// out_nulls[k * nout + j] = nulls of output column j inside batch k, the batches being batch_rows[k] rows each, back to back: the
+// batch's rows for a NullArray, 0 without a bitmap, else its rows less the validity bits segment_bit_counts finds there
+void batch_null_counts(rv_ctx *ctx, const char *what, const rv_dcolumn *const *out, uint32_t nout, const uint64_t *batch_rows, uint64_t nb, int64_t *out_nulls);
+// the outputs of a call that failed after it made them: freed, and the caller's slots nulled
+inline void drop_outputs(rv_dcolumn **out, uint32_t n) {
+    for (uint32_t c = 0; c < n; ++c) {
+        delete out[c];
+        out[c] = nullptr;
+    }
+}
 
 // ---- take_concat.hip ---------------------------------------------------------------------------------------
 // RecordBatch::take with the index list in HBM (bounds pre-pass unless check_bounds is false), one gather per column

@@ -812,102 +812,32 @@ void finish_batch_req(const BatchReq &req, uint64_t *out_rows) {
 // counts are taken here.
 void batch_counts(rv_ctx *ctx, const rv_dcolumn *sel, uint64_t rows, const std::vector<uint64_t> &bounds, uint64_t uniform_rows, size_t nb,
                   rv_dcolumn *const *out, uint32_t nproj, uint64_t *out_rows, int64_t *out_nulls) {
-    DevBufRef d_bounds, d_counts;  // taken when a count is actually run (none is, with the counts out of the pass and no nulls asked for)
-    auto need_tables = [&] {
-        if (!d_counts) d_bounds = pool_alloc(ctx, (nb + 1) * 8), d_counts = pool_alloc(ctx, nb * 8);
-    };
-    std::vector<rvk::SegItem> items;
-    DevBufRef d_items;
-    // set bits of `words` per range of `b` -> dst (host), through segment_popcount_kernel
-    auto segment_counts = [&](const uint64_t *words, const std::vector<uint64_t> &b, uint64_t *dst) {
-        need_tables();
-        items.clear();
-        uint64_t all_words = 0;
-        for (size_t k = 0; k < nb; ++k)
-            if (b[k + 1] > b[k]) all_words += ((b[k + 1] - 1) >> 6) - (b[k] >> 6) + 1;
-        const uint64_t chunk_words = std::max<uint64_t>(rvk::kSegChunkWords, (all_words / (static_cast<uint64_t>(ctx->props.multiProcessorCount) * 8) + 63) & ~63ull);
-        for (size_t k = 0; k < nb; ++k) {
-            if (b[k + 1] <= b[k]) continue;
-            const uint64_t nwords = ((b[k + 1] - 1) >> 6) - (b[k] >> 6) + 1;
-            for (uint64_t c = 0; c * chunk_words < nwords; ++c) items.push_back(rvk::SegItem{static_cast<uint32_t>(k), static_cast<uint32_t>(c)});
-        }
-        RV_HIP(hipMemsetAsync(d_counts->ptr, 0, nb * 8, ctx->stream));
-        // tables go through pinned staging: [bounds | items] in, [counts] out
-        const size_t bb = (nb + 1) * 8, ib = items.size() * sizeof(rvk::SegItem);
-        char *hs = static_cast<char *>(ctx->stage(std::max(bb + ib, nb * 8)));
-        if (!items.empty()) {
-            if (!d_items || d_items->bytes < ib) d_items = pool_alloc(ctx, ib);
-            std::memcpy(hs, b.data(), bb);
-            std::memcpy(hs + bb, items.data(), ib);
-            RV_HIP(hipMemcpyAsync(d_bounds->ptr, hs, bb, hipMemcpyHostToDevice, ctx->stream));
-            RV_HIP(hipMemcpyAsync(d_items->ptr, hs + bb, ib, hipMemcpyHostToDevice, ctx->stream));
-            const dim3 grid(static_cast<uint32_t>(std::min<uint64_t>((items.size() + 3) / 4, static_cast<uint64_t>(ctx->props.multiProcessorCount) * 16)));
-            hipLaunchKernelGGL(rvk::segment_popcount_kernel, grid, dim3(256), 0, ctx->stream, words, static_cast<const uint64_t *>(d_bounds->ptr),
-                               static_cast<const rvk::SegItem *>(d_items->ptr), static_cast<uint64_t>(items.size()), chunk_words,
+    if (sel) {
+        const uint64_t *words = static_cast<const uint64_t *>(sel->values->ptr);
+        if (uniform_rows && uniform_rows <= rvk::kSegChunkWords * 64) {  // ranges of equal length: no tables (uniform_segment_popcount_kernel)
+            DevBufRef d_counts = pool_alloc(ctx, nb * 8);
+            const dim3 grid(static_cast<uint32_t>(std::min<uint64_t>((nb + 3) / 4, static_cast<uint64_t>(ctx->props.multiProcessorCount) * 16)));
+            hipLaunchKernelGGL(rvk::uniform_segment_popcount_kernel, grid, dim3(256), 0, ctx->stream, words, sel->length, uniform_rows, static_cast<uint64_t>(nb),
                                static_cast<unsigned long long *>(d_counts->ptr));
             RV_HIP(hipGetLastError());
-        }
-        RV_HIP(hipMemcpyAsync(hs, d_counts->ptr, nb * 8, hipMemcpyDeviceToHost, ctx->stream));  // stream order: after the uploads read hs
-        RV_HIP(hipStreamSynchronize(ctx->stream));
-        std::memcpy(dst, hs, nb * 8);
-    };
-    // ... per range of equal length: no tables (uniform_segment_popcount_kernel)
-    auto uniform_counts = [&](const uint64_t *words, uint64_t n_bits, uint64_t *dst) {
-        need_tables();
-        const dim3 grid(static_cast<uint32_t>(std::min<uint64_t>((nb + 3) / 4, static_cast<uint64_t>(ctx->props.multiProcessorCount) * 16)));
-        hipLaunchKernelGGL(rvk::uniform_segment_popcount_kernel, grid, dim3(256), 0, ctx->stream, words, n_bits, uniform_rows, static_cast<uint64_t>(nb),
-                           static_cast<unsigned long long *>(d_counts->ptr));
-        RV_HIP(hipGetLastError());
-        char *hs = static_cast<char *>(ctx->stage(nb * 8));
-        RV_HIP(hipMemcpyAsync(hs, d_counts->ptr, nb * 8, hipMemcpyDeviceToHost, ctx->stream));
-        RV_HIP(hipStreamSynchronize(ctx->stream));
-        std::memcpy(dst, hs, nb * 8);
-    };
-    std::vector<uint64_t> made;  // explicit boundaries of long uniform ranges (few of them)
-    const std::vector<uint64_t> *in_bounds = &bounds;
-    if (sel) {
-        if (uniform_rows && uniform_rows <= rvk::kSegChunkWords * 64) {
-            uniform_counts(static_cast<const uint64_t *>(sel->values->ptr), sel->length, out_rows);
+            char *hs = static_cast<char *>(ctx->stage(nb * 8));
+            RV_HIP(hipMemcpyAsync(hs, d_counts->ptr, nb * 8, hipMemcpyDeviceToHost, ctx->stream));
+            RV_HIP(hipStreamSynchronize(ctx->stream));
+            std::memcpy(out_rows, hs, nb * 8);
         } else {
+            std::vector<uint64_t> made;  // explicit boundaries of long uniform ranges (few of them)
             if (uniform_rows) {
                 made.resize(nb + 1);
                 for (size_t k = 0; k <= nb; ++k) made[k] = std::min<uint64_t>(sel->length, static_cast<uint64_t>(k) * uniform_rows);
-                in_bounds = &made;
             }
-            segment_counts(static_cast<const uint64_t *>(sel->values->ptr), *in_bounds, out_rows);
+            segment_bit_counts(ctx, "per-batch counts", &words, 1, uniform_rows ? made.data() : bounds.data(), nb, out_rows);
         }
         uint64_t sum = 0;
         for (size_t b = 0; b < nb; ++b) sum += out_rows[b];
         require(sum == rows, RV_ERR_INTERNAL, "per-batch survivor counts do not add up");
     }
-    if (!out_nulls) return;
-    bool any_validity = false;
-    for (uint32_t j = 0; j < nproj; ++j) any_validity = any_validity || (out[j]->dtype != RV_NULL && out[j]->validity);
-    if (!any_validity) {  // no projected column kept a null (config 3: every nullable column is tested): nothing to read
-        for (size_t b = 0; b < nb; ++b)
-            for (uint32_t j = 0; j < nproj; ++j) out_nulls[b * nproj + j] = out[j]->dtype == RV_NULL ? static_cast<int64_t>(out_rows[b]) : 0;
-        return;
-    }
-    // null count of every output batch: the same segmented count over the compacted validity, at the output boundaries
-    std::vector<uint64_t> obounds;
-    std::vector<uint64_t> valid(nb);
-    for (uint32_t j = 0; j < nproj; ++j) {
-        const rv_dcolumn *o = out[j];
-        if (o->dtype == RV_NULL) {
-            for (size_t b = 0; b < nb; ++b) out_nulls[b * nproj + j] = static_cast<int64_t>(out_rows[b]);
-            continue;
-        }
-        if (!o->validity) {
-            for (size_t b = 0; b < nb; ++b) out_nulls[b * nproj + j] = 0;
-            continue;
-        }
-        if (obounds.empty()) {
-            obounds.assign(nb + 1, 0);
-            for (size_t b = 0; b < nb; ++b) obounds[b + 1] = obounds[b] + out_rows[b];
-        }
-        segment_counts(static_cast<const uint64_t *>(o->validity->ptr), obounds, valid.data());
-        for (size_t b = 0; b < nb; ++b) out_nulls[b * nproj + j] = static_cast<int64_t>(out_rows[b] - valid[b]);
-    }
+    // null count of every output batch: the same segmented count over the compacted validity bitmaps, at the output boundaries
+    if (out_nulls) batch_null_counts(ctx, "per-batch counts", out, nproj, out_rows, nb, out_nulls);
 }
 // The results of a window of RecordBatches filtered in one call (rv_filter_project_chunked / _batches): the total, the survivors per
 // batch (counted in the pass, or now from `sel`) and the null counts per output batch.  The outputs are freed on an error.
@@ -925,10 +855,7 @@ static void batch_results(rv_ctx *ctx, const BatchReq &req, const rv_dcolumn *se
             batch_counts(ctx, req.counted ? nullptr : sel, rows, bounds, uniform, static_cast<size_t>(nb), out, nproj, out_rows, out_nulls);
         }
     } catch (...) {
-        for (uint32_t j = 0; j < nproj; ++j) {
-            delete out[j];
-            out[j] = nullptr;
-        }
+        drop_outputs(out, nproj);
         throw;
     }
 }
@@ -1106,10 +1033,7 @@ void filter_project_batches_sync(rv_ctx *ctx, const rv_dcolumn *const *cols, uin
         std::vector<std::unique_ptr<rv_dcolumn>> spec_views;
         auto drop_speculative = [&] {
             (void)hipStreamSynchronize(ctx->stream);
-            for (uint32_t j = 0; j < nproj; ++j) {
-                delete out[j];
-                out[j] = nullptr;
-            }
+            drop_outputs(out, nproj);
             delete spec_sel;
             spec_sel = nullptr;
             speculative = false;

@@ -68,10 +68,7 @@ void take_on_device(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, 
         }
     } catch (...) {
         (void)hipStreamSynchronize(ctx->stream);
-        for (uint32_t c = 0; c < ncols; ++c) {
-            delete out[c];
-            out[c] = nullptr;
-        }
+        drop_outputs(out, ncols);
         throw;
     }
 }

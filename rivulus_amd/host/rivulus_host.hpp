@@ -575,6 +575,19 @@ struct StreamError : std::runtime_error {
     static StreamError schema_mismatch() { return StreamError(SchemaMismatch, "Schema mismatch"); }
 };
 
+// the library's Error as a stream reports it (StreamError::Execution): the result of f(), or the translated error
+template <class F>
+auto stream_call(F &&f) -> decltype(f()) {
+    try {
+        return f();
+    } catch (const Error &e) {
+        throw StreamError::execution(e.what());
+    }
+}
+inline void check_stream(rv_status st) {
+    stream_call([&] { check(st); });
+}
+
 class DataStream {  // trait DataStream, stream.rs:25-54
   public:
     virtual ~DataStream() = default;
@@ -1209,13 +1222,6 @@ class GpuChunkedFilterProjectStream : public DataStream {
     }
 
   private:
-    static void check_stream(rv_status st) {
-        try {
-            check(st);
-        } catch (const Error &e) {
-            throw StreamError::execution(e.what());
-        }
-    }
     // A window whose pass is queued on the device (rv_filter_project_chunked_begin): its views, predicate and count block stay put
     // until rv_filter_project_window_finish has consumed the pending handle.
     struct Ahead {
@@ -1382,6 +1388,47 @@ class StringKeyEncoder {
     ContextRef dict_ctx_;
 };
 
+// The helper column around one join call.  with_key_helper: the probe handles with the helper (if any) appended as the key.
+struct ProbeColumns {
+    std::vector<const rv_dcolumn *> cols;
+    uint32_t key = 0;
+    std::optional<size_t> helper_at;  // the helper's place among the probe columns, which is its place among the outputs
+};
+inline ProbeColumns with_key_helper(std::vector<const rv_dcolumn *> probe, uint32_t key, const ArrayRef &helper) {
+    ProbeColumns p{std::move(probe), key, std::nullopt};
+    if (helper) {
+        p.helper_at = p.cols.size();
+        p.key = static_cast<uint32_t>(p.cols.size());
+        p.cols.push_back(helper->handle());
+    }
+    return p;
+}
+// counts[batches][ncols], row-major, without column `at`: [batches][ncols - 1]
+inline void drop_count_column(std::vector<int64_t> &counts, size_t batches, size_t ncols, size_t at) {
+    size_t w = 0;
+    for (size_t k = 0; k < batches; ++k)
+        for (size_t j = 0; j < ncols; ++j)
+            if (j != at) counts[w++] = counts[k * ncols + j];
+    counts.resize(w);
+}
+// ... and out again: the helper's output column and, where null counts were asked for, its entry in each batch's row of counts
+inline void without_key_helper(const ProbeColumns &p, std::vector<ArrayRef> &out, std::vector<int64_t> *nulls = nullptr, size_t batches = 0) {
+    if (!p.helper_at) return;
+    if (nulls) drop_count_column(*nulls, batches, out.size(), *p.helper_at);
+    out.erase(out.begin() + static_cast<long>(*p.helper_at));
+}
+
+// materialize_join_result (plan.rs:212-255): every probe field, then every build field but the key, `_right` on a name the probe
+// side has too
+inline std::vector<Field> join_output_fields(const Schema &probe, const Schema &build, size_t build_key) {
+    std::vector<Field> f = probe.fields();
+    for (size_t i = 0; i < build.num_fields(); ++i) {
+        const Field &b = build.field(i);
+        if (i != build_key) f.push_back(Field{probe.field_by_name(b.name()) ? b.name() + "_right" : b.name(), b.data_type(), b.is_nullable()});
+    }
+    return f;
+}
+
 // One side of a streaming join: a stream, or a resident frame (a DataFrameSource: its columns after dataframe_to_batches' null
 // fill, cut into batch_size-row batches).
 struct JoinSide {
@@ -1424,15 +1471,7 @@ class GpuHashJoinStream : public DataStream {
         if (!pk) throw StreamError::execution("Column '" + probe_key_ + "' not found in schema");
         bki_ = static_cast<uint32_t>(*bk);
         pki_ = static_cast<uint32_t>(*pk);
-        // materialize_join_result (plan.rs:212-255): every probe column, then every build column but the key, `_right` on a name the
-        // probe side has too
-        std::vector<Field> f = probe_schema_->fields();
-        for (size_t i = 0; i < build_schema_->num_fields(); ++i) {
-            const Field &b = build_schema_->field(i);
-            if (i == bki_) continue;
-            f.push_back(Field{probe_schema_->field_by_name(b.name()) ? b.name() + "_right" : b.name(), b.data_type(), b.is_nullable()});
-        }
-        output_schema_ = std::make_shared<const Schema>(f);
+        output_schema_ = std::make_shared<const Schema>(join_output_fields(*probe_schema_, *build_schema_, bki_));
         string_keys_ = std::make_unique<StringKeyEncoder>(build_schema_->field(bki_).data_type(), probe_schema_->field(pki_).data_type());
         probe_rows_ = probe_.stream ? 0 : (probe_.columns.empty() ? 0 : probe_.columns[0]->len());
     }
@@ -1462,17 +1501,10 @@ class GpuHashJoinStream : public DataStream {
     }
 
   private:
-    static void check_stream(rv_status st) {
-        try {
-            check(st);
-        } catch (const Error &e) {
-            throw StreamError::execution(e.what());
-        }
-    }
     // the build side drained and hashed, once (ctx: the probe side's, for a build side that yields no batch)
     void ensure_built(const ContextRef &ctx) {
         if (table_) return;
-        try {
+        stream_call([&] {
             if (build_.stream) {
                 std::vector<RecordBatch> parts = build_.stream->collect();
                 RecordBatch whole = parts.empty() ? RecordBatch::empty(ctx, build_schema_) : parts.size() == 1 ? std::move(parts[0]) : RecordBatch::concat(parts);
@@ -1485,44 +1517,27 @@ class GpuHashJoinStream : public DataStream {
             // a String build key: its ids stand in for it, in the table and among the columns (the key is never gathered)
             if ((build_key_ids_ = string_keys_->build_key(build_.columns[bki_]))) build_handles_[bki_] = build_key_ids_->handle();
             check(rv_join_build(table_ctx_->raw(), build_handles_[bki_], &table_));
-        } catch (const Error &e) {
-            throw StreamError::execution(e.what());
-        }
+        });
     }
     // rv_hash_join_chunked over the n rows of `probe` (columns `arrays`) in batches of `chunk`, into out / rows / nulls; returns the
     // batches taken.  A String probe key is encoded first: its ids ride along as one more probe column, which is the key, and that
     // column leaves the outputs and the null counts again.
     uint64_t join_window(const ContextRef &ctx, std::vector<const rv_dcolumn *> probe, const std::vector<ArrayRef> &arrays, uint64_t n, uint64_t chunk,
                          std::vector<ArrayRef> &out, std::vector<uint64_t> &rows, std::vector<int64_t> &nulls, uint64_t &pairs) {
-        ArrayRef helper;
-        uint32_t pki = pki_;
-        try {
-            helper = string_keys_->probe_key(ctx, arrays[pki_]);
-        } catch (const Error &e) {
-            throw StreamError::execution(e.what());
-        }
-        const size_t helper_at = probe.size();
-        if (helper) {
-            probe.push_back(helper->handle());
-            pki = static_cast<uint32_t>(helper_at);
-        }
+        const ArrayRef helper = stream_call([&] { return string_keys_->probe_key(ctx, arrays[pki_]); });
+        const ProbeColumns p = with_key_helper(std::move(probe), pki_, helper);
         const size_t nout = output_schema_->num_fields() + (helper ? 1 : 0);
         const uint64_t nb = (n + chunk - 1) / chunk;
         std::vector<rv_dcolumn *> raw(nout, nullptr);
         rows.assign(std::max<uint64_t>(nb, 1), 0);
         nulls.assign(std::max<uint64_t>(nb, 1) * nout, 0);
         uint64_t taken = 0;
-        check_stream(rv_hash_join_chunked(ctx->raw(), table_, build_handles_.data(), static_cast<uint32_t>(build_handles_.size()), bki_, probe.data(),
-                                          static_cast<uint32_t>(probe.size()), pki, chunk, max_pairs_, raw.data(), rows.data(), nb, nulls.data(), &pairs, &taken));
+        check_stream(rv_hash_join_chunked(ctx->raw(), table_, build_handles_.data(), static_cast<uint32_t>(build_handles_.size()), bki_, p.cols.data(),
+                                          static_cast<uint32_t>(p.cols.size()), p.key, chunk, max_pairs_, raw.data(), rows.data(), nb, nulls.data(), &pairs, &taken));
         out.clear();
         for (auto *h : raw) out.push_back(Array::adopt(ctx, h));
         rows.resize(taken);
-        if (helper) {
-            out.erase(out.begin() + static_cast<long>(helper_at));
-            for (uint64_t k = 0; k < taken; ++k)  // row k of the null counts: nout entries, the helper's at helper_at
-                for (size_t j = 0, w = 0; j < nout; ++j)
-                    if (j != helper_at) nulls[k * (nout - 1) + w++] = nulls[k * nout + j];
-        }
+        without_key_helper(p, out, &nulls, taken);
         return taken;
     }
     void refill() {  // the next window of the resident probe frame
@@ -1576,11 +1591,7 @@ class GpuHashJoinStream : public DataStream {
         return RecordBatch::new_unchecked(output_schema_, std::move(arrays), rows[0]);
     }
     static ContextRef batch_ctx(const RecordBatch &b) {
-        try {
-            return b.ctx();
-        } catch (const Error &e) {
-            throw StreamError::execution(e.what());
-        }
+        return stream_call([&] { return b.ctx(); });
     }
 
     JoinSide build_, probe_;
@@ -2101,28 +2112,16 @@ class PhysicalPlan {
                 execution::StringKeyEncoder string_keys((*bk)->data_type(), (*pk)->data_type());
                 const execution::ArrayRef build_ids = string_keys.build_key(*bk), helper = string_keys.probe_key(ctx, *pk);
                 if (build_ids) bcols[bki] = build_ids->handle();
-                if (helper) {
-                    pki = static_cast<uint32_t>(pcols.size());
-                    pcols.push_back(helper->handle());
-                }
-                std::vector<rv_dcolumn *> out(pcols.size() + bcols.size() - 1, nullptr);
+                const execution::ProbeColumns probe = execution::with_key_helper(std::move(pcols), pki, helper);
+                std::vector<rv_dcolumn *> out(probe.cols.size() + bcols.size() - 1, nullptr);
                 uint64_t rows = 0;
-                check(rv_hash_join(ctx->raw(), bcols.data(), static_cast<uint32_t>(bcols.size()), bki, pcols.data(), static_cast<uint32_t>(pcols.size()),
-                                   pki, out.data(), &rows));
-                // materialize_join_result (plan.rs:212-255): probe names, then the build names but the key, `_right` where the probe
-                // frame has the name too
+                check(rv_hash_join(ctx->raw(), bcols.data(), static_cast<uint32_t>(bcols.size()), bki, probe.cols.data(),
+                                   static_cast<uint32_t>(probe.cols.size()), probe.key, out.data(), &rows));
                 DeviceFrame res;
-                size_t k = 0;
-                for (size_t i = 0; i < p.columns.size(); ++i, ++k) {
-                    res.names.push_back(p.names[i]);
-                    res.columns.push_back(execution::Array::adopt(ctx, out[k]));
-                }
-                if (helper) rv_free(ctx->raw(), out[k++]);  // the helper column's pairs: not part of the frame
-                for (size_t i = 0; i < b.columns.size(); ++i) {
-                    if (b.names[i] == build_key) continue;
-                    res.names.push_back(p.column(b.names[i]) ? b.names[i] + "_right" : b.names[i]);
-                    res.columns.push_back(execution::Array::adopt(ctx, out[k++]));
-                }
+                for (auto *h : out) res.columns.push_back(execution::Array::adopt(ctx, h));
+                execution::without_key_helper(probe, res.columns);  // the helper column's pairs: not part of the frame
+                const execution::JoinSide bs{nullptr, b.names, b.columns, 0}, ps{nullptr, p.names, p.columns, 0};
+                for (auto &f : execution::join_output_fields(*ps.schema(), *bs.schema(), bki)) res.names.push_back(f.name());
                 return res;
             }
         }

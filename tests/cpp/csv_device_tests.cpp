@@ -4,51 +4,20 @@
 //   csv_device_tests [tmp_dir]     every case (needs an MI355X)
 // Output: "ok <name>" / "FAIL <name>: why"; exit status 0 iff all pass.
 #include <algorithm>
-#include <cstdio>
 #include <cstring>
-#include <functional>
 #include <random>
 
 #include "../../oracle/oracle_csv.hpp"
 #include "../../rivulus_amd/csrc/csv_parse.hpp"
-#include "../../rivulus_amd/host/rivulus_host.hpp"
+#define HOST_TEST_ARG_DEFAULT "/tmp"
+#include "host_test_main.hpp"
 
 using namespace rivulus;
 using namespace rivulus::execution;
 
 namespace {
-struct Case {
-    const char *name;
-    std::function<void()> fn;
-};
-std::vector<Case> &cases() {
-    static std::vector<Case> c;
-    return c;
-}
-struct Reg {
-    Reg(const char *n, std::function<void()> f) { cases().push_back({n, std::move(f)}); }
-};
-struct Fail : std::runtime_error {
-    using std::runtime_error::runtime_error;
-};
-#define GPU_TEST(name) \
-    static void name(); \
-    static Reg reg_##name(#name, name); \
-    static void name()
-#define CHECK(cond) \
-    do { \
-        if (!(cond)) throw Fail(std::string(__FILE__ ":") + std::to_string(__LINE__) + " CHECK(" #cond ")"); \
-    } while (0)
-
-ContextRef g_ctx;
-std::string g_dir = "/tmp";
-const ContextRef &ctx() {
-    if (!g_ctx) g_ctx = std::make_shared<Context>(0);
-    return g_ctx;
-}
-
 std::string write_file(const std::string &name, const std::string &text) {
-    const std::string path = g_dir + "/" + name;
+    const std::string path = g_arg + "/" + name;
     FILE *f = std::fopen(path.c_str(), "wb");
     if (!f) throw Fail("cannot write " + path);
     std::fwrite(text.data(), 1, text.size(), f);
@@ -541,23 +510,4 @@ GPU_TEST(csv_source_through_the_gpu_filter_project_plan_device_scan) {  // the h
         }
     }
     std::remove(path.c_str());
-}
-
-int main(int argc, char **argv) {
-    if (argc > 1) g_dir = argv[1];
-    int failed = 0, ran = 0;
-    for (auto &c : cases()) {
-        ++ran;
-        try {
-            c.fn();
-            std::printf("ok %s\n", c.name);
-        } catch (const std::exception &e) {
-            std::printf("FAIL %s: %s\n", c.name, e.what());
-            ++failed;
-        }
-        std::fflush(stdout);
-    }
-    g_ctx.reset();
-    std::printf("%d cases, %d failed\n", ran, failed);
-    return failed ? 1 : 0;
 }

@@ -7,12 +7,10 @@
 #include <unistd.h>
 #include <fstream>
 #include <cmath>
-#include <cstdio>
-#include <functional>
 
 #include "../../oracle/oracle_compose.hpp"  // checker only
 #include "../../oracle/oracle_csv.hpp"      // checker only
-#include "../../rivulus_amd/host/rivulus_host.hpp"
+#include "host_test_main.hpp"
 
 using namespace rivulus;
 using namespace rivulus::execution;
@@ -20,33 +18,6 @@ using namespace rivulus::expressions;
 using namespace rivulus::physical_plan;
 
 namespace {
-struct Case {
-    const char *name;
-    bool needs_gpu;
-    std::function<void()> fn;
-};
-std::vector<Case> &cases() {
-    static std::vector<Case> c;
-    return c;
-}
-struct Reg {
-    Reg(const char *n, bool g, std::function<void()> f) { cases().push_back({n, g, std::move(f)}); }
-};
-struct Fail : std::runtime_error {
-    using std::runtime_error::runtime_error;
-};
-#define GPU_TEST(name) \
-    static void name(); \
-    static Reg reg_##name(#name, true, name); \
-    static void name()
-#define CPU_TEST(name) \
-    static void name(); \
-    static Reg reg_##name(#name, false, name); \
-    static void name()
-#define CHECK(cond) \
-    do { \
-        if (!(cond)) throw Fail(std::string(__FILE__ ":") + std::to_string(__LINE__) + " CHECK(" #cond ")"); \
-    } while (0)
 template <class E, class F>
 bool throws(F f) {
     try {
@@ -66,11 +37,6 @@ std::string error_text(F f) {
     return "<no error>";
 }
 
-ContextRef g_ctx;
-const ContextRef &ctx() {
-    if (!g_ctx) g_ctx = std::make_shared<Context>(0);
-    return g_ctx;
-}
 using OB = std::optional<bool>;
 const OB N = std::nullopt;
 
@@ -911,23 +877,4 @@ GPU_TEST(eager_nulls_sort_lowest) {  // plan.rs:112-130 + series.rs:105-107: <, 
     CHECK(PhysicalPlan::filter(PhysicalPlan::source(df), CompareTerm{"v", RV_GT, Literal(int64_t(10))})->execute().height() == 1);
     CHECK(PhysicalPlan::filter(PhysicalPlan::source(df), CompareTerm{"v", RV_NE, Literal(int64_t(5))})->execute().height() == 2);
     CHECK(PhysicalPlan::filter(PhysicalPlan::source(df), CompareTerm{"v", RV_EQ, Literal()})->execute().height() == 1);  // == Null keeps the null row
-}
-
-int main(int argc, char **argv) {
-    const bool cpu_only = argc > 1 && std::string(argv[1]) == "--cpu";
-    int failed = 0, ran = 0;
-    for (auto &c : cases()) {
-        if (cpu_only && c.needs_gpu) continue;
-        ++ran;
-        try {
-            c.fn();
-            std::printf("ok %s\n", c.name);
-        } catch (const std::exception &e) {
-            std::printf("FAIL %s: %s\n", c.name, e.what());
-            ++failed;
-        }
-    }
-    g_ctx.reset();
-    std::printf("%d cases, %d failed\n", ran, failed);
-    return failed ? 1 : 0;
 }

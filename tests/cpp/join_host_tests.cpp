@@ -3,49 +3,13 @@
 //   join_host_tests --cpu   cases without a device
 //   join_host_tests         every case (needs an MI355X)
 // Output: "ok <name>" / "FAIL <name>: why"; exit status 0 iff all pass.
-#include <cstdio>
-#include <functional>
-
-#include "../../rivulus_amd/host/rivulus_host.hpp"
+#include "host_test_main.hpp"
 
 using namespace rivulus;
 using namespace rivulus::execution;
 using namespace rivulus::physical_plan;
 
 namespace {
-struct Case {
-    const char *name;
-    bool needs_gpu;
-    std::function<void()> fn;
-};
-std::vector<Case> &cases() {
-    static std::vector<Case> c;
-    return c;
-}
-struct Reg {
-    Reg(const char *n, bool g, std::function<void()> f) { cases().push_back({n, g, std::move(f)}); }
-};
-struct Fail : std::runtime_error {
-    using std::runtime_error::runtime_error;
-};
-#define GPU_TEST(name) \
-    static void name(); \
-    static Reg reg_##name(#name, true, name); \
-    static void name()
-#define CPU_TEST(name) \
-    static void name(); \
-    static Reg reg_##name(#name, false, name); \
-    static void name()
-#define CHECK(cond) \
-    do { \
-        if (!(cond)) throw Fail(std::string(__FILE__ ":") + std::to_string(__LINE__) + " CHECK(" #cond ")"); \
-    } while (0)
-
-ContextRef g_ctx;
-const ContextRef &ctx() {
-    if (!g_ctx) g_ctx = std::make_shared<Context>(0);
-    return g_ctx;
-}
 template <class E, class F>
 bool throws(F f) {
     try {
@@ -116,23 +80,4 @@ GPU_TEST(empty_result_keeps_names_and_dtypes) {  // create_empty_join_result (pl
     DeviceFrame out = PhysicalPlan::hash_join(PhysicalPlan::source(users()), PhysicalPlan::source(o), "user_id", "user_id")->execute();
     CHECK(out.height() == 0 && out.width() == 5);
     CHECK(out.columns[2]->data_type() == DataType::Float64 && out.columns[4]->data_type() == DataType::String);
-}
-
-int main(int argc, char **argv) {
-    const bool cpu_only = argc > 1 && std::string(argv[1]) == "--cpu";
-    int failed = 0, ran = 0;
-    for (auto &c : cases()) {
-        if (cpu_only && c.needs_gpu) continue;
-        ++ran;
-        try {
-            c.fn();
-            std::printf("ok %s\n", c.name);
-        } catch (const std::exception &e) {
-            std::printf("FAIL %s: %s\n", c.name, e.what());
-            ++failed;
-        }
-    }
-    g_ctx.reset();
-    std::printf("%d cases, %d failed\n", ran, failed);
-    return failed ? 1 : 0;
 }

@@ -4,95 +4,14 @@
 //   stream_join_host_tests [fixture_dir]         every case (needs an MI355X)
 // fixture_dir holds users.csv / orders.csv / expected.csv, written by tests/test_stream_join_host.py from
 // tests/golden/join_users_orders.json.  Output: "ok <name>" / "FAIL <name>: why"; exit status 0 iff all pass.
-#include <cstdio>
-#include <functional>
-
-#include "../../rivulus_amd/host/rivulus_host.hpp"
+#include "host_test_main.hpp"
+#include "join_test_cells.hpp"
 
 using namespace rivulus;
 using namespace rivulus::execution;
 using namespace rivulus::physical_plan;
 
 namespace {
-struct Case {
-    const char *name;
-    bool needs_gpu;
-    std::function<void()> fn;
-};
-std::vector<Case> &cases() {
-    static std::vector<Case> c;
-    return c;
-}
-struct Reg {
-    Reg(const char *n, bool g, std::function<void()> f) { cases().push_back({n, g, std::move(f)}); }
-};
-struct Fail : std::runtime_error {
-    using std::runtime_error::runtime_error;
-};
-#define GPU_TEST(name) \
-    static void name(); \
-    static Reg reg_##name(#name, true, name); \
-    static void name()
-#define CPU_TEST(name) \
-    static void name(); \
-    static Reg reg_##name(#name, false, name); \
-    static void name()
-#define CHECK(cond) \
-    do { \
-        if (!(cond)) throw Fail(std::string(__FILE__ ":") + std::to_string(__LINE__) + " CHECK(" #cond ")"); \
-    } while (0)
-
-ContextRef g_ctx;
-std::string g_fixture = ".";
-const ContextRef &ctx() {
-    if (!g_ctx) g_ctx = std::make_shared<Context>(0);
-    return g_ctx;
-}
-template <class E, class F>
-std::string thrown(F f) {
-    try {
-        f();
-    } catch (const E &e) {
-        return e.what();
-    }
-    return "";
-}
-
-// one cell as text: the value, "null", a Float64 by its 17 digits (so -0.0 and 0.0 differ)
-std::string cell(const ArrayRef &a, size_t i) {
-    char buf[64];
-    switch (a->data_type()) {
-        case DataType::Int64: {
-            auto v = std::dynamic_pointer_cast<const Int64Array>(a)->value(i);
-            return v ? std::to_string(*v) : "null";
-        }
-        case DataType::Float64: {
-            auto v = std::dynamic_pointer_cast<const Float64Array>(a)->value(i);
-            if (!v) return "null";
-            std::snprintf(buf, sizeof buf, "%.17g", *v);
-            return buf;
-        }
-        case DataType::Boolean: {
-            auto v = std::dynamic_pointer_cast<const BooleanArray>(a)->value(i);
-            return v ? (*v ? "true" : "false") : "null";
-        }
-        case DataType::String: {
-            auto v = std::dynamic_pointer_cast<const StringArray>(a)->value(i);
-            return v ? "'" + *v + "'" : "null";
-        }
-        default: return "null";
-    }
-}
-// a frame's rows [lo, hi) as text, column by column
-std::vector<std::vector<std::string>> cells(const std::vector<ArrayRef> &cols, size_t lo, size_t hi) {
-    std::vector<std::vector<std::string>> out;
-    for (auto &c : cols) {
-        out.emplace_back();
-        for (size_t i = lo; i < hi; ++i) out.back().push_back(cell(c, i));
-    }
-    return out;
-}
-
 DeviceFrame frame_of(const std::vector<RecordBatch> &batches, SchemaRef schema) {
     DeviceFrame f;
     for (auto &fld : schema->fields()) f.names.push_back(fld.name());
@@ -107,7 +26,7 @@ SchemaRef orders_schema() {
     return schema_of({Field{"order_id", DataType::Int64, true}, Field{"user_id", DataType::Int64, true}, Field{"amount", DataType::Float64, true}});
 }
 StreamingPlanPtr csv(const std::string &file, SchemaRef s, size_t batch) {
-    return StreamingPhysicalPlan::csv_file_source(ctx(), g_fixture + "/" + file, std::move(s), batch);
+    return StreamingPhysicalPlan::csv_file_source(ctx(), g_arg + "/" + file, std::move(s), batch);
 }
 DeviceFrame csv_frame(const std::string &file, SchemaRef s) { return frame_of(csv(file, s, 1024)->collect_batches(), s); }
 
@@ -342,27 +261,4 @@ GPU_TEST(concatenation_equals_the_eager_join) {
         CHECK(cells(all.columns(), 0, all.num_rows()) == cells(eager.columns, 0, eager.height()));
         CHECK(s.rows_scanned() == np);
     }
-}
-
-int main(int argc, char **argv) {
-    bool cpu_only = false;
-    for (int i = 1; i < argc; ++i) {
-        if (std::string(argv[i]) == "--cpu") cpu_only = true;
-        else g_fixture = argv[i];
-    }
-    int failed = 0, ran = 0;
-    for (auto &c : cases()) {
-        if (cpu_only && c.needs_gpu) continue;
-        ++ran;
-        try {
-            c.fn();
-            std::printf("ok %s\n", c.name);
-        } catch (const std::exception &e) {
-            std::printf("FAIL %s: %s\n", c.name, e.what());
-            ++failed;
-        }
-    }
-    g_ctx.reset();
-    std::printf("%d cases, %d failed\n", ran, failed);
-    return failed ? 1 : 0;
 }

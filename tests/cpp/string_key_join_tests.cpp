@@ -4,102 +4,18 @@
 //   string_key_join_tests --cpu   cases without a device
 //   string_key_join_tests         every case (needs an MI355X)
 // Output: "ok <name>" / "FAIL <name>: why"; exit status 0 iff all pass.
-#include <cstdio>
-#include <functional>
 #include <map>
 
-#include "../../rivulus_amd/host/rivulus_host.hpp"
+#include "host_test_main.hpp"
+#include "join_test_cells.hpp"
 
 using namespace rivulus;
 using namespace rivulus::execution;
 using namespace rivulus::physical_plan;
 
 namespace {
-struct Case {
-    const char *name;
-    bool needs_gpu;
-    std::function<void()> fn;
-};
-std::vector<Case> &cases() {
-    static std::vector<Case> c;
-    return c;
-}
-struct Reg {
-    Reg(const char *n, bool g, std::function<void()> f) { cases().push_back({n, g, std::move(f)}); }
-};
-struct Fail : std::runtime_error {
-    using std::runtime_error::runtime_error;
-};
-#define GPU_TEST(name) \
-    static void name(); \
-    static Reg reg_##name(#name, true, name); \
-    static void name()
-#define CPU_TEST(name) \
-    static void name(); \
-    static Reg reg_##name(#name, false, name); \
-    static void name()
-#define CHECK(cond) \
-    do { \
-        if (!(cond)) throw Fail(std::string(__FILE__ ":") + std::to_string(__LINE__) + " CHECK(" #cond ")"); \
-    } while (0)
-
-ContextRef g_ctx;
-const ContextRef &ctx() {
-    if (!g_ctx) g_ctx = std::make_shared<Context>(0);
-    return g_ctx;
-}
-template <class E, class F>
-std::string thrown(F f) {
-    try {
-        f();
-    } catch (const E &e) {
-        return e.what();
-    }
-    return "";
-}
-
 using Strs = std::vector<std::optional<std::string>>;
 using Pairs = std::vector<std::pair<size_t, size_t>>;  // (probe row, build row)
-using Table = std::vector<std::vector<std::string>>;   // cells as text, column by column
-
-// one cell as text: the value, "null", a Float64 by its 17 digits
-std::string cell(const ArrayRef &a, size_t i) {
-    char buf[64];
-    switch (a->data_type()) {
-        case DataType::Int64: {
-            auto v = std::dynamic_pointer_cast<const Int64Array>(a)->value(i);
-            return v ? std::to_string(*v) : "null";
-        }
-        case DataType::Float64: {
-            auto v = std::dynamic_pointer_cast<const Float64Array>(a)->value(i);
-            if (!v) return "null";
-            std::snprintf(buf, sizeof buf, "%.17g", *v);
-            return buf;
-        }
-        case DataType::Boolean: {
-            auto v = std::dynamic_pointer_cast<const BooleanArray>(a)->value(i);
-            return v ? (*v ? "true" : "false") : "null";
-        }
-        case DataType::String: {
-            auto v = std::dynamic_pointer_cast<const StringArray>(a)->value(i);
-            return v ? "'" + *v + "'" : "null";
-        }
-        default: return "null";
-    }
-}
-std::string f17(double x) {
-    char buf[64];
-    std::snprintf(buf, sizeof buf, "%.17g", x);
-    return buf;
-}
-Table cells(const std::vector<ArrayRef> &cols, size_t lo, size_t hi) {
-    Table out;
-    for (auto &c : cols) {
-        out.emplace_back();
-        for (size_t i = lo; i < hi; ++i) out.back().push_back(cell(c, i));
-    }
-    return out;
-}
 SchemaRef schema_of(std::vector<Field> f) { return std::make_shared<const Schema>(std::move(f)); }
 
 // The reference's result_pairs (plan.rs:183-204) for two key columns read back from the device: AnyValue keys -- a cell's dtype and
@@ -246,6 +162,50 @@ CPU_TEST(missing_string_key_column_error_text) {
     p.stream = MemoryStream::empty(ps);
     std::string m = thrown<StreamError>([&] { GpuHashJoinStream(std::move(b), std::move(p), "name", "name"); });
     CHECK(m == "Stream execution error: Column 'name' not found in schema");
+}
+
+CPU_TEST(helper_column_leaves_the_null_counts) {  // [batches][ncols] row-major -> [batches][ncols - 1]
+    std::vector<int64_t> none;
+    drop_count_column(none, 0, 4, 2);
+    CHECK(none.empty());
+    std::vector<int64_t> padded = {7, 8, 9};  // room for one batch, none taken
+    drop_count_column(padded, 0, 3, 1);
+    CHECK(padded.empty());
+    std::vector<int64_t> one = {5, 6, 7};
+    drop_count_column(one, 1, 3, 0);
+    CHECK((one == std::vector<int64_t>{6, 7}));
+    std::vector<int64_t> three = {10, 11, 12, 13, 20, 21, 22, 23, 30, 31, 32, 33};
+    drop_count_column(three, 3, 4, 2);
+    CHECK((three == std::vector<int64_t>{10, 11, 13, 20, 21, 23, 30, 31, 33}));
+    std::vector<int64_t> last = {10, 11, 12, 20, 21, 22};
+    drop_count_column(last, 2, 3, 2);
+    CHECK((last == std::vector<int64_t>{10, 11, 20, 21}));
+    std::vector<int64_t> only = {4, 5};  // the helper as the only column
+    drop_count_column(only, 2, 1, 0);
+    CHECK(only.empty());
+}
+
+CPU_TEST(helper_column_is_appended_as_the_key) {
+    const rv_dcolumn *a = reinterpret_cast<const rv_dcolumn *>(0x10), *b = reinterpret_cast<const rv_dcolumn *>(0x20);  // never dereferenced
+    ProbeColumns plain = with_key_helper({a, b}, 1, nullptr);
+    CHECK(plain.cols.size() == 2 && plain.key == 1 && !plain.helper_at);
+    std::vector<ArrayRef> out(3);
+    std::vector<int64_t> nulls = {1, 2, 3};
+    without_key_helper(plain, out, &nulls, 1);  // no helper: nothing leaves
+    CHECK(out.size() == 3 && nulls.size() == 3);
+}
+
+CPU_TEST(join_output_fields_follow_materialize_join_result) {
+    const Schema probe({Field{"id", DataType::Int64, false}, Field{"name", DataType::String, true}});
+    const Schema build({Field{"name", DataType::String, true}, Field{"id", DataType::Float64, false}, Field{"city", DataType::String, false},
+                        Field{"note", DataType::Boolean, true}});
+    const std::vector<Field> f = join_output_fields(probe, build, 1);  // keyed on the build side's `id`
+    CHECK((f == std::vector<Field>{Field{"id", DataType::Int64, false}, Field{"name", DataType::String, true}, Field{"name_right", DataType::String, true},
+                                   Field{"city", DataType::String, false}, Field{"note", DataType::Boolean, true}}));
+    // the key is left out by its index, not its name: keyed on `name`, the build side's `id` clashes and stays
+    const std::vector<Field> g = join_output_fields(probe, build, 0);
+    CHECK(g.size() == 5 && g[2] == (Field{"id_right", DataType::Float64, false}) && g[3].name() == "city" && !g[3].is_nullable());
+    CHECK(join_output_fields(Schema::empty(), build, 3).size() == 3);
 }
 
 // ---- on the device: the eager join -----------------------------------------------------------------------------------------------
@@ -424,25 +384,4 @@ GPU_TEST(stream_under_a_limit_is_the_first_pairs) {
     RecordBatch all = RecordBatch::concat(got);
     CHECK(all.num_rows() == 10);
     CHECK(cells(all.columns(), 0, 10) == cells(eager.columns, 0, 10));
-}
-
-int main(int argc, char **argv) {
-    bool cpu_only = false;
-    for (int i = 1; i < argc; ++i)
-        if (std::string(argv[i]) == "--cpu") cpu_only = true;
-    int failed = 0, ran = 0;
-    for (auto &c : cases()) {
-        if (cpu_only && c.needs_gpu) continue;
-        ++ran;
-        try {
-            c.fn();
-            std::printf("ok %s\n", c.name);
-        } catch (const std::exception &e) {
-            std::printf("FAIL %s: %s\n", c.name, e.what());
-            ++failed;
-        }
-    }
-    g_ctx.reset();
-    std::printf("%d cases, %d failed\n", ran, failed);
-    return failed ? 1 : 0;
 }

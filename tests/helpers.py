@@ -1,7 +1,8 @@
-"""Shared helpers: golden-case loading, column comparison, the constants of thresholds.hpp."""
+"""Shared helpers: golden-case loading, column comparison, the constants of thresholds.hpp, the host layer's test programs."""
 import json
 import os
 import re
+import subprocess
 
 import numpy as np
 
@@ -59,3 +60,32 @@ def const(name):
         a, b = re.findall(r"\d+", v)[-2:]
         return int(a) << int(b)
     return float(v) if "." in v else int(v)
+
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_host_runs = {}
+
+
+def host_cases(binary):
+    """(CPU case names, GPU case names) of tests/cpp/<binary>.cpp"""
+    with open(os.path.join(ROOT, "tests", "cpp", binary + ".cpp")) as f:
+        src = f.read()
+    return re.findall(r"^CPU_TEST\((\w+)\)", src, re.M), re.findall(r"^GPU_TEST\((\w+)\)", src, re.M)
+
+
+def assert_host_case(binary, case, cpu_only, arg=None, timeout=300):
+    """`case` of the host test program `binary` printed "ok".  The library and the program are built, and the program run, once per
+    mode (cpu_only: its --cpu cases alone); arg() gives the program's own argument, a directory, when it takes one."""
+    import pytest
+
+    if (binary, cpu_only) not in _host_runs:
+        subprocess.run(["make", "-C", os.path.join(ROOT, "rivulus_amd", "csrc"), "-j8"], check=True, stdout=subprocess.DEVNULL)
+        subprocess.run(["make", "-C", os.path.join(ROOT, "rivulus_amd", "host"), binary], check=True, stdout=subprocess.DEVNULL)
+        cmd = [os.path.join(ROOT, "rivulus_amd", "host", binary)] + (["--cpu"] if cpu_only else []) + ([arg()] if arg else [])
+        _host_runs[binary, cpu_only] = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout)
+    result = _host_runs[binary, cpu_only]
+    for line in result.stdout.splitlines():
+        if line.split()[1:2] == [case] or line.startswith(f"FAIL {case}:"):
+            assert line.startswith("ok "), line
+            return
+    pytest.fail(f"case {case} produced no line; stdout: {result.stdout[-1000:]} stderr: {result.stderr[-1000:]}")

@@ -806,6 +806,40 @@ def test_filter_project_batches_equals_per_batch_calls(gpu_ctx, oracle, layout, 
     assert "same schema" in e.value.message
 
 
+def test_filter_project_batches_null_counts_of_long_and_empty_batches(gpu_ctx, oracle):
+    """Per-batch null counts where the segmented count cuts a range into chunks: a 300 001-row batch (4688 bitmap words, the chunks
+    are 4096) of which ~95 % survive (its output range spans two chunks as well), empty batches around it, and every later boundary
+    mid-word.  Three projected columns keep nulls: their bitmaps share one table upload and one read-back."""
+    rng = np.random.default_rng(300_001)
+    lengths = [0, 300_001, 0, 1, 63, 1024]
+    n = sum(lengths)
+    words = ["", "a", "Bob", "Ünï", "zz"]
+    x = Column.from_numpy(rng.integers(0, 1000, n).astype(np.int64))
+    f = Column.from_numpy(rng.random(n), rng.random(n) > 0.05)
+    y = Column.from_numpy(rng.integers(-5, 5, n).astype(np.int64), rng.random(n) > 0.3)
+    s = Column.from_strings([None if m else words[k] for m, k in zip(rng.random(n) < 0.1, rng.integers(0, len(words), n))])
+    host = [x, f, y, s]
+    whole = [gpu_ctx.upload(c) for c in host]
+    starts = np.concatenate([[0], np.cumsum(lengths)])
+    batches = [[w.slice(int(starts[k]), ln) for w in whole] for k, ln in enumerate(lengths)]
+    pred = Predicate([Term(0, "<", 950)])
+    proj = [1, 2, 3, 0]
+    outs, rows, nulls_out, total = gpu_ctx.filter_project_batches(batches, pred, proj)
+    assert len(rows) == len(lengths) and int(rows.sum()) == total
+    assert int(rows[1]) > 4096 * 64  # the long batch's output range: more than one chunk
+    at = 0
+    for k, ln in enumerate(lengths):
+        want = oracle.filter_project([c.slice(int(starts[k]), ln) for c in host], pred, proj)
+        assert int(rows[k]) == want[0].length, f"batch {k}"
+        for j, w in enumerate(want):
+            w_nulls = 0 if w.validity is None else int(w.length - w.logical_valid().sum())
+            assert int(nulls_out[k][j]) == w_nulls, f"batch {k} column {j}"
+        got = [gpu_ctx.slice_known(o, at, int(rows[k]), int(nulls_out[k][j])).download() for j, o in enumerate(outs)]
+        assert_columns_equal(got, want, f"batch {k}")
+        at += int(rows[k])
+    assert nulls_out[1][:3].min() > 0 and not nulls_out[:, 3].any()
+
+
 def test_filter_project_batches_many_small_batches(gpu_ctx, oracle):
     """More than 16 384 batches: the handle walk runs on several host threads; same result, and the error reported is the
     FIRST offending batch's, as from the sequential walk."""

@@ -146,6 +146,49 @@ def test_two_calls_give_identical_outputs(gpu_ctx):
     t.free()
 
 
+def test_null_counts_of_long_and_ragged_batches(gpu_ctx):
+    """Per-batch null counts where the segmented count cuts a range into chunks: 601 090 probe rows in batches of 300 001 (about
+    270 000 pairs each, 4219 bitmap words against chunks of 4096; every later boundary mid-word; a ragged last batch), then in
+    batches of 1024.  Three output columns keep nulls -- a probe Int64, a build Float64 and a build String -- so three bitmaps share
+    one table upload and one read-back.  Unique Int64 build keys, ~10 % of the probe rows miss: the model is numpy."""
+    rng = np.random.default_rng(601_090)
+    nb, npr = 50_000, 601_090
+    bkeys = rng.permutation(nb).astype(np.int64) * 10
+    pkeys = rng.integers(0, nb, npr).astype(np.int64) * 10 + (rng.random(npr) < 0.1)  # a key ending in 1 meets nothing
+    pv, pv_valid = rng.integers(0, 1000, npr).astype(np.int64), rng.random(npr) > 0.2
+    bf, bf_valid = rng.random(nb), rng.random(nb) > 0.3
+    bs = [None if m else f"s{i % 97}" for i, m in enumerate(rng.random(nb) < 0.15)]
+    bs_valid = np.array([x is not None for x in bs])
+    bcols = [gpu_ctx.upload(Column.from_numpy(bkeys)), gpu_ctx.upload(Column.from_numpy(bf, bf_valid)), gpu_ctx.upload(Column.from_strings(bs))]
+    pcols = [gpu_ctx.upload(Column.from_numpy(pv, pv_valid)), gpu_ctx.upload(Column.from_numpy(pkeys))]
+    hit = np.nonzero(pkeys % 10 == 0)[0]           # the probe row of every pair, in output order
+    brow = np.argsort(bkeys)[pkeys[hit] // 10]     # ... and its build row (bkeys = 10 x a permutation)
+    assert np.array_equal(bkeys[brow], pkeys[hit])
+    valid_out = [pv_valid[hit], np.ones(len(hit), bool), bf_valid[brow], bs_valid[brow]]  # pv, k, bf, bs
+    t = gpu_ctx.join_build(bcols[0])
+    for chunk in (300_001, 1024):
+        outs, rows, nulls, total, taken = gpu_ctx.hash_join_chunked(t, bcols, 0, pcols, 1, chunk)
+        k = (npr + chunk - 1) // chunk
+        assert taken == k and total == len(hit)
+        assert np.array_equal(rows, np.bincount(hit // chunk, minlength=k).astype(np.uint64))
+        if chunk == 300_001:
+            assert int(rows[0]) > 4096 * 64 and int(rows[2]) < 1088  # two chunks; the ragged batch
+        ends = np.cumsum(rows).astype(np.int64)
+        for j, v in enumerate(valid_out):
+            invalid = np.concatenate([[0], np.cumsum(~v)])
+            assert np.array_equal(nulls[:, j], invalid[ends] - invalid[ends - rows.astype(np.int64)]), (chunk, j)
+        assert nulls[0, 0] > 0 and nulls[0, 2] > 0 and nulls[0, 3] > 0 and not nulls[:, 1].any()
+        got = [o.download() for o in outs]
+        assert np.array_equal(got[0].logical_values()[valid_out[0]], pv[hit][valid_out[0]])
+        assert np.array_equal(got[1].logical_values(), pkeys[hit])
+        assert np.array_equal(got[2].logical_values()[valid_out[2]], bf[brow][valid_out[2]])
+        for j in (0, 2, 3):
+            assert np.array_equal(got[j].logical_valid(), valid_out[j]), (chunk, j)
+        lo = int(ends[0]) - 50  # strings across the first boundary
+        assert outs[3].slice(lo, 100).download().to_strings() == [bs[r] for r in brow[lo:lo + 100]]
+    t.free()
+
+
 # ---- max_pairs -----------------------------------------------------------------------------------------------------------------------
 def test_max_pairs_cuts_the_window(gpu_ctx):
     rng = np.random.default_rng(9)

@@ -9,6 +9,7 @@ Three ways to run the same batches:
                  the window is what a stream operator pulls ahead: at most WINDOW_ROWS rows / WINDOW_BATCHES batches
   chunked        rv_filter_project_chunked: the same windows handed over as one resident table + the batch size (the
                  reference's dataframe_to_batches source): no handles, no boundary table
+Workloads: config2, config3, seam, bool (no null counts asked for), nulls2 (two nullable outputs, per-batch null counts asked for).
 Prints one JSON object per (workload, R) and a summary table; `--json path` also writes them to a file.
 """
 import json
@@ -31,7 +32,7 @@ ctx = capi.Context(0)
 results = []
 
 
-def sweep(name, cols, pred, proj, n, sizes, bytes_per_row):
+def sweep(name, cols, pred, proj, n, sizes, bytes_per_row, want_nulls=False):
     for b in sizes:
         nb_all = (n + b - 1) // b
         # ---- per batch / two in flight (bounded number of calls) ----
@@ -71,13 +72,13 @@ def sweep(name, cols, pred, proj, n, sizes, bytes_per_row):
             windows.append((bs, ctx.batch_handles(bs)))  # the handle array is assembled once, like a stream's batch list
         kept = ctx.pinned_array(np.uint64, k)  # the operator's own pinned array for the counts, as in the chunked form
         for _, h in windows:  # every window once untimed: a shorter last window has its own buffer sizes (first use = hipMalloc)
-            outs, rows, _, _ = ctx.filter_project_batches(None, pred, proj, want_nulls=False, handles=h, rows_buffer=kept)
+            outs, rows, _, _ = ctx.filter_project_batches(None, pred, proj, want_nulls=want_nulls, handles=h, rows_buffer=kept)
             [o.free() for o in outs]
         ctx.synchronize()
         t0 = time.perf_counter()
         total = 0
         for bs, h in windows:
-            outs, rows, _, tot = ctx.filter_project_batches(None, pred, proj, want_nulls=False, handles=h, rows_buffer=kept)
+            outs, rows, _, tot = ctx.filter_project_batches(None, pred, proj, want_nulls=want_nulls, handles=h, rows_buffer=kept)
             total += tot
             for o in outs:
                 o.free()
@@ -88,12 +89,12 @@ def sweep(name, cols, pred, proj, n, sizes, bytes_per_row):
         tables = [[c.slice(w * k * b, min(k * b, n - w * k * b)) for c in cols] for w in range(nwin)]
         # the per-batch counts land in a pinned array the stream operator keeps (rv_host_alloc): written by the device
         counts = ctx.pinned_array(np.uint64, k)
-        outs, rows, _, _ = ctx.filter_project_chunked(tables[0], b, pred, proj, want_nulls=False, rows_buffer=counts)
+        outs, rows, _, _ = ctx.filter_project_chunked(tables[0], b, pred, proj, want_nulls=want_nulls, rows_buffer=counts)
         [o.free() for o in outs]
         ctx.synchronize()
         t0 = time.perf_counter()
         for tb in tables:
-            outs, rows, _, tot = ctx.filter_project_chunked(tb, b, pred, proj, want_nulls=False, rows_buffer=counts)
+            outs, rows, _, tot = ctx.filter_project_chunked(tb, b, pred, proj, want_nulls=want_nulls, rows_buffer=counts)
             for o in outs:
                 o.free()
         ctx.synchronize()
@@ -101,7 +102,7 @@ def sweep(name, cols, pred, proj, n, sizes, bytes_per_row):
         # ... and into an ordinary (pageable) array: staged + copied
         t0 = time.perf_counter()
         for tb in tables:
-            outs, rows, _, tot = ctx.filter_project_chunked(tb, b, pred, proj, want_nulls=False)
+            outs, rows, _, tot = ctx.filter_project_chunked(tb, b, pred, proj, want_nulls=want_nulls)
             for o in outs:
                 o.free()
         ctx.synchronize()
@@ -115,7 +116,7 @@ def sweep(name, cols, pred, proj, n, sizes, bytes_per_row):
             for w in range(nwin):
                 if w + 1 < nwin:
                     q.append(begin(w + 1))
-                outs, rows, _, tot = q.pop(0)(False)
+                outs, rows, _, tot = q.pop(0)(want_nulls)
                 for o in outs:
                     o.free()
             ctx.synchronize()
@@ -150,6 +151,14 @@ if "config3" in which or "seam" in which:
     sweep("config3: (f > 0.5) AND (x < 200) -> [f, x], nullable", [f, xv], Predicate([Term(0, ">", 0.5), Term(1, "<", 200)]), [0, 1], n3,
           sizes3, 16.25)
     f.free(), xv.free()
+if "nulls2" in which:
+    # two nullable outputs that keep their nulls (the predicate reads neither): every window takes per-batch null counts of two bitmaps
+    nn = 1 << 28
+    x = ctx.generate(synth_spec(RV_INT64, seed=42, length=nn))
+    f = ctx.generate(synth_spec(RV_FLOAT64, seed=43, length=nn, validity_seed=44))
+    xv = ctx.generate(synth_spec(RV_INT64, seed=42, length=nn, validity_seed=45))
+    sweep("nulls2: x > 499 -> [f, xv], both nullable", [x, f, xv], Predicate([Term(0, ">", 499)]), [1, 2], nn, [1024, 1000, 1 << 20], 8.0 + 8.25, want_nulls=True)
+    x.free(), f.free(), xv.free()
 if "bool" in which:
     # the reference's literal streaming query: the ONE predicate collect_streaming() accepts is a Boolean column
     # (streaming_planner.rs:137-168 -> FilterStream, stream.rs:136-158 -> RecordBatch::filter, record_batch.rs:221-243)
