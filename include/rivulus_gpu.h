@@ -574,10 +574,18 @@ rv_status rv_filter_project_host(rv_ctx *ctx, const rv_column *host_cols, uint32
 /* ---- filter + global aggregate (K4) --------------------------------------- */
 /* COUNT(*) of surviving rows and SUM(cols[agg_col]) over surviving non-null cells.
  * RV_INT64: two's-complement wrapping sum in *sum_i (order independent => bit exact).
- * RV_FLOAT64: sum in *sum_f, fixed reduction tree: the order of the additions depends on the row count alone (8192
- * workgroups stride over the tiles whatever the device's CU count; option "agg_grid" changes the tree), so a given column
- * sums to the same bits run to run and part to part.  Row-range shards of different sizes sum in a different order:
- * across shardings the Float64 result agrees to rounding (tests: 1e-12 relative), the Int64 result exactly.
+ * RV_FLOAT64: sum in *sum_f, fixed reduction tree.  The order of the additions follows from the row count, from the number
+ * of 8-byte columns the launch reads (the aggregated column, the value columns of the predicate and the nullable value columns
+ * an OR / NOT expression propagates nulls from: 1 / 2 / 3-4 columns sum 16 / 8 / 4 rows per lane, tiles of 4096 / 2048 / 1024
+ * rows; more than 4: the predicate goes through a selection bitmap and the sum is that of 1 column) and from the width of
+ * the loads, which sets which rows of a tile a lane holds: 16 bytes when only the aggregated column is read, 8 bytes otherwise
+ * (option "vec" overrides), and always 8 bytes when the first row of one of those columns is not 16-byte aligned (an odd-offset
+ * slice).  The grid is a constant (8192 workgroups stride over the tiles whatever the device's CU count; option "agg_grid"
+ * changes the tree).  So the same call over the same buffers sums to the same bits run to run and part to part, while another
+ * predicate shape, another alignment or row-range shards of other sizes add in a different order: there the Float64 result
+ * agrees to rounding (tests: 1e-12 relative on uniform data; a derived gamma_k bound on mixed-sign data), and bit for bit
+ * whenever every partial sum is exactly representable (tests: test_agg_float_gpu.py, every kernel variant, load width, grid and
+ * sharding over cells k * 2^s; NaN / inf under null cells and in dropped rows never reach the sum).  The Int64 result is exact.
  * The reference has no aggregate operator; semantics defined in DESIGN.md. */
 rv_status rv_filter_agg(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols,
                         const rv_predicate *pred, uint32_t agg_col, int64_t *sum_i,

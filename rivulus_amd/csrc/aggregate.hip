@@ -146,7 +146,8 @@ rv_status rv_filter_agg(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t nco
         // fetching its kernel arguments before its first load) -- tools/agg_grid.py.  Option "agg_grid": k > 0 = k per CU,
         // -1 = one per tile.
         // The default grid is a CONSTANT (8192 workgroups = 32 per CU of an MI355X), not a multiple of the CU count: the order
-        // of a Float64 sum's additions then depends on the row count alone -- the same bits on any part, in any partition mode.
+        // of a Float64 sum's additions then depends on the row count and on the variant chosen above (columns read, load
+        // width -- 8 bytes when a column starts off a 16-byte boundary) -- the same bits on any part, in any partition mode.
         const uint64_t grid = ctx->opt_agg_grid < 0 ? ntiles
                                                     : std::min<uint64_t>(ntiles, ctx->opt_agg_grid > 0 ? static_cast<uint64_t>(ctx->opt_agg_grid) * static_cast<uint64_t>(ctx->props.multiProcessorCount)
                                                                                                        : 8192);

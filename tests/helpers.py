@@ -2,6 +2,7 @@
 import json
 import os
 import re
+import struct
 import subprocess
 
 import numpy as np
@@ -60,6 +61,135 @@ def const(name):
         a, b = re.findall(r"\d+", v)[-2:]
         return int(a) << int(b)
     return float(v) if "." in v else int(v)
+
+
+# ---- Float64 sums that are exact in any order -----------------------------------------------------------------------------
+# Every cell is k * 2^s with an integer |k| < 2^20.  As long as sum(|k|) < 2^53 every partial sum of any reduction tree is an
+# integer multiple of 2^s below 2^53 * 2^s, hence exactly representable: a Float64 SUM over such cells has ONE correct bit
+# pattern, whatever the launch geometry, and that pattern follows from integer arithmetic on the host.
+DYADIC_SCALES = (-1074, -10, 960)  # subnormal cells throughout / ordinary / sums up to 2^1000 (no overflow below 2^40 * 2^960)
+DYADIC_K_BITS = 20
+NULL_FILL = (float("nan"), float("inf"), float("-inf"), 1e300)  # what lies under a null cell, in rotation
+
+
+def dyadic_cells(seed, n, scale, null_fraction=0.0):
+    """(k, values, valid): n Float64 cells k * 2^scale, k a random integer with |k| < 2^20 (both signs, one in twenty a zero).
+    null_fraction > 0: a validity mask as well, and NULL_FILL in rotation under the null cells -- bit patterns that must never
+    reach a sum."""
+    rng = np.random.default_rng(seed)
+    k = rng.integers(-(1 << DYADIC_K_BITS) + 1, 1 << DYADIC_K_BITS, n, dtype=np.int64)
+    k[rng.random(n) < 0.05] = 0
+    values = np.ldexp(k.astype(np.float64), scale)
+    valid = None
+    if null_fraction > 0:
+        valid = rng.random(n) >= null_fraction
+        nulls = np.flatnonzero(~valid)
+        values[nulls] = np.array(NULL_FILL)[np.arange(len(nulls)) % len(NULL_FILL)]
+    return k, values, valid
+
+
+def dyadic_sum(k, scale, take):
+    """The one correct Float64 sum of the cells k[take] * 2^scale, from integer arithmetic."""
+    return float(int(k[take].sum(dtype=np.int64))) * 2.0 ** scale
+
+
+def float_bits(x):
+    return struct.pack("<d", x)
+
+
+def same_float(got, want):
+    """Bit for bit the same double (so -0.0 is not +0.0), or both a NaN."""
+    return float_bits(got) == float_bits(want) or (got != got and want != want)
+
+
+# filter_agg_kernel<ncols, r, vec, 4, flags> (csrc/agg_table.hip): rows per lane by the number of 8-byte columns a pass reads,
+# so a tile is 256 * r rows; flags 0 or FF_VALIDITY | FF_BOOL
+AGG_R = {1: 16, 2: 8, 3: 4, 4: 4}
+AGG_F = 3
+# case name -> (8-byte columns of the launch, flags, Int64 predicate columns)
+AGG_CASES = {"plain1": (1, 0, 0), "nullable1": (1, AGG_F, 0), "boolean1": (1, AGG_F, 0), "cols2": (2, AGG_F, 1),
+             "cols3": (3, AGG_F, 2), "cols4": (4, AGG_F, 3), "cols5": (1, AGG_F, 4)}
+_PRED_TERMS = [("<", 70), (">=", 15), ("!=", 3), (">", 8)]
+
+
+def agg_kernel_name(ncols, vec, flags):
+    return f"filter_agg_kernel<{ncols},{AGG_R[ncols]},{vec},4,{flags}>"
+
+
+def agg_sizes(ncols):
+    """Row counts round one lane, one wave and the tile of the ncols-column variant."""
+    t = 256 * AGG_R[ncols]
+    return [1, 63, 64, 65, t - 1, t, t + 1, 2 * t + 1]
+
+
+def agg_case(case, n, scale, seed, nulls="drops"):
+    """(cols, k, pred, agg_col) of one launch shape of the aggregate.  The aggregated dyadic Float64 column comes LAST, after the
+    columns the predicate reads (nullable Int64 in [0, 100), or one nullable Boolean), so the predicate never reads it:
+      plain1     no bitmap anywhere; the only column a one-column launch can test is the aggregated one (x != 3 * 2^scale)
+      nullable1  the same over a nullable aggregated column
+      boolean1   is_true(Boolean column), aggregated column without bitmap
+      cols2..5   1..4 Int64 predicate columns + nullable aggregated column (cols5: one column more than a pass reads)"""
+    _, _, npred = AGG_CASES[case]
+    k, values, valid = dyadic_cells(seed, n, scale, 0.0 if case in ("plain1", "boolean1") else 0.2)
+    rng = np.random.default_rng(seed + 7919)
+    cols, terms = [], []
+    for j in range(npred):
+        cols.append(Column.from_numpy(rng.integers(0, 100, n, dtype=np.int64), rng.random(n) >= 0.15))
+        terms.append(Term(j, *_PRED_TERMS[j]))
+    if case == "boolean1":
+        cols.append(Column.from_numpy(rng.random(n) < 0.6, rng.random(n) >= 0.15))
+        terms.append(Term(0, "is_true"))
+    cols.append(Column.from_numpy(values, valid))
+    agg = len(cols) - 1
+    if not terms:
+        terms.append(Term(agg, "!=", float(np.ldexp(3.0, scale))))
+    return cols, k, Predicate(terms, nulls), agg
+
+
+def agg_expected(cols, k, scale, pred, agg):
+    """(sum, count) of filter + SUM/COUNT from the host arrays: COUNT = surviving rows, SUM over the surviving non-null cells."""
+    keep = host_survivors(cols, pred)
+    valid = cols[agg].logical_valid()
+    return dyadic_sum(k, scale, keep if valid is None else keep & valid), int(keep.sum())
+
+
+_COMPARE = {"==": np.equal, "!=": np.not_equal, "<": np.less, ">": np.greater, "<=": np.less_equal, ">=": np.greater_equal}
+
+
+def host_survivors(cols, pred):
+    """The rows `pred` keeps, in numpy from the host columns (include/rivulus_gpu.h, rv_predicate; Int64 / Float64 compares with a
+    literal of the column's type and Boolean is_true only).  "drops": a row survives iff every cell the expression reads is valid
+    and the expression is true.  "least": a null cell orders below every value, so <, <= and != keep it."""
+    n = cols[0].length
+    truth, known = [], []
+    for t in pred.terms:
+        c = cols[t.column]
+        v, ok = c.logical_values(), c.logical_valid()
+        ok = np.ones(n, bool) if ok is None else ok
+        x = v.astype(bool) if t.op == "is_true" else _COMPARE[t.op](v, t.literal)
+        if pred.nulls == "least":
+            assert t.op != "is_true"
+            x = np.where(ok, x, t.op in ("<", "<=", "!="))
+            ok = np.ones(n, bool)
+        truth.append(x)
+        known.append(ok)
+
+    read = set()
+
+    def ev(tree):
+        if isinstance(tree, (int, np.integer)):
+            read.add(int(tree))
+            return truth[int(tree)]
+        op, *args = tree
+        if op == "not":
+            return ~ev(args[0])
+        vals = [ev(a) for a in args]
+        return np.logical_and.reduce(vals) if op == "and" else np.logical_or.reduce(vals)
+
+    keep = ev(pred.expr if pred.expr is not None else ("and", *range(len(pred.terms))))
+    for i in read:
+        keep = keep & known[i]
+    return keep
 
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

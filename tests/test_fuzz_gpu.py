@@ -6,7 +6,7 @@ FF_NONULL, Boolean predicate columns, bit streams, selection bitmap, column grou
 import numpy as np
 import pytest
 
-from helpers import assert_columns_equal
+from helpers import assert_columns_equal, same_float
 from rivulus_amd import capi
 from rivulus_amd.capi import Column, Predicate, Term
 
@@ -135,6 +135,14 @@ def test_random_query_matches_oracle(gpu_ctx, oracle, seed):
         si, _, cnt = gpu_ctx.filter_agg(d, pred, a)
         wi, _, wcnt = oracle.filter_agg(cols, pred, a)
         assert (si, cnt) == (wi, wcnt), "filter_agg " + what
+    # ... and over the first Float64 column.  Every fuzz value is a multiple of 0.25 of magnitude at most 7, or NaN / +-inf: all
+    # partial sums of the finite cells are exact, infinities and NaNs absorb in any order, and every running sum starts at +0.0
+    # -- the result does not depend on the order of the additions, so it is the oracle's row-order sum bit for bit (or both NaN)
+    if "f" in kinds:
+        a = kinds.index("f")
+        _, sf, cnt = gpu_ctx.filter_agg(d, pred, a)
+        _, wf, wcnt = oracle.filter_agg(cols, pred, a)
+        assert cnt == wcnt and same_float(sf, wf), f"Float64 filter_agg {sf!r} != {wf!r} " + what
     for o in outs:
         o.free()
     for c in d:
@@ -263,6 +271,12 @@ def test_random_strings_batches_and_shards_match_oracle(gpu_ctx, oracle, seed):
         si, _, cnt = g.filter_agg(sh, pred, 0)
         wi, _, wcnt = oracle.filter_agg(cols, pred, 0)
         assert (si, cnt) == (wi, wcnt), "group filter_agg " + what
+        # a Float64 column of the fuzz's values next to the table (a generator of its own: the cases above stay what they were);
+        # order independent as in test_random_query_matches_oracle, so the shards' sums add up to the oracle's bits
+        f = _column(np.random.default_rng(9500 + seed), "f", n, int(pad))
+        _, sf, cnt = g.filter_agg(sh + [g.upload(f)], pred, 3)
+        _, wf, wcnt = oracle.filter_agg(cols + [f], pred, 3)
+        assert cnt == wcnt and same_float(sf, wf), f"group Float64 filter_agg {sf!r} != {wf!r} " + what
     finally:
         g.close()
 
@@ -302,3 +316,8 @@ def test_random_large_expressions_match_oracle(gpu_ctx, oracle, seed):
     if "i" in kinds:
         a = kinds.index("i")
         assert gpu_ctx.filter_agg(d, pred, a)[::2] == oracle.filter_agg(cols, pred, a)[::2], "filter_agg " + what
+    if "f" in kinds:  # order independent (test_random_query_matches_oracle): the oracle's bits, or both NaN
+        a = kinds.index("f")
+        _, sf, cnt = gpu_ctx.filter_agg(d, pred, a)
+        _, wf, wcnt = oracle.filter_agg(cols, pred, a)
+        assert cnt == wcnt and same_float(sf, wf), f"Float64 filter_agg {sf!r} != {wf!r} " + what
