@@ -102,6 +102,80 @@ def same_float(got, want):
     return float_bits(got) == float_bits(want) or (got != got and want != want)
 
 
+# ---- the filter kernels' launch tables, read from the sources ---------------------------------------------------------------
+CSRC = os.path.join(os.path.dirname(THRESHOLDS))
+FUSED_SOURCES = ("fused_lean1.hip", "fused_valid1.hip", "fused_multi.hip", "fused_bool.hip", "fused_full.hip", "fused_expr.hip", "fused_roomy.hip")
+DIRECT_SOURCES = ("fused_direct.hip", "fused_direct2.hip")
+REDO_SOURCE = "fused_full.hip"
+_ENTRY = re.compile(r"\b(RV_FUSED|RV_DIRECT3|RV_DIRECT)\(([^()]*)\)")
+
+
+def _table_text(name):
+    """A table source without its comments and its #define lines (the macros' own definitions are no entries)."""
+    with open(os.path.join(CSRC, name)) as f:
+        src = f.read()
+    src = re.sub(r"//[^\n]*", "", src)
+    return "\n".join(line for line in src.splitlines() if not line.lstrip().startswith("#"))
+
+
+def kernel_flags():
+    """{name: value} of the FF_* feature flags of csrc/scan_frontend.hpp."""
+    with open(os.path.join(CSRC, "scan_frontend.hpp")) as f:
+        return {k: int(v) for k, v in re.findall(r"\b(FF_[A-Z0-9_]+) = (\d+)", f.read())}
+
+
+def _flag_value(expr, names):
+    """`FF_A | FF_B | 0` with the names of `names`: an OR of known constants, nothing else."""
+    value = 0
+    for part in expr.split("|"):
+        part = part.strip()
+        value |= int(part) if part.isdigit() else names[part]
+    return value
+
+
+def table_entries(name):
+    """Every entry of table source `name`, in order, as (kernel, a, b, c, d, flags): fused_filter_compact<NC,R,V,W,F> or
+    fused_direct_compact<NP,NQ,R,W,F>, the flags evaluated with the FF_* values and the file's own `constexpr int` aliases."""
+    text = _table_text(name)
+    names = kernel_flags()
+    for decl in re.findall(r"constexpr int ([^;]+);", text):
+        for alias, expr in re.findall(r"(\w+) = ([^,]+)", decl):
+            names[alias] = _flag_value(expr, names)
+    out = []
+    for macro, args in _ENTRY.findall(text):
+        args = [a.strip() for a in args.split(",")]
+        if macro == "RV_DIRECT3":
+            a, b, c, d = (int(v) for v in args)
+            out += [("fused_direct_compact", a, b, c, d, f) for f in (0, names["FF_VALIDITY"], names["FF_VALIDITY"] | names["FF_BOOL"])]
+        else:
+            a, b, c, d = (int(v) for v in args[:4])
+            out.append(("fused_filter_compact" if macro == "RV_FUSED" else "fused_direct_compact", a, b, c, d, _flag_value(args[4], names)))
+    return out
+
+
+def redo_entries():
+    """(ncols, rows per lane) of every fused_redo_waves instantiation behind a case label of redo_kernel()."""
+    text = _table_text(REDO_SOURCE)
+    body = text[text.index("redo_kernel("):]
+    return [(int(a), int(b)) for a, b in re.findall(r"case \d+:\s*return &fused_redo_waves<(\d+), (\d+)>", body)]
+
+
+def kernel_name(entry):
+    """As rv_ctx_last_kernel spells it: fused_filter_compact<3,12,1,16,1>."""
+    return f"{entry[0]}<{','.join(str(v) for v in entry[1:])}>"
+
+
+def table_kernels():
+    """The distinct kernel names of the nine tables, in table order (an entry listed in two tables is one kernel)."""
+    seen = {}
+    for src in FUSED_SOURCES + DIRECT_SOURCES:
+        for e in table_entries(src):
+            seen.setdefault(kernel_name(e), e)
+    return seen
+
+
+# (the aggregate's table is small enough to be listed by hand below; the filter kernels' tables are read by table_entries above:
+#  either way every instantiation has a case, and tests/test_instantiation_table_cpu.py holds the filter tables to it)
 # filter_agg_kernel<ncols, r, vec, 4, flags> (csrc/agg_table.hip): rows per lane by the number of 8-byte columns a pass reads,
 # so a tile is 256 * r rows; flags 0 or FF_VALIDITY | FF_BOOL
 AGG_R = {1: 16, 2: 8, 3: 4, 4: 4}
