@@ -330,6 +330,41 @@ rv_status rv_compare(rv_ctx *ctx, const rv_dcolumn *col, rv_cmp op, rv_dtype lit
  * (`name == "Bob"` over a StringArray column, byte-wise str ordering). */
 rv_status rv_compare_term(rv_ctx *ctx, const rv_dcolumn *col, const rv_term *term, rv_dcolumn **out_bool);
 
+/* ---- arithmetic expressions (K8) ------------------------------------------ */
+/* Expr::add / sub / mul / div (BinaryOperator::{Plus, Minus, Multiply, Divide}, expr.rs:17-20, 44-74) over Int64 / Float64 columns
+ * and literals.  The reference types and names such an expression (logical_plan/plan.rs:204-262) and refuses it at planning
+ * (planner.rs:124-126, :151-156), so the cell rules are this library's:
+ *   - result dtype, bottom-up as infer_binary_result_type: Float64 on either side -> Float64; Int64 o Int64 -> Int64 (Divide
+ *     included); Null o T -> T; Null o Null -> Null; a Boolean / String operand is RV_ERR_TYPE_MISMATCH;
+ *   - a null operand makes the cell null and its slot holds the placeholder 0 / 0.0; a Null leaf (an RV_NULL column, a literal of
+ *     lit_type RV_NULL) makes EVERY cell null: decided on the host, no kernel runs;
+ *   - Int64: + - * wrap in two's complement, / truncates toward zero, x / 0 is null, INT64_MIN / -1 is INT64_MIN;
+ *   - an Int64 operand that meets a Float64 is converted first, round to nearest even;
+ *   - Float64: one correctly rounded IEEE-754 operation per operator (no fused multiply-add; x / 0.0 is +-inf or NaN, not null;
+ *     subnormals are kept; a NaN stays a NaN, its payload is not specified).
+ * steps[0 .. n_steps) is the expression in postfix order: RV_ARITH_COL pushes cols[column], RV_ARITH_LIT pushes the literal
+ * (lit_type RV_INT64: lit.i, RV_FLOAT64: lit.f, RV_NULL: a null), the four operators pop two values and push one.  The program
+ * must leave exactly one value and read at least one column.  Limits: 32 steps, an operand stack of 8, 8 distinct columns.
+ * *out: a new column of the common length of the columns read, offset 0, null_count known; it carries a validity bitmap iff a
+ * column read carries one or the program has an Int64 division (or every cell is null).
+ * Errors (the context stays usable, nothing is created): NULL arguments, a malformed program (an operator with fewer than two
+ * operands, more than one value left, no column read, an unknown step) or a column index >= ncols: RV_ERR_INVALID_ARG; columns read
+ * of unequal length: RV_ERR_LENGTH_MISMATCH; a Boolean / String column or literal: RV_ERR_TYPE_MISMATCH; over a limit:
+ * RV_ERR_UNSUPPORTED.  rv_ctx_last_kernel: arith_kernel<2> / <4> / <8> (the larger of the operand stack and the columns read), arith_all_null when
+ * every cell is null, arith_empty for zero rows -- neither of the two launches anything. */
+typedef enum rv_arith_op { RV_ARITH_COL = 0, RV_ARITH_LIT = 1, RV_ARITH_ADD = 2, RV_ARITH_SUB = 3, RV_ARITH_MUL = 4, RV_ARITH_DIV = 5 } rv_arith_op;
+typedef struct rv_arith_step {
+    rv_arith_op op;
+    uint32_t column;   /* RV_ARITH_COL: index into the cols[] array handed to the call */
+    rv_dtype lit_type; /* RV_ARITH_LIT */
+    union {
+        int64_t i;
+        double f;
+    } lit;
+} rv_arith_step;
+rv_status rv_eval_arith(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols,
+                        const rv_arith_step *steps, uint32_t n_steps, rv_dcolumn **out);
+
 /* ---- BooleanArray logic (K3, boolean.rs:120-180) -------------------------- */
 rv_status rv_boolean_and(rv_ctx *ctx, const rv_dcolumn *a, const rv_dcolumn *b, rv_dcolumn **out);
 rv_status rv_boolean_or(rv_ctx *ctx, const rv_dcolumn *a, const rv_dcolumn *b, rv_dcolumn **out);

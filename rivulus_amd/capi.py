@@ -27,6 +27,7 @@ OPS = {"==": RV_EQ, "!=": RV_NE, "<": RV_LT, ">": RV_GT, "<=": RV_LE, ">=": RV_G
 STATUS_NAMES = ["RV_OK", "RV_ERR_INVALID_ARG", "RV_ERR_LENGTH_MISMATCH", "RV_ERR_TYPE_MISMATCH",
                 "RV_ERR_OUT_OF_BOUNDS", "RV_ERR_UNSUPPORTED", "RV_ERR_DEVICE", "RV_ERR_OOM", "RV_ERR_INTERNAL", "RV_ERR_PARSE"]
 RV_ERR_INVALID_ARG, RV_ERR_UNSUPPORTED, RV_ERR_PARSE = 1, 5, 9
+RV_ERR_LENGTH_MISMATCH, RV_ERR_TYPE_MISMATCH = 2, 3
 RV_CSV_NULLS_AS_REFERENCE = 1
 
 
@@ -70,6 +71,56 @@ def postfix(tree) -> List[int]:
     for a in args[1:]:
         out += postfix(a) + [code]
     return out
+
+
+class _ArithLit(C.Union):
+    _fields_ = [("i", C.c_int64), ("f", C.c_double)]
+
+
+class RvArithStep(C.Structure):
+    _fields_ = [("op", C.c_int), ("column", C.c_uint32), ("lit_type", C.c_int), ("lit", _ArithLit)]
+
+
+RV_ARITH_COL, RV_ARITH_LIT, RV_ARITH_ADD, RV_ARITH_SUB, RV_ARITH_MUL, RV_ARITH_DIV = range(6)
+ARITH_OPS = {"+": RV_ARITH_ADD, "-": RV_ARITH_SUB, "*": RV_ARITH_MUL, "/": RV_ARITH_DIV}
+
+
+def arith_postfix(tree) -> list:
+    """Nested arithmetic expression -> the steps of rv_eval_arith, in postfix order.
+    tree: ("col", index) | ("lit", value) with value None (a Null literal) / int / float / bool | ("+" | "-" | "*" | "/", a, b).
+    A step is ("col", index), ("lit", value) or the operator's string."""
+    op, *args = tree
+    if op in ("col", "lit"):
+        return [(op, args[0])]
+    a, b = args
+    return arith_postfix(a) + arith_postfix(b) + [op]
+
+
+def arith_steps(steps):
+    """The rv_arith_step array of a step list (arith_postfix, or written by hand: a malformed program is the caller's to send)."""
+    arr = (RvArithStep * max(1, len(steps)))()
+    for k, s in enumerate(steps):
+        if isinstance(s, str):
+            arr[k].op = ARITH_OPS[s]
+            continue
+        kind, v = s
+        if kind == "col":
+            arr[k].op, arr[k].column = RV_ARITH_COL, int(v)
+            continue
+        arr[k].op = RV_ARITH_LIT
+        if v is None:
+            arr[k].lit_type = RV_NULL
+        elif isinstance(v, (bool, np.bool_)):
+            arr[k].lit_type, arr[k].lit.i = RV_BOOLEAN, int(v)
+        elif isinstance(v, (int, np.integer)):
+            arr[k].lit_type, arr[k].lit.i = RV_INT64, int(v)
+        elif isinstance(v, (float, np.floating)):
+            arr[k].lit_type, arr[k].lit.f = RV_FLOAT64, float(v)
+        elif isinstance(v, str):
+            arr[k].lit_type = RV_STRING  # refused by the library: no arithmetic on strings
+        else:
+            raise TypeError(f"unsupported literal {v!r}")
+    return arr
 
 
 class RvSynthSpec(C.Structure):
@@ -119,6 +170,7 @@ PROTOTYPES = {
     "rv_device_ptrs": (C.c_int, [_P, _P, C.POINTER(RvColumn)]),
     "rv_eval_predicate": (C.c_int, [_P, _PP, C.c_uint32, C.POINTER(RvPredicate), _PP, _U64P]),
     "rv_compare": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, C.c_double, _PP]),
+    "rv_eval_arith": (C.c_int, [_P, _PP, C.c_uint32, C.POINTER(RvArithStep), C.c_uint32, _PP]),
     "rv_boolean_and": (C.c_int, [_P, _P, _P, _PP]),
     "rv_boolean_or": (C.c_int, [_P, _P, _P, _PP]),
     "rv_boolean_not": (C.c_int, [_P, _P, _PP]),
@@ -680,6 +732,14 @@ class Context:
             return DeviceColumn(self, out)
         _check(load().rv_compare(self.handle, col.handle, t.op, t.lit_type, t.lit.i if t.lit_type != RV_FLOAT64 else 0,
                                  t.lit.f if t.lit_type == RV_FLOAT64 else 0.0, C.byref(out)))
+        return DeviceColumn(self, out)
+
+    def eval_arith(self, cols: Sequence[DeviceColumn], steps) -> DeviceColumn:
+        """rv_eval_arith: `steps` is a step list (arith_postfix(tree)) or a nested tree."""
+        if isinstance(steps, tuple):
+            steps = arith_postfix(steps)
+        out = C.c_void_p()
+        _check(load().rv_eval_arith(self.handle, _handles(cols), len(cols), arith_steps(steps), len(steps), C.byref(out)))
         return DeviceColumn(self, out)
 
     def boolean_and(self, a, b):

@@ -93,4 +93,9 @@ constexpr uint64_t kJoinFastBatchRows = 1024;
 // table has (join.hip).  Not a crossover and not swept: with linear probing the expected chain at 50 % is 1.5 slots for a hit and 2.5
 // for a miss, and every slot is one 8-byte word -- 16 bytes per row at most, next to the strings themselves.   tools/string_key_bench.py
 constexpr uint64_t kStrDictSlotsPerRow = 2;
+
+// ---- arithmetic expressions (arith.hip) -----------------------------------------------------------------------------------------------
+// Workgroups of 256 lanes one arith_kernel launch takes at most: eight per CU of a 256-CU part, what the other one-lane-per-row kernels
+// take (grid_for_words); longer columns are grid-strided.  Not a crossover and not swept.              tools/arith_bench.py
+constexpr uint64_t kArithGridMost = 2048;
 }  // namespace rvt

@@ -16,6 +16,10 @@
 //                   extract_column_names_from_expressions}   planner.rs:113-189, streaming_planner.rs:102-168
 //   physical_plan::lower_predicate                           compare / AND / OR lowering (replaces the rejection at
 //                                                            streaming_planner.rs:141-162)
+//   physical_plan::{lower_select_exprs,
+//                   lower_computed_predicate}               arithmetic select / filter expressions (expr.rs:44-74; refused by the
+//                                                            reference at planner.rs:124-126, :151-156) -> rv_eval_arith
+//   execution::GpuProjectStream                              select([...]) with computed columns, batch by batch
 //   physical_plan::StreamingPhysicalPlan                     streaming.rs:29-133, :235-238, :343-352
 //   physical_plan::PhysicalPlan (Source/Filter/Select)       plan.rs:8-150 over typed device columns
 //
@@ -965,6 +969,120 @@ inline rv_term to_rv_term(const CompareTerm &t, uint32_t column_index) {
     return r;
 }
 
+// ---- arithmetic expressions (rv_eval_arith) ----------------------------------------------------------------------------
+// One step of a postfix program over NAMED columns: what Expr::add / sub / mul / div trees are lowered to (expr.rs:44-74).
+struct ArithStep {
+    rv_arith_op op = RV_ARITH_COL;
+    std::string column;  // RV_ARITH_COL
+    Literal literal;     // RV_ARITH_LIT; monostate == Literal(AnyValue::Null)
+    bool operator==(const ArithStep &o) const { return op == o.op && column == o.column && literal == o.literal; }
+};
+// One output column of a projection: a plain column of the input (`source`), or an arithmetic program over its columns.  Name and
+// dtype are resolve_expr_schema's (logical_plan/plan.rs:204-233).
+struct LoweredSelect {
+    std::string name;
+    DataType data_type = DataType::Null;
+    std::string source;              // plain column: the input column it passes through
+    std::vector<ArithStep> program;  // computed column
+    bool computed() const { return !program.empty(); }
+};
+// `<arith> <cmp> <literal>` terms of a filter: every computed left side is a helper column appended to the batch, and the
+// predicate is an ordinary one over the batch's columns and the helpers (rv_filter_project); the helpers never leave the filter.
+struct ComputedPredicate {
+    std::vector<LoweredSelect> helpers;
+    LoweredPredicate predicate;
+};
+
+// The program's value over the columns `column(name)` finds (nullptr: the caller's `missing(name)` throws): one rv_eval_arith.
+inline ArrayRef eval_arith(const std::vector<ArithStep> &program, const std::function<const ArrayRef *(const std::string &)> &column,
+                           const std::function<void(const std::string &)> &missing) {
+    std::vector<const rv_dcolumn *> cols;
+    std::vector<std::string> names;
+    std::vector<rv_arith_step> steps;
+    ContextRef ctx;
+    for (auto &s : program) {
+        rv_arith_step r{};
+        r.op = s.op;
+        if (s.op == RV_ARITH_COL) {
+            size_t k = 0;
+            while (k < names.size() && names[k] != s.column) ++k;
+            if (k == names.size()) {
+                const ArrayRef *a = column(s.column);
+                if (!a) missing(s.column);
+                if (!a || !(*a)->on_device()) throw Error(RV_ERR_UNSUPPORTED, "columns off the device are outside the device path");
+                if (!ctx) ctx = (*a)->context();
+                names.push_back(s.column);
+                cols.push_back((*a)->handle());
+            }
+            r.column = static_cast<uint32_t>(k);
+        } else if (s.op == RV_ARITH_LIT) {
+            switch (s.literal.index()) {
+                case 0: r.lit_type = RV_NULL; break;
+                case 1: r.lit_type = RV_INT64; r.lit.i = std::get<1>(s.literal); break;
+                case 2: r.lit_type = RV_FLOAT64; r.lit.f = std::get<2>(s.literal); break;
+                case 3: r.lit_type = RV_BOOLEAN; r.lit.i = std::get<3>(s.literal); break;  // refused by the library
+                default: r.lit_type = RV_STRING; break;                                    // likewise
+            }
+        }
+        steps.push_back(r);
+    }
+    if (!ctx) throw Error(RV_ERR_INVALID_ARG, "arithmetic expression reads no column");
+    rv_dcolumn *out = nullptr;
+    check(rv_eval_arith(ctx->raw(), cols.data(), static_cast<uint32_t>(cols.size()), steps.data(), static_cast<uint32_t>(steps.size()), &out));
+    return Array::adopt(ctx, out);
+}
+
+// GpuProjectStream -- select([...]) with computed columns, batch by batch: a plain column passes through zero-copy (as
+// SelectStream does, under the name the lowering gave it), a computed one is one rv_eval_arith over the batch.  A projection
+// keeps every row, so a consumer's limit_hint goes on to the input.
+class GpuProjectStream : public DataStream {
+  public:
+    GpuProjectStream(DataStreamRef input, std::vector<LoweredSelect> outputs) : input_(std::move(input)), outputs_(std::move(outputs)) {
+        auto in = input_->schema();
+        auto need = [&](const std::string &n) -> const Field & {
+            auto fld = in->field_by_name(n);
+            if (!fld) throw StreamError::execution("Column '" + n + "' not found in schema");
+            return *fld;
+        };
+        std::vector<Field> f;
+        for (auto &o : outputs_) {
+            if (!o.computed()) {
+                const Field &src = need(o.source);
+                f.push_back(Field{o.name, src.data_type(), src.is_nullable()});
+                continue;
+            }
+            for (auto &s : o.program)
+                if (s.op == RV_ARITH_COL) need(s.column);
+            f.push_back(Field{o.name, o.data_type, true});
+        }
+        output_schema_ = std::make_shared<Schema>(f);
+    }
+    SchemaRef schema() const override { return output_schema_; }
+    void limit_hint(size_t rows) override { input_->limit_hint(rows); }
+    std::optional<RecordBatch> next_batch() override {
+        auto batch = input_->next_batch();
+        if (!batch) return std::nullopt;
+        auto missing = [](const std::string &n) { throw StreamError::execution("Column '" + n + "' not found in schema"); };
+        auto column = [&](const std::string &n) { return batch->column_by_name(n); };
+        std::vector<ArrayRef> arrays;
+        for (auto &o : outputs_) {
+            if (o.computed()) {
+                arrays.push_back(stream_call([&] { return eval_arith(o.program, column, missing); }));
+            } else {
+                const ArrayRef *a = column(o.source);
+                if (!a) missing(o.source);
+                arrays.push_back(*a);
+            }
+        }
+        return RecordBatch::new_unchecked(output_schema_, std::move(arrays), batch->num_rows());
+    }
+
+  private:
+    DataStreamRef input_;
+    std::vector<LoweredSelect> outputs_;
+    SchemaRef output_schema_;
+};
+
 // Per-batch survivor counts in memory the device can write (rv_host_alloc): rv_filter_project_chunked then lets the fused
 // pass drop the counts there itself -- 8 bytes per batch cross PCIe once and the host copies nothing.
 class PinnedCounts {
@@ -1668,6 +1786,9 @@ struct Expr {
     Expr and_(const Expr &o) const { return binary(BinaryOperator::And, o); }
     Expr or_(const Expr &o) const { return binary(BinaryOperator::Or, o); }
     Expr add(const Expr &o) const { return binary(BinaryOperator::Plus, o); }
+    Expr sub(const Expr &o) const { return binary(BinaryOperator::Minus, o); }
+    Expr mul(const Expr &o) const { return binary(BinaryOperator::Multiply, o); }
+    Expr div(const Expr &o) const { return binary(BinaryOperator::Divide, o); }
 };
 }  // namespace expressions
 
@@ -1753,7 +1874,9 @@ inline std::string extract_boolean_predicate_column(const Expr &p) {
 
 // The lowering the new backend adds: `Column <cmp> Literal`, a bare Boolean column, and AND / OR trees of those
 // (BinaryOperator::{And, Or}, expr.rs:27-28) become the term list + postfix program of one fused device pass.
-// Arithmetic stays unsupported (ExpressionError, like the reference).
+// Arithmetic is not this function's: it keeps refusing it (ExpressionError, like the reference), and
+// lower_computed_predicate / lower_select_exprs below take `<arith> <cmp> <literal>` filters and computed select
+// expressions to the device through rv_eval_arith.
 inline void lower_predicate(const Expr &p, execution::LoweredPredicate &out, bool &has_or) {
     auto push_term = [&](CompareTerm t) {
         if (out.terms.size() >= 16) throw StreamingPlannerError("Expression conversion error: more than 16 compare terms in one filter");
@@ -1780,6 +1903,132 @@ inline execution::LoweredPredicate lower_predicate(const Expr &p) {
     return out;
 }
 
+// ---- arithmetic: Expr::add / sub / mul / div (expr.rs:17-20, 44-74) -----------------------------------------------------------
+inline bool is_arithmetic(BinaryOperator op) { return op <= BinaryOperator::Divide; }
+inline bool is_arithmetic(const Expr &e) { return e.kind == Expr::BinaryExpr && is_arithmetic(e.op); }
+inline rv_arith_op to_arith_op(BinaryOperator op) { return static_cast<rv_arith_op>(RV_ARITH_ADD + static_cast<int>(op)); }
+inline execution::DataType literal_data_type(const execution::Literal &v) {  // AnyValue::data_type
+    static const execution::DataType t[] = {execution::DataType::Null, execution::DataType::Int64, execution::DataType::Float64,
+                                            execution::DataType::Boolean, execution::DataType::String};
+    return t[v.index()];
+}
+// infer_binary_result_type for the four arithmetic operators (logical_plan/plan.rs:250-260).  Where the reference infers Null for a
+// Boolean / String operand (:259) this is a type mismatch: there is no arithmetic on those cells.
+inline execution::DataType infer_arith_result_type(execution::DataType left, execution::DataType right) {
+    using execution::DataType;
+    for (DataType t : {left, right})
+        if (t == DataType::Boolean || t == DataType::String) throw Error(RV_ERR_TYPE_MISMATCH, std::string("no arithmetic on ") + to_string(t) + " operands");
+    if (left == DataType::Float64 || right == DataType::Float64) return DataType::Float64;
+    if (left == DataType::Int64 || right == DataType::Int64) return DataType::Int64;
+    return DataType::Null;
+}
+// resolve_expr_schema (plan.rs:204-233) of an arithmetic tree, and its postfix program: {name of the left-most leaf, dtype}.
+// An alias inside the tree names its subtree and changes nothing else; a column the schema lacks types as Null, as there.
+inline std::pair<std::string, execution::DataType> lower_arith(const Expr &e, const execution::Schema &schema, std::vector<execution::ArithStep> &out) {
+    switch (e.kind) {
+        case Expr::Column: {
+            out.push_back(execution::ArithStep{RV_ARITH_COL, e.name, {}});
+            const execution::Field *f = schema.field_by_name(e.name);
+            return {e.name, f ? f->data_type() : execution::DataType::Null};
+        }
+        case Expr::Literal: out.push_back(execution::ArithStep{RV_ARITH_LIT, "", e.literal}); return {"literal", literal_data_type(e.literal)};
+        case Expr::Alias: return {e.name, lower_arith(*e.left, schema, out).second};
+        default: {
+            if (!is_arithmetic(e.op)) throw ConversionError(ConversionError::UnsupportedExpression, "Unsupported expression: a comparison inside an arithmetic expression");
+            auto l = lower_arith(*e.left, schema, out);
+            auto r = lower_arith(*e.right, schema, out);
+            out.push_back(execution::ArithStep{to_arith_op(e.op), "", {}});
+            return {l.first, infer_arith_result_type(l.second, r.second)};
+        }
+    }
+}
+inline bool reads_a_column(const std::vector<execution::ArithStep> &program) {
+    return std::any_of(program.begin(), program.end(), [](const execution::ArithStep &s) { return s.op == RV_ARITH_COL; });
+}
+
+// select([...]) with arithmetic: every expression becomes a plain column (Column, or an alias of one: convert_select_expr's two
+// forms) or an arithmetic program; name and dtype follow resolve_expr_schema.  A bare literal stays InvalidSelectExpression.
+inline std::vector<execution::LoweredSelect> lower_select_exprs(const std::vector<Expr> &exprs, const execution::Schema &schema) {
+    std::vector<execution::LoweredSelect> out;
+    for (const Expr &top : exprs) {
+        execution::LoweredSelect s;
+        const Expr *e = &top;
+        std::optional<std::string> alias;
+        while (e->kind == Expr::Alias) {  // the outermost alias names the column
+            if (!alias) alias = e->name;
+            e = e->left.get();
+        }
+        if (e->kind == Expr::Literal) {
+            if (alias) throw ConversionError(ConversionError::UnsupportedExpression, "Unsupported expression");
+            throw ConversionError(ConversionError::InvalidSelectExpression, "Select expression must be a column or alias");
+        }
+        if (e->kind == Expr::Column) {
+            const execution::Field *f = schema.field_by_name(e->name);
+            s.source = e->name;
+            s.name = e->name;
+            s.data_type = f ? f->data_type() : execution::DataType::Null;
+        } else {
+            if (!is_arithmetic(*e)) throw ConversionError(ConversionError::UnsupportedExpression, "Unsupported expression");
+            auto named = lower_arith(*e, schema, s.program);
+            if (!reads_a_column(s.program)) throw ConversionError(ConversionError::UnsupportedExpression, "Unsupported expression: arithmetic over literals alone");
+            s.name = named.first;
+            s.data_type = named.second;
+        }
+        if (alias) s.name = *alias;
+        out.push_back(std::move(s));
+    }
+    return out;
+}
+
+// filter(...) with arithmetic on the left of a compare: `<arith> <cmp> <literal>`, alone or under AND / OR with the terms
+// lower_predicate takes.  Every computed left side becomes the helper column "__arith<k>".
+inline void lower_computed_predicate(const Expr &p, const execution::Schema &schema, execution::ComputedPredicate &out, bool &has_or) {
+    auto push_term = [&](CompareTerm t) {
+        if (out.predicate.terms.size() >= 16) throw StreamingPlannerError("Expression conversion error: more than 16 compare terms in one filter");
+        out.predicate.expr.push_back(static_cast<uint8_t>(out.predicate.terms.size()));
+        out.predicate.terms.push_back(std::move(t));
+    };
+    if (p.kind == Expr::BinaryExpr && (p.op == BinaryOperator::And || p.op == BinaryOperator::Or)) {
+        lower_computed_predicate(*p.left, schema, out, has_or);
+        lower_computed_predicate(*p.right, schema, out, has_or);
+        out.predicate.expr.push_back(p.op == BinaryOperator::And ? RV_EXPR_AND : RV_EXPR_OR);
+        has_or = has_or || p.op == BinaryOperator::Or;
+        return;
+    }
+    if (p.kind == Expr::BinaryExpr && is_compare(p.op) && is_arithmetic(*p.left) && p.right->kind == Expr::Literal) {
+        execution::LoweredSelect helper;
+        helper.data_type = lower_arith(*p.left, schema, helper.program).second;
+        if (!reads_a_column(helper.program)) throw StreamingPlannerError("Expression conversion error: arithmetic over literals alone");
+        helper.name = "__arith" + std::to_string(out.helpers.size());
+        push_term(CompareTerm{helper.name, to_cmp(p.op), p.right->literal});
+        out.helpers.push_back(std::move(helper));
+        return;
+    }
+    execution::LoweredPredicate plain;  // a term of the existing grammar (or its refusal)
+    bool unused = false;
+    lower_predicate(p, plain, unused);
+    push_term(std::move(plain.terms.at(0)));
+}
+inline execution::ComputedPredicate lower_computed_predicate(const Expr &p, const execution::Schema &schema) {
+    execution::ComputedPredicate out;
+    bool has_or = false;
+    lower_computed_predicate(p, schema, out, has_or);
+    if (!has_or) out.predicate.expr.clear();
+    return out;
+}
+// the columns of `in` and then the helper columns: the projection that feeds a computed filter
+inline std::vector<execution::LoweredSelect> with_arith_helpers(const execution::Schema &in, const std::vector<execution::LoweredSelect> &helpers) {
+    std::vector<execution::LoweredSelect> all;
+    for (auto &f : in.fields()) {
+        execution::LoweredSelect s;
+        s.name = s.source = f.name();
+        s.data_type = f.data_type();
+        all.push_back(std::move(s));
+    }
+    all.insert(all.end(), helpers.begin(), helpers.end());
+    return all;
+}
+
 // StreamingPhysicalPlan -- streaming.rs:29-133, collect :235-238 + :343-352
 struct StreamingExecutionError : std::runtime_error {
     using std::runtime_error::runtime_error;
@@ -1795,6 +2044,12 @@ struct DeviceFrame {  // the typed-column stand-in for datatypes::DataFrame
         return nullptr;
     }
 };
+
+inline execution::Schema frame_schema(const DeviceFrame &df) {  // every field nullable, as dataframe_to_batches declares them
+    std::vector<execution::Field> f;
+    for (size_t c = 0; c < df.columns.size(); ++c) f.push_back(execution::Field{df.names[c], df.columns[c]->data_type(), true});
+    return execution::Schema(f);
+}
 
 // dataframe_to_batches -- streaming.rs:135-233: batch_size-row chunks (zero-copy slices); the null cells of
 // Int64 / Float64 / Boolean columns become 0 / 0.0 / false and the column loses its bitmap (the reference
@@ -1826,7 +2081,9 @@ class StreamingPhysicalPlan;
 using StreamingPlanPtr = std::shared_ptr<const StreamingPhysicalPlan>;
 class StreamingPhysicalPlan {
   public:
-    enum Kind { MemorySource, DataFrameSource, CsvFileSource, Filter, GpuFilterProject, Select, Limit, HashJoin } kind = MemorySource;
+    enum Kind { MemorySource, DataFrameSource, CsvFileSource, Filter, GpuFilterProject, Select, Limit, HashJoin, Project, ComputedFilterProject } kind = MemorySource;
+    std::vector<Expr> exprs;  // Project: select expressions, arithmetic included
+    Expr predicate_expr;      // ComputedFilterProject: a filter with `<arith> <cmp> <literal>` terms
     // DataFrameSource (streaming.rs:85-94)
     DeviceFrame df;
     size_t df_batch_size = 0;
@@ -1897,6 +2154,24 @@ class StreamingPhysicalPlan {
         p->columns = std::move(columns);
         return p;
     }
+    // select([...]) whose expressions may be arithmetic (lower_select_exprs): GpuProjectStream
+    static StreamingPlanPtr project(StreamingPlanPtr in, std::vector<Expr> exprs) {
+        auto p = std::make_shared<StreamingPhysicalPlan>();
+        p->kind = Project;
+        p->input = std::move(in);
+        p->exprs = std::move(exprs);
+        return p;
+    }
+    // Filter(expr) with computed terms (lower_computed_predicate) followed by Select(columns): the helper columns are appended by a
+    // GpuProjectStream and dropped again by the fused operator's projection
+    static StreamingPlanPtr computed_filter_project(StreamingPlanPtr in, Expr predicate, std::vector<std::string> columns) {
+        auto p = std::make_shared<StreamingPhysicalPlan>();
+        p->kind = ComputedFilterProject;
+        p->input = std::move(in);
+        p->predicate_expr = std::move(predicate);
+        p->columns = std::move(columns);
+        return p;
+    }
     static StreamingPlanPtr limit(StreamingPlanPtr in, size_t n) {
         auto p = std::make_shared<StreamingPhysicalPlan>();
         p->kind = Limit;
@@ -1943,6 +2218,18 @@ class StreamingPhysicalPlan {
                     return std::make_unique<GpuFilterProjectStream>(input->execute(), predicate, columns);
                 case Select: return std::make_unique<SelectStream>(input->execute(), columns);
                 case Limit: return std::make_unique<LimitStream>(input->execute(), n);
+                case Project: {
+                    auto in = input->execute();
+                    auto lowered = lower_select_exprs(exprs, *in->schema());
+                    return std::make_unique<GpuProjectStream>(std::move(in), std::move(lowered));
+                }
+                case ComputedFilterProject: {  // RV_NULL_DROPS on the helper columns, exactly as on any other column
+                    auto in = input->execute();
+                    const SchemaRef schema = in->schema();
+                    ComputedPredicate lowered = lower_computed_predicate(predicate_expr, *schema);
+                    auto widened = std::make_unique<GpuProjectStream>(std::move(in), with_arith_helpers(*schema, lowered.helpers));
+                    return std::make_unique<GpuFilterProjectStream>(std::move(widened), std::move(lowered.predicate), columns);
+                }
                 case HashJoin: {
                     // a resident frame is taken whole, after the null fill: windows of the probe frame, the build frame as it is (an
                     // empty frame too: it still has its columns' names and dtypes)
@@ -2011,8 +2298,10 @@ class PhysicalPlan;
 using PhysicalPlanPtr = std::shared_ptr<const PhysicalPlan>;
 class PhysicalPlan {
   public:
-    enum Kind { DataFrameSource, Select, Filter, HashJoin } kind = DataFrameSource;
+    enum Kind { DataFrameSource, Select, Filter, HashJoin, Project, ComputedFilter } kind = DataFrameSource;
     DeviceFrame df;
+    std::vector<Expr> exprs;  // Project: select expressions, arithmetic included
+    Expr predicate_expr;      // ComputedFilter: `<arith> <cmp> <literal>` terms, alone or under AND / OR
     PhysicalPlanPtr input;
     std::vector<std::string> columns, final_names;
     CompareTerm term;  // Filter { column, value, op }
@@ -2037,6 +2326,24 @@ class PhysicalPlan {
         p->input = std::move(in);
         p->columns = std::move(cols);
         p->final_names = std::move(finals);
+        return p;
+    }
+    // Select whose expressions may be arithmetic (lower_select_exprs): plain columns pass through as Select passes them, computed
+    // ones are one rv_eval_arith each
+    static PhysicalPlanPtr project(PhysicalPlanPtr in, std::vector<Expr> exprs) {
+        auto p = std::make_shared<PhysicalPlan>();
+        p->kind = Project;
+        p->input = std::move(in);
+        p->exprs = std::move(exprs);
+        return p;
+    }
+    // Filter over computed terms (lower_computed_predicate): every column kept, AnyValue ordering for nulls -- on the helper
+    // columns as on any other
+    static PhysicalPlanPtr computed_filter(PhysicalPlanPtr in, Expr predicate) {
+        auto p = std::make_shared<PhysicalPlan>();
+        p->kind = ComputedFilter;
+        p->input = std::move(in);
+        p->predicate_expr = std::move(predicate);
         return p;
     }
     // planner.rs:102-108: the left frame is the build side, the right frame the probe side
@@ -2083,6 +2390,62 @@ class PhysicalPlan {
                 const ContextRef ctx = (*fc)->context();
                 check(rv_filter_project(ctx->raw(), cols.data(), static_cast<uint32_t>(cols.size()), &pred, proj.data(),
                                         static_cast<uint32_t>(proj.size()), out.data(), &rows, nullptr));
+                DeviceFrame res;
+                res.names = in.names;
+                for (auto *h : out) res.columns.push_back(execution::Array::adopt(ctx, h));
+                return res;
+            }
+            case Project: {
+                DeviceFrame in = input->execute();
+                const auto lowered = lower_select_exprs(exprs, frame_schema(in));
+                auto missing = [](const std::string &c) { throw ExecutionError(ExecutionError::ColumnNotFound, "Column not found: '" + c + "'"); };
+                auto column = [&](const std::string &c) { return in.column(c); };
+                for (auto &o : lowered) {  // as Select: every name is checked before anything is built
+                    if (!o.computed() && !in.column(o.source)) missing(o.source);
+                    for (auto &s : o.program)
+                        if (s.op == RV_ARITH_COL && !in.column(s.column)) missing(s.column);
+                }
+                DeviceFrame out;
+                for (auto &o : lowered) {
+                    out.names.push_back(o.name);
+                    out.columns.push_back(o.computed() ? execution::eval_arith(o.program, column, missing) : *in.column(o.source));
+                }
+                return out;
+            }
+            case ComputedFilter: {  // helper columns behind the frame's, one rv_filter_project, the helpers left out of its projection
+                DeviceFrame in = input->execute();
+                if (in.columns.empty()) throw Error(RV_ERR_INVALID_ARG, "filter over a frame without columns");
+                const execution::ComputedPredicate lowered = lower_computed_predicate(predicate_expr, frame_schema(in));
+                auto missing = [](const std::string &c) { throw ExecutionError(ExecutionError::ColumnNotFound, "Column not found: '" + c + "'"); };
+                auto column = [&](const std::string &c) { return in.column(c); };
+                std::vector<std::string> names = in.names;
+                std::vector<execution::ArrayRef> helpers;
+                for (auto &h : lowered.helpers) {
+                    helpers.push_back(execution::eval_arith(h.program, column, missing));
+                    names.push_back(h.name);
+                }
+                std::vector<const rv_dcolumn *> cols;
+                std::vector<uint32_t> proj;
+                for (size_t i = 0; i < in.columns.size(); ++i) {
+                    if (!in.columns[i]->on_device()) throw Error(RV_ERR_UNSUPPORTED, "columns off the device are outside the device path");
+                    cols.push_back(in.columns[i]->handle());
+                    proj.push_back(static_cast<uint32_t>(i));
+                }
+                for (auto &h : helpers) cols.push_back(h->handle());
+                std::vector<rv_term> terms;
+                for (auto &t : lowered.predicate.terms) {
+                    const auto at = std::find(names.begin(), names.end(), t.column);
+                    if (at == names.end()) missing(t.column);  // a plain term beside the computed ones that names no column of the frame
+                    terms.push_back(execution::to_rv_term(t, static_cast<uint32_t>(at - names.begin())));
+                }
+                const auto &expr = lowered.predicate.expr;
+                rv_predicate pred{terms.data(), static_cast<uint32_t>(terms.size()), RV_NULL_IS_LEAST, expr.empty() ? nullptr : expr.data(),
+                                  static_cast<uint32_t>(expr.size())};
+                const ContextRef ctx = in.columns[0]->context();
+                std::vector<rv_dcolumn *> out(proj.size(), nullptr);
+                uint64_t rows = 0;
+                check(rv_filter_project(ctx->raw(), cols.data(), static_cast<uint32_t>(cols.size()), &pred, proj.data(), static_cast<uint32_t>(proj.size()),
+                                        out.data(), &rows, nullptr));
                 DeviceFrame res;
                 res.names = in.names;
                 for (auto *h : out) res.columns.push_back(execution::Array::adopt(ctx, h));
