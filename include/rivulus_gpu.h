@@ -253,7 +253,9 @@ rv_status rv_ctx_device_info(rv_ctx *ctx, int *compute_units, uint64_t *hbm_byte
  * survivors + 25 %; more survivors than that and the column takes the scan path after the pass: this forces that fallback in tests).
  * "csv_slow_cap" = k > 0: a CSV chunk's first list of Float64 cells left to the exact slow kernel holds at most k cells (default:
  * rows x Float64 columns, at most 2^20); more such cells and the chunk is parsed again with a list of the exact size (forces
- * that path in tests). */
+ * that path in tests).
+ * "agg_max_groups" = k > 0: rv_hash_aggregate / rv_group_ids refuse more than k groups (0: the default, 2^26) and size the group
+ * table by min(rows, k); "agg_hash_bits" = b (tests): the key hash of group tables truncated to b low bits (see rv_hash_aggregate). */
 rv_status rv_ctx_set_option(rv_ctx *ctx, const char *key, int64_t value);
 /* current value of an option, or of the read-only counters "overflow_reruns" (launches re-run because speculatively sized
  * outputs were too small), "last_selectivity_ppm" (survivors per million rows of the last fused launch, -1: none yet),
@@ -625,6 +627,66 @@ rv_status rv_filter_project_host(rv_ctx *ctx, const rv_column *host_cols, uint32
 rv_status rv_filter_agg(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols,
                         const rv_predicate *pred, uint32_t agg_col, int64_t *sum_i,
                         double *sum_f, uint64_t *count);
+
+/* ---- grouped aggregation (K9) ----------------------------------------------- */
+/* group_by(key).agg([a_0 .. a_{m-1}]): one key column, m >= 1 aggregates, each (op, value column).  The reference has
+ * no aggregate operator; the semantics are defined here and in DESIGN.md section 4 K9.
+ *
+ * Groups.  One group per distinct key value; all null keys form ONE group (AnyValue: Null == Null, as in the join).
+ * Key dtypes: RV_INT64; RV_NULL (one group when the column has rows).  RV_FLOAT64, RV_BOOLEAN and RV_STRING keys are
+ * RV_ERR_UNSUPPORTED -- String keys go through rv_string_dict_build ids (the host layer does that).
+ *
+ * Order.  The output rows are the groups by ascending FIRST ROW: a group's smallest row index in the key column as
+ * given (slice offset excluded).  Positions come from the first rows and a scan, never from the order atomics land in:
+ * the same input gives the same output on every run.  An empty key gives zero groups and zero-row outputs of the right
+ * dtypes.
+ *
+ * Aggregates.  RV_AGG_COUNT_ROWS takes no value column and counts the group's rows; RV_AGG_COUNT counts the non-null
+ * cells of a value column of any dtype; RV_AGG_SUM / MIN / MAX run over the non-null cells of an RV_INT64 or
+ * RV_FLOAT64 value column (any other dtype: RV_ERR_TYPE_MISMATCH).
+ *   counts   Int64, no bitmap.
+ *   SUM      the value column's dtype, no bitmap; a group without a non-null cell sums to 0 / +0.0 (as rv_filter_agg
+ *            over an empty selection).  Int64: wraps in two's complement, order independent, exact.  Float64: NO
+ *            floating-point atomics anywhere on the path.  The rows are grouped by a stable sort, each group's rows
+ *            ascending, and a group's additions are ordered by the LENGTH L of its row list (null cells included: each
+ *            adds +0.0) and every row's POSITION in it, nothing else: L <= 1024: lane l of one wave adds positions l,
+ *            l + 64, ... from +0.0, then the xor butterfly 32, 16, .., 1 over the lanes; longer: thread t of 256 adds
+ *            positions t, t + 256, ..., the same butterfly per wave, then (w0 + w1) + (w2 + w3); the result is +0.0 +
+ *            that sum (never -0.0).  So the same call over the same buffers gives the same bits run to run; the sum is
+ *            bit exact whenever every partial sum is representable, and otherwise |got - exact| <= gamma_{n-1} x
+ *            sum|x| per group (n = its non-null cells, gamma_k = k u / (1 - k u), u = 2^-53: the bound of any
+ *            summation order).  NaN / inf under null cells never reach a sum.
+ *   MIN/MAX  the value column's dtype; null for a group without a non-null cell.  Float64: -0.0 orders below +0.0; if
+ *            any non-null cell of the group is NaN the result is NaN (payload unspecified); otherwise the bits of the
+ *            smallest / largest cell.  (One integer atomic min / max over an order-preserving map of the bits: exact.)
+ *   A bitmap is attached iff some output cell is null; null_count is known; values under nulls are 0.
+ *
+ * Errors leave the context usable and create nothing: NULL arguments, n_specs == 0, a `col` out of range or an unknown
+ * op RV_ERR_INVALID_ARG; a value column whose length differs from the key's RV_ERR_LENGTH_MISMATCH; keys of 2^32 rows
+ * or more RV_ERR_UNSUPPORTED (32-bit row ids inside, as the join); more groups than context option "agg_max_groups"
+ * (0 = the default 2^26: a group table of at most 1 GiB) RV_ERR_UNSUPPORTED, with the number of distinct keys found
+ * before the insert stopped in rv_last_error().  Slices of keys and values at any element offset are fine.  Context
+ * option "agg_hash_bits" = b (tests; 0 = all 64) truncates the key hash to b low bits: long probe chains on small
+ * inputs, the twin of "join_hash_bits".
+ *
+ * rv_ctx_last_kernel after rv_hash_aggregate names the accumulate stage: "group_accumulate<lds>" (up to 16384 groups:
+ * LDS accumulators per workgroup), "group_accumulate<global>" (more), with "+group_f64_sum" appended -- or
+ * "group_f64_sum" alone -- when a Float64 SUM ran.  rv_ctx_kernel_stats (option "profile_kernels") times that stage:
+ * the accumulate launches and the Float64 SUM path (its sort included), not the group-id passes before it. */
+typedef enum rv_agg_op { RV_AGG_COUNT_ROWS = 0, RV_AGG_COUNT = 1, RV_AGG_SUM = 2, RV_AGG_MIN = 3, RV_AGG_MAX = 4 } rv_agg_op;
+typedef struct rv_agg_spec {
+    uint32_t op;  /* rv_agg_op */
+    uint32_t col; /* index into value_cols; ignored by RV_AGG_COUNT_ROWS */
+} rv_agg_spec;
+/* Dense group ids: out_gids an Int64 column of key's length without nulls (row -> its group's position in the output),
+ * out_first_row an Int64 column of *out_groups rows, ascending (what rv_take_device takes to gather the key cells).
+ * out_groups may be NULL. */
+rv_status rv_group_ids(rv_ctx *ctx, const rv_dcolumn *key, rv_dcolumn **out_gids, rv_dcolumn **out_first_row, uint64_t *out_groups);
+/* The whole operator: out[0] = the key cells of the groups (rv_take_device of key by first_row: null for the null
+ * group), out[1 + j] = aggregate j: out has room for n_specs + 1 handles.  out_first_row and out_groups may be NULL. */
+rv_status rv_hash_aggregate(rv_ctx *ctx, const rv_dcolumn *key, const rv_dcolumn *const *value_cols, uint32_t n_values,
+                            const rv_agg_spec *specs, uint32_t n_specs, rv_dcolumn **out, rv_dcolumn **out_first_row,
+                            uint64_t *out_groups);
 
 /* ---- multi-GPU (one process per GPU) --------------------------------------- */
 /* Row-range shard of rank `rank` of `world`: [*begin, *end), boundaries at multiples of

@@ -123,6 +123,15 @@ def arith_steps(steps):
     return arr
 
 
+# rv_agg_op
+RV_AGG_COUNT_ROWS, RV_AGG_COUNT, RV_AGG_SUM, RV_AGG_MIN, RV_AGG_MAX = range(5)
+AGG_OPS = {"count_rows": RV_AGG_COUNT_ROWS, "count": RV_AGG_COUNT, "sum": RV_AGG_SUM, "min": RV_AGG_MIN, "max": RV_AGG_MAX}
+
+
+class RvAggSpec(C.Structure):
+    _fields_ = [("op", C.c_uint32), ("col", C.c_uint32)]
+
+
 class RvSynthSpec(C.Structure):
     _fields_ = [("dtype", C.c_int), ("seed", C.c_uint64), ("first_row", C.c_uint64), ("length", C.c_uint64),
                 ("modulus", C.c_uint64), ("true_percent", C.c_uint32), ("with_validity", C.c_int32),
@@ -189,6 +198,8 @@ PROTOTYPES = {
     "rv_string_dict_info": (C.c_int, [_P, _U64P, _U64P, _U64P]),
     "rv_string_dict_free": (C.c_int, [_P, _P]),
     "rv_hash_join": (C.c_int, [_P, _PP, C.c_uint32, C.c_uint32, _PP, C.c_uint32, C.c_uint32, _PP, _U64P]),
+    "rv_group_ids": (C.c_int, [_P, _P, _PP, _PP, _U64P]),
+    "rv_hash_aggregate": (C.c_int, [_P, _P, _PP, C.c_uint32, C.POINTER(RvAggSpec), C.c_uint32, _PP, _PP, _U64P]),
     "rv_hash_join_chunked": (C.c_int, [_P, _P, _PP, C.c_uint32, C.c_uint32, _PP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
                                        _PP, _U64P, C.c_uint64, C.POINTER(C.c_int64), _U64P, _U64P]),
     "rv_filter_project": (C.c_int, [_P, _PP, C.c_uint32, C.POINTER(RvPredicate), C.POINTER(C.c_uint32), C.c_uint32,
@@ -814,6 +825,26 @@ class Context:
         out, ids = C.c_void_p(), C.c_void_p()
         _check(load().rv_string_dict_build(self.handle, col.handle, C.byref(out), C.byref(ids) if want_ids else None))
         return StringDict(self, out), (DeviceColumn(self, ids) if want_ids else None)
+
+    def group_ids(self, key: DeviceColumn):
+        """rv_group_ids: (gids, first_row, groups) -- every row's group position, the groups' ascending first rows."""
+        gids, first, groups = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        _check(load().rv_group_ids(self.handle, key.handle, C.byref(gids), C.byref(first), C.byref(groups)))
+        return DeviceColumn(self, gids), DeviceColumn(self, first), groups.value
+
+    def hash_aggregate(self, key: DeviceColumn, value_cols: Sequence[DeviceColumn], specs, want_first_row: bool = True):
+        """rv_hash_aggregate: group_by(key).agg(specs), specs a list of (op, value column index) with op a name of AGG_OPS or an
+        rv_agg_op number (the index of "count_rows" is ignored).  Returns ([key cells, aggregate 0, ...], first_row or None, groups)."""
+        arr = (RvAggSpec * max(1, len(specs)))()
+        for j, (op, col) in enumerate(specs):
+            arr[j].op = AGG_OPS[op] if isinstance(op, str) else op
+            arr[j].col = 0 if col is None else col
+        out = (C.c_void_p * (len(specs) + 1))()
+        first, groups = C.c_void_p(), C.c_uint64()
+        _check(load().rv_hash_aggregate(self.handle, key.handle, _handles(value_cols), len(value_cols), arr, len(specs), out,
+                                        C.byref(first) if want_first_row else None, C.byref(groups)))
+        return ([DeviceColumn(self, C.c_void_p(out[i])) for i in range(len(specs) + 1)], DeviceColumn(self, first) if want_first_row else None,
+                groups.value)
 
     def hash_join(self, build_cols: Sequence[DeviceColumn], build_key: int, probe_cols: Sequence[DeviceColumn], probe_key: int):
         """Inner hash join (plan.rs:174-284): (every probe column, then the build columns but the key), rows."""

@@ -404,6 +404,14 @@ rv_status rv_ctx_set_option(rv_ctx *ctx, const char *key, int64_t value) {
             require(value >= 0 && value < 64, RV_ERR_INVALID_ARG, "string_hash_bits must be in [0, 64)");
             ctx->opt_string_hash_bits = value;
         }
+        else if (k == "agg_hash_bits") {
+            require(value >= 0 && value < 64, RV_ERR_INVALID_ARG, "agg_hash_bits must be in [0, 64)");
+            ctx->opt_agg_hash_bits = value;
+        }
+        else if (k == "agg_max_groups") {
+            require(value >= 0 && value < (int64_t(1) << 32), RV_ERR_INVALID_ARG, "agg_max_groups must be in [0, 2^32)");
+            ctx->opt_agg_max_groups = value;
+        }
         else if (k == "out_sizing") {
             require(value >= -1 && value <= 1000000, RV_ERR_INVALID_ARG, "out_sizing: -1, 0, 1 or a bound in rows per million");
             ctx->opt_out_sizing = value;
@@ -452,6 +460,8 @@ rv_status rv_ctx_get_option(rv_ctx *ctx, const char *key, int64_t *value) {
         else if (k == "inject_failure") *value = ctx->opt_inject_failure;
         else if (k == "join_hash_bits") *value = ctx->opt_join_hash_bits;
         else if (k == "string_hash_bits") *value = ctx->opt_string_hash_bits;
+        else if (k == "agg_hash_bits") *value = ctx->opt_agg_hash_bits;
+        else if (k == "agg_max_groups") *value = ctx->opt_agg_max_groups;
         else if (k == "out_sizing") *value = ctx->opt_out_sizing;
         else if (k == "overflow_reruns") *value = static_cast<int64_t>(ctx->overflow_reruns);  // read-only counter
         else if (k == "batch_counts_in_pass") *value = static_cast<int64_t>(ctx->batch_counts_in_pass);  // read-only counter

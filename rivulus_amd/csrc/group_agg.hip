@@ -1,0 +1,379 @@
+// Grouped aggregation on the device: group_by(key).agg(count / sum / min / max) -- rv_group_ids and rv_hash_aggregate.
+// One unit of the backend library behind include/rivulus_gpu.h (gfx950 only; compiled with hipcc).  Shared helpers are declared in
+// launch.hpp (namespace rvl); the kernels and the layout of the group table are in group_agg_kernel.hpp.
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include "group_agg_kernel.hpp"
+#include "launch.hpp"
+
+using namespace rvh;
+using namespace rvl;
+
+namespace rvl {
+namespace {
+
+// the dense group ids of a key column: what both entry points start from
+struct GroupIds {
+    uint64_t groups = 0;
+    DevBufRef gids;       // [n] uint32, or int64 when asked for the ABI's column
+    DevBufRef first_row;  // [groups] uint64, ascending
+};
+
+void check_group_key(const rv_dcolumn *key, const char *what) {
+    require(key->dtype == RV_INT64 || key->dtype == RV_NULL, RV_ERR_UNSUPPORTED,
+            fmt("%s: only Int64 (and Null) key columns are supported on the device; String keys go through rv_string_dict_build ids", what));
+    require(key->length < (uint64_t{1} << 32), RV_ERR_UNSUPPORTED, fmt("%s: keys of 2^32 rows or more are not supported (32-bit row ids, as the join)", what));
+}
+
+dim3 row_grid(uint64_t n) { return dim3(static_cast<uint32_t>((n + rvk::kGroupAggThreads - 1) / rvk::kGroupAggThreads)); }
+
+// insert, rank, ids.  One read-back here: the group count after the insert (everything behind it is sized by it).  The id pass is
+// left QUEUED with a freshly prepared control block whose `err` is its flag: the caller reads it with its own last read-back.
+GroupIds group_ids_of(rv_ctx *ctx, const rv_dcolumn *key, const char *what, bool wide) {
+    GroupIds r;
+    const uint64_t n = key->length;
+    r.gids = pool_alloc(ctx, std::max<size_t>(n * (wide ? 8 : 4), 16));
+    if (n == 0) {
+        r.first_row = pool_alloc(ctx, 16);
+        (void)prepare_ctrl(ctx, 0);
+        return r;
+    }
+    const uint64_t max_groups = ctx->opt_agg_max_groups > 0 ? static_cast<uint64_t>(ctx->opt_agg_max_groups) : rvt::kGroupAggGroupsMostDefault;
+    uint64_t nslots = 16;
+    if (key->dtype != RV_NULL)
+        while (nslots < 2 * std::min(n, max_groups)) nslots *= 2;
+    DevBufRef slots = pool_alloc(ctx, nslots * 8), null_first = pool_alloc(ctx, 16);
+    RV_HIP(hipMemsetAsync(slots->ptr, 0, nslots * 8, ctx->stream));
+    RV_HIP(hipMemsetAsync(null_first->ptr, 0xFF, 16, ctx->stream));
+    rvk::GroupTableView t{};
+    t.slots = static_cast<unsigned long long *>(slots->ptr);
+    t.null_first = static_cast<unsigned long long *>(null_first->ptr);
+    t.slot_mask = nslots - 1;
+    t.hash_mask = ctx->opt_agg_hash_bits > 0 && ctx->opt_agg_hash_bits < 64 ? (uint64_t{1} << ctx->opt_agg_hash_bits) - 1 : ~0ull;
+    t.key = dev_view(key);
+    t.n = n;
+
+    // 1. insert: every distinct key's slot ends up holding the key's first row
+    Ctrl *ctrl = prepare_ctrl(ctx, 0);
+    rvk::GroupInsertParams q{};
+    q.t = t;
+    q.distinct = striped(ctx, &ctrl->pops[0]);
+    q.claimed = n > max_groups ? &ctrl->pops[1] : nullptr;
+    q.max_groups = max_groups;
+    q.error = &ctrl->err;
+    hipLaunchKernelGGL(rvk::group_insert, row_grid(n), dim3(rvk::kGroupAggThreads), 0, ctx->stream, q);
+    RV_HIP(hipGetLastError());
+    RV_HIP(hipMemcpyAsync(&ctrl->pops[2], null_first->ptr, 8, hipMemcpyDeviceToDevice, ctx->stream));
+    const Ctrl *h = fetch_ctrl(ctx);
+    const uint64_t found = h->pops[0] + (h->pops[2] != ~0ull ? 1 : 0);
+    require(!(h->err & 2u) && found <= max_groups, RV_ERR_UNSUPPORTED,
+            fmt("%s: at least %llu distinct keys, more than option agg_max_groups = %llu allows", what, static_cast<unsigned long long>(found),
+                static_cast<unsigned long long>(max_groups)));
+    require(h->err == 0, RV_ERR_INTERNAL, fmt("%s: a chain walk exhausted the group table", what));
+    r.groups = found;
+
+    // 2. rank: bit `first row` per group, the selection scan, the ascending first rows
+    const uint64_t nwords = (n + 63) / 64;
+    DevBufRef marks = pool_alloc(ctx, nwords * 8 + 16);
+    RV_HIP(hipMemsetAsync(marks->ptr, 0, nwords * 8 + 16, ctx->stream));
+    hipLaunchKernelGGL(rvk::group_mark_first, dim3(grid_for_words(ctx, nslots + 1, rvk::kGroupAggThreads)), dim3(rvk::kGroupAggThreads), 0, ctx->stream, t, nslots,
+                       static_cast<unsigned long long *>(marks->ptr));
+    RV_HIP(hipGetLastError());
+    rv_dcolumn sel;
+    sel.dtype = RV_BOOLEAN;
+    sel.values = marks;
+    sel.length = n;
+    sel.null_count = 0;
+    DevBufRef excl = selection_prefix(ctx, &sel, r.groups);
+    r.first_row = selection_to_indices(ctx, &sel, r.groups, excl);
+
+    // 3. ids: every row's group position
+    ctrl = prepare_ctrl(ctx, 0);
+    if (wide)
+        hipLaunchKernelGGL(rvk::group_ids<int64_t>, row_grid(n), dim3(rvk::kGroupAggThreads), 0, ctx->stream, t, static_cast<const uint64_t *>(marks->ptr),
+                           static_cast<const uint64_t *>(excl->ptr), static_cast<int64_t *>(r.gids->ptr), &ctrl->err);
+    else
+        hipLaunchKernelGGL(rvk::group_ids<uint32_t>, row_grid(n), dim3(rvk::kGroupAggThreads), 0, ctx->stream, t, static_cast<const uint64_t *>(marks->ptr),
+                           static_cast<const uint64_t *>(excl->ptr), static_cast<uint32_t *>(r.gids->ptr), &ctrl->err);
+    RV_HIP(hipGetLastError());
+    ctx->last_kernel = "group_ids";
+    return r;  // (the table, the marks and the scan go back to the pool; their next user runs behind these kernels on the stream)
+}
+
+rv_dcolumn *int64_column(const DevBufRef &buf, uint64_t rows) {
+    auto o = std::make_unique<rv_dcolumn>();
+    o->dtype = RV_INT64;
+    o->length = rows;
+    o->null_count = 0;
+    o->values = buf;
+    return o.release();
+}
+
+// one accumulator of the integer pass
+struct Acc {
+    uint32_t kind;
+    const rv_dcolumn *col;  // nullptr: AK_COUNT_ROWS
+    DevBufRef buf;
+};
+
+DevBufRef new_acc(rv_ctx *ctx, uint64_t groups, bool ones) {
+    const size_t bytes = std::max<size_t>(groups * 8, 16);
+    DevBufRef b = pool_alloc(ctx, bytes);
+    RV_HIP(hipMemsetAsync(b->ptr, ones ? 0xFF : 0, bytes, ctx->stream));
+    return b;
+}
+
+// the accumulators, at most kAggOpsMost per launch -- in the LDS form as many as fit the LDS of one accumulator at the most groups
+// (kGroupAggLdsGroupsMost x 8 bytes: 4 up to a quarter of that many groups, 1 from half on); returns the launches and names the form
+uint64_t launch_accumulate(rv_ctx *ctx, const std::vector<Acc> &accs, const GroupIds &ids, uint64_t n, std::string &name) {
+    const bool lds = ids.groups <= rvt::kGroupAggLdsGroupsMost;
+    const size_t per_launch = lds ? std::min<size_t>(rvk::kAggOpsMost, rvt::kGroupAggLdsGroupsMost / ids.groups) : rvk::kAggOpsMost;
+    const uint64_t ntiles = (n + rvk::kGroupAggTileRows - 1) / rvk::kGroupAggTileRows;
+    // as many workgroups as are resident at once (8 per CU, fewer when their LDS fills the CU's 160 KiB first): each strides over the
+    // tiles and, in the LDS form, flushes its accumulators once
+    const size_t lds_bytes = lds ? std::min(per_launch, accs.size()) * ids.groups * 8 : 0;
+    const uint64_t per_cu = lds_bytes ? std::clamp<uint64_t>((uint64_t{160} << 10) / lds_bytes, 1, 8) : 8;
+    const dim3 grid(static_cast<uint32_t>(std::min<uint64_t>(ntiles, static_cast<uint64_t>(ctx->props.multiProcessorCount) * per_cu)));
+    uint64_t launches = 0;
+    for (size_t at = 0; at < accs.size(); at += per_launch, ++launches) {
+        rvk::GroupAccParams p{};
+        p.gids = static_cast<const uint32_t *>(ids.gids->ptr);
+        p.n = n;
+        p.groups = static_cast<uint32_t>(ids.groups);
+        std::vector<const rv_dcolumn *> cols;
+        for (size_t k = at; k < std::min(accs.size(), at + per_launch); ++k) {
+            rvk::AggAcc &a = p.acc[p.nacc++];
+            a.acc = static_cast<unsigned long long *>(accs[k].buf->ptr);
+            a.kind = accs[k].kind;
+            if (!accs[k].col) continue;
+            size_t c = 0;
+            while (c < cols.size() && cols[c] != accs[k].col) ++c;
+            if (c == cols.size()) {
+                cols.push_back(accs[k].col);
+                p.cols[c] = dev_view(accs[k].col);
+            }
+            a.col = static_cast<uint32_t>(c);
+        }
+        if (lds) {
+            const size_t bytes = static_cast<size_t>(p.nacc) * p.groups * 8;  // past 64 KiB a kernel's dynamic LDS has to be enabled, once
+            const void *fn = reinterpret_cast<const void *>(&rvk::group_accumulate<true>);
+            size_t &enabled = ctx->lds_enabled[fn];
+            if (bytes > (size_t{64} << 10) && bytes > enabled) {
+                RV_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(rvt::kGroupAggLdsGroupsMost * 8)));
+                enabled = rvt::kGroupAggLdsGroupsMost * 8;
+            }
+            hipLaunchKernelGGL(rvk::group_accumulate<true>, grid, dim3(rvk::kGroupAggThreads), bytes, ctx->stream, p);
+        }
+        else hipLaunchKernelGGL(rvk::group_accumulate<false>, grid, dim3(rvk::kGroupAggThreads), 0, ctx->stream, p);
+        RV_HIP(hipGetLastError());
+    }
+    if (launches) name = lds ? "group_accumulate<lds>" : "group_accumulate<global>";
+    return launches;
+}
+
+// rows grouped by id, each group ascending: a stable radix sort of (gid, row) over the bits the ids take
+struct GroupLists {
+    DevBufRef rows, starts;
+};
+GroupLists group_lists(rv_ctx *ctx, const GroupIds &ids, uint64_t n) {
+    GroupLists L;
+    L.rows = pool_alloc(ctx, n * 4 + 16);
+    L.starts = pool_alloc(ctx, (ids.groups + 1) * 8 + 16);
+    DevBufRef rows_in = pool_alloc(ctx, n * 4 + 16), gids_out = pool_alloc(ctx, n * 4 + 16);
+    const int grid = grid_for_words(ctx, n, rvk::kGroupAggThreads);
+    hipLaunchKernelGGL(rvk::group_iota_rows, dim3(grid), dim3(rvk::kGroupAggThreads), 0, ctx->stream, n, static_cast<uint32_t *>(rows_in->ptr));
+    RV_HIP(hipGetLastError());
+    unsigned end_bit = 1;
+    while (end_bit < 32 && (uint64_t{1} << end_bit) < ids.groups) ++end_bit;
+    const uint32_t *gids = static_cast<const uint32_t *>(ids.gids->ptr);
+    size_t temp_bytes = 0;
+    RV_HIP(rocprim::radix_sort_pairs(nullptr, temp_bytes, gids, static_cast<uint32_t *>(gids_out->ptr), static_cast<const uint32_t *>(rows_in->ptr),
+                                     static_cast<uint32_t *>(L.rows->ptr), static_cast<size_t>(n), 0u, end_bit, ctx->stream));
+    DevBufRef temp = pool_alloc(ctx, std::max<size_t>(temp_bytes, 16));
+    RV_HIP(rocprim::radix_sort_pairs(temp->ptr, temp_bytes, gids, static_cast<uint32_t *>(gids_out->ptr), static_cast<const uint32_t *>(rows_in->ptr),
+                                     static_cast<uint32_t *>(L.rows->ptr), static_cast<size_t>(n), 0u, end_bit, ctx->stream));
+    hipLaunchKernelGGL(rvk::group_list_starts, dim3(grid), dim3(rvk::kGroupAggThreads), 0, ctx->stream, static_cast<const uint32_t *>(gids_out->ptr), n,
+                       static_cast<uint32_t>(ids.groups), static_cast<uint64_t *>(L.starts->ptr));
+    RV_HIP(hipGetLastError());
+    return L;
+}
+
+void check_specs(const rv_dcolumn *key, const rv_dcolumn *const *value_cols, uint32_t n_values, const rv_agg_spec *specs, uint32_t n_specs) {
+    require(n_specs >= 1, RV_ERR_INVALID_ARG, "rv_hash_aggregate: no aggregates");
+    for (uint32_t c = 0; c < n_values; ++c) require(value_cols[c] != nullptr, RV_ERR_INVALID_ARG, fmt("rv_hash_aggregate: value column %u is NULL", c));
+    for (uint32_t j = 0; j < n_specs; ++j) {
+        require(specs[j].op <= static_cast<uint32_t>(RV_AGG_MAX), RV_ERR_INVALID_ARG, fmt("rv_hash_aggregate: aggregate %u has the unknown op %u", j, specs[j].op));
+        require(specs[j].op == RV_AGG_COUNT_ROWS || specs[j].col < n_values, RV_ERR_INVALID_ARG,
+                fmt("rv_hash_aggregate: aggregate %u reads value column %u of %u", j, specs[j].col, n_values));
+    }
+    for (uint32_t c = 0; c < n_values; ++c)
+        require(value_cols[c]->length == key->length, RV_ERR_LENGTH_MISMATCH,
+                fmt("rv_hash_aggregate: value column %u has %llu rows, the key %llu", c, static_cast<unsigned long long>(value_cols[c]->length),
+                    static_cast<unsigned long long>(key->length)));
+    for (uint32_t j = 0; j < n_specs; ++j) {
+        if (specs[j].op == RV_AGG_COUNT_ROWS) continue;
+        const rv_dtype d = value_cols[specs[j].col]->dtype;
+        if (specs[j].op == RV_AGG_COUNT)
+            require(is_value_type(d) || d == RV_BOOLEAN || d == RV_STRING || d == RV_NULL, RV_ERR_UNSUPPORTED, fmt("rv_hash_aggregate: aggregate %u: unsupported dtype", j));
+        else
+            require(is_value_type(d), RV_ERR_TYPE_MISMATCH, fmt("rv_hash_aggregate: aggregate %u: SUM / MIN / MAX take an Int64 or Float64 column", j));
+    }
+    check_group_key(key, "rv_hash_aggregate");
+}
+
+// events around the accumulate stage (option profile_kernels)
+struct StageTimer {
+    rv_ctx *ctx;
+    bool started = false;
+    explicit StageTimer(rv_ctx *c) : ctx(c) {}
+    void start() {
+        if (ctx->opt_profile && !started) RV_HIP(hipEventRecord(ctx->evk0, ctx->stream));
+        started = true;
+    }
+    void stop() {
+        if (ctx->opt_profile && started) RV_HIP(hipEventRecord(ctx->evk1, ctx->stream));
+    }
+    void add(uint64_t launches) {  // after a wait
+        if (!ctx->opt_profile || !started) return;
+        float ms = 0.f;
+        RV_HIP(hipEventElapsedTime(&ms, ctx->evk0, ctx->evk1));
+        ctx->kernel_ms += ms;
+        ctx->kernel_launches += launches;
+    }
+};
+
+void hash_aggregate(rv_ctx *ctx, const rv_dcolumn *key, const rv_dcolumn *const *value_cols, const rv_agg_spec *specs, uint32_t n_specs, rv_dcolumn **out,
+                    rv_dcolumn **out_first_row, uint64_t *out_groups) {
+    const uint64_t n = key->length;
+    GroupIds ids = group_ids_of(ctx, key, "rv_hash_aggregate", false);
+    const uint64_t G = ids.groups;
+    std::vector<std::unique_ptr<rv_dcolumn>> outs(n_specs);
+    std::vector<Acc> accs;
+    struct MinMax {
+        uint32_t j;
+        DevBufRef counts;
+    };
+    std::vector<MinMax> minmax;
+    std::vector<uint32_t> fsums;
+    for (uint32_t j = 0; j < n_specs; ++j) {
+        const uint32_t op = specs[j].op;
+        const rv_dcolumn *col = op == RV_AGG_COUNT_ROWS ? nullptr : value_cols[specs[j].col];
+        auto o = std::make_unique<rv_dcolumn>();
+        o->dtype = op <= static_cast<uint32_t>(RV_AGG_COUNT) ? RV_INT64 : col->dtype;
+        o->length = G;
+        o->null_count = 0;
+        o->values = new_acc(ctx, G, op == RV_AGG_MIN);
+        if (op == RV_AGG_SUM && col->dtype == RV_FLOAT64) fsums.push_back(j);
+        else {
+            accs.push_back(Acc{op, col, o->values});  // rv_agg_op and the AK_ kinds share their values
+            if (op == RV_AGG_MIN || op == RV_AGG_MAX) {
+                minmax.push_back(MinMax{j, new_acc(ctx, G, false)});
+                accs.push_back(Acc{rvk::AK_COUNT, col, minmax.back().counts});
+            }
+        }
+        outs[j] = std::move(o);
+    }
+    static_assert(int(RV_AGG_COUNT_ROWS) == int(rvk::AK_COUNT_ROWS) && int(RV_AGG_COUNT) == int(rvk::AK_COUNT) && int(RV_AGG_SUM) == int(rvk::AK_SUM_I64) &&
+                      int(RV_AGG_MIN) == int(rvk::AK_MIN) && int(RV_AGG_MAX) == int(rvk::AK_MAX), "rv_agg_op and the accumulator kinds");
+    if (G) {
+        // group_ids_of left its id pass queued with a fresh control block: ctrl->err is that pass's flag
+        Ctrl *ctrl = static_cast<Ctrl *>(ctx->d_ctrl);
+        StageTimer timer(ctx);
+        std::string name;
+        uint64_t launches = 0;
+        if (!accs.empty()) {
+            timer.start();
+            launches += launch_accumulate(ctx, accs, ids, n, name);
+        }
+        if (!fsums.empty()) {
+            timer.start();
+            GroupLists L = group_lists(ctx, ids, n);
+            for (uint32_t j : fsums) {
+                hipLaunchKernelGGL(rvk::group_f64_sum, dim3(static_cast<uint32_t>((G + 3) / 4)), dim3(rvk::kGroupAggThreads), 0, ctx->stream,
+                                   dev_view(value_cols[specs[j].col]), static_cast<const uint32_t *>(L.rows->ptr), static_cast<const uint64_t *>(L.starts->ptr),
+                                   static_cast<uint32_t>(G), rvt::kGroupAggWaveListMost, static_cast<double *>(outs[j]->values->ptr));
+                RV_HIP(hipGetLastError());
+                ++launches;
+            }
+            name += name.empty() ? "group_f64_sum" : "+group_f64_sum";
+        }
+        timer.stop();
+        ctx->last_kernel = name;
+        // MIN / MAX: the winning bits in place, the validity, the nulls -- eight striped counters per read-back
+        size_t done = 0;
+        do {
+            const size_t upto = std::min(minmax.size(), done + 8);
+            for (size_t k = done; k < upto; ++k) {
+                rv_dcolumn *o = outs[minmax[k].j].get();
+                o->validity = pool_alloc(ctx, zeroed_bitmap_bytes(G));
+                RV_HIP(hipMemsetAsync(o->validity->ptr, 0, zeroed_bitmap_bytes(G), ctx->stream));
+                hipLaunchKernelGGL(rvk::group_minmax_finish, row_grid(G), dim3(rvk::kGroupAggThreads), 0, ctx->stream, static_cast<unsigned long long *>(o->values->ptr),
+                                   static_cast<const unsigned long long *>(minmax[k].counts->ptr), G, o->dtype == RV_FLOAT64 ? 1 : 0,
+                                   static_cast<uint64_t *>(o->validity->ptr), striped(ctx, &ctrl->valid_pop[k - done]));
+                RV_HIP(hipGetLastError());
+            }
+            const Ctrl *h = fetch_ctrl(ctx);
+            require(h->err == 0, RV_ERR_INTERNAL, "rv_hash_aggregate: a row's key was not found in the group table");
+            for (size_t k = done; k < upto; ++k) {
+                rv_dcolumn *o = outs[minmax[k].j].get();
+                o->null_count = static_cast<int64_t>(h->valid_pop[k - done]);
+                if (o->null_count == 0) o->validity.reset();  // attached iff some cell is null
+            }
+            done = upto;
+            if (done < minmax.size()) ctrl = prepare_ctrl(ctx, 0);
+        } while (done < minmax.size());
+        timer.add(launches);
+    }
+    // out[0]: the key cells at the first rows (a gather with read-backs of its own: after this call's control block has been read)
+    rv_dcolumn *key_cells = nullptr;
+    take_on_device(ctx, &key, 1, static_cast<const uint64_t *>(ids.first_row->ptr), G, &key_cells, false);
+    RV_HIP(hipStreamSynchronize(ctx->stream));  // the ids, the lists and the count accumulators go back to the pool
+    out[0] = key_cells;
+    for (uint32_t j = 0; j < n_specs; ++j) out[1 + j] = outs[j].release();
+    if (out_first_row) *out_first_row = int64_column(ids.first_row, G);
+    if (out_groups) *out_groups = G;
+}
+
+}  // namespace
+}  // namespace rvl
+
+extern "C" {
+
+rv_status rv_group_ids(rv_ctx *ctx, const rv_dcolumn *key, rv_dcolumn **out_gids, rv_dcolumn **out_first_row, uint64_t *out_groups) {
+    return guarded([&] {
+        require(ctx && key && out_gids && out_first_row, RV_ERR_INVALID_ARG, "rv_group_ids: NULL argument");
+        *out_gids = *out_first_row = nullptr;
+        check_group_key(key, "rv_group_ids");
+        set_device(ctx);
+        try {
+            GroupIds ids = group_ids_of(ctx, key, "rv_group_ids", true);
+            require(fetch_ctrl(ctx)->err == 0, RV_ERR_INTERNAL, "rv_group_ids: a row's key was not found in the group table");
+            std::unique_ptr<rv_dcolumn> a(int64_column(ids.gids, key->length)), b(int64_column(ids.first_row, ids.groups));
+            *out_gids = a.release();
+            *out_first_row = b.release();
+            if (out_groups) *out_groups = ids.groups;
+        } catch (...) {
+            (void)hipStreamSynchronize(ctx->stream);  // whatever was queued has run before its buffers go back to the pool
+            throw;
+        }
+    });
+}
+
+rv_status rv_hash_aggregate(rv_ctx *ctx, const rv_dcolumn *key, const rv_dcolumn *const *value_cols, uint32_t n_values, const rv_agg_spec *specs,
+                            uint32_t n_specs, rv_dcolumn **out, rv_dcolumn **out_first_row, uint64_t *out_groups) {
+    return guarded([&] {
+        require(ctx && key && specs && out && (value_cols || n_values == 0), RV_ERR_INVALID_ARG, "rv_hash_aggregate: NULL argument");
+        check_specs(key, value_cols, n_values, specs, n_specs);
+        for (uint32_t j = 0; j <= n_specs; ++j) out[j] = nullptr;
+        if (out_first_row) *out_first_row = nullptr;
+        set_device(ctx);
+        try {
+            hash_aggregate(ctx, key, value_cols, specs, n_specs, out, out_first_row, out_groups);
+        } catch (...) {
+            (void)hipStreamSynchronize(ctx->stream);
+            throw;
+        }
+    });
+}
+
+}  // extern "C"

@@ -98,4 +98,22 @@ constexpr uint64_t kStrDictSlotsPerRow = 2;
 // Workgroups of 256 lanes one arith_kernel launch takes at most: eight per CU of a 256-CU part, what the other one-lane-per-row kernels
 // take (grid_for_words); longer columns are grid-strided.  Not a crossover and not swept.              tools/arith_bench.py
 constexpr uint64_t kArithGridMost = 2048;
+
+// ---- grouped aggregation (group_agg.hip) -------------------------------------------------------------------------------------------------
+// Up to this many groups every workgroup of the accumulate kernel keeps its own accumulators in LDS (group_accumulate<lds>: LDS integer
+// atomics per run of equal ids, one global integer atomic per group, accumulator and workgroup at the end); more groups take global
+// integer atomics per run (group_accumulate<global>).  The value is what 128 KiB of a CU's 160 KiB of LDS hold of ONE accumulator (8 bytes per group): a
+// launch takes as many accumulators as fit that budget (4 up to a quarter of this many groups, 1 from half on), so more aggregates
+// cost more passes over the ids, never the global form.  Not a crossover but
+// the LDS's capacity: the sweep of G at 2^28 rows, SUM + COUNT_ROWS, shows the LDS form ahead wherever it fits -- accumulate stage 0.98 /
+// 2.9 / 4.1 / 7.7 ms at G = 1024 / 4096 / 8193 / 16384 against 22.5 ms for the global form at G = 16385 and 22.6 at 65536 (the global
+// form runs at the rate of scattered 8-byte atomics whatever G is).          profiles/group_agg_bench.txt, tools/group_agg_bench.py --sweep
+constexpr uint64_t kGroupAggLdsGroupsMost = 16384;
+// Float64 SUM (group_f64_sum): a group's list of up to this many rows is summed by one wave (16 strided additions per lane, then the
+// butterfly), a longer one by the four waves of the workgroup.  Part of what fixes the order of the additions: changing it changes the
+// bits of inexact sums.  Set by reasoning, not by a sweep (the path's speed is not tuned).
+constexpr uint32_t kGroupAggWaveListMost = 1024;
+// rv_hash_aggregate / rv_group_ids refuse more distinct keys than this unless option "agg_max_groups" says otherwise: 2^27 slots of
+// 8 bytes bound the group table at 1 GiB.  A limit, not a crossover.
+constexpr uint64_t kGroupAggGroupsMostDefault = uint64_t{1} << 26;
 }  // namespace rvt

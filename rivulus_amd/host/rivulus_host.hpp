@@ -1732,6 +1732,145 @@ class GpuHashJoinStream : public DataStream {
     LimitWindow limit_;
 };
 
+// ---------------------------------------------------------------------------------------
+// group_by(key).agg([...]) -- the reference has no aggregate operator: include/rivulus_gpu.h, rv_hash_aggregate
+// ---------------------------------------------------------------------------------------
+enum class AggOp { CountRows, Count, Sum, Min, Max };  // rv_agg_op, in its order
+inline const char *to_string(AggOp op) {
+    static const char *n[] = {"COUNT(*)", "COUNT", "SUM", "MIN", "MAX"};
+    return n[static_cast<int>(op)];
+}
+// One aggregate: `op` over `column` (ignored by CountRows), under the output name `name`.
+struct AggSpec {
+    AggOp op;
+    std::string column;
+    std::string name;
+};
+struct GroupByPlanError : std::runtime_error {  // what planning a group_by refuses, with the column it refuses it for
+    using std::runtime_error::runtime_error;
+};
+
+// The output schema of group_by(key).agg(aggs) over `in`: the key under its own name, then every aggregate under its name -- counts
+// Int64, SUM / MIN / MAX of the column's dtype.  Throws GroupByPlanError for an unknown column, a duplicate output name, SUM / MIN /
+// MAX over a column that is not Int64 or Float64, and a key the device does not group by (Float64, Boolean: not built).
+inline SchemaRef group_by_schema(const Schema &in, const std::string &key, const std::vector<AggSpec> &aggs) {
+    const Field *kf = in.field_by_name(key);
+    if (!kf) throw GroupByPlanError("group_by: unknown key column '" + key + "'");
+    if (kf->data_type() == DataType::Float64 || kf->data_type() == DataType::Boolean)
+        throw GroupByPlanError("group_by: key column '" + key + "' is " + to_string(kf->data_type()) + "; only Int64 and String keys are grouped");
+    if (aggs.empty()) throw GroupByPlanError("group_by: no aggregates");
+    std::vector<Field> out{Field{key, kf->data_type(), true}};
+    for (auto &a : aggs) {
+        DataType t = DataType::Int64;
+        if (a.op != AggOp::CountRows) {
+            const Field *f = in.field_by_name(a.column);
+            if (!f) throw GroupByPlanError("group_by: aggregate '" + a.name + "' reads the unknown column '" + a.column + "'");
+            if (a.op != AggOp::Count) {
+                t = f->data_type();
+                if (t != DataType::Int64 && t != DataType::Float64)
+                    throw GroupByPlanError(std::string("group_by: ") + to_string(a.op) + " over column '" + a.column + "' of dtype " + to_string(t));
+            }
+        }
+        for (auto &f : out)
+            if (f.name() == a.name) throw GroupByPlanError("group_by: duplicate output name '" + a.name + "'");
+        out.push_back(Field{a.name, t, a.op == AggOp::Min || a.op == AggOp::Max});
+    }
+    return std::make_shared<const Schema>(out);
+}
+
+// One rv_hash_aggregate over the named columns of one frame (`columns` in the order of `schema`); the output columns in the order of
+// group_by_schema.  A String key goes through the string dictionary: the ids of the key (null strings are null ids: the null group;
+// "" is a value) are grouped, and the key cells are gathered from the String column itself at the groups' first rows.
+inline std::vector<ArrayRef> group_by_columns(const ContextRef &ctx, const Schema &schema, const std::vector<ArrayRef> &columns, const std::string &key,
+                                              const std::vector<AggSpec> &aggs) {
+    (void)group_by_schema(schema, key, aggs);
+    auto handle_of = [&](const std::string &n) {
+        const ArrayRef &c = columns[*schema.index_of(n)];
+        if (!c->on_device()) throw Error(RV_ERR_UNSUPPORTED, "columns off the device are outside the device path");
+        return c->handle();
+    };
+    std::vector<const rv_dcolumn *> values;
+    std::vector<rv_agg_spec> specs;
+    for (auto &a : aggs) {
+        rv_agg_spec s{static_cast<uint32_t>(a.op), 0};
+        if (a.op != AggOp::CountRows) {
+            const rv_dcolumn *h = handle_of(a.column);
+            const auto at = std::find(values.begin(), values.end(), h);
+            s.col = static_cast<uint32_t>(at - values.begin());
+            if (at == values.end()) values.push_back(h);
+        }
+        specs.push_back(s);
+    }
+    const rv_dcolumn *key_col = handle_of(key);
+    const bool string_key = schema.field_by_name(key)->data_type() == DataType::String;
+    ArrayRef ids;
+    if (string_key) {
+        rv_string_dict *dict = nullptr;
+        rv_dcolumn *h = nullptr;
+        check(rv_string_dict_build(ctx->raw(), key_col, &dict, &h));
+        ids = Array::adopt(ctx, h);
+        check(rv_string_dict_free(ctx->raw(), dict));  // only the ids are needed: equal strings share an id
+    }
+    std::vector<rv_dcolumn *> out(specs.size() + 1, nullptr);
+    rv_dcolumn *first_row = nullptr;
+    uint64_t groups = 0;
+    check(rv_hash_aggregate(ctx->raw(), string_key ? ids->handle() : key_col, values.data(), static_cast<uint32_t>(values.size()), specs.data(),
+                            static_cast<uint32_t>(specs.size()), out.data(), &first_row, &groups));
+    std::vector<ArrayRef> res;
+    for (auto *h : out) res.push_back(Array::adopt(ctx, h));
+    const ArrayRef first = Array::adopt(ctx, first_row);
+    if (string_key) {  // the strings at the first rows in place of their ids
+        rv_dcolumn *cells = nullptr;
+        check(rv_take_device(ctx->raw(), &key_col, 1, first->handle(), &cells));
+        res[0] = Array::adopt(ctx, cells);
+    }
+    return res;
+}
+
+// group_by as a stream: a PIPELINE BREAKER.  It drains its input -- a resident frame is taken as it is, the batches of any other
+// stream are concatenated (RecordBatch::concat) -- and emits EXACTLY ONE batch: the groups in first-row order.  An input without rows
+// gives one zero-row batch with the output schema.  (Aggregating batch by batch without the concatenation -- a begin / update /
+// finish handle -- is not built.)
+class GpuGroupByStream : public DataStream {
+  public:
+    // `fallback_ctx`: where the zero-row batch of an input that yields no batch at all is created
+    GpuGroupByStream(JoinSide input, std::string key, std::vector<AggSpec> aggs, ContextRef fallback_ctx)
+        : input_(std::move(input)), key_(std::move(key)), aggs_(std::move(aggs)), ctx_(std::move(fallback_ctx)) {
+        input_schema_ = input_.schema();
+        schema_ = group_by_schema(*input_schema_, key_, aggs_);
+    }
+    SchemaRef schema() const override { return schema_; }
+    std::optional<RecordBatch> next_batch() override {
+        if (done_) return std::nullopt;
+        done_ = true;
+        std::vector<ArrayRef> columns = input_.columns;
+        if (input_.stream) {
+            std::vector<RecordBatch> all;
+            while (auto b = input_.stream->next_batch()) all.push_back(std::move(*b));
+            if (all.empty()) {
+                if (!ctx_) throw StreamError::execution("group_by: the input yielded no batch and the plan holds no device context");
+                return RecordBatch::empty(ctx_, schema_);
+            }
+            RecordBatch whole = all.size() == 1 ? all[0] : stream_call([&] { return RecordBatch::concat(all); });
+            columns = whole.columns();
+        }
+        return stream_call([&] {
+            const ContextRef ctx = columns.empty() ? ctx_ : columns[0]->context();
+            std::vector<ArrayRef> out = group_by_columns(ctx, *input_schema_, columns, key_, aggs_);
+            const size_t rows = out[0]->len();
+            return RecordBatch::new_unchecked(schema_, std::move(out), rows);
+        });
+    }
+
+  private:
+    JoinSide input_;
+    std::string key_;
+    std::vector<AggSpec> aggs_;
+    ContextRef ctx_;
+    SchemaRef input_schema_, schema_;
+    bool done_ = false;
+};
+
 }  // namespace execution
 
 // ---------------------------------------------------------------------------------------
@@ -2081,7 +2220,7 @@ class StreamingPhysicalPlan;
 using StreamingPlanPtr = std::shared_ptr<const StreamingPhysicalPlan>;
 class StreamingPhysicalPlan {
   public:
-    enum Kind { MemorySource, DataFrameSource, CsvFileSource, Filter, GpuFilterProject, Select, Limit, HashJoin, Project, ComputedFilterProject } kind = MemorySource;
+    enum Kind { MemorySource, DataFrameSource, CsvFileSource, Filter, GpuFilterProject, Select, Limit, HashJoin, Project, ComputedFilterProject, GroupBy } kind = MemorySource;
     std::vector<Expr> exprs;  // Project: select expressions, arithmetic included
     Expr predicate_expr;      // ComputedFilterProject: a filter with `<arith> <cmp> <literal>` terms
     // DataFrameSource (streaming.rs:85-94)
@@ -2103,6 +2242,8 @@ class StreamingPhysicalPlan {
     size_t n = 0;
     StreamingPlanPtr build_side;  // HashJoin { build_side, probe_side = input, build_key, probe_key }, inner
     std::string build_key, probe_key;
+    std::string group_key;  // GroupBy { input, group_key, aggs }
+    std::vector<execution::AggSpec> aggs;
 
     static StreamingPlanPtr memory_source(std::vector<execution::RecordBatch> b) {
         auto p = std::make_shared<StreamingPhysicalPlan>();
@@ -2192,6 +2333,29 @@ class StreamingPhysicalPlan {
         return p;
     }
 
+    // group_by(key).agg(aggs): a pipeline breaker that emits exactly one batch (GpuGroupByStream); the reference has no such operator
+    static StreamingPlanPtr group_by(StreamingPlanPtr in, std::string key, std::vector<execution::AggSpec> aggs) {
+        auto p = std::make_shared<StreamingPhysicalPlan>();
+        p->kind = GroupBy;
+        p->input = std::move(in);
+        p->group_key = std::move(key);
+        p->aggs = std::move(aggs);
+        return p;
+    }
+    // a device context some source of the plan holds (nullptr: none does)
+    ContextRef any_context() const {
+        if (csv_ctx) return csv_ctx;
+        for (auto &c : df.columns)
+            if (c->on_device()) return c->context();
+        for (auto &b : batches)
+            for (auto &c : b.columns())
+                if (c->on_device()) return c->context();
+        for (const StreamingPlanPtr &p : {input, build_side})
+            if (p)
+                if (ContextRef c = p->any_context()) return c;
+        return nullptr;
+    }
+
     execution::DataStreamRef execute() const {  // streaming.rs:71-133
         using namespace execution;
         try {
@@ -2246,6 +2410,17 @@ class StreamingPhysicalPlan {
                     };
                     return std::make_unique<GpuHashJoinStream>(side(*build_side), side(*input), build_key, probe_key);
                 }
+                case GroupBy: {  // a resident frame is taken whole, after the null fill, as the join takes it
+                    JoinSide s;
+                    if (input->kind == DataFrameSource && !input->df.columns.empty() && input->df_batch_size > 0) {
+                        s.names = input->df.names;
+                        s.columns = input->filled_columns();
+                        s.batch_size = input->df_batch_size;
+                    } else {
+                        s.stream = input->execute();
+                    }
+                    return std::make_unique<GpuGroupByStream>(std::move(s), group_key, aggs, any_context());
+                }
             }
         } catch (const StreamError &e) {
             throw StreamingExecutionError(std::string("Stream error: ") + e.what());
@@ -2298,7 +2473,7 @@ class PhysicalPlan;
 using PhysicalPlanPtr = std::shared_ptr<const PhysicalPlan>;
 class PhysicalPlan {
   public:
-    enum Kind { DataFrameSource, Select, Filter, HashJoin, Project, ComputedFilter } kind = DataFrameSource;
+    enum Kind { DataFrameSource, Select, Filter, HashJoin, Project, ComputedFilter, GroupBy } kind = DataFrameSource;
     DeviceFrame df;
     std::vector<Expr> exprs;  // Project: select expressions, arithmetic included
     Expr predicate_expr;      // ComputedFilter: `<arith> <cmp> <literal>` terms, alone or under AND / OR
@@ -2307,6 +2482,8 @@ class PhysicalPlan {
     CompareTerm term;  // Filter { column, value, op }
     PhysicalPlanPtr build_side;          // HashJoin { build_side, probe_side = input, build_key, probe_key, Inner }
     std::string build_key, probe_key;
+    std::string group_key;  // GroupBy { input, group_key, aggs }
+    std::vector<execution::AggSpec> aggs;
 
     static PhysicalPlanPtr source(DeviceFrame f) {
         auto p = std::make_shared<PhysicalPlan>();
@@ -2356,9 +2533,28 @@ class PhysicalPlan {
         p->probe_key = std::move(probe_key);
         return p;
     }
+    // group_by(key).agg(aggs), eager: one rv_hash_aggregate; the key under its own name, then every aggregate under its name, the
+    // groups in the order of their first rows.  The nulls of the frame stay nulls (no fill: this is not a stream).
+    static PhysicalPlanPtr group_by(PhysicalPlanPtr in, std::string key, std::vector<execution::AggSpec> aggs) {
+        auto p = std::make_shared<PhysicalPlan>();
+        p->kind = GroupBy;
+        p->input = std::move(in);
+        p->group_key = std::move(key);
+        p->aggs = std::move(aggs);
+        return p;
+    }
     DeviceFrame execute() const {
         switch (kind) {
             case DataFrameSource: return df;  // plan.rs:67
+            case GroupBy: {
+                DeviceFrame in = input->execute();
+                const execution::Schema schema = frame_schema(in);
+                const execution::SchemaRef out_schema = execution::group_by_schema(schema, group_key, aggs);  // the planning errors
+                DeviceFrame out;
+                out.columns = execution::group_by_columns((*in.column(group_key))->context(), schema, in.columns, group_key, aggs);
+                for (auto &f : out_schema->fields()) out.names.push_back(f.name());
+                return out;
+            }
             case Select: {                     // plan.rs:68-96
                 DeviceFrame in = input->execute();
                 DeviceFrame out;
