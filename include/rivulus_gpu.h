@@ -255,7 +255,10 @@ rv_status rv_ctx_device_info(rv_ctx *ctx, int *compute_units, uint64_t *hbm_byte
  * rows x Float64 columns, at most 2^20); more such cells and the chunk is parsed again with a list of the exact size (forces
  * that path in tests).
  * "agg_max_groups" = k > 0: rv_hash_aggregate / rv_group_ids refuse more than k groups (0: the default, 2^26) and size the group
- * table by min(rows, k); "agg_hash_bits" = b (tests): the key hash of group tables truncated to b low bits (see rv_hash_aggregate). */
+ * table by min(rows, k); "agg_hash_bits" = b (tests): the key hash of group tables truncated to b low bits (see rv_hash_aggregate).
+ * "sort_engine": 0, the default = rv_sort_indices runs its own radix passes; 1 (measurements and tests, never chosen by the library) = the
+ * pair sort goes through rocprim::radix_sort_pairs over all 64 bits, everything around it unchanged (see rv_sort_indices).  The read-only
+ * "sort_last_passes" is the number of scatter passes the last sort call of the context ran. */
 rv_status rv_ctx_set_option(rv_ctx *ctx, const char *key, int64_t value);
 /* current value of an option, or of the read-only counters "overflow_reruns" (launches re-run because speculatively sized
  * outputs were too small), "last_selectivity_ppm" (survivors per million rows of the last fused launch, -1: none yet),
@@ -687,6 +690,51 @@ rv_status rv_group_ids(rv_ctx *ctx, const rv_dcolumn *key, rv_dcolumn **out_gids
 rv_status rv_hash_aggregate(rv_ctx *ctx, const rv_dcolumn *key, const rv_dcolumn *const *value_cols, uint32_t n_values,
                             const rv_agg_spec *specs, uint32_t n_specs, rv_dcolumn **out, rv_dcolumn **out_first_row,
                             uint64_t *out_groups);
+
+/* ---- sort (K10) ------------------------------------------------------------- */
+/* ORDER BY: rv_sort_indices gives the stable permutation of one key column, rv_sort reorders a frame by one or more keys.  The
+ * reference has no sort; the semantics are defined here (this comment is the normative text, tests/sort_model.py the executable
+ * one) and argued in DESIGN.md section 4 K10.
+ *
+ * Stability.  Rows whose keys compare equal keep their ascending input order under every flag combination, descending included.
+ * The permutation is therefore unique: the same input gives the same indices on every run.
+ *
+ * Keys.  RV_INT64: the numeric order.  RV_FLOAT64: the order of the map the grouped MIN / MAX use (sign bit set: every bit
+ * flipped; otherwise the sign bit set), so -inf < ... < -0.0 < +0.0 < ... < +inf; every NaN, whatever its sign or payload,
+ * compares equal to every other NaN and above +inf, so the NaNs stay in row order among themselves.  RV_NULL: every row is null
+ * -- the identity, or `prior` unchanged.  RV_BOOLEAN and RV_STRING keys are RV_ERR_UNSUPPORTED.
+ *
+ * Nulls.  All null cells compare equal and come first (AnyValue: Null is below every value) unless RV_SORT_NULLS_LAST is set.
+ * RV_SORT_DESCENDING reverses the order of the VALUES only, by complementing the mapped key -- it never reverses positions, so
+ * equal keys stay in row order -- and does not move the nulls: the two flags are independent.  Whatever bits lie under a null
+ * cell are never read as a value.
+ *
+ * Chaining.  `prior` is NULL or an Int64 column without nulls holding a permutation of the key's rows; the result is `prior`
+ * reordered stably by key[prior[i]].  Sorting by the keys (k0, k1, ...) is the chain from the last key to the first; there are
+ * no composite keys.  A `prior` of another length: RV_ERR_LENGTH_MISMATCH; of another dtype: RV_ERR_TYPE_MISMATCH; with nulls:
+ * RV_ERR_INVALID_ARG; an index outside [0, rows): RV_ERR_OUT_OF_BOUNDS with the text rv_take_device gives ("Index 9 out of
+ * bounds for 4 rows", the first such index) -- nothing is read through it.
+ *
+ * Slices of the key (and of its validity) at any offset are fine; indices are relative to the slice.  An empty key gives a
+ * zero-row Int64 column.  Keys of 2^32 rows or more: RV_ERR_UNSUPPORTED (32-bit row ids inside, as rv_group_ids).  Unknown flag
+ * bits: RV_ERR_INVALID_ARG.  Errors leave the context usable and create nothing.
+ *
+ * The passes.  An LSD radix sort over the 8-bit digits of the mapped key; a digit position at which all non-null keys agree is
+ * skipped (values below 2^16: two passes; an all-equal key: none), and a key with some but not all cells null costs one more
+ * pass.  Context option "sort_last_passes" reports the passes of the last call, rv_ctx_last_kernel names "sort_scatter" (or
+ * "sort_widen" when no pass ran), rv_ctx_kernel_stats (option "profile_kernels") times the whole sort stage of
+ * rv_sort_indices.  Option "sort_engine" = 1 replaces the value passes by rocprim::radix_sort_pairs over all 64 bits. */
+#define RV_SORT_DESCENDING 1u
+#define RV_SORT_NULLS_LAST 2u
+/* the stable permutation: an Int64 column of key->length rows without nulls, what rv_take_device takes */
+rv_status rv_sort_indices(rv_ctx *ctx, const rv_dcolumn *key, uint32_t flags, const rv_dcolumn *prior, rv_dcolumn **out_indices);
+/* the whole operator: every column of the frame reordered by the keys cols[key_cols[0]], cols[key_cols[1]], ... (flags per key);
+ * out has room for ncols handles.  nkeys == 0, a key index out of range or unknown flag bits: RV_ERR_INVALID_ARG; columns of
+ * different lengths: RV_ERR_LENGTH_MISMATCH; a key dtype rv_sort_indices refuses: RV_ERR_UNSUPPORTED.  Columns that are no key
+ * may be of any dtype rv_take_device gathers (String and Boolean included).  Two keys are two chained rv_sort_indices calls and
+ * ONE gather of the frame. */
+rv_status rv_sort(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, const uint32_t *key_cols, const uint32_t *key_flags,
+                  uint32_t nkeys, rv_dcolumn **out);
 
 /* ---- multi-GPU (one process per GPU) --------------------------------------- */
 /* Row-range shard of rank `rank` of `world`: [*begin, *end), boundaries at multiples of

@@ -128,6 +128,9 @@ RV_AGG_COUNT_ROWS, RV_AGG_COUNT, RV_AGG_SUM, RV_AGG_MIN, RV_AGG_MAX = range(5)
 AGG_OPS = {"count_rows": RV_AGG_COUNT_ROWS, "count": RV_AGG_COUNT, "sum": RV_AGG_SUM, "min": RV_AGG_MIN, "max": RV_AGG_MAX}
 
 
+RV_SORT_DESCENDING, RV_SORT_NULLS_LAST = 1, 2
+
+
 class RvAggSpec(C.Structure):
     _fields_ = [("op", C.c_uint32), ("col", C.c_uint32)]
 
@@ -200,6 +203,8 @@ PROTOTYPES = {
     "rv_hash_join": (C.c_int, [_P, _PP, C.c_uint32, C.c_uint32, _PP, C.c_uint32, C.c_uint32, _PP, _U64P]),
     "rv_group_ids": (C.c_int, [_P, _P, _PP, _PP, _U64P]),
     "rv_hash_aggregate": (C.c_int, [_P, _P, _PP, C.c_uint32, C.POINTER(RvAggSpec), C.c_uint32, _PP, _PP, _U64P]),
+    "rv_sort_indices": (C.c_int, [_P, _P, C.c_uint32, _P, _PP]),
+    "rv_sort": (C.c_int, [_P, _PP, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, _PP]),
     "rv_hash_join_chunked": (C.c_int, [_P, _P, _PP, C.c_uint32, C.c_uint32, _PP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
                                        _PP, _U64P, C.c_uint64, C.POINTER(C.c_int64), _U64P, _U64P]),
     "rv_filter_project": (C.c_int, [_P, _PP, C.c_uint32, C.POINTER(RvPredicate), C.POINTER(C.c_uint32), C.c_uint32,
@@ -845,6 +850,26 @@ class Context:
                                         C.byref(first) if want_first_row else None, C.byref(groups)))
         return ([DeviceColumn(self, C.c_void_p(out[i])) for i in range(len(specs) + 1)], DeviceColumn(self, first) if want_first_row else None,
                 groups.value)
+
+    def sort_indices(self, key: DeviceColumn, descending: bool = False, nulls_last: bool = False, prior: Optional[DeviceColumn] = None,
+                     flags: Optional[int] = None) -> DeviceColumn:
+        """rv_sort_indices: the stable permutation of `key` (of `prior` reordered by it) as an Int64 column; `flags` overrides the two
+        booleans with a raw flag word."""
+        if flags is None:
+            flags = (RV_SORT_DESCENDING if descending else 0) | (RV_SORT_NULLS_LAST if nulls_last else 0)
+        out = C.c_void_p()
+        _check(load().rv_sort_indices(self.handle, key.handle, flags, prior.handle if prior is not None else None, C.byref(out)))
+        return DeviceColumn(self, out)
+
+    def sort(self, cols: Sequence[DeviceColumn], keys):
+        """rv_sort: every column of the frame reordered by `keys`, a list of column indices or of (column index, flags) pairs, the
+        first key the most significant."""
+        keys = [(k, 0) if isinstance(k, int) else tuple(k) for k in keys]
+        kc = (C.c_uint32 * max(1, len(keys)))(*[k[0] for k in keys])
+        kf = (C.c_uint32 * max(1, len(keys)))(*[k[1] for k in keys])
+        out = (C.c_void_p * max(1, len(cols)))()
+        _check(load().rv_sort(self.handle, _handles(cols), len(cols), kc, kf, len(keys), out))
+        return [DeviceColumn(self, C.c_void_p(out[i])) for i in range(len(cols))]
 
     def hash_join(self, build_cols: Sequence[DeviceColumn], build_key: int, probe_cols: Sequence[DeviceColumn], probe_key: int):
         """Inner hash join (plan.rs:174-284): (every probe column, then the build columns but the key), rows."""

@@ -16,6 +16,7 @@
 
 #include "device_common.hpp"
 #include "join_kernel.hpp"  // join_hash: murmur3's 64-bit finaliser
+#include "order_key.hpp"    // the order map MIN / MAX share with the sort
 
 namespace rvk {
 
@@ -168,14 +169,12 @@ struct GroupAccParams {
 };
 
 __host__ __device__ __forceinline__ uint64_t agg_order_key(uint64_t bits, bool is_float, bool is_max) {
-    if (!is_float) return bits ^ 0x8000000000000000ull;
-    if ((bits & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull) return is_max ? ~0ull : 0ull;
-    return (bits >> 63) ? ~bits : bits | 0x8000000000000000ull;
+    if (is_float && rvorder::order_key_is_nan(bits)) return is_max ? ~0ull : 0ull;
+    return rvorder::order_key(bits, is_float);
 }
 __host__ __device__ __forceinline__ uint64_t agg_order_value(uint64_t key, bool is_float) {
-    if (!is_float) return key ^ 0x8000000000000000ull;
-    if (key == 0 || key == ~0ull) return 0x7FF8000000000000ull;  // a NaN won
-    return (key >> 63) ? key & 0x7FFFFFFFFFFFFFFFull : ~key;
+    if (is_float && (key == 0 || key == ~0ull)) return 0x7FF8000000000000ull;  // a NaN won
+    return rvorder::order_value(key, is_float);
 }
 
 __device__ __forceinline__ uint64_t agg_identity(uint32_t kind) { return kind == AK_MIN ? ~0ull : 0ull; }

@@ -252,6 +252,8 @@ struct rv_ctx {
     int64_t opt_string_hash_bits = 0; // tests: string dictionaries built from now on hash to this many low bits (long collision chains); 0: all 64
     int64_t opt_agg_hash_bits = 0;  // tests: group tables built from now on hash keys to this many low bits (long collision chains); 0: all 64
     int64_t opt_agg_max_groups = 0; // rv_hash_aggregate / rv_group_ids refuse more distinct keys than this; 0: rvt::kGroupAggGroupsMostDefault
+    int64_t opt_sort_engine = 0;    // 0: the sort's own radix passes; 1 (measurements, tests): the pair sort by rocprim::radix_sort_pairs over all 64 bits
+    uint64_t sort_last_passes = 0;  // scatter passes the last sort call ran (the null pass included)
     int64_t opt_bools_in_pass = 0;  // 1: projected Boolean columns are compacted inside the fused pass (lane-form PEXT)
     int64_t opt_csv_slow_cap = 0;   // tests: k > 0 caps a CSV chunk's first list of undecided Float64 cells at k (forces the re-parse)
     uint64_t csv_slow_cells = 0;    // Float64 cells the CSV scan's exact slow kernel decided (csv_f64_slow), context total

@@ -116,4 +116,11 @@ constexpr uint32_t kGroupAggWaveListMost = 1024;
 // rv_hash_aggregate / rv_group_ids refuse more distinct keys than this unless option "agg_max_groups" says otherwise: 2^27 slots of
 // 8 bytes bound the group table at 1 GiB.  A limit, not a crossover.
 constexpr uint64_t kGroupAggGroupsMostDefault = uint64_t{1} << 26;
+
+// ---- sort (sort.hip) ------------------------------------------------------------------------------------------------------------------------
+// Rows per lane of a tile of the radix passes (sort_tile_hist, sort_scatter: one workgroup of 256 lanes per tile, so 2048 rows).  It
+// decides what a tile stages in LDS (12 bytes per row + 1 for the digit, with the counters 32 KiB: four workgroups per CU) and how many per-tile digit counts
+// a pass scans (256 per 2048 rows: 1 byte per row through the scan against the 32 a pass moves).  Not a crossover; set by that reasoning,
+// NOT by a sweep -- 16 rows per lane would halve the counts and leave two workgroups per CU.                       tools/sort_bench.py
+constexpr uint32_t kSortRowsPerLane = 8;
 }  // namespace rvt

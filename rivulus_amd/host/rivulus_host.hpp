@@ -1871,6 +1871,95 @@ class GpuGroupByStream : public DataStream {
     bool done_ = false;
 };
 
+// ---------------------------------------------------------------------------------------
+// sort(keys) -- ORDER BY; the reference has no sort: include/rivulus_gpu.h, rv_sort_indices
+// ---------------------------------------------------------------------------------------
+// One sort key: the column, the direction of its values, and where its nulls go (first unless nulls_last; `descending` does not move them).
+struct SortKey {
+    std::string column;
+    bool descending = false;
+    bool nulls_last = false;
+};
+struct SortPlanError : std::runtime_error {  // what planning a sort refuses, with the column it refuses it for
+    using std::runtime_error::runtime_error;
+};
+
+// Checks `keys` against `in` and returns the output schema -- the input's: a sort changes neither names nor dtypes.  Throws SortPlanError
+// for an empty key list, an unknown column, and a key the device does not sort by (String, Boolean: not built).
+inline SchemaRef sort_schema(const Schema &in, const std::vector<SortKey> &keys) {
+    if (keys.empty()) throw SortPlanError("sort: no sort keys");
+    for (auto &k : keys) {
+        const Field *f = in.field_by_name(k.column);
+        if (!f) throw SortPlanError("sort: unknown key column '" + k.column + "'");
+        if (f->data_type() == DataType::String || f->data_type() == DataType::Boolean)
+            throw SortPlanError("sort: key column '" + k.column + "' is " + to_string(f->data_type()) + "; only Int64 and Float64 keys are sorted");
+    }
+    return std::make_shared<const Schema>(in);
+}
+
+// One rv_sort over one frame (`columns` in the order of `schema`): every column reordered, the first key the most significant.  Columns
+// that are no key ride along whatever their dtype.
+inline std::vector<ArrayRef> sort_columns(const ContextRef &ctx, const Schema &schema, const std::vector<ArrayRef> &columns, const std::vector<SortKey> &keys) {
+    (void)sort_schema(schema, keys);
+    std::vector<const rv_dcolumn *> handles;
+    for (auto &c : columns) {
+        if (!c->on_device()) throw Error(RV_ERR_UNSUPPORTED, "columns off the device are outside the device path");
+        handles.push_back(c->handle());
+    }
+    std::vector<uint32_t> key_cols, key_flags;
+    for (auto &k : keys) {
+        key_cols.push_back(static_cast<uint32_t>(*schema.index_of(k.column)));
+        key_flags.push_back((k.descending ? RV_SORT_DESCENDING : 0u) | (k.nulls_last ? RV_SORT_NULLS_LAST : 0u));
+    }
+    std::vector<rv_dcolumn *> out(handles.size(), nullptr);
+    check(rv_sort(ctx->raw(), handles.data(), static_cast<uint32_t>(handles.size()), key_cols.data(), key_flags.data(), static_cast<uint32_t>(keys.size()),
+                  out.data()));
+    std::vector<ArrayRef> res;
+    for (auto *h : out) res.push_back(Array::adopt(ctx, h));
+    return res;
+}
+
+// sort as a stream: a PIPELINE BREAKER like GpuGroupByStream.  It drains its input the same way -- a resident frame is taken as it is,
+// the batches of any other stream are concatenated (RecordBatch::concat) -- and emits EXACTLY ONE batch: every row, in order.  An input
+// without rows gives one zero-row batch with the schema.  (Merging sorted runs in place of the concatenation is not built.)
+class GpuSortStream : public DataStream {
+  public:
+    // `fallback_ctx`: where the zero-row batch of an input that yields no batch at all is created
+    GpuSortStream(JoinSide input, std::vector<SortKey> keys, ContextRef fallback_ctx) : input_(std::move(input)), keys_(std::move(keys)), ctx_(std::move(fallback_ctx)) {
+        schema_ = sort_schema(*input_.schema(), keys_);
+    }
+    SchemaRef schema() const override { return schema_; }
+    std::optional<RecordBatch> next_batch() override {
+        if (done_) return std::nullopt;
+        done_ = true;
+        std::vector<ArrayRef> columns = input_.columns;
+        if (input_.stream) {
+            std::vector<RecordBatch> all;
+            while (auto b = input_.stream->next_batch()) all.push_back(std::move(*b));
+            if (all.empty()) {
+                if (!ctx_) throw StreamError::execution("sort: the input yielded no batch and the plan holds no device context");
+                return RecordBatch::empty(ctx_, schema_);
+            }
+            RecordBatch whole = all.size() == 1 ? all[0] : stream_call([&] { return RecordBatch::concat(all); });
+            columns = whole.columns();
+        }
+        return stream_call([&] {
+            const ContextRef ctx = columns.empty() ? ctx_ : columns[0]->context();
+            if (columns.empty() || columns[0]->len() == 0) return RecordBatch::empty(ctx, schema_);
+            std::vector<ArrayRef> out = sort_columns(ctx, *schema_, columns, keys_);
+            const size_t rows = out[0]->len();
+            return RecordBatch::new_unchecked(schema_, std::move(out), rows);
+        });
+    }
+
+  private:
+    JoinSide input_;
+    std::vector<SortKey> keys_;
+    ContextRef ctx_;
+    SchemaRef schema_;
+    bool done_ = false;
+};
+
 }  // namespace execution
 
 // ---------------------------------------------------------------------------------------
@@ -2220,7 +2309,7 @@ class StreamingPhysicalPlan;
 using StreamingPlanPtr = std::shared_ptr<const StreamingPhysicalPlan>;
 class StreamingPhysicalPlan {
   public:
-    enum Kind { MemorySource, DataFrameSource, CsvFileSource, Filter, GpuFilterProject, Select, Limit, HashJoin, Project, ComputedFilterProject, GroupBy } kind = MemorySource;
+    enum Kind { MemorySource, DataFrameSource, CsvFileSource, Filter, GpuFilterProject, Select, Limit, HashJoin, Project, ComputedFilterProject, GroupBy, Sort } kind = MemorySource;
     std::vector<Expr> exprs;  // Project: select expressions, arithmetic included
     Expr predicate_expr;      // ComputedFilterProject: a filter with `<arith> <cmp> <literal>` terms
     // DataFrameSource (streaming.rs:85-94)
@@ -2244,6 +2333,7 @@ class StreamingPhysicalPlan {
     std::string build_key, probe_key;
     std::string group_key;  // GroupBy { input, group_key, aggs }
     std::vector<execution::AggSpec> aggs;
+    std::vector<execution::SortKey> sort_keys;  // Sort { input, sort_keys }
 
     static StreamingPlanPtr memory_source(std::vector<execution::RecordBatch> b) {
         auto p = std::make_shared<StreamingPhysicalPlan>();
@@ -2342,6 +2432,14 @@ class StreamingPhysicalPlan {
         p->aggs = std::move(aggs);
         return p;
     }
+    // sort(keys): a pipeline breaker that emits exactly one batch (GpuSortStream); the reference has no such operator
+    static StreamingPlanPtr sort(StreamingPlanPtr in, std::vector<execution::SortKey> keys) {
+        auto p = std::make_shared<StreamingPhysicalPlan>();
+        p->kind = Sort;
+        p->input = std::move(in);
+        p->sort_keys = std::move(keys);
+        return p;
+    }
     // a device context some source of the plan holds (nullptr: none does)
     ContextRef any_context() const {
         if (csv_ctx) return csv_ctx;
@@ -2421,6 +2519,17 @@ class StreamingPhysicalPlan {
                     }
                     return std::make_unique<GpuGroupByStream>(std::move(s), group_key, aggs, any_context());
                 }
+                case Sort: {  // drains its input as GroupBy does
+                    JoinSide s;
+                    if (input->kind == DataFrameSource && !input->df.columns.empty() && input->df_batch_size > 0) {
+                        s.names = input->df.names;
+                        s.columns = input->filled_columns();
+                        s.batch_size = input->df_batch_size;
+                    } else {
+                        s.stream = input->execute();
+                    }
+                    return std::make_unique<GpuSortStream>(std::move(s), sort_keys, any_context());
+                }
             }
         } catch (const StreamError &e) {
             throw StreamingExecutionError(std::string("Stream error: ") + e.what());
@@ -2473,7 +2582,7 @@ class PhysicalPlan;
 using PhysicalPlanPtr = std::shared_ptr<const PhysicalPlan>;
 class PhysicalPlan {
   public:
-    enum Kind { DataFrameSource, Select, Filter, HashJoin, Project, ComputedFilter, GroupBy } kind = DataFrameSource;
+    enum Kind { DataFrameSource, Select, Filter, HashJoin, Project, ComputedFilter, GroupBy, Sort } kind = DataFrameSource;
     DeviceFrame df;
     std::vector<Expr> exprs;  // Project: select expressions, arithmetic included
     Expr predicate_expr;      // ComputedFilter: `<arith> <cmp> <literal>` terms, alone or under AND / OR
@@ -2484,6 +2593,7 @@ class PhysicalPlan {
     std::string build_key, probe_key;
     std::string group_key;  // GroupBy { input, group_key, aggs }
     std::vector<execution::AggSpec> aggs;
+    std::vector<execution::SortKey> sort_keys;  // Sort { input, sort_keys }
 
     static PhysicalPlanPtr source(DeviceFrame f) {
         auto p = std::make_shared<PhysicalPlan>();
@@ -2543,9 +2653,28 @@ class PhysicalPlan {
         p->aggs = std::move(aggs);
         return p;
     }
+    // sort(keys), eager: one rv_sort; names and dtypes unchanged, the first key the most significant, equal rows in input order.  The nulls
+    // of the frame stay nulls (no fill: this is not a stream).
+    static PhysicalPlanPtr sort(PhysicalPlanPtr in, std::vector<execution::SortKey> keys) {
+        auto p = std::make_shared<PhysicalPlan>();
+        p->kind = Sort;
+        p->input = std::move(in);
+        p->sort_keys = std::move(keys);
+        return p;
+    }
     DeviceFrame execute() const {
         switch (kind) {
             case DataFrameSource: return df;  // plan.rs:67
+            case Sort: {
+                DeviceFrame in = input->execute();
+                const execution::Schema schema = frame_schema(in);
+                (void)execution::sort_schema(schema, sort_keys);  // the planning errors
+                if (in.height() == 0) return in;
+                DeviceFrame out;
+                out.names = in.names;
+                out.columns = execution::sort_columns((*in.column(sort_keys[0].column))->context(), schema, in.columns, sort_keys);
+                return out;
+            }
             case GroupBy: {
                 DeviceFrame in = input->execute();
                 const execution::Schema schema = frame_schema(in);
