@@ -392,6 +392,13 @@ rv_status rv_take(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols,
  * offending position, so the error text is the reference's ("Index 7 out of bounds for 5 rows"). */
 rv_status rv_take_device(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, const rv_dcolumn *indices,
                          rv_dcolumn **out);
+/* rv_take_device with a NULLABLE index list: a null index yields a null cell of the column's dtype -- value 0 / false /
+ * the empty string, validity attached (to the outputs that got a null cell) -- whatever lies under the null.  Non-null
+ * indices are bounds-checked with the same text as rv_take_device.  RV_NULL columns stay RV_NULL; String and Boolean
+ * columns are included.  An index list without nulls gives exactly rv_take_device's outputs.  The outer joins gather
+ * the side that can lack a partner through this (rv_join_probe_kind's index columns are what it takes). */
+rv_status rv_take_device_nullable(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, const rv_dcolumn *indices,
+                                  rv_dcolumn **out);
 /* The ascending index list RecordBatch::filter builds from its predicate (record_batch.rs:235-240): the rows of a
  * BooleanArray that are Some(true), as an Int64 device array. */
 rv_status rv_selection_indices(rv_ctx *ctx, const rv_dcolumn *selection, rv_dcolumn **out_indices);
@@ -472,6 +479,65 @@ rv_status rv_hash_join_chunked(rv_ctx *ctx, const rv_join_table *table,
                                uint64_t chunk_rows, uint64_t max_pairs,
                                rv_dcolumn **out, uint64_t *out_rows, uint64_t nchunks, int64_t *out_nulls,
                                uint64_t *out_total, uint64_t *out_batches);
+
+/* ---- outer, semi and anti hash joins --------------------------------------- */
+/* The other kinds of the join above (the reference's enum stops at Inner: logical_plan/plan.rs has //Left, //Outer).
+ * Build side and probe side are as in rv_hash_join; key equality is unchanged (AnyValue's, see above), hence:
+ *   - a NaN probe key is always unmatched: PROBE_OUTER keeps it with a null partner, PROBE_ANTI keeps it, PROBE_SEMI
+ *     drops it;
+ *   - a null probe key is matched if and only if the build key has a null: PROBE_ANTI is NOT SQL's NOT IN;
+ *   - a NaN build row is never met: FULL_OUTER always emits it as unmatched;
+ *   - key columns of different dtypes meet null to null only, so every non-null probe row is unmatched.
+ * Row order is fully determined and identical run to run (positions come from scans, never from the order atomics
+ * land in):
+ *   - INNER / PROBE_OUTER: probe-row order; within a probe row ascending build row; an unmatched probe row
+ *     contributes one pair (p, none) at its place;
+ *   - FULL_OUTER: the PROBE_OUTER rows, then one pair (none, b) per unmatched build row, ascending b;
+ *   - PROBE_SEMI / PROBE_ANTI: ascending probe row, each row once. */
+typedef enum rv_join_kind {
+    RV_JOIN_INNER = 0,       /* exactly rv_join_probe / rv_hash_join */
+    RV_JOIN_PROBE_OUTER = 1, /* every probe row at least once; a probe row without a match pairs with "no build row" */
+    RV_JOIN_FULL_OUTER = 2,  /* PROBE_OUTER, then every build row no probe row met */
+    RV_JOIN_PROBE_SEMI = 3,  /* the probe rows that have at least one match, once each, probe columns only */
+    RV_JOIN_PROBE_ANTI = 4   /* the probe rows that have none, probe columns only */
+} rv_join_kind;
+/* (the calls below take the kind as `int kind`, one of the values above, as the other calls of this header take their enums) */
+/* rv_join_probe for any kind.  The index columns are Int64; a cell with no partner is a NULL cell: validity attached
+ * only when some cell is null, null_count known, value 0 under a null -- what rv_take_device_nullable takes.
+ * PROBE_SEMI / PROBE_ANTI set *out_build_idx = NULL.  kind == RV_JOIN_INNER gives exactly rv_join_probe's output.  The
+ * row total, unmatched rows included, is known on the device before any output is allocated (a FULL_OUTER probe holds
+ * its scratch by then: a bit per hash slot and two bits per build row): more than the device holds
+ * is RV_ERR_OOM with the context still usable.  An unknown kind: RV_ERR_INVALID_ARG.  `table` is not changed: the
+ * record of the build rows a FULL_OUTER probe met lives in the call.
+ * rv_ctx_last_kernel: the inner names for RV_JOIN_INNER; otherwise the emit kernel with the kind appended --
+ *   PROBE_OUTER  join_probe_emit<0,outer>  join_probe_emit<1,outer>  join_probe_emit<2,outer>
+ *   FULL_OUTER   join_probe_emit<0,full>   join_probe_emit<1,full>   join_probe_emit<2,full>
+ *   PROBE_SEMI   join_probe_emit<0,semi>   PROBE_ANTI   join_probe_emit<0,anti>
+ * (0 / 1 / 2 by the longest list as for the inner join; semi and anti joins are always the compaction, 0) -- and
+ * join_probe_count when the emit pass had no row to write. */
+rv_status rv_join_probe_kind(rv_ctx *ctx, const rv_join_table *table, const rv_dcolumn *probe_key, int kind,
+                             rv_dcolumn **out_probe_idx, rv_dcolumn **out_build_idx, uint64_t *out_rows);
+/* rv_hash_join for any kind.  Output columns:
+ *   - INNER, PROBE_OUTER: every probe column, then every build column but the key: n_probe + n_build - 1;
+ *   - FULL_OUTER: every probe column, then EVERY build column, the key included, at its place: n_probe + n_build (a
+ *     row without a probe partner would otherwise lose its key);
+ *   - PROBE_SEMI, PROBE_ANTI: the probe columns only: n_probe.
+ * A cell of the side without a partner is null.  Zero rows give zero-row columns of the right dtypes.  Errors as
+ * rv_hash_join. */
+rv_status rv_hash_join_kind(rv_ctx *ctx, const rv_dcolumn *const *build_cols, uint32_t n_build, uint32_t build_key,
+                            const rv_dcolumn *const *probe_cols, uint32_t n_probe, uint32_t probe_key,
+                            int kind, rv_dcolumn **out, uint64_t *out_rows);
+/* rv_hash_join_chunked for the probe-preserving kinds INNER, PROBE_OUTER, PROBE_SEMI and PROBE_ANTI; FULL_OUTER is
+ * RV_ERR_UNSUPPORTED (its unmatched build rows belong to no probe batch).  The contract is unchanged: output batch k ==
+ * rv_hash_join_kind of the whole build side against probe batch k alone; all K batch counts come from one count pass
+ * and one read-back; max_pairs cuts a prefix of batches.  out[] holds the kind's columns (see rv_hash_join_kind);
+ * rv_ctx_last_kernel as rv_join_probe_kind, or join_probe_count_batched when no row came out. */
+rv_status rv_hash_join_chunked_kind(rv_ctx *ctx, const rv_join_table *table,
+                                    const rv_dcolumn *const *build_cols, uint32_t n_build, uint32_t build_key,
+                                    const rv_dcolumn *const *probe_cols, uint32_t n_probe, uint32_t probe_key,
+                                    int kind, uint64_t chunk_rows, uint64_t max_pairs,
+                                    rv_dcolumn **out, uint64_t *out_rows, uint64_t nchunks, int64_t *out_nulls,
+                                    uint64_t *out_total, uint64_t *out_batches);
 
 /* ---- string dictionary (String join keys) --------------------------------- */
 /* The join kernels take 64 key bits per cell.  A String key column gets there through a DICTIONARY: the distinct

@@ -190,10 +190,12 @@ PROTOTYPES = {
     "rv_filter": (C.c_int, [_P, _PP, C.c_uint32, _P, _PP, _U64P]),
     "rv_take": (C.c_int, [_P, _PP, C.c_uint32, _U64P, C.c_uint64, _PP]),
     "rv_take_device": (C.c_int, [_P, _PP, C.c_uint32, _P, _PP]),
+    "rv_take_device_nullable": (C.c_int, [_P, _PP, C.c_uint32, _P, _PP]),
     "rv_selection_indices": (C.c_int, [_P, _P, _PP]),
     "rv_concat": (C.c_int, [_P, _PP, C.c_uint32, _PP]),
     "rv_join_build": (C.c_int, [_P, _P, _PP]),
     "rv_join_probe": (C.c_int, [_P, _P, _P, _PP, _PP, _U64P]),
+    "rv_join_probe_kind": (C.c_int, [_P, _P, _P, C.c_int, _PP, _PP, _U64P]),
     "rv_join_table_info": (C.c_int, [_P, _U64P, _U64P, _U64P]),
     "rv_join_table_free": (C.c_int, [_P, _P]),
     "rv_string_dict_build": (C.c_int, [_P, _P, _PP, _PP]),
@@ -205,6 +207,9 @@ PROTOTYPES = {
     "rv_hash_aggregate": (C.c_int, [_P, _P, _PP, C.c_uint32, C.POINTER(RvAggSpec), C.c_uint32, _PP, _PP, _U64P]),
     "rv_sort_indices": (C.c_int, [_P, _P, C.c_uint32, _P, _PP]),
     "rv_sort": (C.c_int, [_P, _PP, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, _PP]),
+    "rv_hash_join_kind": (C.c_int, [_P, _PP, C.c_uint32, C.c_uint32, _PP, C.c_uint32, C.c_uint32, C.c_int, _PP, _U64P]),
+    "rv_hash_join_chunked_kind": (C.c_int, [_P, _P, _PP, C.c_uint32, C.c_uint32, _PP, C.c_uint32, C.c_uint32, C.c_int, C.c_uint64, C.c_uint64,
+                                            _PP, _U64P, C.c_uint64, C.POINTER(C.c_int64), _U64P, _U64P]),
     "rv_hash_join_chunked": (C.c_int, [_P, _P, _PP, C.c_uint32, C.c_uint32, _PP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
                                        _PP, _U64P, C.c_uint64, C.POINTER(C.c_int64), _U64P, _U64P]),
     "rv_filter_project": (C.c_int, [_P, _PP, C.c_uint32, C.POINTER(RvPredicate), C.POINTER(C.c_uint32), C.c_uint32,
@@ -549,16 +554,32 @@ class DeviceColumn:
             pass
 
 
+# rv_join_kind
+RV_JOIN_INNER, RV_JOIN_PROBE_OUTER, RV_JOIN_FULL_OUTER, RV_JOIN_PROBE_SEMI, RV_JOIN_PROBE_ANTI = range(5)
+
+
+def join_output_columns(kind: int, n_probe: int, n_build: int) -> int:
+    """Output columns of rv_hash_join_kind: the probe columns, then the build columns without the key (with it for FULL_OUTER, none of
+    them for a semi or anti join)."""
+    if kind in (RV_JOIN_PROBE_SEMI, RV_JOIN_PROBE_ANTI):
+        return n_probe
+    return n_probe + n_build - (0 if kind == RV_JOIN_FULL_OUTER else 1)
+
+
 class JoinTable:
     """rv_join_table: a build side hashed on the device, probed by any number of key columns."""
     def __init__(self, ctx: "Context", handle):
         self.ctx, self.handle = ctx, handle
 
-    def probe(self, key: DeviceColumn):
-        """result_pairs (plan.rs:194-204): (probe_idx, build_idx) Int64 device columns and the pair count."""
+    def probe(self, key: DeviceColumn, kind: Optional[int] = None):
+        """result_pairs (plan.rs:194-204): (probe_idx, build_idx) Int64 device columns and the pair count.  kind: an rv_join_kind
+        (rv_join_probe_kind): a cell without a partner is null; build_idx is None for a semi or anti join."""
         pi, bi, rows = C.c_void_p(), C.c_void_p(), C.c_uint64()
-        _check(load().rv_join_probe(self.ctx.handle, self.handle, key.handle, C.byref(pi), C.byref(bi), C.byref(rows)))
-        return DeviceColumn(self.ctx, pi), DeviceColumn(self.ctx, bi), rows.value
+        if kind is None:
+            _check(load().rv_join_probe(self.ctx.handle, self.handle, key.handle, C.byref(pi), C.byref(bi), C.byref(rows)))
+        else:
+            _check(load().rv_join_probe_kind(self.ctx.handle, self.handle, key.handle, kind, C.byref(pi), C.byref(bi), C.byref(rows)))
+        return DeviceColumn(self.ctx, pi), (DeviceColumn(self.ctx, bi) if bi.value else None), rows.value
 
     def info(self):
         """(build rows, hash slots, longest match list)"""
@@ -796,6 +817,12 @@ class Context:
         _check(load().rv_take_device(self.handle, _handles(cols), len(cols), indices.handle, out))
         return [DeviceColumn(self, C.c_void_p(out[i])) for i in range(len(cols))]
 
+    def take_device_nullable(self, cols: Sequence[DeviceColumn], indices: DeviceColumn):
+        """rv_take_device_nullable: a null index yields a null cell."""
+        out = (C.c_void_p * max(1, len(cols)))()
+        _check(load().rv_take_device_nullable(self.handle, _handles(cols), len(cols), indices.handle, out))
+        return [DeviceColumn(self, C.c_void_p(out[i])) for i in range(len(cols))]
+
     def selection_indices(self, selection: DeviceColumn) -> DeviceColumn:
         out = C.c_void_p()
         _check(load().rv_selection_indices(self.handle, selection.handle, C.byref(out)))
@@ -871,30 +898,42 @@ class Context:
         _check(load().rv_sort(self.handle, _handles(cols), len(cols), kc, kf, len(keys), out))
         return [DeviceColumn(self, C.c_void_p(out[i])) for i in range(len(cols))]
 
-    def hash_join(self, build_cols: Sequence[DeviceColumn], build_key: int, probe_cols: Sequence[DeviceColumn], probe_key: int):
-        """Inner hash join (plan.rs:174-284): (every probe column, then the build columns but the key), rows."""
-        n = len(probe_cols) + len(build_cols) - 1
+    def hash_join(self, build_cols: Sequence[DeviceColumn], build_key: int, probe_cols: Sequence[DeviceColumn], probe_key: int,
+                  kind: Optional[int] = None):
+        """Inner hash join (plan.rs:174-284): (every probe column, then the build columns but the key), rows.  kind: an rv_join_kind
+        (rv_hash_join_kind), with that kind's columns."""
+        n = join_output_columns(kind or RV_JOIN_INNER, len(probe_cols), len(build_cols))
         out = (C.c_void_p * max(1, n))()
         rows = C.c_uint64()
-        _check(load().rv_hash_join(self.handle, _handles(build_cols), len(build_cols), build_key, _handles(probe_cols), len(probe_cols),
-                                   probe_key, out, C.byref(rows)))
+        if kind is None:
+            _check(load().rv_hash_join(self.handle, _handles(build_cols), len(build_cols), build_key, _handles(probe_cols), len(probe_cols),
+                                       probe_key, out, C.byref(rows)))
+        else:
+            _check(load().rv_hash_join_kind(self.handle, _handles(build_cols), len(build_cols), build_key, _handles(probe_cols), len(probe_cols),
+                                            probe_key, kind, out, C.byref(rows)))
         return [DeviceColumn(self, C.c_void_p(out[i])) for i in range(max(0, n))], rows.value
 
     def hash_join_chunked(self, table: "JoinTable", build_cols: Sequence[DeviceColumn], build_key: int, probe_cols: Sequence[DeviceColumn],
-                          probe_key: int, chunk_rows: int, max_pairs: int = 0, want_nulls: bool = True, nchunks: Optional[int] = None):
+                          probe_key: int, chunk_rows: int, max_pairs: int = 0, want_nulls: bool = True, nchunks: Optional[int] = None,
+                          kind: Optional[int] = None):
         """rv_hash_join_chunked: the probe frame cut into chunk_rows-row batches, every batch joined against the whole build side
         in one call.  Returns (outs, rows_per_batch[K], nulls[batches taken, nout] or None, total, batches taken)."""
         n = probe_cols[0].length if probe_cols else 0
         k = (n + chunk_rows - 1) // chunk_rows if chunk_rows > 0 else 0  # 0: the library reports the argument
         cap = k if nchunks is None else nchunks
-        nout = len(probe_cols) + len(build_cols) - 1
+        nout = join_output_columns(kind or RV_JOIN_INNER, len(probe_cols), len(build_cols))
         out = (C.c_void_p * max(1, nout))()
         rows = np.zeros(max(1, k, cap), dtype=np.uint64)
         nulls = np.zeros(max(1, k) * max(1, nout), dtype=np.int64) if want_nulls else None
         total, taken = C.c_uint64(), C.c_uint64()
-        _check(load().rv_hash_join_chunked(self.handle, table.handle, _handles(build_cols), len(build_cols), build_key, _handles(probe_cols),
-                                           len(probe_cols), probe_key, chunk_rows, max_pairs, out, rows.ctypes.data_as(_U64P), cap,
-                                           nulls.ctypes.data_as(C.POINTER(C.c_int64)) if want_nulls else None, C.byref(total), C.byref(taken)))
+        tail = (chunk_rows, max_pairs, out, rows.ctypes.data_as(_U64P), cap, nulls.ctypes.data_as(C.POINTER(C.c_int64)) if want_nulls else None,
+                C.byref(total), C.byref(taken))
+        if kind is None:
+            _check(load().rv_hash_join_chunked(self.handle, table.handle, _handles(build_cols), len(build_cols), build_key, _handles(probe_cols),
+                                               len(probe_cols), probe_key, *tail))
+        else:
+            _check(load().rv_hash_join_chunked_kind(self.handle, table.handle, _handles(build_cols), len(build_cols), build_key,
+                                                    _handles(probe_cols), len(probe_cols), probe_key, kind, *tail))
         outs = [DeviceColumn(self, C.c_void_p(out[i])) for i in range(max(0, nout))]
         b = taken.value
         return outs, rows[:k], (nulls.reshape(max(1, k), max(1, nout))[:b] if want_nulls else None), total.value, b

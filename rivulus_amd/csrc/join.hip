@@ -1,4 +1,5 @@
-// Inner hash join on the device (reference PhysicalPlan::HashJoin, plan.rs:174-284): build table, probe, gather.
+// Hash join on the device (reference PhysicalPlan::HashJoin, plan.rs:174-284): build table, probe, gather; the inner join and the
+// outer, semi and anti joins (rv_join_kind).
 // One unit of the backend library behind include/rivulus_gpu.h (gfx950 only; compiled with hipcc).  Shared helpers and the
 // functions the units call across each other are declared in launch.hpp (namespace rvl); the kernels are in join_kernel.hpp.
 #include <rocprim/device/device_radix_sort.hpp>
@@ -150,19 +151,63 @@ uint64_t device_pair_cap(const rv_ctx *ctx) { return static_cast<uint64_t>(ctx->
 
 // the emit pass over the first p.n rows, into fresh index buffers of `pairs` pairs: by lists of at most one row, of at most a lane's
 // share, or longer
-void emit_pairs(rv_ctx *ctx, rvk::JoinProbeParams &p, uint64_t longest, uint64_t pairs, DevBufRef &out_probe, DevBufRef &out_build) {
-    out_probe = pool_alloc(ctx, std::max<size_t>(pairs * 8, 16));
-    out_build = pool_alloc(ctx, std::max<size_t>(pairs * 8, 16));
+// `kind` other than RV_JOIN_INNER: the kind's instantiation, named with the kind appended.  `pairs` are the rows the emit pass writes,
+// `room` >= pairs the rows the buffers hold (the full outer join's tail goes behind); semi and anti joins get no build buffer.
+bool kind_has_pairs(rv_join_kind kind) { return kind != RV_JOIN_PROBE_SEMI && kind != RV_JOIN_PROBE_ANTI; }
+const char *kind_name(rv_join_kind kind) {
+    switch (kind) {
+        case RV_JOIN_PROBE_OUTER: return "outer";
+        case RV_JOIN_FULL_OUTER: return "full";
+        case RV_JOIN_PROBE_SEMI: return "semi";
+        case RV_JOIN_PROBE_ANTI: return "anti";
+        default: return "inner";
+    }
+}
+void check_kind(const char *what, int kind) {
+    require(kind >= RV_JOIN_INNER && kind <= RV_JOIN_PROBE_ANTI, RV_ERR_INVALID_ARG, fmt("%s: unknown join kind %d", what, kind));
+}
+// f(std::integral_constant<int, KIND>) for the kernel kind of a kind other than RV_JOIN_INNER: the one place a run-time kind becomes
+// a template argument
+template <class F>
+void with_kind(rv_join_kind kind, F f) {
+    switch (kind) {
+        case RV_JOIN_PROBE_OUTER: return f(std::integral_constant<int, rvk::JOIN_OUTER>{});
+        case RV_JOIN_FULL_OUTER: return f(std::integral_constant<int, rvk::JOIN_FULL>{});
+        case RV_JOIN_PROBE_SEMI: return f(std::integral_constant<int, rvk::JOIN_SEMI>{});
+        case RV_JOIN_PROBE_ANTI: return f(std::integral_constant<int, rvk::JOIN_ANTI>{});
+        default: throw Error(RV_ERR_INTERNAL, "join: no kernel kind for this join kind");
+    }
+}
+void emit_pairs(rv_ctx *ctx, rvk::JoinProbeParams &p, uint64_t longest, uint64_t pairs, DevBufRef &out_probe, DevBufRef &out_build,
+                rv_join_kind kind = RV_JOIN_INNER, uint64_t room = 0) {
+    room = std::max(room, pairs);
+    out_probe = pool_alloc(ctx, std::max<size_t>(room * 8, 16));
+    if (kind_has_pairs(kind)) out_build = pool_alloc(ctx, std::max<size_t>(room * 8, 16));
     if (!pairs) return;
     p.out_probe = static_cast<int64_t *>(out_probe->ptr);
-    p.out_build = static_cast<int64_t *>(out_build->ptr);
+    p.out_build = out_build ? static_cast<int64_t *>(out_build->ptr) : nullptr;
     const dim3 grid(static_cast<uint32_t>((p.n + rvk::kJoinTileRows - 1) / rvk::kJoinTileRows)), block(rvk::kJoinThreads);
-    const int mode = longest <= 1 ? 0 : longest <= rvt::kJoinLaneListMost ? 1 : 2;
-    if (mode == 0) hipLaunchKernelGGL(rvk::join_probe_emit<0>, grid, block, 0, ctx->stream, p);
-    else if (mode == 1) hipLaunchKernelGGL(rvk::join_probe_emit<1>, grid, block, 0, ctx->stream, p);
-    else hipLaunchKernelGGL(rvk::join_probe_emit<2>, grid, block, 0, ctx->stream, p);
+    const int mode = !kind_has_pairs(kind) || longest <= 1 ? 0 : longest <= rvt::kJoinLaneListMost ? 1 : 2;
+    if (kind == RV_JOIN_INNER) {
+        if (mode == 0) hipLaunchKernelGGL(rvk::join_probe_emit<0>, grid, block, 0, ctx->stream, p);
+        else if (mode == 1) hipLaunchKernelGGL(rvk::join_probe_emit<1>, grid, block, 0, ctx->stream, p);
+        else hipLaunchKernelGGL(rvk::join_probe_emit<2>, grid, block, 0, ctx->stream, p);
+        RV_HIP(hipGetLastError());
+        ctx->last_kernel = fmt("join_probe_emit<%d>", mode);
+        return;
+    }
+    with_kind(kind, [&](auto k) {
+        constexpr int K = decltype(k)::value;
+        if constexpr (K == rvk::JOIN_SEMI || K == rvk::JOIN_ANTI) {
+            hipLaunchKernelGGL((rvk::join_probe_emit_kind<0, K>), grid, block, 0, ctx->stream, p);
+        } else {
+            if (mode == 0) hipLaunchKernelGGL((rvk::join_probe_emit_kind<0, K>), grid, block, 0, ctx->stream, p);
+            else if (mode == 1) hipLaunchKernelGGL((rvk::join_probe_emit_kind<1, K>), grid, block, 0, ctx->stream, p);
+            else hipLaunchKernelGGL((rvk::join_probe_emit_kind<2, K>), grid, block, 0, ctx->stream, p);
+        }
+    });
     RV_HIP(hipGetLastError());
-    ctx->last_kernel = fmt("join_probe_emit<%d>", mode);
+    ctx->last_kernel = fmt("join_probe_emit<%d,%s>", mode, kind_name(kind));
 }
 
 // result_pairs of plan.rs:196-204 as two Int64 index buffers: count pass, scan of the tile counts, one read-back of the total,
@@ -193,15 +238,95 @@ uint64_t probe_table(rv_ctx *ctx, const rv_join_table *t, const rv_dcolumn *key,
     return total;
 }
 
+// (The size check of a full outer join comes before any OUTPUT is allocated; its marks and the two build-row bitmaps -- a bit per slot
+// and two bits per build row -- are scratch of the count pass and are there before it.)
+// The probe of the other kinds (rv_join_probe_kind): the count pass with the kind's row rule -- run even against a table without a
+// single list, where every probe row is unmatched -- the scan, one read-back of the total, the size check, the emit pass.  A cell
+// without a partner is kJoinNone in the buffers.  RV_JOIN_FULL_OUTER: the count pass marks the groups it meets; the build rows of
+// the unmarked groups and of no group are counted before the size check and written behind the probe rows, ascending.
+uint64_t probe_table_kind(rv_ctx *ctx, const rv_join_table *t, const rv_dcolumn *key, rv_join_kind kind, DevBufRef &out_probe, DevBufRef &out_build) {
+    if (kind == RV_JOIN_INNER) return probe_table(ctx, t, key, out_probe, out_build);
+    check_key(key, "rv_join_probe_kind");
+    uint64_t longest = 0;
+    rvk::JoinProbeParams p = probe_params(t, key, longest);
+    const bool full = kind == RV_JOIN_FULL_OUTER;
+    const uint64_t ntiles = (p.n + rvk::kJoinTileRows - 1) / rvk::kJoinTileRows;
+    uint64_t total = 0, tail = 0;
+    DevBufRef tiles, marks, matched, unmatched, tail_rows;
+    Ctrl *ctrl = prepare_ctrl(ctx, 0);
+    if (full) {
+        const size_t mark_bytes = ((t->nslots + 1 + 31) / 32) * 4, row_bytes = ((t->n_build + 63) / 64) * 8;
+        marks = pool_alloc(ctx, mark_bytes + 16);
+        matched = pool_alloc(ctx, row_bytes + 16);
+        unmatched = pool_alloc(ctx, row_bytes + 16);
+        RV_HIP(hipMemsetAsync(marks->ptr, 0, mark_bytes, ctx->stream));
+        RV_HIP(hipMemsetAsync(matched->ptr, 0, row_bytes + 16, ctx->stream));
+    }
+    if (p.n) {
+        tiles = pool_alloc(ctx, ntiles * 8 + 16);
+        p.tile_counts = static_cast<uint64_t *>(tiles->ptr);
+        const dim3 grid(static_cast<uint32_t>(ntiles)), block(rvk::kJoinThreads);
+        uint32_t *m = full ? static_cast<uint32_t *>(marks->ptr) : nullptr;
+        with_kind(kind, [&](auto k) { hipLaunchKernelGGL(rvk::join_probe_count_kind<decltype(k)::value>, grid, block, 0, ctx->stream, p, m); });
+        hipLaunchKernelGGL(rvk::scan_sums_inplace, dim3(1), dim3(1024), 0, ctx->stream, p.tile_counts, ntiles, &ctrl->pops[0]);
+        RV_HIP(hipGetLastError());
+    }
+    if (full && t->n_build) {
+        const rvk::JoinTableView v = table_view(t, key->dtype);
+        if (p.n)
+            hipLaunchKernelGGL(rvk::join_mark_rows, dim3(static_cast<uint32_t>((t->nslots + 1 + 255) / 256)), dim3(256), 0, ctx->stream, v,
+                               static_cast<const uint32_t *>(marks->ptr), static_cast<unsigned long long *>(matched->ptr));
+        hipLaunchKernelGGL(rvk::join_unmatched_words, dim3(grid_for_words(ctx, (t->n_build + 63) / 64, 256)), dim3(256), 0, ctx->stream,
+                           static_cast<const unsigned long long *>(matched->ptr), t->n_build, static_cast<uint64_t *>(unmatched->ptr), &ctrl->pops[1]);
+        RV_HIP(hipGetLastError());
+    }
+    ctx->last_kernel = "join_probe_count";
+    {
+        const Ctrl *h = fetch_ctrl(ctx);
+        total = p.n ? h->pops[0] : 0;
+        tail = h->pops[1];
+    }
+    // refuse what the device cannot hold before anything is allocated
+    require(total <= device_pair_cap(ctx) && tail <= device_pair_cap(ctx) - total, RV_ERR_OOM,
+            fmt("rv_join_probe_kind: %llu rows need %llu x 16 bytes of output, more than the device's %llu bytes", static_cast<unsigned long long>(total + tail),
+                static_cast<unsigned long long>(total + tail), static_cast<unsigned long long>(ctx->props.totalGlobalMem)));
+    if (tail) tail_rows = ascending_rows(ctx, unmatched, t->n_build, tail);  // before the outputs: its scratch is freed first
+    ctx->last_kernel = "join_probe_count";
+    emit_pairs(ctx, p, longest, total, out_probe, out_build, kind, total + tail);
+    if (tail) {
+        hipLaunchKernelGGL(rvk::join_unmatched_tail, dim3(grid_for_words(ctx, tail, 256)), dim3(256), 0, ctx->stream, static_cast<const uint64_t *>(tail_rows->ptr),
+                           tail, static_cast<int64_t *>(out_probe->ptr) + total, static_cast<int64_t *>(out_build->ptr) + total);
+        RV_HIP(hipGetLastError());
+    }
+    RV_HIP(hipStreamSynchronize(ctx->stream));  // the scratch goes back to the pool
+    return total + tail;
+}
+
+// An index buffer of the probe as a public Int64 column: kJoinNone cells become null cells (value 0, validity attached only when
+// there is one, null_count known).
+rv_dcolumn *nullable_index_column(rv_ctx *ctx, const DevBufRef &buf, uint64_t rows) {
+    std::unique_ptr<rv_dcolumn> o(index_column(buf, rows));
+    if (!rows) return o.release();
+    DevBufRef validity = pool_alloc(ctx, std::max<size_t>(bitmap_words_bytes(rows), 16));
+    Ctrl *ctrl = prepare_ctrl(ctx, 0);
+    hipLaunchKernelGGL(rvk::join_index_nulls, dim3(grid_for_words(ctx, rows, 256)), dim3(256), 0, ctx->stream, static_cast<int64_t *>(buf->ptr), rows,
+                       static_cast<uint64_t *>(validity->ptr), &ctrl->pops[0]);
+    RV_HIP(hipGetLastError());
+    o->null_count = static_cast<int64_t>(rows - fetch_ctrl(ctx)->pops[0]);
+    if (o->null_count) o->validity = validity;
+    return o.release();
+}
+
 static_assert(rvt::kJoinFastBatchRows * 4 == static_cast<uint64_t>(rvk::kJoinTileRows), "the fast count pass takes four batches per tile");
 
 // The probe of a window cut into batches of chunk_rows rows (rv_hash_join_chunked): ONE count pass that also counts every batch,
 // the tile scan, ONE read-back of the total and the K batch counts (into batch_rows[K]), the size check, then the emit pass over
 // the longest prefix of batches whose pairs fit `max_pairs` (0: no cap of the caller's) and the device -- at least one batch.
 // Returns the pairs of the prefix; *taken = its batches.
-uint64_t probe_table_batched(rv_ctx *ctx, const rv_join_table *t, const rv_dcolumn *key, uint64_t chunk_rows, uint64_t max_pairs,
-                             uint64_t *batch_rows, uint64_t &taken, DevBufRef &out_probe, DevBufRef &out_build) {
-    check_key(key, "rv_hash_join_chunked");
+// `kind`: RV_JOIN_INNER or a probe-preserving kind; the batch counts then follow the kind's row rule.  `what` names the entry point.
+uint64_t probe_table_batched(rv_ctx *ctx, const char *what, rv_join_kind kind, const rv_join_table *t, const rv_dcolumn *key, uint64_t chunk_rows,
+                             uint64_t max_pairs, uint64_t *batch_rows, uint64_t &taken, DevBufRef &out_probe, DevBufRef &out_build) {
+    check_key(key, what);
     const uint64_t n = key->length;
     const uint64_t nb = (n + chunk_rows - 1) / chunk_rows;
     uint64_t longest = 0;
@@ -219,8 +344,18 @@ uint64_t probe_table_batched(rv_ctx *ctx, const rv_join_table *t, const rv_dcolu
         if (!fast) RV_HIP(hipMemsetAsync(counts->ptr, 0, nb * 8, ctx->stream));
         Ctrl *ctrl = prepare_ctrl(ctx, 0);
         const dim3 grid(static_cast<uint32_t>(ntiles)), block(rvk::kJoinThreads);
-        if (fast) hipLaunchKernelGGL(rvk::join_probe_count_batched<true>, grid, block, 0, ctx->stream, p, b);
-        else hipLaunchKernelGGL(rvk::join_probe_count_batched<false>, grid, block, 0, ctx->stream, p, b);
+        if (kind == RV_JOIN_INNER) {
+            if (fast) hipLaunchKernelGGL(rvk::join_probe_count_batched<true>, grid, block, 0, ctx->stream, p, b);
+            else hipLaunchKernelGGL(rvk::join_probe_count_batched<false>, grid, block, 0, ctx->stream, p, b);
+        } else {
+            with_kind(kind, [&](auto k) {
+                constexpr int K = decltype(k)::value;
+                if constexpr (K != rvk::JOIN_FULL) {  // a full outer join has no batched form: refused by the entry point
+                    if (fast) hipLaunchKernelGGL((rvk::join_probe_count_batched_kind<true, K>), grid, block, 0, ctx->stream, p, b);
+                    else hipLaunchKernelGGL((rvk::join_probe_count_batched_kind<false, K>), grid, block, 0, ctx->stream, p, b);
+                }
+            });
+        }
         hipLaunchKernelGGL(rvk::scan_sums_inplace, dim3(1), dim3(1024), 0, ctx->stream, p.tile_counts, ntiles, &ctrl->pops[0]);
         RV_HIP(hipGetLastError());
         void *hs = ctx->stage(nb * 8);
@@ -229,19 +364,19 @@ uint64_t probe_table_batched(rv_ctx *ctx, const rv_join_table *t, const rv_dcolu
         std::memcpy(batch_rows, hs, nb * 8);
         uint64_t sum = 0;
         for (uint64_t k = 0; k < nb; ++k) sum += batch_rows[k];
-        require(sum == total, RV_ERR_INTERNAL, "rv_hash_join_chunked: per-batch pair counts do not add up");
+        require(sum == total, RV_ERR_INTERNAL, fmt("%s: per-batch pair counts do not add up", what));
     }
     // the longest prefix that fits; one batch the device cannot hold on its own is RV_ERR_OOM before anything is allocated
     const uint64_t device_most = device_pair_cap(ctx);
     const uint64_t cap = max_pairs ? std::min(max_pairs, device_most) : device_most;
     require(nb == 0 || batch_rows[0] <= device_most, RV_ERR_OOM,
-            fmt("rv_hash_join_chunked: batch 0 has %llu pairs, more than the device's %llu bytes hold at 16 bytes each",
+            fmt("%s: batch 0 has %llu pairs, more than the device's %llu bytes hold at 16 bytes each", what,
                 static_cast<unsigned long long>(nb ? batch_rows[0] : 0), static_cast<unsigned long long>(ctx->props.totalGlobalMem)));
     uint64_t pairs = 0;
     taken = 0;
     while (taken < nb && (taken == 0 || (pairs <= cap && batch_rows[taken] <= cap - pairs))) pairs += batch_rows[taken++];
     p.n = std::min(n, taken * chunk_rows);  // the prefix's rows: its tiles' prefixes are those of the whole window
-    emit_pairs(ctx, p, longest, pairs, out_probe, out_build);
+    emit_pairs(ctx, p, longest, pairs, out_probe, out_build, kind);
     // no wait here: `tiles` goes back to the pool, and its next user runs behind the emit pass on the stream
     return pairs;
 }
@@ -264,15 +399,25 @@ void check_join_sides(const char *what, const rv_dcolumn *const *build_cols, uin
 
 // materialize_join_result (plan.rs:212-255): every probe column by probe_idx, then every build column but the key by build_idx.
 // The indices come from the tables themselves: no bounds pre-pass.  The outputs are freed on an error.
+// Other kinds (rv_hash_join_kind): the side that can lack a partner goes through the nullable gather, kJoinNone being the null index;
+// RV_JOIN_FULL_OUTER keeps the build key at its place; semi and anti joins gather the probe columns only.
+uint32_t join_output_columns(rv_join_kind kind, uint32_t n_probe, uint32_t n_build) {
+    return !kind_has_pairs(kind) ? n_probe : kind == RV_JOIN_FULL_OUTER ? n_probe + n_build : n_probe + n_build - 1;
+}
 void gather_pairs(rv_ctx *ctx, const rv_dcolumn *const *build_cols, uint32_t n_build, uint32_t build_key, const rv_dcolumn *const *probe_cols,
-                  uint32_t n_probe, const DevBufRef &pi, const DevBufRef &bi, uint64_t rows, rv_dcolumn **out) {
-    const uint32_t nout = n_probe + n_build - 1;
+                  uint32_t n_probe, const DevBufRef &pi, const DevBufRef &bi, uint64_t rows, rv_dcolumn **out, rv_join_kind kind = RV_JOIN_INNER) {
+    const uint32_t nout = join_output_columns(kind, n_probe, n_build);
     std::vector<const rv_dcolumn *> build_rest;
     for (uint32_t c = 0; c < n_build; ++c)
-        if (c != build_key) build_rest.push_back(build_cols[c]);
+        if (c != build_key || kind == RV_JOIN_FULL_OUTER) build_rest.push_back(build_cols[c]);
+    const IndexNulls none{};  // kJoinNone is the null index
+    const uint64_t *p_idx = static_cast<const uint64_t *>(pi->ptr), *b_idx = bi ? static_cast<const uint64_t *>(bi->ptr) : nullptr;
+    const uint32_t n_rest = static_cast<uint32_t>(build_rest.size());
     try {
-        take_on_device(ctx, probe_cols, n_probe, static_cast<const uint64_t *>(pi->ptr), rows, out, false);
-        take_on_device(ctx, build_rest.data(), static_cast<uint32_t>(build_rest.size()), static_cast<const uint64_t *>(bi->ptr), rows, out + n_probe, false);
+        if (kind == RV_JOIN_FULL_OUTER) take_nullable_on_device(ctx, probe_cols, n_probe, p_idx, rows, out, false, none);
+        else take_on_device(ctx, probe_cols, n_probe, p_idx, rows, out, false);
+        if (kind == RV_JOIN_FULL_OUTER || kind == RV_JOIN_PROBE_OUTER) take_nullable_on_device(ctx, build_rest.data(), n_rest, b_idx, rows, out + n_probe, false, none);
+        else if (kind_has_pairs(kind)) take_on_device(ctx, build_rest.data(), n_rest, b_idx, rows, out + n_probe, false);
         RV_HIP(hipStreamSynchronize(ctx->stream));  // the index buffers go back to the pool
     } catch (...) {
         (void)hipStreamSynchronize(ctx->stream);
@@ -304,6 +449,27 @@ rv_status rv_join_probe(rv_ctx *ctx, const rv_join_table *table, const rv_dcolum
         DevBufRef pi, bi;
         const uint64_t rows = probe_table(ctx, table, probe_key, pi, bi);
         std::unique_ptr<rv_dcolumn> a(index_column(pi, rows)), b(index_column(bi, rows));
+        *out_probe_idx = a.release();
+        *out_build_idx = b.release();
+        if (out_rows) *out_rows = rows;
+    });
+}
+
+rv_status rv_join_probe_kind(rv_ctx *ctx, const rv_join_table *table, const rv_dcolumn *probe_key, int kind_arg, rv_dcolumn **out_probe_idx,
+                             rv_dcolumn **out_build_idx, uint64_t *out_rows) {
+    return guarded([&] {
+        require(ctx && table && probe_key && out_probe_idx && out_build_idx, RV_ERR_INVALID_ARG, "rv_join_probe_kind: NULL argument");
+        check_kind("rv_join_probe_kind", kind_arg);
+        const rv_join_kind kind = static_cast<rv_join_kind>(kind_arg);
+        *out_probe_idx = *out_build_idx = nullptr;
+        set_device(ctx);
+        DevBufRef pi, bi;
+        const uint64_t rows = probe_table_kind(ctx, table, probe_key, kind, pi, bi);
+        std::unique_ptr<rv_dcolumn> a, b;
+        a.reset(kind == RV_JOIN_FULL_OUTER ? nullable_index_column(ctx, pi, rows) : index_column(pi, rows));
+        if (kind == RV_JOIN_FULL_OUTER || kind == RV_JOIN_PROBE_OUTER) b.reset(nullable_index_column(ctx, bi, rows));
+        else if (kind == RV_JOIN_INNER) b.reset(index_column(bi, rows));
+        RV_HIP(hipStreamSynchronize(ctx->stream));
         *out_probe_idx = a.release();
         *out_build_idx = b.release();
         if (out_rows) *out_rows = rows;
@@ -345,32 +511,51 @@ rv_status rv_hash_join(rv_ctx *ctx, const rv_dcolumn *const *build_cols, uint32_
     });
 }
 
-rv_status rv_hash_join_chunked(rv_ctx *ctx, const rv_join_table *table, const rv_dcolumn *const *build_cols, uint32_t n_build, uint32_t build_key,
-                               const rv_dcolumn *const *probe_cols, uint32_t n_probe, uint32_t probe_key, uint64_t chunk_rows, uint64_t max_pairs,
-                               rv_dcolumn **out, uint64_t *out_rows, uint64_t nchunks, int64_t *out_nulls, uint64_t *out_total, uint64_t *out_batches) {
+rv_status rv_hash_join_kind(rv_ctx *ctx, const rv_dcolumn *const *build_cols, uint32_t n_build, uint32_t build_key, const rv_dcolumn *const *probe_cols,
+                            uint32_t n_probe, uint32_t probe_key, int kind_arg, rv_dcolumn **out, uint64_t *out_rows) {
     return guarded([&] {
-        require(ctx && table && build_cols && probe_cols && out && out_batches, RV_ERR_INVALID_ARG, "rv_hash_join_chunked: NULL argument");
-        require(chunk_rows >= 1, RV_ERR_INVALID_ARG, "rv_hash_join_chunked: chunk_rows is 0");
-        check_join_sides("rv_hash_join_chunked", build_cols, n_build, build_key, probe_cols, n_probe, probe_key);
+        require(ctx && build_cols && probe_cols && out, RV_ERR_INVALID_ARG, "rv_hash_join_kind: NULL argument");
+        check_kind("rv_hash_join_kind", kind_arg);
+        const rv_join_kind kind = static_cast<rv_join_kind>(kind_arg);
+        check_join_sides("rv_hash_join_kind", build_cols, n_build, build_key, probe_cols, n_probe, probe_key);
+        set_device(ctx);
+        const uint32_t nout = join_output_columns(kind, n_probe, n_build);
+        for (uint32_t c = 0; c < nout; ++c) out[c] = nullptr;
+        std::unique_ptr<rv_join_table> t = build_table(ctx, build_cols[build_key]);
+        DevBufRef pi, bi;
+        const uint64_t rows = probe_table_kind(ctx, t.get(), probe_cols[probe_key], kind, pi, bi);
+        gather_pairs(ctx, build_cols, n_build, build_key, probe_cols, n_probe, pi, bi, rows, out, kind);
+        if (out_rows) *out_rows = rows;
+    });
+}
+
+// rv_hash_join_chunked and rv_hash_join_chunked_kind, `what` the entry point's name
+static void hash_join_chunked(rv_ctx *ctx, const char *what, rv_join_kind kind, const rv_join_table *table, const rv_dcolumn *const *build_cols, uint32_t n_build,
+                       uint32_t build_key, const rv_dcolumn *const *probe_cols, uint32_t n_probe, uint32_t probe_key, uint64_t chunk_rows, uint64_t max_pairs,
+                       rv_dcolumn **out, uint64_t *out_rows, uint64_t nchunks, int64_t *out_nulls, uint64_t *out_total, uint64_t *out_batches) {
+    {
+        require(ctx && table && build_cols && probe_cols && out && out_batches, RV_ERR_INVALID_ARG, fmt("%s: NULL argument", what));
+        require(chunk_rows >= 1, RV_ERR_INVALID_ARG, fmt("%s: chunk_rows is 0", what));
+        check_join_sides(what, build_cols, n_build, build_key, probe_cols, n_probe, probe_key);
         require(build_cols[build_key]->length == table->n_build, RV_ERR_LENGTH_MISMATCH,
-                fmt("rv_hash_join_chunked: build columns of %llu rows, the table was built from %llu", static_cast<unsigned long long>(build_cols[build_key]->length),
+                fmt("%s: build columns of %llu rows, the table was built from %llu", what, static_cast<unsigned long long>(build_cols[build_key]->length),
                     static_cast<unsigned long long>(table->n_build)));
         const uint64_t n = probe_cols[0]->length;
         // dataframe_to_batches: ceil(n / chunk_rows) batches, none for an empty frame (streaming.rs:135-233)
         const uint64_t nb = (n + chunk_rows - 1) / chunk_rows;
         require(nb <= nchunks && (out_rows || nb == 0), RV_ERR_INVALID_ARG,
-                fmt("rv_hash_join_chunked: %llu batches, room for %llu", static_cast<unsigned long long>(nb), static_cast<unsigned long long>(nchunks)));
+                fmt("%s: %llu batches, room for %llu", what, static_cast<unsigned long long>(nb), static_cast<unsigned long long>(nchunks)));
         set_device(ctx);
-        const uint32_t nout = n_probe + n_build - 1;
+        const uint32_t nout = join_output_columns(kind, n_probe, n_build);
         for (uint32_t c = 0; c < nout; ++c) out[c] = nullptr;
         *out_batches = 0;
         std::vector<uint64_t> counts(nb);
         uint64_t taken = 0;
         DevBufRef pi, bi;
-        const uint64_t rows = probe_table_batched(ctx, table, probe_cols[probe_key], chunk_rows, max_pairs, counts.data(), taken, pi, bi);
-        gather_pairs(ctx, build_cols, n_build, build_key, probe_cols, n_probe, pi, bi, rows, out);
+        const uint64_t rows = probe_table_batched(ctx, what, kind, table, probe_cols[probe_key], chunk_rows, max_pairs, counts.data(), taken, pi, bi);
+        gather_pairs(ctx, build_cols, n_build, build_key, probe_cols, n_probe, pi, bi, rows, out, kind);
         try {
-            if (out_nulls) batch_null_counts(ctx, "rv_hash_join_chunked", out, nout, counts.data(), taken, out_nulls);
+            if (out_nulls) batch_null_counts(ctx, what, out, nout, counts.data(), taken, out_nulls);
         } catch (...) {
             drop_outputs(out, nout);
             throw;
@@ -378,6 +563,29 @@ rv_status rv_hash_join_chunked(rv_ctx *ctx, const rv_join_table *table, const rv
         if (nb) std::memcpy(out_rows, counts.data(), nb * 8);
         if (out_total) *out_total = rows;
         *out_batches = taken;
+    }
+}
+
+rv_status rv_hash_join_chunked(rv_ctx *ctx, const rv_join_table *table, const rv_dcolumn *const *build_cols, uint32_t n_build, uint32_t build_key,
+                               const rv_dcolumn *const *probe_cols, uint32_t n_probe, uint32_t probe_key, uint64_t chunk_rows, uint64_t max_pairs,
+                               rv_dcolumn **out, uint64_t *out_rows, uint64_t nchunks, int64_t *out_nulls, uint64_t *out_total, uint64_t *out_batches) {
+    return guarded([&] {
+        hash_join_chunked(ctx, "rv_hash_join_chunked", RV_JOIN_INNER, table, build_cols, n_build, build_key, probe_cols, n_probe, probe_key, chunk_rows, max_pairs,
+                          out, out_rows, nchunks, out_nulls, out_total, out_batches);
+    });
+}
+
+rv_status rv_hash_join_chunked_kind(rv_ctx *ctx, const rv_join_table *table, const rv_dcolumn *const *build_cols, uint32_t n_build, uint32_t build_key,
+                                    const rv_dcolumn *const *probe_cols, uint32_t n_probe, uint32_t probe_key, int kind_arg, uint64_t chunk_rows,
+                                    uint64_t max_pairs, rv_dcolumn **out, uint64_t *out_rows, uint64_t nchunks, int64_t *out_nulls, uint64_t *out_total,
+                                    uint64_t *out_batches) {
+    return guarded([&] {
+        check_kind("rv_hash_join_chunked_kind", kind_arg);
+        const rv_join_kind kind = static_cast<rv_join_kind>(kind_arg);
+        require(kind != RV_JOIN_FULL_OUTER, RV_ERR_UNSUPPORTED,
+                "rv_hash_join_chunked_kind: RV_JOIN_FULL_OUTER has no batched form (its unmatched build rows belong to no probe batch); use rv_hash_join_kind");
+        hash_join_chunked(ctx, "rv_hash_join_chunked_kind", kind, table, build_cols, n_build, build_key, probe_cols, n_probe, probe_key, chunk_rows, max_pairs,
+                          out, out_rows, nchunks, out_nulls, out_total, out_batches);
     });
 }
 

@@ -1,4 +1,5 @@
-// Inner hash join (reference PhysicalPlan::HashJoin, plan.rs:174-284): the build-side table and the probe kernels.
+// Hash join (reference PhysicalPlan::HashJoin, plan.rs:174-284): the build-side table and the probe kernels, for the inner join and
+// the outer, semi and anti joins.
 //
 // Layout of a build table (join.hip, build_table):
 //   rows   uint32 build row ids: the non-null, non-NaN rows grouped by key, each group ascending (a stable radix sort of
@@ -91,6 +92,51 @@ __device__ __forceinline__ uint32_t join_lookup(const JoinTableView &t, uint32_t
     }
 }
 
+// ---- join kinds -----------------------------------------------------------------------------------------------------------------
+// rv_join_kind as a compile-time constant of the probe kernels.  The inner join is the kernels below under their old names; every
+// other kind is the same body with another row rule.
+enum : int { JOIN_INNER = 0, JOIN_OUTER = 1, JOIN_FULL = 2, JOIN_SEMI = 3, JOIN_ANTI = 4 };
+constexpr uint64_t kJoinNone = ~0ull;  // "no partner" inside the index buffers; the public columns get a null cell for it
+
+// Output rows of a probe row with c matches: the one rule the count passes and the emit pass share.
+template <int KIND>
+__device__ __forceinline__ uint32_t join_rows(uint32_t c) {
+    if (KIND == JOIN_OUTER || KIND == JOIN_FULL) return c ? c : 1u;
+    if (KIND == JOIN_SEMI) return c != 0;
+    if (KIND == JOIN_ANTI) return c == 0;
+    return c;
+}
+
+// join_lookup that also names the group it met, for the marks of the full outer join: the slot of a key group, the table's slot
+// count for the null group (bit `slots` of the marks).  Meaningful only where the returned count is not 0.
+__device__ __forceinline__ uint32_t join_lookup_at(const JoinTableView &t, uint32_t cls, uint64_t bits, uint32_t &start, uint64_t &group) {
+    start = 0;
+    group = t.slot_mask + 1;
+    if (cls == JK_NULL) {
+        start = t.null_start;
+        return t.null_count;
+    }
+    if (cls != JK_VALUE || !t.match_values) return 0;
+    uint64_t s = join_hash(bits) & t.hash_mask & t.slot_mask;
+    for (;;) {
+        const ulonglong2 e = *reinterpret_cast<const ulonglong2 *>(&t.slots[2 * s]);
+        if (e.y == 0) return 0;
+        if (e.x == bits) {
+            start = static_cast<uint32_t>(e.y);
+            group = s;
+            return static_cast<uint32_t>(e.y >> 32);
+        }
+        s = (s + 1) & t.slot_mask;
+    }
+}
+
+// One bit per group a probe row met (JOIN_FULL's count pass): a plain load first, the atomic only while the bit is clear, so a hot
+// key costs one atomic and not one per probe row.  A stale load only repeats an idempotent OR.
+__device__ __forceinline__ void join_mark(uint32_t *marks, uint64_t group) {
+    const uint32_t bit = 1u << (group & 31);
+    if (!(marks[group >> 5] & bit)) atomicOr(&marks[group >> 5], bit);
+}
+
 // ---- build ----------------------------------------------------------------------------------------------------------------------
 // Bitmaps (offset 0) of the rows whose key goes into the table (`keep`: valid, not NaN) and of the null rows; their popcounts
 // are added to counts[0] / counts[1] once per wave.
@@ -176,8 +222,10 @@ struct JoinProbeParams {
     uint32_t lane_most;     // emit, mode 2: lists longer than this are written by the whole workgroup
 };
 
-// Pass 1: matches per tile of kJoinTileRows probe rows (64-bit: one row can match every build row).
-static __global__ __launch_bounds__(kJoinThreads) void join_probe_count(JoinProbeParams p) {
+// Pass 1: output rows per tile of kJoinTileRows probe rows (64-bit: one row can match every build row).  JOIN_FULL also marks
+// the groups it meets.
+template <int KIND>
+__device__ __forceinline__ void join_count_body(const JoinProbeParams p, uint32_t *marks) {
     __shared__ uint64_t s_wave[kJoinThreads / 64];
     const uint64_t base = static_cast<uint64_t>(blockIdx.x) * kJoinTileRows + threadIdx.x;
     uint64_t mine = 0;
@@ -188,7 +236,14 @@ static __global__ __launch_bounds__(kJoinThreads) void join_probe_count(JoinProb
             uint64_t bits;
             const uint32_t cls = join_key(p.key, i, bits);
             uint32_t start;
-            mine += join_lookup(p.table, cls, bits, start);
+            if (KIND == JOIN_FULL) {
+                uint64_t group;
+                const uint32_t c = join_lookup_at(p.table, cls, bits, start, group);
+                if (c) join_mark(marks, group);
+                mine += join_rows<KIND>(c);
+            } else {
+                mine += join_rows<KIND>(join_lookup(p.table, cls, bits, start));
+            }
         }
     }
     mine = wave_sum64(mine);
@@ -201,6 +256,9 @@ static __global__ __launch_bounds__(kJoinThreads) void join_probe_count(JoinProb
         p.tile_counts[blockIdx.x] = t;
     }
 }
+static __global__ __launch_bounds__(kJoinThreads) void join_probe_count(JoinProbeParams p) { join_count_body<JOIN_INNER>(p, nullptr); }
+template <int KIND>
+static __global__ __launch_bounds__(kJoinThreads) void join_probe_count_kind(JoinProbeParams p, uint32_t *marks) { join_count_body<KIND>(p, marks); }
 
 // Pass 1 of a probe cut into batches of chunk_rows rows (rv_hash_join_chunked): the tile counts of join_probe_count and, in the
 // same pass, the pairs of every batch -- batch b is probe rows [b * chunk_rows, min((b + 1) * chunk_rows, n)).
@@ -218,8 +276,8 @@ struct JoinBatchParams {
     unsigned long long *batch_counts;  // [nbatches]
 };
 
-template <bool FAST>
-static __global__ __launch_bounds__(kJoinThreads) void join_probe_count_batched(JoinProbeParams p, JoinBatchParams b) {
+template <bool FAST, int KIND>
+__device__ __forceinline__ void join_count_batched_body(const JoinProbeParams p, const JoinBatchParams b) {
     __shared__ uint64_t s_wave[4][kJoinThreads / 64];
     __shared__ unsigned long long s_batch[FAST ? 1 : kJoinTileBatchSlots];
     const int lane = lane_id(), wave = threadIdx.x >> 6;
@@ -233,7 +291,7 @@ static __global__ __launch_bounds__(kJoinThreads) void join_probe_count_batched(
                 uint64_t bits;
                 const uint32_t cls = join_key(p.key, i, bits);
                 uint32_t start;
-                part[k >> 2] += join_lookup(p.table, cls, bits, start);
+                part[k >> 2] += join_rows<KIND>(join_lookup(p.table, cls, bits, start));
             }
         }
 #pragma unroll
@@ -276,7 +334,7 @@ static __global__ __launch_bounds__(kJoinThreads) void join_probe_count_batched(
             uint64_t bits;
             const uint32_t cls = join_key(p.key, i, bits);
             uint32_t start;
-            c = join_lookup(p.table, cls, bits, start);
+            c = join_rows<KIND>(join_lookup(p.table, cls, bits, start));
         }
         mine += c;
         uint64_t incl = c;
@@ -318,6 +376,14 @@ static __global__ __launch_bounds__(kJoinThreads) void join_probe_count_batched(
         else if (s_batch[t]) atomicAdd(&b.batch_counts[bi], s_batch[t]);
     }
 }
+template <bool FAST>
+static __global__ __launch_bounds__(kJoinThreads) void join_probe_count_batched(JoinProbeParams p, JoinBatchParams b) {
+    join_count_batched_body<FAST, JOIN_INNER>(p, b);
+}
+template <bool FAST, int KIND>
+static __global__ __launch_bounds__(kJoinThreads) void join_probe_count_batched_kind(JoinProbeParams p, JoinBatchParams b) {
+    join_count_batched_body<FAST, KIND>(p, b);
+}
 
 // exclusive prefix of v over the workgroup, in thread order; *total = the workgroup's sum (every thread)
 __device__ __forceinline__ uint64_t join_block_scan(uint64_t v, uint64_t *s_wave, uint64_t &total) {
@@ -345,8 +411,13 @@ __device__ __forceinline__ uint64_t join_block_scan(uint64_t v, uint64_t *s_wave
 // foreign-key join): a stream compaction, positions from a ballot.  MODE 1: lists of at most lane_most rows, each written by its
 // lane.  MODE 2: longer lists as well -- queued in LDS and written by the whole workgroup, so that a key with thousands of build
 // rows does not serialise on one lane.
-template <int MODE>
-static __global__ __launch_bounds__(kJoinThreads) void join_probe_emit(JoinProbeParams p) {
+// KIND: JOIN_OUTER / JOIN_FULL write (row, kJoinNone) for a probe row without a match, at its place.  JOIN_SEMI / JOIN_ANTI keep
+// or drop a probe row as a whole and write its index only: always MODE 0's compaction, whatever the lists' lengths.
+template <int MODE, int KIND>
+__device__ __forceinline__ void join_emit_body(const JoinProbeParams p) {
+    constexpr bool kPairs = KIND != JOIN_SEMI && KIND != JOIN_ANTI;
+    constexpr bool kKeepsMisses = KIND == JOIN_OUTER || KIND == JOIN_FULL;
+    static_assert(kPairs || MODE == 0, "semi and anti joins are compactions");
     __shared__ uint64_t s_wave[kJoinThreads / 64];
     __shared__ uint64_t s_q_out[kJoinThreads], s_q_row[kJoinThreads];
     __shared__ uint32_t s_q_start[kJoinThreads], s_q_count[kJoinThreads];
@@ -365,7 +436,8 @@ static __global__ __launch_bounds__(kJoinThreads) void join_probe_emit(JoinProbe
             count = join_lookup(p.table, cls, bits, start);
         }
         if (MODE == 0) {
-            const uint64_t m = ballot64(count != 0);
+            const bool keep = KIND == JOIN_INNER ? count != 0 : (i < p.n && join_rows<KIND>(count) != 0);
+            const uint64_t m = ballot64(keep);
             if (lane == 0) s_wave[wave] = __popcll(m);
             __syncthreads();
             uint64_t before = 0, all = 0;
@@ -374,16 +446,17 @@ static __global__ __launch_bounds__(kJoinThreads) void join_probe_emit(JoinProbe
                 before += w < wave ? s_wave[w] : 0;
                 all += s_wave[w];
             }
-            if (count) {
+            if (keep) {
                 const uint64_t o = out + before + __popcll(m & low_mask(lane));
                 p.out_probe[o] = static_cast<int64_t>(i);
-                p.out_build[o] = p.table.rows[start];
+                if (kPairs) p.out_build[o] = (!kKeepsMisses || count) ? static_cast<int64_t>(p.table.rows[start]) : static_cast<int64_t>(kJoinNone);
             }
             out += all;
             __syncthreads();
         } else {
+            const uint32_t rows = KIND == JOIN_INNER ? count : (i < p.n ? join_rows<KIND>(count) : 0u);
             uint64_t all;
-            const uint64_t o = out + join_block_scan(count, s_wave, all);
+            const uint64_t o = out + join_block_scan(rows, s_wave, all);
             if (MODE == 2 && count > p.lane_most) {
                 const uint32_t q = atomicAdd(&s_q_n, 1u);
                 s_q_out[q] = o;
@@ -394,6 +467,10 @@ static __global__ __launch_bounds__(kJoinThreads) void join_probe_emit(JoinProbe
                 for (uint32_t j = 0; j < count; ++j) {
                     p.out_probe[o + j] = static_cast<int64_t>(i);
                     p.out_build[o + j] = p.table.rows[start + j];
+                }
+                if (kKeepsMisses && rows && !count) {
+                    p.out_probe[o] = static_cast<int64_t>(i);
+                    p.out_build[o] = static_cast<int64_t>(kJoinNone);
                 }
             }
             out += all;
@@ -414,6 +491,91 @@ static __global__ __launch_bounds__(kJoinThreads) void join_probe_emit(JoinProbe
             }
         }
     }
+}
+template <int MODE>
+static __global__ __launch_bounds__(kJoinThreads) void join_probe_emit(JoinProbeParams p) { join_emit_body<MODE, JOIN_INNER>(p); }
+template <int MODE, int KIND>
+static __global__ __launch_bounds__(kJoinThreads) void join_probe_emit_kind(JoinProbeParams p) { join_emit_body<MODE, KIND>(p); }
+
+// ---- full outer join: the build rows no probe row met ----------------------------------------------------------------------------
+// marks (one bit per slot, bit `slots` for the null group) -> a bitmap of the build rows of the marked groups.  A wave takes 64 slots:
+// short groups are set by their lane, longer ones by the whole wave.  The bits are ORed in: the bitmap is the same whatever order
+// the atomics land in.  Rows in no group (NaN keys) are never set.
+constexpr uint32_t kJoinMarkLaneMost = 8;
+static __global__ __launch_bounds__(256) void join_mark_rows(JoinTableView t, const uint32_t *marks, unsigned long long *matched) {
+    const int lane = lane_id();
+    const uint64_t nslots = t.slot_mask + 1;
+    const uint64_t g = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;  // group: a slot, or nslots for the null group
+    uint32_t start = 0, count = 0;
+    if (g <= nslots && ((marks[g >> 5] >> (g & 31)) & 1)) {
+        if (g == nslots) {
+            start = t.null_start;
+            count = t.null_count;
+        } else {
+            const uint64_t y = t.slots[2 * g + 1];
+            start = static_cast<uint32_t>(y);
+            count = static_cast<uint32_t>(y >> 32);
+        }
+    }
+    if (count <= kJoinMarkLaneMost)
+        for (uint32_t j = 0; j < count; ++j) {
+            const uint32_t r = t.rows[start + j];
+            atomicOr(&matched[r >> 6], 1ull << (r & 63));
+        }
+    uint64_t wide = ballot64(count > kJoinMarkLaneMost);
+    while (wide) {  // wave-uniform
+        const int src = __ffsll(static_cast<long long>(wide)) - 1;
+        wide &= wide - 1;
+        const uint32_t s = __shfl(start, src, 64), c = __shfl(count, src, 64);
+        for (uint32_t j = lane; j < c; j += 64) {
+            const uint32_t r = t.rows[s + j];
+            atomicOr(&matched[r >> 6], 1ull << (r & 63));
+        }
+    }
+}
+
+// unmatched = the complement of `matched` over [0, n), bits past the last row zero; *count += its set bits
+static __global__ __launch_bounds__(256) void join_unmatched_words(const unsigned long long *matched, uint64_t n, uint64_t *unmatched, unsigned long long *count) {
+    const uint64_t nwords = (n + 63) / 64;
+    unsigned long long pop = 0;
+    for (uint64_t w = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; w < nwords; w += static_cast<uint64_t>(gridDim.x) * blockDim.x) {
+        const uint64_t u = ~matched[w] & low_mask(n - w * 64);
+        unmatched[w] = u;
+        pop += __popcll(u);
+    }
+    pop = wave_sum64(pop);
+    if (lane_id() == 0 && pop) atomicAdd(count, pop);
+}
+
+// the tail of the full outer join: (none, b) for the unmatched build rows, ascending
+static __global__ __launch_bounds__(256) void join_unmatched_tail(const uint64_t *rows, uint64_t n, int64_t *out_probe, int64_t *out_build) {
+    for (uint64_t j = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; j < n; j += static_cast<uint64_t>(gridDim.x) * blockDim.x) {
+        out_probe[j] = static_cast<int64_t>(kJoinNone);
+        out_build[j] = static_cast<int64_t>(rows[j]);
+    }
+}
+
+// An index buffer with kJoinNone cells as a nullable Int64 column: the validity words, 0 under a null, *valid_pop += the valid cells.
+static __global__ __launch_bounds__(256) void join_index_nulls(int64_t *idx, uint64_t n, uint64_t *validity, unsigned long long *valid_pop) {
+    const int lane = lane_id();
+    const uint64_t nchunks = (n + 63) / 64;
+    const uint64_t wave0 = (static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x) >> 6;
+    const uint64_t nwaves = (static_cast<uint64_t>(gridDim.x) * blockDim.x) >> 6;
+    unsigned long long pop = 0;
+    for (uint64_t c = wave0; c < nchunks; c += nwaves) {
+        const uint64_t i = c * 64 + lane;
+        bool valid = false;
+        if (i < n) {
+            valid = static_cast<uint64_t>(idx[i]) != kJoinNone;
+            if (!valid) idx[i] = 0;
+        }
+        const uint64_t m = ballot64(valid);
+        if (lane == 0) {
+            validity[c] = m;
+            pop += static_cast<unsigned long long>(__popcll(m));
+        }
+    }
+    if (lane == 0 && pop) atomicAdd(valid_pop, pop);
 }
 
 }  // namespace rvk

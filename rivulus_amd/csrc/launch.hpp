@@ -193,6 +193,9 @@ DevBufRef selection_prefix(rv_ctx *ctx, const rv_dcolumn *sel, uint64_t rows);
 DevBufRef selection_to_indices(rv_ctx *ctx, const rv_dcolumn *sel, uint64_t rows, const DevBufRef &excl);
 rv_dcolumn *compact_boolean(rv_ctx *ctx, const rv_dcolumn *src, const rv_dcolumn *sel, uint64_t rows, const DevBufRef &excl);
 rv_dcolumn *gather_strings(rv_ctx *ctx, const rv_dcolumn *src, const uint64_t *d_indices, uint64_t n);
+// the two ends of a String gather, shared with the nullable gather (take_nullable.hip)
+std::unique_ptr<rv_dcolumn> empty_string_gather(rv_ctx *ctx, uint64_t n);
+void finish_string_gather(rv_ctx *ctx, rv_dcolumn *o, rvk::StrGather &g, uint64_t n, Ctrl *ctrl);
 rv_dcolumn *gather_strings_selected(rv_ctx *ctx, const rv_dcolumn *src, const rv_dcolumn *sel, uint64_t rows, const DevBufRef &excl);
 bool str_sel_eligible(const rv_dcolumn *sel, const RangeOffsets &ranges);
 void str_sel_queue(rv_ctx *ctx, const rv_dcolumn *src, const rv_dcolumn *sel, const RangeOffsets &ranges, Ctrl *ctrl, int slot, StrSelLaunch &L);
@@ -253,6 +256,17 @@ inline void drop_outputs(rv_dcolumn **out, uint32_t n) {
 // RecordBatch::take with the index list in HBM (bounds pre-pass unless check_bounds is false), one gather per column
 void take_on_device(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, const uint64_t *d_idx, uint64_t n_indices, rv_dcolumn **out,
                     bool check_bounds = true);
+
+// ---- take_nullable.hip -------------------------------------------------------------------------------------
+// A nullable index list of the gathers: a null index yields a null cell of the column's dtype.  validity: the list's bitmap, read
+// at bit offset + i; nullptr: an all-ones index is the null (what the join's probe leaves in its index buffers).
+struct IndexNulls {
+    const uint8_t *validity = nullptr;
+    uint64_t offset = 0;
+};
+// take_on_device over such a list; the outputs carry validity wherever a null index fell
+void take_nullable_on_device(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, const uint64_t *d_idx, uint64_t n_indices, rv_dcolumn **out,
+                             bool check_bounds, const IndexNulls &nulls);
 
 // ---- query.hip ---------------------------------------------------------------------------------------------
 uint64_t filter_by_groups(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, const rv_term *terms, uint32_t nterms, rv_null_policy policy,

@@ -1536,15 +1536,49 @@ inline void without_key_helper(const ProbeColumns &p, std::vector<ArrayRef> &out
     out.erase(out.begin() + static_cast<long>(*p.helper_at));
 }
 
+// The join types of the plans.  The reference has Inner alone (logical_plan/plan.rs: //Left, //Outer) and makes the LEFT frame the
+// build side (planner.rs:102-108).  Inner, Right and Outer keep that: Right is rv_join_kind PROBE_OUTER, Outer FULL_OUTER.  For
+// Left, Semi and Anti the plan SWAPS the sides -- the left frame probes a table built on the right frame -- so that Left is
+// PROBE_OUTER with the left frame's columns first, and Semi / Anti keep (drop) the left frame's rows that have a partner.
+enum class JoinType { Inner, Left, Right, Outer, Semi, Anti };
+struct JoinShape {
+    rv_join_kind kind;
+    bool swapped;  // the left frame is the probe side
+};
+inline JoinShape join_shape(JoinType t) {
+    switch (t) {
+        case JoinType::Inner: return {RV_JOIN_INNER, false};
+        case JoinType::Right: return {RV_JOIN_PROBE_OUTER, false};
+        case JoinType::Outer: return {RV_JOIN_FULL_OUTER, false};
+        case JoinType::Left: return {RV_JOIN_PROBE_OUTER, true};
+        case JoinType::Semi: return {RV_JOIN_PROBE_SEMI, true};
+        case JoinType::Anti: return {RV_JOIN_PROBE_ANTI, true};
+    }
+    throw Panic("unreachable");
+}
+
 // materialize_join_result (plan.rs:212-255): every probe field, then every build field but the key, `_right` on a name the probe
-// side has too
-inline std::vector<Field> join_output_fields(const Schema &probe, const Schema &build, size_t build_key) {
-    std::vector<Field> f = probe.fields();
+// side has too.  The other kinds: FULL_OUTER keeps the build key at its place (under the same rule: `_right` when the probe side
+// has the name, as it does for equally named keys); a semi or anti join has the probe fields only.  A side that can lack a partner
+// is nullable.
+inline std::vector<Field> join_output_fields(const Schema &probe, const Schema &build, size_t build_key, rv_join_kind kind = RV_JOIN_INNER) {
+    std::vector<Field> f;
+    for (const Field &p : probe.fields()) f.push_back(kind == RV_JOIN_FULL_OUTER ? Field{p.name(), p.data_type(), true} : p);
+    if (kind == RV_JOIN_PROBE_SEMI || kind == RV_JOIN_PROBE_ANTI) return f;
+    const bool partial = kind == RV_JOIN_PROBE_OUTER || kind == RV_JOIN_FULL_OUTER;
     for (size_t i = 0; i < build.num_fields(); ++i) {
         const Field &b = build.field(i);
-        if (i != build_key) f.push_back(Field{probe.field_by_name(b.name()) ? b.name() + "_right" : b.name(), b.data_type(), b.is_nullable()});
+        if (i != build_key || kind == RV_JOIN_FULL_OUTER)
+            f.push_back(Field{probe.field_by_name(b.name()) ? b.name() + "_right" : b.name(), b.data_type(), partial || b.is_nullable()});
     }
     return f;
+}
+// FULL_OUTER with a String build key: the ids stand in for the key inside the table, but the key column of the result must be the
+// strings.  The original key rides along as one more build column (the last) and takes the ids column's place among the outputs:
+// `out` = n_probe probe columns (a key helper included), then the build columns, then the carried key.
+inline void restore_build_key(std::vector<ArrayRef> &out, size_t n_probe, size_t build_key) {
+    out[n_probe + build_key] = out.back();
+    out.pop_back();
 }
 
 // One side of a streaming join: a stream, or a resident frame (a DataFrameSource: its columns after dataframe_to_batches' null
@@ -1562,7 +1596,8 @@ struct JoinSide {
     }
 };
 
-// GpuHashJoinStream -- StreamingPhysicalPlan::HashJoin, inner (the reference's arm is todo!(), streaming.rs:128-131), defined by
+// GpuHashJoinStream -- StreamingPhysicalPlan::HashJoin (the reference's arm is todo!(), streaming.rs:128-131), for the inner join and
+// the probe-preserving kinds PROBE_OUTER, PROBE_SEMI and PROBE_ANTI (rv_hash_join_chunked_kind; a full outer join is refused), defined by
 // the eager join: the build side is drained once (one batch as it is, several joined by RecordBatch::concat) and hashed
 // (rv_join_build); then EXACTLY one output batch per probe batch, empty ones included, in probe order, each == rv_hash_join of
 // the whole build side against that probe batch alone -- names, `_right` suffixes, row order and key rules of the eager join.
@@ -1578,9 +1613,12 @@ struct JoinSide {
 class GpuHashJoinStream : public DataStream {
   public:
     GpuHashJoinStream(JoinSide build, JoinSide probe, std::string build_key, std::string probe_key, size_t window_rows = size_t(1) << 28,
-                      uint64_t max_pairs = uint64_t(1) << 28)
+                      uint64_t max_pairs = uint64_t(1) << 28, rv_join_kind kind = RV_JOIN_INNER)
         : build_(std::move(build)), probe_(std::move(probe)), build_key_(std::move(build_key)), probe_key_(std::move(probe_key)),
-          window_rows_(std::max<size_t>(1, window_rows)), max_pairs_(max_pairs) {
+          window_rows_(std::max<size_t>(1, window_rows)), max_pairs_(max_pairs), kind_(kind) {
+        if (kind_ == RV_JOIN_FULL_OUTER)
+            throw Error(RV_ERR_UNSUPPORTED, "GpuHashJoinStream: a full outer join is not streamed (its unmatched build rows belong to no probe batch); "
+                                            "use the eager plan, PhysicalPlan::hash_join");
         build_schema_ = build_.schema();
         probe_schema_ = probe_.schema();
         auto bk = build_schema_->index_of(build_key_);
@@ -1589,7 +1627,7 @@ class GpuHashJoinStream : public DataStream {
         if (!pk) throw StreamError::execution("Column '" + probe_key_ + "' not found in schema");
         bki_ = static_cast<uint32_t>(*bk);
         pki_ = static_cast<uint32_t>(*pk);
-        output_schema_ = std::make_shared<const Schema>(join_output_fields(*probe_schema_, *build_schema_, bki_));
+        output_schema_ = std::make_shared<const Schema>(join_output_fields(*probe_schema_, *build_schema_, bki_, kind_));
         string_keys_ = std::make_unique<StringKeyEncoder>(build_schema_->field(bki_).data_type(), probe_schema_->field(pki_).data_type());
         probe_rows_ = probe_.stream ? 0 : (probe_.columns.empty() ? 0 : probe_.columns[0]->len());
     }
@@ -1650,8 +1688,14 @@ class GpuHashJoinStream : public DataStream {
         rows.assign(std::max<uint64_t>(nb, 1), 0);
         nulls.assign(std::max<uint64_t>(nb, 1) * nout, 0);
         uint64_t taken = 0;
-        check_stream(rv_hash_join_chunked(ctx->raw(), table_, build_handles_.data(), static_cast<uint32_t>(build_handles_.size()), bki_, p.cols.data(),
-                                          static_cast<uint32_t>(p.cols.size()), p.key, chunk, max_pairs_, raw.data(), rows.data(), nb, nulls.data(), &pairs, &taken));
+        if (kind_ == RV_JOIN_INNER)
+            check_stream(rv_hash_join_chunked(ctx->raw(), table_, build_handles_.data(), static_cast<uint32_t>(build_handles_.size()), bki_, p.cols.data(),
+                                              static_cast<uint32_t>(p.cols.size()), p.key, chunk, max_pairs_, raw.data(), rows.data(), nb, nulls.data(), &pairs,
+                                              &taken));
+        else
+            check_stream(rv_hash_join_chunked_kind(ctx->raw(), table_, build_handles_.data(), static_cast<uint32_t>(build_handles_.size()), bki_, p.cols.data(),
+                                                   static_cast<uint32_t>(p.cols.size()), p.key, kind_, chunk, max_pairs_, raw.data(), rows.data(), nb,
+                                                   nulls.data(), &pairs, &taken));
         out.clear();
         for (auto *h : raw) out.push_back(Array::adopt(ctx, h));
         rows.resize(taken);
@@ -1716,6 +1760,7 @@ class GpuHashJoinStream : public DataStream {
     std::string build_key_, probe_key_;
     size_t window_rows_;
     uint64_t max_pairs_;
+    rv_join_kind kind_;
     SchemaRef build_schema_, probe_schema_, output_schema_;
     uint32_t bki_ = 0, pki_ = 0;
     rv_join_table *table_ = nullptr;
@@ -2025,6 +2070,7 @@ struct Expr {
 // ---------------------------------------------------------------------------------------
 namespace physical_plan {
 using execution::CompareTerm;
+using execution::JoinType;
 using expressions::BinaryOperator;
 using expressions::Expr;
 
@@ -2329,7 +2375,8 @@ class StreamingPhysicalPlan {
     execution::LoweredPredicate predicate;
     std::vector<std::string> columns;
     size_t n = 0;
-    StreamingPlanPtr build_side;  // HashJoin { build_side, probe_side = input, build_key, probe_key }, inner
+    StreamingPlanPtr build_side;  // HashJoin { build_side, probe_side = input, build_key, probe_key, join_kind }: the sides as joined
+    rv_join_kind join_kind = RV_JOIN_INNER;
     std::string build_key, probe_key;
     std::string group_key;  // GroupBy { input, group_key, aggs }
     std::vector<execution::AggSpec> aggs;
@@ -2413,13 +2460,25 @@ class StreamingPhysicalPlan {
 
     // streaming.rs:128-131 (todo!() in the reference), defined by the eager join: the left plan is the build side, the right the
     // probe side (planner.rs:102-108); one output batch per probe batch
-    static StreamingPlanPtr hash_join(StreamingPlanPtr build, StreamingPlanPtr probe, std::string build_key, std::string probe_key) {
+    // `type`: Inner, Left, Right, Semi or Anti (execution::join_shape: Left, Semi and Anti swap the sides, so the left plan is then the
+    // streamed probe side).  Outer is refused: a trailing batch of unmatched build rows is not built; the eager plan has it.
+    static StreamingPlanPtr hash_join(StreamingPlanPtr build, StreamingPlanPtr probe, std::string build_key, std::string probe_key,
+                                      JoinType type = JoinType::Inner) {
+        if (type == JoinType::Outer)
+            throw Error(RV_ERR_UNSUPPORTED, "StreamingPhysicalPlan::hash_join: JoinType::Outer is not streamed (its unmatched build rows belong to no probe "
+                                            "batch); use the eager plan, PhysicalPlan::hash_join");
+        const execution::JoinShape shape = execution::join_shape(type);
+        if (shape.swapped) {
+            std::swap(build, probe);
+            std::swap(build_key, probe_key);
+        }
         auto p = std::make_shared<StreamingPhysicalPlan>();
         p->kind = HashJoin;
         p->build_side = std::move(build);
         p->input = std::move(probe);
         p->build_key = std::move(build_key);
         p->probe_key = std::move(probe_key);
+        p->join_kind = shape.kind;
         return p;
     }
 
@@ -2506,7 +2565,8 @@ class StreamingPhysicalPlan {
                         }
                         return s;
                     };
-                    return std::make_unique<GpuHashJoinStream>(side(*build_side), side(*input), build_key, probe_key);
+                    return std::make_unique<GpuHashJoinStream>(side(*build_side), side(*input), build_key, probe_key, size_t(1) << 28, uint64_t(1) << 28,
+                                                               join_kind);
                 }
                 case GroupBy: {  // a resident frame is taken whole, after the null fill, as the join takes it
                     JoinSide s;
@@ -2589,7 +2649,8 @@ class PhysicalPlan {
     PhysicalPlanPtr input;
     std::vector<std::string> columns, final_names;
     CompareTerm term;  // Filter { column, value, op }
-    PhysicalPlanPtr build_side;          // HashJoin { build_side, probe_side = input, build_key, probe_key, Inner }
+    PhysicalPlanPtr build_side;          // HashJoin { build_side, probe_side = input, build_key, probe_key, join_kind }: the sides as joined
+    rv_join_kind join_kind = RV_JOIN_INNER;
     std::string build_key, probe_key;
     std::string group_key;  // GroupBy { input, group_key, aggs }
     std::vector<execution::AggSpec> aggs;
@@ -2633,14 +2694,22 @@ class PhysicalPlan {
         p->predicate_expr = std::move(predicate);
         return p;
     }
-    // planner.rs:102-108: the left frame is the build side, the right frame the probe side
-    static PhysicalPlanPtr hash_join(PhysicalPlanPtr build, PhysicalPlanPtr probe, std::string build_key, std::string probe_key) {
+    // planner.rs:102-108: the left frame is the build side, the right frame the probe side -- for Inner, Right and Outer; Left, Semi
+    // and Anti swap the sides (execution::join_shape), so their output starts with the left frame's columns
+    static PhysicalPlanPtr hash_join(PhysicalPlanPtr build, PhysicalPlanPtr probe, std::string build_key, std::string probe_key,
+                                     JoinType type = JoinType::Inner) {
+        const execution::JoinShape shape = execution::join_shape(type);
+        if (shape.swapped) {
+            std::swap(build, probe);
+            std::swap(build_key, probe_key);
+        }
         auto p = std::make_shared<PhysicalPlan>();
         p->kind = HashJoin;
         p->build_side = std::move(build);
         p->input = std::move(probe);
         p->build_key = std::move(build_key);
         p->probe_key = std::move(probe_key);
+        p->join_kind = shape.kind;
         return p;
     }
     // group_by(key).agg(aggs), eager: one rv_hash_aggregate; the key under its own name, then every aggregate under its name, the
@@ -2776,7 +2845,7 @@ class PhysicalPlan {
                 for (auto *h : out) res.columns.push_back(execution::Array::adopt(ctx, h));
                 return res;
             }
-            case HashJoin: {  // plan.rs:174-207 (JoinType::Inner), one rv_hash_join
+            case HashJoin: {  // plan.rs:174-207 (JoinType::Inner), one rv_hash_join; the other kinds one rv_hash_join_kind
                 DeviceFrame b = build_side->execute();
                 const execution::ArrayRef *bk = b.column(build_key);
                 if (!bk) throw Panic("called `Option::unwrap()` on a `None` value");  // plan.rs:184: build_df.column(..).unwrap()
@@ -2800,16 +2869,26 @@ class PhysicalPlan {
                 execution::StringKeyEncoder string_keys((*bk)->data_type(), (*pk)->data_type());
                 const execution::ArrayRef build_ids = string_keys.build_key(*bk), helper = string_keys.probe_key(ctx, *pk);
                 if (build_ids) bcols[bki] = build_ids->handle();
+                // a full outer join returns the build key: the strings, carried as one more build column, not their ids
+                const bool carried_key = build_ids && join_kind == RV_JOIN_FULL_OUTER;
+                if (carried_key) bcols.push_back((*bk)->handle());
                 const execution::ProbeColumns probe = execution::with_key_helper(std::move(pcols), pki, helper);
-                std::vector<rv_dcolumn *> out(probe.cols.size() + bcols.size() - 1, nullptr);
+                const bool probe_only = join_kind == RV_JOIN_PROBE_SEMI || join_kind == RV_JOIN_PROBE_ANTI;
+                const size_t nout = probe_only ? probe.cols.size() : probe.cols.size() + bcols.size() - (join_kind == RV_JOIN_FULL_OUTER ? 0 : 1);
+                std::vector<rv_dcolumn *> out(nout, nullptr);
                 uint64_t rows = 0;
-                check(rv_hash_join(ctx->raw(), bcols.data(), static_cast<uint32_t>(bcols.size()), bki, probe.cols.data(),
-                                   static_cast<uint32_t>(probe.cols.size()), probe.key, out.data(), &rows));
+                if (join_kind == RV_JOIN_INNER)
+                    check(rv_hash_join(ctx->raw(), bcols.data(), static_cast<uint32_t>(bcols.size()), bki, probe.cols.data(),
+                                       static_cast<uint32_t>(probe.cols.size()), probe.key, out.data(), &rows));
+                else
+                    check(rv_hash_join_kind(ctx->raw(), bcols.data(), static_cast<uint32_t>(bcols.size()), bki, probe.cols.data(),
+                                            static_cast<uint32_t>(probe.cols.size()), probe.key, join_kind, out.data(), &rows));
                 DeviceFrame res;
                 for (auto *h : out) res.columns.push_back(execution::Array::adopt(ctx, h));
+                if (carried_key) execution::restore_build_key(res.columns, probe.cols.size(), bki);
                 execution::without_key_helper(probe, res.columns);  // the helper column's pairs: not part of the frame
                 const execution::JoinSide bs{nullptr, b.names, b.columns, 0}, ps{nullptr, p.names, p.columns, 0};
-                for (auto &f : execution::join_output_fields(*ps.schema(), *bs.schema(), bki)) res.names.push_back(f.name());
+                for (auto &f : execution::join_output_fields(*ps.schema(), *bs.schema(), bki, join_kind)) res.names.push_back(f.name());
                 return res;
             }
         }
