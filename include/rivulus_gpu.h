@@ -757,6 +757,50 @@ rv_status rv_hash_aggregate(rv_ctx *ctx, const rv_dcolumn *key, const rv_dcolumn
                             const rv_agg_spec *specs, uint32_t n_specs, rv_dcolumn **out, rv_dcolumn **out_first_row,
                             uint64_t *out_groups);
 
+/* ---- grouped aggregation over several key columns (K9a) ---------------------- */
+/* group_by([k_0 .. k_{nkeys-1}]).agg([a_0 .. a_{m-1}]): 1 <= nkeys <= 8 key columns of one length.  A row's key is the TUPLE
+ * of its cells, one cell per key column in the order given; two rows are in one group iff their tuples are equal cell by cell.
+ * This comment is the normative text (tests/group_keys_model.py the executable one); DESIGN.md section 4 K9a argues it.
+ *
+ * Cells.  A cell is null, or a value of the column's dtype:
+ *   RV_INT64    equal iff the bits are equal.
+ *   RV_FLOAT64  every NaN, whatever its sign or payload, equals every other NaN; every other value equals only its own bit
+ *               pattern, so -0.0 and +0.0 are DIFFERENT keys.  This is the equality the order of rv_sort induces (all NaNs
+ *               compare equal, -0.0 < +0.0): the rows a sort puts side by side as equal are exactly the rows of one group.
+ *   RV_BOOLEAN  equal iff the bit is equal.
+ *   RV_NULL     every cell is null.
+ *   RV_STRING   RV_ERR_UNSUPPORTED -- String keys go through rv_string_dict_build ids (the host layer does that).
+ * Nulls.  A null cell equals a null cell of the same column (AnyValue: Null == Null, as K9 and the join have it) and no
+ * value; whatever bits lie under a null cell are never read as a value.  There is no special null group: (null, 0),
+ * (0, null), (0, 0) and (null, null) are four ordinary, different keys.  With nkeys == 1 this is K9's grouping.
+ *
+ * Outputs.  rv_hash_aggregate_keys: out[k], k < nkeys = the cells of key column k at the groups' first rows (rv_take_device
+ * of the column by first_row: a null stays null, a NaN keeps the bits its first row has); out[nkeys + j] = aggregate j: out
+ * has room for nkeys + n_specs handles.  rv_group_ids_keys: out_gids, out_first_row and out_groups as rv_group_ids gives
+ * them.  out_first_row (of rv_hash_aggregate_keys) and out_groups may be NULL.
+ *
+ * Everything else is rv_hash_aggregate's, word for word: the order (groups by ascending first row, the same bytes run to
+ * run; an empty key gives zero groups and zero-row outputs of the right dtypes), the aggregates and every numeric rule
+ * (Int64 exact, the Float64 SUM order, the MIN / MAX NaN rule), options "agg_max_groups" and "agg_hash_bits" (which
+ * truncates the hash of the tuple), slices at any element offset (each column its own), the 2^32-row limit and the names
+ * rv_ctx_last_kernel gives the accumulate stage.
+ *
+ * Errors leave the context usable and create nothing: NULL arguments (a NULL entry of keys included), nkeys == 0,
+ * nkeys > 8 and what rv_hash_aggregate calls so RV_ERR_INVALID_ARG; key columns of different lengths, or a value column
+ * of another length, RV_ERR_LENGTH_MISMATCH; an RV_STRING key, keys of 2^32 rows or more (checked before anything is
+ * read), or more groups than "agg_max_groups" (with the number of distinct keys found so far in rv_last_error())
+ * RV_ERR_UNSUPPORTED.
+ *
+ * rv_ctx_last_kernel after rv_group_ids_keys says "group_ids<keys>" when the passes over tuples ran (group_insert_keys,
+ * group_ids_keys: one lane per row, a slot's tuple read at the slot's row, the hash a fold of the cells in key order and
+ * of their null flags).  A call with ONE RV_INT64 or RV_NULL key is K9's grouping and runs K9's passes: it says
+ * "group_ids".  rv_group_ids and rv_hash_aggregate are unchanged; they still refuse Float64 and Boolean keys. */
+rv_status rv_group_ids_keys(rv_ctx *ctx, const rv_dcolumn *const *keys, uint32_t nkeys, rv_dcolumn **out_gids,
+                            rv_dcolumn **out_first_row, uint64_t *out_groups);
+rv_status rv_hash_aggregate_keys(rv_ctx *ctx, const rv_dcolumn *const *keys, uint32_t nkeys, const rv_dcolumn *const *value_cols,
+                                 uint32_t n_values, const rv_agg_spec *specs, uint32_t n_specs, rv_dcolumn **out,
+                                 rv_dcolumn **out_first_row, uint64_t *out_groups);
+
 /* ---- sort (K10) ------------------------------------------------------------- */
 /* ORDER BY: rv_sort_indices gives the stable permutation of one key column, rv_sort reorders a frame by one or more keys.  The
  * reference has no sort; the semantics are defined here (this comment is the normative text, tests/sort_model.py the executable

@@ -205,6 +205,8 @@ PROTOTYPES = {
     "rv_hash_join": (C.c_int, [_P, _PP, C.c_uint32, C.c_uint32, _PP, C.c_uint32, C.c_uint32, _PP, _U64P]),
     "rv_group_ids": (C.c_int, [_P, _P, _PP, _PP, _U64P]),
     "rv_hash_aggregate": (C.c_int, [_P, _P, _PP, C.c_uint32, C.POINTER(RvAggSpec), C.c_uint32, _PP, _PP, _U64P]),
+    "rv_group_ids_keys": (C.c_int, [_P, _PP, C.c_uint32, _PP, _PP, _U64P]),
+    "rv_hash_aggregate_keys": (C.c_int, [_P, _PP, C.c_uint32, _PP, C.c_uint32, C.POINTER(RvAggSpec), C.c_uint32, _PP, _PP, _U64P]),
     "rv_sort_indices": (C.c_int, [_P, _P, C.c_uint32, _P, _PP]),
     "rv_sort": (C.c_int, [_P, _PP, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, _PP]),
     "rv_hash_join_kind": (C.c_int, [_P, _PP, C.c_uint32, C.c_uint32, _PP, C.c_uint32, C.c_uint32, C.c_int, _PP, _U64P]),
@@ -637,6 +639,15 @@ def _handles(cols: Sequence[DeviceColumn]):
     return arr
 
 
+def _agg_specs(specs):
+    """the rv_agg_spec array of a list of (op, value column index): op a name of AGG_OPS or an rv_agg_op number"""
+    arr = (RvAggSpec * max(1, len(specs)))()
+    for j, (op, col) in enumerate(specs):
+        arr[j].op = AGG_OPS[op] if isinstance(op, str) else op
+        arr[j].col = 0 if col is None else col
+    return arr
+
+
 class CsvReader:
     """rv_csv_reader: a CSV file parsed on the device.  Iterating yields one list of DeviceColumn per batch, the batches
     CsvFileStream::next_batch returns; a bad line raises RvError(RV_ERR_PARSE) and the next call goes on after it."""
@@ -867,15 +878,30 @@ class Context:
     def hash_aggregate(self, key: DeviceColumn, value_cols: Sequence[DeviceColumn], specs, want_first_row: bool = True):
         """rv_hash_aggregate: group_by(key).agg(specs), specs a list of (op, value column index) with op a name of AGG_OPS or an
         rv_agg_op number (the index of "count_rows" is ignored).  Returns ([key cells, aggregate 0, ...], first_row or None, groups)."""
-        arr = (RvAggSpec * max(1, len(specs)))()
-        for j, (op, col) in enumerate(specs):
-            arr[j].op = AGG_OPS[op] if isinstance(op, str) else op
-            arr[j].col = 0 if col is None else col
+        arr = _agg_specs(specs)
         out = (C.c_void_p * (len(specs) + 1))()
         first, groups = C.c_void_p(), C.c_uint64()
         _check(load().rv_hash_aggregate(self.handle, key.handle, _handles(value_cols), len(value_cols), arr, len(specs), out,
                                         C.byref(first) if want_first_row else None, C.byref(groups)))
         return ([DeviceColumn(self, C.c_void_p(out[i])) for i in range(len(specs) + 1)], DeviceColumn(self, first) if want_first_row else None,
+                groups.value)
+
+    def group_ids_keys(self, keys: Sequence[DeviceColumn]):
+        """rv_group_ids_keys: (gids, first_row, groups) of the tuples of `keys`' cells."""
+        gids, first, groups = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        _check(load().rv_group_ids_keys(self.handle, _handles(keys), len(keys), C.byref(gids), C.byref(first), C.byref(groups)))
+        return DeviceColumn(self, gids), DeviceColumn(self, first), groups.value
+
+    def hash_aggregate_keys(self, keys: Sequence[DeviceColumn], value_cols: Sequence[DeviceColumn], specs, want_first_row: bool = True):
+        """rv_hash_aggregate_keys: group_by(keys).agg(specs), specs as hash_aggregate takes them.  Returns ([key cells of every key column,
+        aggregate 0, ...], first_row or None, groups)."""
+        arr = _agg_specs(specs)
+        nout = len(keys) + len(specs)
+        out = (C.c_void_p * max(1, nout))()
+        first, groups = C.c_void_p(), C.c_uint64()
+        _check(load().rv_hash_aggregate_keys(self.handle, _handles(keys), len(keys), _handles(value_cols), len(value_cols), arr, len(specs), out,
+                                             C.byref(first) if want_first_row else None, C.byref(groups)))
+        return ([DeviceColumn(self, C.c_void_p(out[i])) for i in range(nout)], DeviceColumn(self, first) if want_first_row else None,
                 groups.value)
 
     def sort_indices(self, key: DeviceColumn, descending: bool = False, nulls_last: bool = False, prior: Optional[DeviceColumn] = None,

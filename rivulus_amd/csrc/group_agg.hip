@@ -1,9 +1,12 @@
-// Grouped aggregation on the device: group_by(key).agg(count / sum / min / max) -- rv_group_ids and rv_hash_aggregate.
+// Grouped aggregation on the device: group_by(key).agg(count / sum / min / max) -- rv_group_ids and rv_hash_aggregate over one key
+// column, rv_group_ids_keys and rv_hash_aggregate_keys over a tuple of them.
 // One unit of the backend library behind include/rivulus_gpu.h (gfx950 only; compiled with hipcc).  Shared helpers are declared in
-// launch.hpp (namespace rvl); the kernels and the layout of the group table are in group_agg_kernel.hpp.
+// launch.hpp (namespace rvl); the kernels and the layout of the group table are in group_agg_kernel.hpp, the passes over tuples in
+// group_keys_kernel.hpp.
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "group_agg_kernel.hpp"
+#include "group_keys_kernel.hpp"
 #include "launch.hpp"
 
 using namespace rvh;
@@ -27,11 +30,46 @@ void check_group_key(const rv_dcolumn *key, const char *what) {
 
 dim3 row_grid(uint64_t n) { return dim3(static_cast<uint32_t>((n + rvk::kGroupAggThreads - 1) / rvk::kGroupAggThreads)); }
 
+// the key columns of one call.  tuple = false: ONE Int64 (or Null) column through the single-key passes of group_agg_kernel.hpp, all its
+// null keys one group; tuple = true: the passes of group_keys_kernel.hpp over nkeys columns
+struct KeyCols {
+    const rv_dcolumn *const *cols;
+    uint32_t nkeys;
+    bool tuple;
+    uint64_t rows() const { return cols[0]->length; }
+};
+
+// the three passes over tuples, one instantiation per number of key columns
+template <int NK>
+void launch_insert_keys(rv_ctx *ctx, uint64_t n, const rvk::GroupKeysInsertParams &q) {
+    hipLaunchKernelGGL(rvk::group_insert_keys<NK>, row_grid(n), dim3(rvk::kGroupAggThreads), 0, ctx->stream, q);
+}
+template <int NK>
+void launch_ids_keys(rv_ctx *ctx, const rvk::GroupKeysView &t, const uint64_t *marks, const uint64_t *excl, void *gids, bool wide, uint32_t *error) {
+    if (wide)
+        hipLaunchKernelGGL((rvk::group_ids_keys<NK, int64_t>), row_grid(t.n), dim3(rvk::kGroupAggThreads), 0, ctx->stream, t, marks, excl, static_cast<int64_t *>(gids), error);
+    else
+        hipLaunchKernelGGL((rvk::group_ids_keys<NK, uint32_t>), row_grid(t.n), dim3(rvk::kGroupAggThreads), 0, ctx->stream, t, marks, excl, static_cast<uint32_t *>(gids), error);
+}
+#define RV_KEYS_DISPATCH(nkeys, fn, ...)                                        \
+    switch (nkeys) {                                                            \
+        case 1: fn<1>(__VA_ARGS__); break;                                      \
+        case 2: fn<2>(__VA_ARGS__); break;                                      \
+        case 3: fn<3>(__VA_ARGS__); break;                                      \
+        case 4: fn<4>(__VA_ARGS__); break;                                      \
+        case 5: fn<5>(__VA_ARGS__); break;                                      \
+        case 6: fn<6>(__VA_ARGS__); break;                                      \
+        case 7: fn<7>(__VA_ARGS__); break;                                      \
+        case 8: fn<8>(__VA_ARGS__); break;                                      \
+        default: require(false, RV_ERR_INTERNAL, "group keys: no kernel for this many key columns"); \
+    }
+static_assert(rvk::kGroupKeysMost == 8, "RV_KEYS_DISPATCH lists the instantiations");
+
 // insert, rank, ids.  One read-back here: the group count after the insert (everything behind it is sized by it).  The id pass is
 // left QUEUED with a freshly prepared control block whose `err` is its flag: the caller reads it with its own last read-back.
-GroupIds group_ids_of(rv_ctx *ctx, const rv_dcolumn *key, const char *what, bool wide) {
+GroupIds group_ids_of(rv_ctx *ctx, const KeyCols &keys, const char *what, bool wide) {
     GroupIds r;
-    const uint64_t n = key->length;
+    const uint64_t n = keys.rows();
     r.gids = pool_alloc(ctx, std::max<size_t>(n * (wide ? 8 : 4), 16));
     if (n == 0) {
         r.first_row = pool_alloc(ctx, 16);
@@ -39,29 +77,54 @@ GroupIds group_ids_of(rv_ctx *ctx, const rv_dcolumn *key, const char *what, bool
         return r;
     }
     const uint64_t max_groups = ctx->opt_agg_max_groups > 0 ? static_cast<uint64_t>(ctx->opt_agg_max_groups) : rvt::kGroupAggGroupsMostDefault;
+    bool keyed = false;  // a column with a word in it: without one there is one group and a table of 16 slots will do
+    for (uint32_t k = 0; k < keys.nkeys; ++k) keyed = keyed || keys.cols[k]->dtype != RV_NULL;
     uint64_t nslots = 16;
-    if (key->dtype != RV_NULL)
+    if (keyed)
         while (nslots < 2 * std::min(n, max_groups)) nslots *= 2;
     DevBufRef slots = pool_alloc(ctx, nslots * 8), null_first = pool_alloc(ctx, 16);
     RV_HIP(hipMemsetAsync(slots->ptr, 0, nslots * 8, ctx->stream));
     RV_HIP(hipMemsetAsync(null_first->ptr, 0xFF, 16, ctx->stream));
+    // the single-key view; over tuples what the passes behind the ids read of it: the slots, and a null word that stays ~0 (no null group)
     rvk::GroupTableView t{};
     t.slots = static_cast<unsigned long long *>(slots->ptr);
     t.null_first = static_cast<unsigned long long *>(null_first->ptr);
     t.slot_mask = nslots - 1;
     t.hash_mask = ctx->opt_agg_hash_bits > 0 && ctx->opt_agg_hash_bits < 64 ? (uint64_t{1} << ctx->opt_agg_hash_bits) - 1 : ~0ull;
-    t.key = dev_view(key);
     t.n = n;
+    rvk::GroupKeysView tk{};
+    if (keys.tuple) {
+        tk.slots = t.slots;
+        tk.slot_mask = t.slot_mask;
+        tk.hash_mask = t.hash_mask;
+        tk.n = n;
+        tk.nkeys = keys.nkeys;
+        for (uint32_t k = 0; k < keys.nkeys; ++k) tk.key[k] = dev_view(keys.cols[k]);
+    }
+    else t.key = dev_view(keys.cols[0]);
 
     // 1. insert: every distinct key's slot ends up holding the key's first row
     Ctrl *ctrl = prepare_ctrl(ctx, 0);
-    rvk::GroupInsertParams q{};
-    q.t = t;
-    q.distinct = striped(ctx, &ctrl->pops[0]);
-    q.claimed = n > max_groups ? &ctrl->pops[1] : nullptr;
-    q.max_groups = max_groups;
-    q.error = &ctrl->err;
-    hipLaunchKernelGGL(rvk::group_insert, row_grid(n), dim3(rvk::kGroupAggThreads), 0, ctx->stream, q);
+    unsigned long long *distinct = striped(ctx, &ctrl->pops[0]);
+    unsigned long long *claimed = n > max_groups ? &ctrl->pops[1] : nullptr;
+    if (keys.tuple) {
+        rvk::GroupKeysInsertParams q{};
+        q.t = tk;
+        q.distinct = distinct;
+        q.claimed = claimed;
+        q.max_groups = max_groups;
+        q.error = &ctrl->err;
+        RV_KEYS_DISPATCH(keys.nkeys, launch_insert_keys, ctx, n, q)
+    }
+    else {
+        rvk::GroupInsertParams q{};
+        q.t = t;
+        q.distinct = distinct;
+        q.claimed = claimed;
+        q.max_groups = max_groups;
+        q.error = &ctrl->err;
+        hipLaunchKernelGGL(rvk::group_insert, row_grid(n), dim3(rvk::kGroupAggThreads), 0, ctx->stream, q);
+    }
     RV_HIP(hipGetLastError());
     RV_HIP(hipMemcpyAsync(&ctrl->pops[2], null_first->ptr, 8, hipMemcpyDeviceToDevice, ctx->stream));
     const Ctrl *h = fetch_ctrl(ctx);
@@ -89,14 +152,18 @@ GroupIds group_ids_of(rv_ctx *ctx, const rv_dcolumn *key, const char *what, bool
 
     // 3. ids: every row's group position
     ctrl = prepare_ctrl(ctx, 0);
-    if (wide)
+    if (keys.tuple) {
+        RV_KEYS_DISPATCH(keys.nkeys, launch_ids_keys, ctx, tk, static_cast<const uint64_t *>(marks->ptr), static_cast<const uint64_t *>(excl->ptr), r.gids->ptr, wide,
+                         &ctrl->err)
+    }
+    else if (wide)
         hipLaunchKernelGGL(rvk::group_ids<int64_t>, row_grid(n), dim3(rvk::kGroupAggThreads), 0, ctx->stream, t, static_cast<const uint64_t *>(marks->ptr),
                            static_cast<const uint64_t *>(excl->ptr), static_cast<int64_t *>(r.gids->ptr), &ctrl->err);
     else
         hipLaunchKernelGGL(rvk::group_ids<uint32_t>, row_grid(n), dim3(rvk::kGroupAggThreads), 0, ctx->stream, t, static_cast<const uint64_t *>(marks->ptr),
                            static_cast<const uint64_t *>(excl->ptr), static_cast<uint32_t *>(r.gids->ptr), &ctrl->err);
     RV_HIP(hipGetLastError());
-    ctx->last_kernel = "group_ids";
+    ctx->last_kernel = keys.tuple ? "group_ids<keys>" : "group_ids";
     return r;  // (the table, the marks and the scan go back to the pool; their next user runs behind these kernels on the stream)
 }
 
@@ -198,27 +265,47 @@ GroupLists group_lists(rv_ctx *ctx, const GroupIds &ids, uint64_t n) {
     return L;
 }
 
-void check_specs(const rv_dcolumn *key, const rv_dcolumn *const *value_cols, uint32_t n_values, const rv_agg_spec *specs, uint32_t n_specs) {
-    require(n_specs >= 1, RV_ERR_INVALID_ARG, "rv_hash_aggregate: no aggregates");
-    for (uint32_t c = 0; c < n_values; ++c) require(value_cols[c] != nullptr, RV_ERR_INVALID_ARG, fmt("rv_hash_aggregate: value column %u is NULL", c));
+void check_specs(const char *what, uint64_t rows, const rv_dcolumn *const *value_cols, uint32_t n_values, const rv_agg_spec *specs, uint32_t n_specs) {
+    require(n_specs >= 1, RV_ERR_INVALID_ARG, fmt("%s: no aggregates", what));
+    for (uint32_t c = 0; c < n_values; ++c) require(value_cols[c] != nullptr, RV_ERR_INVALID_ARG, fmt("%s: value column %u is NULL", what, c));
     for (uint32_t j = 0; j < n_specs; ++j) {
-        require(specs[j].op <= static_cast<uint32_t>(RV_AGG_MAX), RV_ERR_INVALID_ARG, fmt("rv_hash_aggregate: aggregate %u has the unknown op %u", j, specs[j].op));
+        require(specs[j].op <= static_cast<uint32_t>(RV_AGG_MAX), RV_ERR_INVALID_ARG, fmt("%s: aggregate %u has the unknown op %u", what, j, specs[j].op));
         require(specs[j].op == RV_AGG_COUNT_ROWS || specs[j].col < n_values, RV_ERR_INVALID_ARG,
-                fmt("rv_hash_aggregate: aggregate %u reads value column %u of %u", j, specs[j].col, n_values));
+                fmt("%s: aggregate %u reads value column %u of %u", what, j, specs[j].col, n_values));
     }
     for (uint32_t c = 0; c < n_values; ++c)
-        require(value_cols[c]->length == key->length, RV_ERR_LENGTH_MISMATCH,
-                fmt("rv_hash_aggregate: value column %u has %llu rows, the key %llu", c, static_cast<unsigned long long>(value_cols[c]->length),
-                    static_cast<unsigned long long>(key->length)));
+        require(value_cols[c]->length == rows, RV_ERR_LENGTH_MISMATCH,
+                fmt("%s: value column %u has %llu rows, the key %llu", what, c, static_cast<unsigned long long>(value_cols[c]->length),
+                    static_cast<unsigned long long>(rows)));
     for (uint32_t j = 0; j < n_specs; ++j) {
         if (specs[j].op == RV_AGG_COUNT_ROWS) continue;
         const rv_dtype d = value_cols[specs[j].col]->dtype;
         if (specs[j].op == RV_AGG_COUNT)
-            require(is_value_type(d) || d == RV_BOOLEAN || d == RV_STRING || d == RV_NULL, RV_ERR_UNSUPPORTED, fmt("rv_hash_aggregate: aggregate %u: unsupported dtype", j));
+            require(is_value_type(d) || d == RV_BOOLEAN || d == RV_STRING || d == RV_NULL, RV_ERR_UNSUPPORTED, fmt("%s: aggregate %u: unsupported dtype", what, j));
         else
-            require(is_value_type(d), RV_ERR_TYPE_MISMATCH, fmt("rv_hash_aggregate: aggregate %u: SUM / MIN / MAX take an Int64 or Float64 column", j));
+            require(is_value_type(d), RV_ERR_TYPE_MISMATCH, fmt("%s: aggregate %u: SUM / MIN / MAX take an Int64 or Float64 column", what, j));
     }
-    check_group_key(key, "rv_hash_aggregate");
+}
+
+// the key list of the _keys entry points: one to kGroupKeysMost columns of one length, none of them String
+void check_group_keys(const rv_dcolumn *const *keys, uint32_t nkeys, const char *what) {
+    require(nkeys >= 1 && nkeys <= static_cast<uint32_t>(rvk::kGroupKeysMost), RV_ERR_INVALID_ARG,
+            fmt("%s: %u key columns; one to %d are taken", what, nkeys, rvk::kGroupKeysMost));
+    for (uint32_t k = 0; k < nkeys; ++k) require(keys[k] != nullptr, RV_ERR_INVALID_ARG, fmt("%s: key column %u is NULL", what, k));
+    for (uint32_t k = 1; k < nkeys; ++k)
+        require(keys[k]->length == keys[0]->length, RV_ERR_LENGTH_MISMATCH,
+                fmt("%s: key column %u has %llu rows, key column 0 %llu", what, k, static_cast<unsigned long long>(keys[k]->length),
+                    static_cast<unsigned long long>(keys[0]->length)));
+    for (uint32_t k = 0; k < nkeys; ++k)
+        require(keys[k]->dtype == RV_INT64 || keys[k]->dtype == RV_FLOAT64 || keys[k]->dtype == RV_BOOLEAN || keys[k]->dtype == RV_NULL, RV_ERR_UNSUPPORTED,
+                fmt("%s: key column %u: Int64, Float64, Boolean (and Null) key columns are supported on the device; String keys go through rv_string_dict_build ids",
+                    what, k));
+    require(keys[0]->length < (uint64_t{1} << 32), RV_ERR_UNSUPPORTED, fmt("%s: keys of 2^32 rows or more are not supported (32-bit row ids, as the join)", what));
+}
+
+// one Int64 or Null key is what the single-key passes take: same groups by definition, one hash and one cell per probe
+KeyCols key_cols(const rv_dcolumn *const *keys, uint32_t nkeys) {
+    return KeyCols{keys, nkeys, !(nkeys == 1 && (keys[0]->dtype == RV_INT64 || keys[0]->dtype == RV_NULL))};
 }
 
 // events around the accumulate stage (option profile_kernels)
@@ -242,10 +329,11 @@ struct StageTimer {
     }
 };
 
-void hash_aggregate(rv_ctx *ctx, const rv_dcolumn *key, const rv_dcolumn *const *value_cols, const rv_agg_spec *specs, uint32_t n_specs, rv_dcolumn **out,
-                    rv_dcolumn **out_first_row, uint64_t *out_groups) {
-    const uint64_t n = key->length;
-    GroupIds ids = group_ids_of(ctx, key, "rv_hash_aggregate", false);
+// everything behind the group ids; out: the key cells of every key column, then the aggregates
+void hash_aggregate(rv_ctx *ctx, const KeyCols &keys, const char *what, const rv_dcolumn *const *value_cols, const rv_agg_spec *specs, uint32_t n_specs,
+                    rv_dcolumn **out, rv_dcolumn **out_first_row, uint64_t *out_groups) {
+    const uint64_t n = keys.rows();
+    GroupIds ids = group_ids_of(ctx, keys, what, false);
     const uint64_t G = ids.groups;
     std::vector<std::unique_ptr<rv_dcolumn>> outs(n_specs);
     std::vector<Acc> accs;
@@ -313,7 +401,7 @@ void hash_aggregate(rv_ctx *ctx, const rv_dcolumn *key, const rv_dcolumn *const 
                 RV_HIP(hipGetLastError());
             }
             const Ctrl *h = fetch_ctrl(ctx);
-            require(h->err == 0, RV_ERR_INTERNAL, "rv_hash_aggregate: a row's key was not found in the group table");
+            require(h->err == 0, RV_ERR_INTERNAL, fmt("%s: a row's key was not found in the group table", what));
             for (size_t k = done; k < upto; ++k) {
                 rv_dcolumn *o = outs[minmax[k].j].get();
                 o->null_count = static_cast<int64_t>(h->valid_pop[k - done]);
@@ -324,12 +412,14 @@ void hash_aggregate(rv_ctx *ctx, const rv_dcolumn *key, const rv_dcolumn *const 
         } while (done < minmax.size());
         timer.add(launches);
     }
-    // out[0]: the key cells at the first rows (a gather with read-backs of its own: after this call's control block has been read)
-    rv_dcolumn *key_cells = nullptr;
-    take_on_device(ctx, &key, 1, static_cast<const uint64_t *>(ids.first_row->ptr), G, &key_cells, false);
+    // out[0 .. nkeys): the key cells at the first rows (a gather with read-backs of its own: after this call's control block has been read)
+    rv_dcolumn *key_cells[rvk::kGroupKeysMost] = {};
+    take_on_device(ctx, keys.cols, keys.nkeys, static_cast<const uint64_t *>(ids.first_row->ptr), G, key_cells, false);
+    std::vector<std::unique_ptr<rv_dcolumn>> cells(keys.nkeys);
+    for (uint32_t k = 0; k < keys.nkeys; ++k) cells[k].reset(key_cells[k]);
     RV_HIP(hipStreamSynchronize(ctx->stream));  // the ids, the lists and the count accumulators go back to the pool
-    out[0] = key_cells;
-    for (uint32_t j = 0; j < n_specs; ++j) out[1 + j] = outs[j].release();
+    for (uint32_t k = 0; k < keys.nkeys; ++k) out[k] = cells[k].release();
+    for (uint32_t j = 0; j < n_specs; ++j) out[keys.nkeys + j] = outs[j].release();
     if (out_first_row) *out_first_row = int64_column(ids.first_row, G);
     if (out_groups) *out_groups = G;
 }
@@ -346,7 +436,7 @@ rv_status rv_group_ids(rv_ctx *ctx, const rv_dcolumn *key, rv_dcolumn **out_gids
         check_group_key(key, "rv_group_ids");
         set_device(ctx);
         try {
-            GroupIds ids = group_ids_of(ctx, key, "rv_group_ids", true);
+            GroupIds ids = group_ids_of(ctx, KeyCols{&key, 1, false}, "rv_group_ids", true);
             require(fetch_ctrl(ctx)->err == 0, RV_ERR_INTERNAL, "rv_group_ids: a row's key was not found in the group table");
             std::unique_ptr<rv_dcolumn> a(int64_column(ids.gids, key->length)), b(int64_column(ids.first_row, ids.groups));
             *out_gids = a.release();
@@ -363,12 +453,51 @@ rv_status rv_hash_aggregate(rv_ctx *ctx, const rv_dcolumn *key, const rv_dcolumn
                             uint32_t n_specs, rv_dcolumn **out, rv_dcolumn **out_first_row, uint64_t *out_groups) {
     return guarded([&] {
         require(ctx && key && specs && out && (value_cols || n_values == 0), RV_ERR_INVALID_ARG, "rv_hash_aggregate: NULL argument");
-        check_specs(key, value_cols, n_values, specs, n_specs);
+        check_specs("rv_hash_aggregate", key->length, value_cols, n_values, specs, n_specs);
+        check_group_key(key, "rv_hash_aggregate");
         for (uint32_t j = 0; j <= n_specs; ++j) out[j] = nullptr;
         if (out_first_row) *out_first_row = nullptr;
         set_device(ctx);
         try {
-            hash_aggregate(ctx, key, value_cols, specs, n_specs, out, out_first_row, out_groups);
+            hash_aggregate(ctx, KeyCols{&key, 1, false}, "rv_hash_aggregate", value_cols, specs, n_specs, out, out_first_row, out_groups);
+        } catch (...) {
+            (void)hipStreamSynchronize(ctx->stream);
+            throw;
+        }
+    });
+}
+
+rv_status rv_group_ids_keys(rv_ctx *ctx, const rv_dcolumn *const *keys, uint32_t nkeys, rv_dcolumn **out_gids, rv_dcolumn **out_first_row, uint64_t *out_groups) {
+    return guarded([&] {
+        require(ctx && keys && out_gids && out_first_row, RV_ERR_INVALID_ARG, "rv_group_ids_keys: NULL argument");
+        *out_gids = *out_first_row = nullptr;
+        check_group_keys(keys, nkeys, "rv_group_ids_keys");
+        set_device(ctx);
+        try {
+            GroupIds ids = group_ids_of(ctx, key_cols(keys, nkeys), "rv_group_ids_keys", true);
+            require(fetch_ctrl(ctx)->err == 0, RV_ERR_INTERNAL, "rv_group_ids_keys: a row's key was not found in the group table");
+            std::unique_ptr<rv_dcolumn> a(int64_column(ids.gids, keys[0]->length)), b(int64_column(ids.first_row, ids.groups));
+            *out_gids = a.release();
+            *out_first_row = b.release();
+            if (out_groups) *out_groups = ids.groups;
+        } catch (...) {
+            (void)hipStreamSynchronize(ctx->stream);  // whatever was queued has run before its buffers go back to the pool
+            throw;
+        }
+    });
+}
+
+rv_status rv_hash_aggregate_keys(rv_ctx *ctx, const rv_dcolumn *const *keys, uint32_t nkeys, const rv_dcolumn *const *value_cols, uint32_t n_values,
+                                 const rv_agg_spec *specs, uint32_t n_specs, rv_dcolumn **out, rv_dcolumn **out_first_row, uint64_t *out_groups) {
+    return guarded([&] {
+        require(ctx && keys && specs && out && (value_cols || n_values == 0), RV_ERR_INVALID_ARG, "rv_hash_aggregate_keys: NULL argument");
+        check_group_keys(keys, nkeys, "rv_hash_aggregate_keys");
+        check_specs("rv_hash_aggregate_keys", keys[0]->length, value_cols, n_values, specs, n_specs);
+        for (uint32_t j = 0; j < nkeys + n_specs; ++j) out[j] = nullptr;
+        if (out_first_row) *out_first_row = nullptr;
+        set_device(ctx);
+        try {
+            hash_aggregate(ctx, key_cols(keys, nkeys), "rv_hash_aggregate_keys", value_cols, specs, n_specs, out, out_first_row, out_groups);
         } catch (...) {
             (void)hipStreamSynchronize(ctx->stream);
             throw;

@@ -1795,16 +1795,9 @@ struct GroupByPlanError : std::runtime_error {  // what planning a group_by refu
     using std::runtime_error::runtime_error;
 };
 
-// The output schema of group_by(key).agg(aggs) over `in`: the key under its own name, then every aggregate under its name -- counts
-// Int64, SUM / MIN / MAX of the column's dtype.  Throws GroupByPlanError for an unknown column, a duplicate output name, SUM / MIN /
-// MAX over a column that is not Int64 or Float64, and a key the device does not group by (Float64, Boolean: not built).
-inline SchemaRef group_by_schema(const Schema &in, const std::string &key, const std::vector<AggSpec> &aggs) {
-    const Field *kf = in.field_by_name(key);
-    if (!kf) throw GroupByPlanError("group_by: unknown key column '" + key + "'");
-    if (kf->data_type() == DataType::Float64 || kf->data_type() == DataType::Boolean)
-        throw GroupByPlanError("group_by: key column '" + key + "' is " + to_string(kf->data_type()) + "; only Int64 and String keys are grouped");
+// the aggregates' fields behind the key fields `out` (both forms of group_by_schema)
+inline SchemaRef group_by_agg_fields(const Schema &in, std::vector<Field> out, const std::vector<AggSpec> &aggs) {
     if (aggs.empty()) throw GroupByPlanError("group_by: no aggregates");
-    std::vector<Field> out{Field{key, kf->data_type(), true}};
     for (auto &a : aggs) {
         DataType t = DataType::Int64;
         if (a.op != AggOp::CountRows) {
@@ -1821,6 +1814,40 @@ inline SchemaRef group_by_schema(const Schema &in, const std::string &key, const
         out.push_back(Field{a.name, t, a.op == AggOp::Min || a.op == AggOp::Max});
     }
     return std::make_shared<const Schema>(out);
+}
+
+// The output schema of group_by(key).agg(aggs) over `in`: the key under its own name, then every aggregate under its name -- counts
+// Int64, SUM / MIN / MAX of the column's dtype.  Throws GroupByPlanError for an unknown column, a duplicate output name, SUM / MIN /
+// MAX over a column that is not Int64 or Float64, and a key the device does not group by (Float64, Boolean: not built).
+inline SchemaRef group_by_schema(const Schema &in, const std::string &key, const std::vector<AggSpec> &aggs) {
+    const Field *kf = in.field_by_name(key);
+    if (!kf) throw GroupByPlanError("group_by: unknown key column '" + key + "'");
+    if (kf->data_type() == DataType::Float64 || kf->data_type() == DataType::Boolean)
+        throw GroupByPlanError("group_by: key column '" + key + "' is " + to_string(kf->data_type()) + "; only Int64 and String keys are grouped");
+    std::vector<Field> out{Field{key, kf->data_type(), true}};
+    return group_by_agg_fields(in, std::move(out), aggs);
+}
+
+// group_by over a LIST of key columns (rv_hash_aggregate_keys): the keys first, in the order given and under their own names, each
+// nullable and of its own dtype -- Int64, Float64, Boolean, String and Null keys are all grouped -- then the aggregates.  A row's key is
+// the tuple of its cells; a Float64 key groups every NaN together and keeps -0.0 and +0.0 apart (the equality the sort's order
+// induces), a null cell equals only a null cell of the same column.  The list with ONE name is how a Float64 or Boolean key is
+// grouped.  Throws GroupByPlanError for an empty key list, an unknown key, a key named twice, more than 8 keys, an aggregate name that
+// collides with a key, and what the aggregates of the single-key form are refused for.
+constexpr size_t kGroupByKeysMost = 8;
+inline SchemaRef group_by_schema(const Schema &in, const std::vector<std::string> &keys, const std::vector<AggSpec> &aggs) {
+    if (keys.empty()) throw GroupByPlanError("group_by: no key columns");
+    if (keys.size() > kGroupByKeysMost)
+        throw GroupByPlanError("group_by: " + std::to_string(keys.size()) + " key columns; at most " + std::to_string(kGroupByKeysMost) + " are grouped");
+    std::vector<Field> out;
+    for (auto &key : keys) {
+        const Field *kf = in.field_by_name(key);
+        if (!kf) throw GroupByPlanError("group_by: unknown key column '" + key + "'");
+        for (auto &f : out)
+            if (f.name() == key) throw GroupByPlanError("group_by: key column '" + key + "' is named twice");
+        out.push_back(Field{key, kf->data_type(), true});
+    }
+    return group_by_agg_fields(in, std::move(out), aggs);
 }
 
 // One rv_hash_aggregate over the named columns of one frame (`columns` in the order of `schema`); the output columns in the order of
@@ -1872,6 +1899,61 @@ inline std::vector<ArrayRef> group_by_columns(const ContextRef &ctx, const Schem
     return res;
 }
 
+// One rv_hash_aggregate_keys over the named columns of one frame; the output columns in the order of group_by_schema(keys).  Every
+// String key goes through the string dictionary on its own: its ids (a null string is a null id; "" is a value) stand in the tuple,
+// and its key cells are gathered from the String column itself at the groups' first rows.
+inline std::vector<ArrayRef> group_by_columns(const ContextRef &ctx, const Schema &schema, const std::vector<ArrayRef> &columns,
+                                              const std::vector<std::string> &keys, const std::vector<AggSpec> &aggs) {
+    (void)group_by_schema(schema, keys, aggs);
+    auto handle_of = [&](const std::string &n) {
+        const ArrayRef &c = columns[*schema.index_of(n)];
+        if (!c->on_device()) throw Error(RV_ERR_UNSUPPORTED, "columns off the device are outside the device path");
+        return c->handle();
+    };
+    std::vector<const rv_dcolumn *> values;
+    std::vector<rv_agg_spec> specs;
+    for (auto &a : aggs) {
+        rv_agg_spec s{static_cast<uint32_t>(a.op), 0};
+        if (a.op != AggOp::CountRows) {
+            const rv_dcolumn *h = handle_of(a.column);
+            const auto at = std::find(values.begin(), values.end(), h);
+            s.col = static_cast<uint32_t>(at - values.begin());
+            if (at == values.end()) values.push_back(h);
+        }
+        specs.push_back(s);
+    }
+    std::vector<const rv_dcolumn *> key_cols, strings(keys.size(), nullptr);
+    std::vector<ArrayRef> ids;  // keeps the ids of the String keys alive over the call
+    for (size_t k = 0; k < keys.size(); ++k) {
+        const rv_dcolumn *col = handle_of(keys[k]);
+        if (schema.field_by_name(keys[k])->data_type() == DataType::String) {
+            rv_string_dict *dict = nullptr;
+            rv_dcolumn *h = nullptr;
+            check(rv_string_dict_build(ctx->raw(), col, &dict, &h));
+            ids.push_back(Array::adopt(ctx, h));
+            check(rv_string_dict_free(ctx->raw(), dict));  // only the ids are needed: equal strings share an id
+            strings[k] = col;
+            col = ids.back()->handle();
+        }
+        key_cols.push_back(col);
+    }
+    std::vector<rv_dcolumn *> out(keys.size() + specs.size(), nullptr);
+    rv_dcolumn *first_row = nullptr;
+    uint64_t groups = 0;
+    check(rv_hash_aggregate_keys(ctx->raw(), key_cols.data(), static_cast<uint32_t>(key_cols.size()), values.data(), static_cast<uint32_t>(values.size()),
+                                 specs.data(), static_cast<uint32_t>(specs.size()), out.data(), &first_row, &groups));
+    std::vector<ArrayRef> res;
+    for (auto *h : out) res.push_back(Array::adopt(ctx, h));
+    const ArrayRef first = Array::adopt(ctx, first_row);
+    for (size_t k = 0; k < keys.size(); ++k) {
+        if (!strings[k]) continue;  // the strings at the first rows in place of their ids
+        rv_dcolumn *cells = nullptr;
+        check(rv_take_device(ctx->raw(), &strings[k], 1, first->handle(), &cells));
+        res[k] = Array::adopt(ctx, cells);
+    }
+    return res;
+}
+
 // group_by as a stream: a PIPELINE BREAKER.  It drains its input -- a resident frame is taken as it is, the batches of any other
 // stream are concatenated (RecordBatch::concat) -- and emits EXACTLY ONE batch: the groups in first-row order.  An input without rows
 // gives one zero-row batch with the output schema.  (Aggregating batch by batch without the concatenation -- a begin / update /
@@ -1883,6 +1965,12 @@ class GpuGroupByStream : public DataStream {
         : input_(std::move(input)), key_(std::move(key)), aggs_(std::move(aggs)), ctx_(std::move(fallback_ctx)) {
         input_schema_ = input_.schema();
         schema_ = group_by_schema(*input_schema_, key_, aggs_);
+    }
+    // the same over a list of key columns (group_by_schema(keys)): one batch, the keys first
+    GpuGroupByStream(JoinSide input, std::vector<std::string> keys, std::vector<AggSpec> aggs, ContextRef fallback_ctx)
+        : input_(std::move(input)), keys_(std::move(keys)), by_list_(true), aggs_(std::move(aggs)), ctx_(std::move(fallback_ctx)) {
+        input_schema_ = input_.schema();
+        schema_ = group_by_schema(*input_schema_, keys_, aggs_);
     }
     SchemaRef schema() const override { return schema_; }
     std::optional<RecordBatch> next_batch() override {
@@ -1901,7 +1989,8 @@ class GpuGroupByStream : public DataStream {
         }
         return stream_call([&] {
             const ContextRef ctx = columns.empty() ? ctx_ : columns[0]->context();
-            std::vector<ArrayRef> out = group_by_columns(ctx, *input_schema_, columns, key_, aggs_);
+            std::vector<ArrayRef> out = by_list_ ? group_by_columns(ctx, *input_schema_, columns, keys_, aggs_)
+                                                 : group_by_columns(ctx, *input_schema_, columns, key_, aggs_);
             const size_t rows = out[0]->len();
             return RecordBatch::new_unchecked(schema_, std::move(out), rows);
         });
@@ -1910,6 +1999,8 @@ class GpuGroupByStream : public DataStream {
   private:
     JoinSide input_;
     std::string key_;
+    std::vector<std::string> keys_;  // by_list_: the key-list form
+    bool by_list_ = false;
     std::vector<AggSpec> aggs_;
     ContextRef ctx_;
     SchemaRef input_schema_, schema_;
@@ -2379,6 +2470,8 @@ class StreamingPhysicalPlan {
     rv_join_kind join_kind = RV_JOIN_INNER;
     std::string build_key, probe_key;
     std::string group_key;  // GroupBy { input, group_key, aggs }
+    std::vector<std::string> group_keys;  // GroupBy { input, group_keys, aggs } when group_by_list: the key-list form
+    bool group_by_list = false;
     std::vector<execution::AggSpec> aggs;
     std::vector<execution::SortKey> sort_keys;  // Sort { input, sort_keys }
 
@@ -2491,6 +2584,17 @@ class StreamingPhysicalPlan {
         p->aggs = std::move(aggs);
         return p;
     }
+    // group_by([k0, k1, ...]).agg(aggs): the same over tuples of up to 8 key columns of any dtype (group_by_schema(keys)); the keys come
+    // first in the batch
+    static StreamingPlanPtr group_by(StreamingPlanPtr in, std::vector<std::string> keys, std::vector<execution::AggSpec> aggs) {
+        auto p = std::make_shared<StreamingPhysicalPlan>();
+        p->kind = GroupBy;
+        p->input = std::move(in);
+        p->group_keys = std::move(keys);
+        p->group_by_list = true;
+        p->aggs = std::move(aggs);
+        return p;
+    }
     // sort(keys): a pipeline breaker that emits exactly one batch (GpuSortStream); the reference has no such operator
     static StreamingPlanPtr sort(StreamingPlanPtr in, std::vector<execution::SortKey> keys) {
         auto p = std::make_shared<StreamingPhysicalPlan>();
@@ -2577,6 +2681,7 @@ class StreamingPhysicalPlan {
                     } else {
                         s.stream = input->execute();
                     }
+                    if (group_by_list) return std::make_unique<GpuGroupByStream>(std::move(s), group_keys, aggs, any_context());
                     return std::make_unique<GpuGroupByStream>(std::move(s), group_key, aggs, any_context());
                 }
                 case Sort: {  // drains its input as GroupBy does
@@ -2653,6 +2758,8 @@ class PhysicalPlan {
     rv_join_kind join_kind = RV_JOIN_INNER;
     std::string build_key, probe_key;
     std::string group_key;  // GroupBy { input, group_key, aggs }
+    std::vector<std::string> group_keys;  // GroupBy { input, group_keys, aggs } when group_by_list: the key-list form
+    bool group_by_list = false;
     std::vector<execution::AggSpec> aggs;
     std::vector<execution::SortKey> sort_keys;  // Sort { input, sort_keys }
 
@@ -2722,6 +2829,18 @@ class PhysicalPlan {
         p->aggs = std::move(aggs);
         return p;
     }
+    // group_by([k0, k1, ...]).agg(aggs), eager: one rv_hash_aggregate_keys over tuples of up to 8 key columns -- Int64, Float64, Boolean,
+    // String or Null, each with its nulls; the keys under their own names in the order given, then the aggregates.  The list with one
+    // name is how a Float64 or Boolean key is grouped.
+    static PhysicalPlanPtr group_by(PhysicalPlanPtr in, std::vector<std::string> keys, std::vector<execution::AggSpec> aggs) {
+        auto p = std::make_shared<PhysicalPlan>();
+        p->kind = GroupBy;
+        p->input = std::move(in);
+        p->group_keys = std::move(keys);
+        p->group_by_list = true;
+        p->aggs = std::move(aggs);
+        return p;
+    }
     // sort(keys), eager: one rv_sort; names and dtypes unchanged, the first key the most significant, equal rows in input order.  The nulls
     // of the frame stay nulls (no fill: this is not a stream).
     static PhysicalPlanPtr sort(PhysicalPlanPtr in, std::vector<execution::SortKey> keys) {
@@ -2747,9 +2866,11 @@ class PhysicalPlan {
             case GroupBy: {
                 DeviceFrame in = input->execute();
                 const execution::Schema schema = frame_schema(in);
-                const execution::SchemaRef out_schema = execution::group_by_schema(schema, group_key, aggs);  // the planning errors
+                const execution::SchemaRef out_schema =
+                    group_by_list ? execution::group_by_schema(schema, group_keys, aggs) : execution::group_by_schema(schema, group_key, aggs);  // the planning errors
                 DeviceFrame out;
-                out.columns = execution::group_by_columns((*in.column(group_key))->context(), schema, in.columns, group_key, aggs);
+                if (group_by_list) out.columns = execution::group_by_columns((*in.column(group_keys[0]))->context(), schema, in.columns, group_keys, aggs);
+                else out.columns = execution::group_by_columns((*in.column(group_key))->context(), schema, in.columns, group_key, aggs);
                 for (auto &f : out_schema->fields()) out.names.push_back(f.name());
                 return out;
             }
