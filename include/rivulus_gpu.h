@@ -240,7 +240,15 @@ rv_status rv_ctx_device_info(rv_ctx *ctx, int *compute_units, uint64_t *hbm_byte
  * 1 = the context's last observed selectivity x 1.5 + 1 %; k >= 2 = a caller-given bound of k rows per
  * million.  A launch whose survivors do not fit still counts exactly and is re-run once with outputs of the exact size, so
  * the bound is a hint, never a correctness matter), "bools_in_pass" (1: projected Boolean columns are compacted inside the fused pass instead
- * of by the bit-compaction kernel after it; measured slower, kept selectable).  Diagnostics only, never for results: "stamp" (per-phase cycle
+ * of by the bit-compaction kernel after it; measured slower, kept selectable), "narrow_codes" (narrow companions of resident Int64
+ * columns: a values buffer of 2^25 elements and more that the lean one-column filter pass -- one compare term, no null bitmap -- has
+ * read from end to end twice gets frame-of-reference codes, code = value - column minimum in 2 bytes, or 4 when the value range needs
+ * them, and the lean passes after that, over the column or any slice of it that starts at an even element, read the codes instead of
+ * the 8-byte values; same rows, same order, same bits.  MEMORY: + 25 % of the column for 2-byte codes, + 50 % for 4-byte codes, held
+ * until the column's buffer is freed; a range of 2^32 and more, or no memory for the codes, means no companion and never a failed
+ * query.  Only buffers the library allocated qualify -- columns are immutable once their handle is out; rv_wrap memory is the caller's
+ * to write and is never packed.  0 = as described, -1 = never, 1 = at the first whole scan whatever the size (tests); read-only
+ * counters "narrow_builds", "narrow_passes", "narrow_bytes").  Diagnostics only, never for results: "stamp" (per-phase cycle
  * counters, printed to stderr) and "debug" (bit 0 skip the value stores, bit 1 skip the
  * output-offset lookup -- both make the output WRONG, timing shares only -- bit 2 print
  * scanner / fallback look-back counts, bit 3 run without the scanner wave: results stay correct, bit 4 fault injection: tile 1 never

@@ -131,6 +131,7 @@ rv_status rv_slice(rv_ctx *ctx, const rv_dcolumn *col, uint64_t offset, uint64_t
     return guarded([&] {
         require(ctx && col && out, RV_ERR_INVALID_ARG, "rv_slice: NULL argument");
         require(offset + length <= col->length, RV_ERR_OUT_OF_BOUNDS, "Slice out of bounds");  // boolean.rs:209
+        narrow_note_extent(ctx, col);  // (narrow.hip: the windows of a stream are slices -- the parent says how far its buffer's column reaches)
         auto s = std::make_unique<rv_dcolumn>(*col);
         s->offset = col->offset + offset;
         s->length = length;
@@ -143,6 +144,7 @@ rv_status rv_slice_known(rv_ctx *ctx, const rv_dcolumn *col, uint64_t offset, ui
     return guarded([&] {
         require(ctx && col && out, RV_ERR_INVALID_ARG, "rv_slice_known: NULL argument");
         require(offset + length <= col->length, RV_ERR_OUT_OF_BOUNDS, "Slice out of bounds");
+        narrow_note_extent(ctx, col);
         require(null_count >= 0 && static_cast<uint64_t>(null_count) <= length, RV_ERR_INVALID_ARG, "rv_slice_known: null count out of range");
         auto s = std::make_unique<rv_dcolumn>(*col);
         s->offset = col->offset + offset;

@@ -391,6 +391,10 @@ rv_status rv_ctx_set_option(rv_ctx *ctx, const char *key, int64_t value) {
         else if (k == "spin_limit") ctx->opt_spin_limit = value;
         else if (k == "agg_grid") ctx->opt_agg_grid = value;
         else if (k == "bools_in_pass") ctx->opt_bools_in_pass = value;
+        else if (k == "narrow_codes") {
+            require(value >= -1 && value <= 1, RV_ERR_INVALID_ARG, "narrow_codes: 0 (auto), -1 (never) or 1 (at the first whole scan)");
+            ctx->opt_narrow_codes = value;
+        }
         else if (k == "inject_failure") ctx->opt_inject_failure = value;
         else if (k == "csv_slow_cap") {
             require(value >= 0 && value < (int64_t(1) << 31), RV_ERR_INVALID_ARG, "csv_slow_cap must be in [0, 2^31)");
@@ -458,6 +462,10 @@ rv_status rv_ctx_get_option(rv_ctx *ctx, const char *key, int64_t *value) {
         else if (k == "spin_limit") *value = ctx->opt_spin_limit;
         else if (k == "agg_grid") *value = ctx->opt_agg_grid;
         else if (k == "bools_in_pass") *value = ctx->opt_bools_in_pass;
+        else if (k == "narrow_codes") *value = ctx->opt_narrow_codes;
+        else if (k == "narrow_builds") *value = static_cast<int64_t>(ctx->narrow_builds);  // read-only counters
+        else if (k == "narrow_passes") *value = static_cast<int64_t>(ctx->narrow_passes);
+        else if (k == "narrow_bytes") *value = static_cast<int64_t>(ctx->narrow_bytes);
         else if (k == "csv_slow_cap") *value = ctx->opt_csv_slow_cap;
         else if (k == "csv_slow_cells") *value = static_cast<int64_t>(ctx->csv_slow_cells);
         else if (k == "csv_slow_reparses") *value = static_cast<int64_t>(ctx->csv_slow_reparses);

@@ -77,6 +77,9 @@ struct FusedParams {
     // it).  Bit-packed columns are compacted after the pass by the selection bitmap (bits_compact_kernel); with these a
     // wave of that kernel finds its output position with one load instead of a scan over the whole bitmap before it.
     uint64_t *wave_offsets;
+    // FF_NARROW16 / FF_NARROW32 launches: the companion of value slot 0's buffer (scan_frontend.hpp); in.cols[0] still describes the
+    // 8-byte original, which the redo kernel and a re-run's plain kernel read
+    NarrowView narrow;
 };
 
 // The dynamic LDS block of the fused kernel.  Helpers address it by byte offset (generic
@@ -197,6 +200,8 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
     // propagate strictly through an expression): nothing of the validity is staged or written.  With FF_PROJALL every
     // loaded column is projected; without it the per-column projection checks stay in the staging loop.
     static_assert(!kOne || (NCOLS == 1 && (FLAGS & (FF_VALIDITY | FF_BOOL | FF_XS)) == 0), "single-term fast path");
+    constexpr int kNarrow = (FLAGS & FF_NARROW16) ? 2 : ((FLAGS & FF_NARROW32) ? 4 : 0);  // bytes of a code; 0: the 8-byte rows
+    static_assert(!kNarrow || ((FLAGS & FF_ONE_I64) != 0 && VEC == 2 && (FLAGS & (FF_NARROW16 | FF_NARROW32)) != (FF_NARROW16 | FF_NARROW32)), "narrow codes: lean Int64 form");
     // selector masks of term 0 (all ones / all zeros), fixed for the launch
     const DevTerm term0 = p.in.terms[0];
     const uint64_t SLT = term0.sel_lt() ? ~0ull : 0, SEQ = term0.sel_eq() ? ~0ull : 0, SGT = term0.sel_gt() ? ~0ull : 0,
@@ -317,8 +322,11 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
     __syncthreads();
     uint32_t tile = uniform32(s_tick[0]);
     uint64_t v[NV][R];
-    if (tile < p.ntiles)
-        load_rows<NCOLS, R, VEC>(p.in, static_cast<uint64_t>(tile) * TILE + static_cast<uint64_t>(wave) * ROWS_PER_WAVE, lane, v);
+    auto load_tile_rows = [&](uint64_t first_row) {  // of this wave
+        if constexpr (kNarrow != 0) load_rows_narrow<R, kNarrow>(p.narrow, p.in.cols[0].offset + first_row, lane, v[0]);
+        else load_rows<NCOLS, R, VEC>(p.in, first_row, lane, v);
+    };
+    if (tile < p.ntiles) load_tile_rows(static_cast<uint64_t>(tile) * TILE + static_cast<uint64_t>(wave) * ROWS_PER_WAVE);
     uint64_t vw[NV];  // validity words of the loaded rows (generic shapes with null bitmaps)
     // words of the Boolean predicate columns (values, validity) and of the Boolean columns travelling with
     // the rows (source, mask): fetched with the row prefetch, like vw
@@ -452,11 +460,16 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
             } else {
 #pragma unroll
                 for (int j = 0; j < R / 2; ++j) {
-                    const uint64_t m0 = row_mask(v[0][2 * j], j * 128, 2 * lane), m1 = row_mask(v[0][2 * j + 1], j * 128, 2 * lane + 1);
+                    // the pair's rows: registers of the 16-byte load, or -- a pass over codes -- widened here, pair by pair (value =
+                    // base + code), so that only the raw codes occupy registers while the tile is in flight
+                    uint64_t a, b;
+                    if constexpr (kNarrow != 0) widen_pair<kNarrow>(p.narrow.base, v[0][j], a, b);
+                    else a = v[0][2 * j], b = v[0][2 * j + 1];
+                    const uint64_t m0 = row_mask(a, j * 128, 2 * lane), m1 = row_mask(b, j * 128, 2 * lane + 1);
                     const bool p0 = lane_of(m0), p1 = lane_of(m1);
                     const uint32_t r0 = wave_total + mbcnt(m0) + mbcnt(m1), r1 = r0 + (p0 ? 1u : 0u);
-                    if (project && p0 && r0 < cap) sv[r0] = v[0][2 * j];
-                    if (project && p1 && r1 < cap) sv[r1] = v[0][2 * j + 1];
+                    if (project && p0 && r0 < cap) sv[r0] = a;
+                    if (project && p1 && r1 < cap) sv[r1] = b;
                     if constexpr (kSel) if (want_sel) sel_collect<2>(selw, 2 * j, m0, m1, lane);
                     wave_total += static_cast<uint32_t>(__popcll(m0) + __popcll(m1));
                 }
@@ -769,7 +782,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
         if (wave == 0 && ret.have)
             resolve(ret, Desc{uniform32(static_cast<uint32_t>(prev_desc)), uniform32(static_cast<uint32_t>(prev_desc >> 32))}, s_excl);
         if (more) {
-            load_rows<NCOLS, R, VEC>(p.in, ntb + static_cast<uint64_t>(wave) * ROWS_PER_WAVE, lane, v);
+            load_tile_rows(ntb + static_cast<uint64_t>(wave) * ROWS_PER_WAVE);
             prefetch_bits(ntb + static_cast<uint64_t>(wave) * ROWS_PER_WAVE);
         }
         if (lane == 0) s_wtot[wave] = wave_total;

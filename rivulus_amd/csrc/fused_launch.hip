@@ -15,12 +15,14 @@ namespace rvl {
 // ---------------------------------------------------------------------------------------
 // Smallest instantiation whose feature flags cover `need`; for one-column lean/validity
 // launches the geometry can be steered with rv_ctx_set_option("rows_per_lane", R | waves << 8).
-const rvk::FusedEntry *find_fused(rv_ctx *ctx, int ncols, int vec, int need, int roomy = 0, int below_r = 1 << 30) {
+constexpr int kNarrowFlags = rvk::FF_NARROW16 | rvk::FF_NARROW32;
+// `prefer_r` > 0: that many rows per lane among the default level's geometries, when the class has one
+const rvk::FusedEntry *find_fused(rv_ctx *ctx, int ncols, int vec, int need, int roomy = 0, int below_r = 1 << 30, int prefer_r = 0) {
     const rvk::FusedEntry *best = nullptr;
     auto scan = [&](const rvk::FusedEntry *t, size_t n) {
         for (size_t i = 0; i < n; ++i) {
             const rvk::FusedEntry &e = t[i];
-            constexpr int kShape = rvk::FF_ONE_I64 | rvk::FF_ONE_F64 | rvk::FF_STAMP | rvk::FF_PROJALL | rvk::FF_NONULL | rvk::FF_EXPR;  // must match exactly
+            constexpr int kShape = rvk::FF_ONE_I64 | rvk::FF_ONE_F64 | rvk::FF_STAMP | rvk::FF_PROJALL | rvk::FF_NONULL | rvk::FF_EXPR | kNarrowFlags;  // must match exactly
             // the generic FF_PROJALL instantiations write the selection bitmap on request (fused_kernel.hpp, kSel)
             const int has = e.flags | (((e.flags & rvk::FF_PROJALL) && !(e.flags & (rvk::FF_ONE_I64 | rvk::FF_ONE_F64))) ? rvk::FF_SEL : 0);
             if (e.ncols != ncols || (ncols > 0 && e.vec != vec) || (has & need) != need) continue;
@@ -30,6 +32,8 @@ const rvk::FusedEntry *find_fused(rv_ctx *ctx, int ncols, int vec, int need, int
                 const int want_r = static_cast<int>(ctx->opt_rows_per_lane & 0xFF);
                 const int want_w = static_cast<int>((ctx->opt_rows_per_lane >> 8) & 0xFF);
                 wanted = e.r == want_r && (want_w == 0 || e.waves == want_w);
+            } else if (prefer_r > 0 && roomy == 0) {
+                wanted = e.r == prefer_r;
             }
             // roomy 1: a 16-wave geometry with fewer rows per lane -- its LDS slots hold a larger share of a wave's
             // rows; roomy 2: the 8-wave geometries of fused_roomy.hip, whose slots hold every row of a wave
@@ -52,22 +56,42 @@ const rvk::FusedEntry *find_fused(rv_ctx *ctx, int ncols, int vec, int need, int
         t = rvk::fused_entries_full(&n), scan(t, n);
         t = rvk::fused_entries_expr(&n), scan(t, n);
         t = rvk::fused_entries_roomy(&n), scan(t, n);
+        t = rvk::fused_entries_narrow(&n), scan(t, n);
         vec = 1;  // every feature set exists with 8-byte loads
     }
     return best;
 }
 // `prefer`: shape flags worth having when an instantiation exists (FF_PROJALL)
-const rvk::FusedEntry &pick_fused(rv_ctx *ctx, int ncols, int vec, int need, int prefer = 0, int roomy = 0, int below_r = 1 << 30) {
+const rvk::FusedEntry &pick_fused(rv_ctx *ctx, int ncols, int vec, int need, int prefer = 0, int roomy = 0, int below_r = 1 << 30, int prefer_r = 0) {
     // the refinements the launch qualifies for, dropped one by one (FF_NONULL first) until an instantiation exists
     const rvk::FusedEntry *best = nullptr;
     for (const int pf : {prefer, prefer & ~rvk::FF_NONULL}) {
         if (best || !pf) continue;
-        best = find_fused(ctx, ncols, vec, need | pf, roomy, below_r);
+        best = find_fused(ctx, ncols, vec, need | pf, roomy, below_r, prefer_r);
         if (best && (best->flags & ~(need | pf)) != 0) best = nullptr;  // not at the price of features the launch does not need
     }
-    if (!best) best = find_fused(ctx, ncols, vec, need, roomy, below_r);
+    if (!best) best = find_fused(ctx, ncols, vec, need, roomy, below_r, prefer_r);
     require(best != nullptr, RV_ERR_INTERNAL, fmt("no fused kernel variant for %d columns, flags %d", ncols, need));
     return *best;
+}
+
+// The plain lean Int64 instantiation of a narrow one's geometry: what re-runs a pass over codes after an output overflow.
+static void (*plain_twin(const rvk::FusedEntry &e))(const rvk::FusedParams) {
+    size_t n = 0;
+    const rvk::FusedEntry *t = rvk::fused_entries_lean1(&n);
+    for (size_t i = 0; i < n; ++i)
+        if (t[i].ncols == e.ncols && t[i].r == e.r && t[i].vec == e.vec && t[i].waves == e.waves && t[i].flags == (e.flags & ~kNarrowFlags)) return t[i].fn;
+    const rvk::FusedEntry tall = rvk::narrow_tall_plain();  // (not a geometry of the lean table)
+    if (tall.ncols == e.ncols && tall.r == e.r && tall.vec == e.vec && tall.waves == e.waves && tall.flags == (e.flags & ~kNarrowFlags)) return tall.fn;
+    return nullptr;
+}
+// (costs several microseconds: once per (kernel, LDS size) and context)
+static void enable_lds(rv_ctx *ctx, const void *fn, size_t lds) {
+    size_t &enabled = ctx->lds_enabled[fn];
+    if (lds > enabled) {
+        RV_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+        enabled = lds;
+    }
 }
 
 // Selectivity of the lowered predicate `in` over a strided sample of its rows; -1 when the sample could not be taken.
@@ -374,6 +398,7 @@ struct LaunchChoice {
     uint32_t cap = 0, ntiles = 0;
     uint64_t tile_rows = 0;
     bool make_selection = false;  // the selection bitmap deferred for per-batch counts is wanted after all (the pass cannot count them)
+    const NarrowCodes *narrow = nullptr;  // the pass reads these codes instead of the column's 8-byte values (FF_NARROW16 / FF_NARROW32)
     double redo_expected = 0.0;   // share of the staged pass's wave ranges expected to outgrow their slots
 };
 
@@ -521,7 +546,7 @@ static double redo_estimate(rv_ctx *ctx, const FusedLaunch &L, double seen, bool
 // `sampled_now`: out of a sample this call took), the caller's side outputs and the context's options and predicate memory.  Allocates
 // nothing, queues nothing, writes nothing of the context.  `row_bytes`: what a row of the outputs takes in an LDS slot (bind_outputs).
 static LaunchChoice choose_launch(rv_ctx *ctx, const FusedLaunch &L, const Bound &b, size_t row_bytes, bool expr, bool sel_deferred, double seen,
-                                  bool sampled_now, const BatchReq *req, const RangeOffsets *ranges) {
+                                  bool sampled_now, const BatchReq *req, const RangeOffsets *ranges, const NarrowCodes *narrow) {
     const rvk::FusedParams &p = L.p;
     const int nvals = b.nvals, npred = b.npred, nxs = p.nxs;
     const uint64_t n = p.in.n;
@@ -544,6 +569,10 @@ static LaunchChoice choose_launch(rv_ctx *ctx, const FusedLaunch &L, const Bound
     // predicate shape: one compare term on the only loaded column, no nulls -> single-pass fast path
     if (!expr && (c.need & ~rvk::FF_SEL) == 0 && nvals == 1 && p.in.nterms == 1 && !p.in.terms[0].is_bool() && p.in.terms[0].code() != rvk::TC_CONST)
         c.need |= p.in.terms[0].is_float() ? rvk::FF_ONE_F64 : rvk::FF_ONE_I64;
+    // the lean Int64 form over a column whose buffer has a narrow companion (narrow.hip: built, covering this view, first element even)
+    // reads the codes: the default row mapping only (16-byte loads, no forced geometry), no diagnostics
+    if (narrow && c.need == rvk::FF_ONE_I64 && vec == 2 && !L.place && ctx->opt_rows_per_lane <= 0 && !ctx->opt_stamp && !ctx->opt_debug)
+        c.need |= narrow->code_bytes == 2 ? rvk::FF_NARROW16 : rvk::FF_NARROW32;
     // diagnostics (per-phase stamps, ablations) exist in the FF_STAMP instantiations only; "debug" implies them
     if ((ctx->opt_stamp || ctx->opt_debug) && (c.need == rvk::FF_ONE_I64 || (nvals == 2 && c.need == rvk::FF_VALIDITY))) c.need |= rvk::FF_STAMP;
     // every loaded column projected, output bitmap exactly where there is an input bitmap?
@@ -592,7 +621,10 @@ static LaunchChoice choose_launch(rv_ctx *ctx, const FusedLaunch &L, const Bound
     int min_r = 0, below_r = 1 << 30;  // pick_fused's `roomy` level (0 default, 1 walk down the 16-wave geometries, 2 fewest waves)
     bool dense_sizing = false;
     while (!c.direct) {
-        c.staged = &pick_fused(ctx, nvals, vec, c.need, prefer, min_r, below_r);
+        // (a pass over codes without per-batch counts: the tall geometry, fused_narrow.hip -- a 1024-row batch is no whole number of its
+        // 2048-row wave ranges)
+        const int tall_r = ((c.need & kNarrowFlags) && !(req && req->counts)) ? rvk::kNarrowTallRows : 0;
+        c.staged = &pick_fused(ctx, nvals, vec, c.need, prefer, min_r, below_r, tall_r);
         if (min_r == 1 && (c.staged->waves != 16 || c.staged->r >= below_r)) {  // no 16-wave geometry below that many rows per lane left
             if (!dense_sizing) {  // the walk again, sized for a dense selection
                 dense_sizing = true;
@@ -604,7 +636,7 @@ static LaunchChoice choose_launch(rv_ctx *ctx, const FusedLaunch &L, const Bound
         }
         if (sel_deferred && !c.make_selection && !counts_in_pass(req, c.staged->r)) {  // the caller will count the selection bitmap instead
             c.make_selection = true;
-            c.need |= rvk::FF_SEL;
+            c.need = (c.need | rvk::FF_SEL) & ~kNarrowFlags;  // (the forms that write the selection bitmap read the 8-byte values)
             c.staged = &pick_fused(ctx, nvals, vec, c.need, prefer, min_r, below_r);
         }
         size_staged(ctx, c, *c.staged, n, nvals, nxs, row_bytes, dense_sizing);
@@ -629,6 +661,7 @@ static LaunchChoice choose_launch(rv_ctx *ctx, const FusedLaunch &L, const Bound
     }
     if (c.direct) c.r = c.direct->r, c.vec = 1, c.waves = c.direct->waves, c.flags = c.direct->flags, c.fn = c.direct->fn;
     else c.r = c.staged->r, c.vec = c.staged->vec, c.waves = c.staged->waves, c.flags = c.staged->flags, c.fn = c.staged->fn;
+    if (!c.direct && (c.flags & kNarrowFlags)) c.narrow = narrow;
     return c;
 }
 
@@ -659,12 +692,15 @@ static void launch_pass(rv_ctx *ctx, FusedLaunch &L, const LaunchChoice &c, int 
     p.redo_count = &ctrl->redo_count;
     p.redo = L.nranges ? reinterpret_cast<unsigned long long *>(static_cast<unsigned char *>(L.ctrl.dev) + kCtrlBytes + static_cast<size_t>(p.ntiles) * 8) : nullptr;
 
-    // both calls cost several microseconds: once per (kernel, LDS size) and context
     const void *fn = reinterpret_cast<const void *>(c.fn);
-    size_t &enabled = ctx->lds_enabled[fn];
-    if (c.lds > enabled) {
-        RV_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(c.lds)));
-        enabled = c.lds;
+    enable_lds(ctx, fn, c.lds);
+    if (c.narrow) {
+        p.narrow.codes = c.narrow->codes->ptr;
+        p.narrow.bytes = c.narrow->codes->bytes;
+        p.narrow.base = c.narrow->base;
+        L.fn_plain = plain_twin(*c.staged);
+        require(L.fn_plain != nullptr, RV_ERR_INTERNAL, "narrow pass without a plain instantiation of its geometry");
+        ctx->narrow_passes += 1;
     }
     // persistent grid: as many workgroups as the device keeps resident (tiles are handed out
     // by the ticket counter, so residency is a speed matter only, never correctness)
@@ -807,7 +843,14 @@ void fused_begin(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, con
         L.launched = false;
         return;
     }
-    const LaunchChoice c = choose_launch(ctx, L, b, row_bytes, ex != nullptr, sel_deferred, seen, sampled_now, req, ranges);
+    // the lean one-column Int64 pass: the buffer's narrow companion, when it has one this view can read (narrow.hip)
+    const rv_dcolumn *lean = (b.nvals == 1 && nterms == 1 && !ex && !L.place && cols[terms[0].column]->dtype == RV_INT64) ? cols[terms[0].column] : nullptr;
+    narrow_note_extent(ctx, lean);
+    const LaunchChoice c = choose_launch(ctx, L, b, row_bytes, ex != nullptr, sel_deferred, seen, sampled_now, req, ranges, lean ? narrow_codes_for(ctx, lean) : nullptr);
+    if (lean && c.staged && !c.direct && (c.flags & rvk::FF_ONE_I64)) {  // counted towards the buffer's whole scans by fused_finish
+        L.lean_values = lean->values;
+        L.lean_offset = lean->offset;
+    }
     launch_pass(ctx, L, c, b.nvals, sel_out, req, ranges, seen);
 }
 
@@ -864,7 +907,8 @@ uint64_t fused_finish(rv_ctx *ctx, FusedLaunch &L) {
         alloc_outputs(ctx, L, exact);
         const size_t zeroed = kCtrlBytes + (static_cast<size_t>(p.ntiles) + L.nranges) * 8;
         RV_HIP(hipMemsetAsync(L.ctrl.dev, 0, (zeroed + 15) & ~size_t(15), ctx->stream));
-        hipLaunchKernelGGL(L.fn, dim3(L.grid), dim3(L.block), L.lds, ctx->stream, p);
+        if (L.fn_plain) enable_lds(ctx, reinterpret_cast<const void *>(L.fn_plain), L.lds);  // a pass over codes: re-run over the 8-byte values
+        hipLaunchKernelGGL(L.fn_plain ? L.fn_plain : L.fn, dim3(L.grid), dim3(L.block), L.lds, ctx->stream, p);
         RV_HIP(hipGetLastError());
         RV_HIP(hipMemcpyAsync(L.ctrl.host, L.ctrl.dev, kCtrlBytes, hipMemcpyDeviceToHost, ctx->stream));
         RV_HIP(hipStreamSynchronize(ctx->stream));
@@ -929,6 +973,11 @@ uint64_t fused_finish(rv_ctx *ctx, FusedLaunch &L) {
             // builder drops it (primitive.rs:179-185) -- a stretch keeps its own: the table's bitmap is put together from all of them
             if (o.col->null_count == 0 && !L.place) o.col->validity.reset();
         }
+    }
+    if (L.lean_values) {  // a whole scan more of the column's buffer?  Its narrow companion is queued behind this pass then (narrow.hip)
+        const DevBufRef values = std::move(L.lean_values);
+        L.lean_values.reset();
+        narrow_after_pass(ctx, *values, L.lean_offset, L.n);
     }
     return rows;
 }

@@ -26,6 +26,9 @@ const FusedEntry *fused_entries_bool(size_t *n);    // Boolean-column predicate,
 const FusedEntry *fused_entries_full(size_t *n);    // every feature (Boolean terms/columns, selection)
 const FusedEntry *fused_entries_expr(size_t *n);    // OR / NOT expressions (conjunctive normal form)
 const FusedEntry *fused_entries_roomy(size_t *n);   // 2..4 columns, slots that hold every row of a wave (dense selections)
+const FusedEntry *fused_entries_narrow(size_t *n);  // 1 Int64 column read as 2- / 4-byte codes of its narrow companion
+constexpr int kNarrowTallRows = 32;                 // rows per lane of a narrow pass without per-batch counts (fused_narrow.hip)
+FusedEntry narrow_tall_plain();                     // the plain lean Int64 form of that geometry
 // the direct (register-staged) kernel for dense selections (direct_kernel.hpp): np 8-byte columns the predicate reads, nq more
 // that are only projected; flags: FF_VALIDITY / FF_BOOL of the predicate's inputs
 struct DirectEntry {

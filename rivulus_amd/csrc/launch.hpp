@@ -1,4 +1,4 @@
-// Internal interface between the translation units of librivulus_gpu.so (core / fused_launch / strings / predicate / arrays /
+// Internal interface between the translation units of librivulus_gpu.so (core / fused_launch / narrow / strings / predicate / arrays /
 // query / take_concat / host_table / aggregate / join / string_dict / csv / group / group_agg / sort .hip): the control block, the request / launch
 // records that travel with a fused pass, and the functions the units call across each other.  Nothing here is part of the C ABI.
 #pragma once
@@ -128,6 +128,12 @@ struct FusedLaunch {
     bool place_edge = false;  // a sparse stretch next to a dense one: the block the edge falls into leaves a few wave ranges to the redo kernel
     bool overflowed = false;
     uint32_t out_bias = 0;  // out: FusedParams::out_bias of the launch (place_base & 15)
+    // ---- the lean one-column Int64 pass (FF_ONE_I64) and the narrow companion of the buffer it reads (narrow.hip): fused_finish counts
+    //      the pass towards the buffer's whole scans; a pass that read CODES is re-run after an output overflow by `fn_plain`, the same
+    //      geometry over the 8-byte values
+    DevBufRef lean_values;
+    uint64_t lean_offset = 0;
+    void (*fn_plain)(const rvk::FusedParams) = nullptr;
 };
 struct SegmentOverflow {};  // thrown by run_segmented_pass's callee chain: the shared outputs were too small -- the caller falls back to one pass
 
@@ -183,6 +189,11 @@ struct BoolCompactLaunch {
     bool launched = false;
 };
 
+
+// ---- narrow.hip --------------------------------------------------------------------------------------------
+void narrow_note_extent(rv_ctx *ctx, const rv_dcolumn *col);
+const NarrowCodes *narrow_codes_for(rv_ctx *ctx, const rv_dcolumn *col);
+void narrow_after_pass(rv_ctx *ctx, DevBuf &buf, uint64_t offset, uint64_t rows);
 
 // ---- strings.hip -------------------------------------------------------------------------------------------
 // total_dst (device, zeroed by the caller): where the scan leaves its total instead of the context's control block -- nothing of the

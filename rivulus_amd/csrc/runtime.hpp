@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/rivulus_gpu.h"
+#include "narrow_rule.hpp"
 
 namespace rvh {
 
@@ -119,17 +120,39 @@ class Pool {
     std::multimap<size_t, void *> free_;
 };
 
+struct NarrowCodes;
 struct DevBuf {
     void *ptr = nullptr;
     size_t bytes = 0;  // readable bytes (pool blocks: the whole block)
     uint64_t id = 0;   // pool blocks: unique per allocation (the pool hands a freed table's address to the next one: what a predicate's
                        // remembered selectivity is keyed on must not be inherited with it); 0: caller-owned memory, keyed by address
     std::shared_ptr<Pool> pool;  // null: caller-owned memory (rv_wrap)
+    // The narrow companion of an Int64 values buffer (below), what the lean passes have read of the buffer so far, and whether a
+    // companion was refused (a value range of 2^32 and more, or no memory for it: not tried again).  They live and die with THIS
+    // record, which pool_alloc makes anew for every allocation: a freed table's block handed out again starts without codes.
+    std::shared_ptr<NarrowCodes> narrow;
+    rvn::ScanCover scan;
+    bool narrow_refused = false;
     ~DevBuf() {
         if (pool && ptr) pool->give_back(ptr, bytes);
     }
 };
 using DevBufRef = std::shared_ptr<DevBuf>;
+
+// Frame-of-reference codes of a resident Int64 column: codes[i] = uint(value[i] - base) for every element i < count of the values
+// buffer, 2 or 4 bytes each, base = the column minimum.  A column is immutable once its handle is out (like Arc<[T]>) and scanned
+// again and again while it is resident; the lean one-column filter pass decides its predicate over values that need 16 or 32 bits by
+// reading 64, so it reads the codes instead (scan_frontend.hpp, FF_NARROW16 / FF_NARROW32) and widens them in registers.  The codes
+// depend on the column alone: every predicate over it uses them, and so does every slice of it -- they hang off the values buffer.
+// The 8-byte original always stays (the redo kernel, the sampler, every other shape read it).
+// MEMORY: + 25 % of the column for 2-byte codes, + 50 % for 4-byte codes, held until the buffer is freed (option "narrow_codes" = -1:
+// never built).  Built by narrow.hip when the buffer has been scanned often enough (narrow_rule.hpp, thresholds.hpp).
+struct NarrowCodes {
+    DevBufRef codes;
+    int code_bytes = 0;  // 2 or 4
+    int64_t base = 0;
+    uint64_t count = 0;  // elements covered, from element 0 of the values buffer
+};
 
 }  // namespace rvh
 
@@ -255,6 +278,10 @@ struct rv_ctx {
     int64_t opt_sort_engine = 0;    // 0: the sort's own radix passes; 1 (measurements, tests): the pair sort by rocprim::radix_sort_pairs over all 64 bits
     uint64_t sort_last_passes = 0;  // scatter passes the last sort call ran (the null pass included)
     int64_t opt_bools_in_pass = 0;  // 1: projected Boolean columns are compacted inside the fused pass (lane-form PEXT)
+    int64_t opt_narrow_codes = 0;   // narrow companions of Int64 columns (NarrowCodes): 0 auto, -1 never, 1 at the first whole scan at any size (tests)
+    uint64_t narrow_builds = 0;     // companions built by this context
+    uint64_t narrow_passes = 0;     // fused passes that read codes instead of the 8-byte values
+    uint64_t narrow_bytes = 0;      // bytes of codes those builds allocated
     int64_t opt_csv_slow_cap = 0;   // tests: k > 0 caps a CSV chunk's first list of undecided Float64 cells at k (forces the re-parse)
     uint64_t csv_slow_cells = 0;    // Float64 cells the CSV scan's exact slow kernel decided (csv_f64_slow), context total
     uint64_t csv_slow_reparses = 0; // CSV chunks parsed twice because their undecided cells outgrew the first list

@@ -38,6 +38,10 @@ enum : int { FF_EXPR = 512 };
 // direct kernel only (direct_kernel.hpp): some projected column keeps nulls among the survivors -- validity bits are compacted with
 // the rows (a byte per survivor next to its value in the LDS slot, packed to words on the way out)
 enum : int { FF_OUTVALID = 2048 };
+// Lean Int64 form only (FF_ONE_I64, one column, 16-byte row mapping): the rows are read as the 2- or 4-byte frame-of-reference codes
+// of the column's narrow companion (runtime.hpp, NarrowCodes; narrow.hip) and widened in registers, value = base + code.  Only the
+// load differs: everything behind it sees the same Int64 values.
+enum : int { FF_NARROW16 = 4096, FF_NARROW32 = 8192 };
 
 // A bit stream compacted with the rows: out bit = src bit (& mask bit).
 struct BitStream {
@@ -158,6 +162,46 @@ __device__ __forceinline__ void load_rows(const ScanInputs &in, uint64_t wave_ba
             }
         }
     }
+}
+
+// ---- the same rows out of the column's narrow companion (FF_NARROW16 / FF_NARROW32) -------------------------------------------
+// codes[i] = uint(value[i] - base) for every element of the values buffer, 2 or 4 bytes each (narrow_kernel.hpp).  The row-to-lane
+// mapping is that of VEC == 2: lane l takes rows 2l, 2l + 1 of each 128-row group j -- ONE 4-byte (2-byte codes) or 8-byte (4-byte
+// codes) nontemporal buffer load per pair, kept RAW in v[j] until the tile is evaluated (widen_pair): an addition issued with the
+// prefetch would wait for it on the spot.  The descriptor is bounded by the code bytes left in the companion, not by the rows of
+// the slice: a pair that straddles the slice's last row is still read whole (the ragged tile's row mask drops what lies past it), and
+// what lies past the companion reads 0.  `first` (element of the buffer) must be even: the pair's load is then aligned.
+struct NarrowView {
+    const void *codes;  // of element 0 of the values buffer
+    uint64_t bytes;     // readable bytes behind it
+    int64_t base;       // the column minimum
+};
+template <int R, int BYTES>
+__device__ __forceinline__ void load_rows_narrow(const NarrowView &nv, uint64_t first, int lane, uint64_t (&v)[R]) {
+    static_assert((BYTES == 2 || BYTES == 4) && R % 2 == 0, "narrow codes");
+    constexpr uint64_t WAVE_BYTES = 64u * R * BYTES;
+    const uint64_t at = first * BYTES;
+    const uint64_t left = nv.bytes > at ? nv.bytes - at : 0;
+    const uint32_t nbytes = uniform32(static_cast<uint32_t>(left < WAVE_BYTES ? left : WAVE_BYTES));
+    const uint64_t base = uniform64(reinterpret_cast<uint64_t>(nv.codes) + at);
+    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void *>(base), 0, nbytes, 0x00020000);
+#pragma unroll
+    for (int j = 0; j < R / 2; ++j) {
+        if constexpr (BYTES == 2) {
+            v[j] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, lane * 4, j * 256, kStreamPolicy);
+        } else {
+            const rv_u32x2 t = __builtin_amdgcn_raw_buffer_load_b64(rsrc, lane * 8, j * 512, kStreamPolicy);
+            v[j] = (static_cast<uint64_t>(t.y) << 32) | t.x;
+        }
+    }
+}
+// a raw pair -> the Int64 values of its two rows (rows 2l, 2l + 1 of the pair's 128-row group)
+template <int BYTES>
+__device__ __forceinline__ void widen_pair(int64_t base, uint64_t raw, uint64_t &row0, uint64_t &row1) {
+    const uint32_t c0 = BYTES == 2 ? static_cast<uint32_t>(raw) & 0xFFFFu : static_cast<uint32_t>(raw);
+    const uint32_t c1 = BYTES == 2 ? static_cast<uint32_t>(raw) >> 16 : static_cast<uint32_t>(raw >> 32);
+    row0 = static_cast<uint64_t>(base) + c0;
+    row1 = static_cast<uint64_t>(base) + c1;
 }
 
 // The validity words of a wave's rows travel with the row prefetch: lane k holds the aligned 64-bit

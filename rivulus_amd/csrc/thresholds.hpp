@@ -51,6 +51,18 @@ constexpr int kStretchLeastBlocks = 24, kStretchesMost = 4;
 // 1.046 against 0.128 / 0.326 / 0.629 / 1.140)                                             profiles/r05d_stretches_by_rows.txt, tools/stretch_rows.py
 constexpr uint64_t kStretchFromRows = uint64_t{1} << 28;
 
+// ---- narrow companions of resident Int64 columns (narrow.hip, narrow_rule.hpp) ------------------------------------------------------
+// A values buffer the lean one-column pass has read from end to end this many times gets 2- or 4-byte frame-of-reference codes, and the
+// lean passes after that read those.  The build is a min/max pass and a pack pass over the 8-byte values (1.27 + 1.85 ms of kernels per
+// 1e9 rows, 4.4 ms on the calls around it), the pass over codes saves 0.53 ms of 1.33 per scan -- break-even after ~8 further scans (~6
+// at 2^28 rows, ~11 at 2^25): the first scan alone says nothing about a second one (a one-shot collect() must
+// not pay for codes nobody reads), the second one does.  Buffers below kNarrowFromRows elements are left alone: a pass over them is
+// launch and read-back time, not bytes (plain / codes, ms per call: 2^20 0.032 / 0.036, 2^22 0.041 / 0.038, 2^24 0.054 / 0.047, 2^25 0.077 /
+// 0.058, 2^28 0.388 / 0.235; the size below which a first call is not sampled either).  Option "narrow_codes": 1 packs at
+// the first whole scan whatever the size (tests), -1 never.                      tests/test_narrow_codes_gpu.py, profiles/narrow_costs.json
+constexpr uint64_t kNarrowAfterWholeScans = 2;
+constexpr uint64_t kNarrowFromRows = uint64_t{1} << 25;
+
 // ---- which columns the pass carries (query.hip, filter_by_groups) ---------------------------------------------------------------
 // Columns compacted AFTER the pass at its wave offsets (compact_ranges_kernel) instead of inside it, for tables this big:
 constexpr uint64_t kRangesFromRows = uint64_t{1} << 24;
