@@ -233,6 +233,8 @@ rv_status rv_ctx_device_info(rv_ctx *ctx, int *compute_units, uint64_t *hbm_byte
  * every selectivity; 1 = always; -1 = never),
  * "speculative_batches" (rv_filter_project_batches launches the pass of a window that looks regular before its handles are
  * validated and validates meanwhile: 0 = from 4096 batches on, -1 = never), "wgs_per_cu" (0 = occupancy query),
+ * "grid_limit" (tests: a staged pass launches at most k worker workgroups next to its scanner workgroup, so that a small table makes one
+ * workgroup walk many tiles; 0 = as many as the device keeps resident.  Tiles are handed out by a ticket counter: a speed matter only),
  * "agg_grid" (rv_filter_agg: workgroups per CU striding over the tiles; 0 = 8192 workgroups whatever the CU count, -1 = one workgroup per tile),
  * "profile_kernels" (0/1), "out_sizing" (capacity of the output buffers: 0, the default = a table of 2^25 rows and more gets outputs
  * for what its predicate is known to keep -- its last pass over these buffers, or the first call's sample -- x 1.2 + 2 % of the rows,
@@ -247,7 +249,10 @@ rv_status rv_ctx_device_info(rv_ctx *ctx, int *compute_units, uint64_t *hbm_byte
  * the 8-byte values; same rows, same order, same bits.  MEMORY: + 25 % of the column for 2-byte codes, + 50 % for 4-byte codes, held
  * until the column's buffer is freed; a range of 2^32 and more, or no memory for the codes, means no companion and never a failed
  * query.  Only buffers the library allocated qualify -- columns are immutable once their handle is out; rv_wrap memory is the caller's
- * to write and is never packed.  0 = as described, -1 = never, 1 = at the first whole scan whatever the size (tests); read-only
+ * to write and is never packed.  0 = as described, -1 = never, 1 = at the first whole scan whatever the size (tests) -- and only with 1 does a launch with a
+ * forced "rows_per_lane" geometry or the "stamp" / "debug" diagnostics read the codes, and only where exactly that instantiation exists
+ * over codes (the forced geometry; for the diagnostics 2-byte codes at 32 or 16 rows per lane): every other such launch reads the
+ * 8-byte values at the geometry asked for, a 4-byte companion under the diagnostics included; read-only
  * counters "narrow_builds", "narrow_passes", "narrow_bytes").  Diagnostics only, never for results: "stamp" (per-phase cycle
  * counters, printed to stderr) and "debug" (bit 0 skip the value stores, bit 1 skip the
  * output-offset lookup -- both make the output WRONG, timing shares only -- bit 2 print

@@ -374,6 +374,10 @@ rv_status rv_ctx_set_option(rv_ctx *ctx, const char *key, int64_t value) {
         else if (k == "vec") ctx->opt_vec = value;
         else if (k == "cap_rows") ctx->opt_cap_rows = value;
         else if (k == "wgs_per_cu") ctx->opt_wgs_per_cu = value;
+        else if (k == "grid_limit") {
+            require(value >= 0, RV_ERR_INVALID_ARG, "grid_limit: 0 (none) or a number of worker workgroups");
+            ctx->opt_grid_limit = value;
+        }
         else if (k == "stamp") ctx->opt_stamp = value;
         else if (k == "debug") ctx->opt_debug = value;
         else if (k == "depth") ctx->opt_depth = value;
@@ -437,6 +441,7 @@ rv_status rv_ctx_get_option(rv_ctx *ctx, const char *key, int64_t *value) {
         else if (k == "vec") *value = ctx->opt_vec;
         else if (k == "cap_rows") *value = ctx->opt_cap_rows;
         else if (k == "wgs_per_cu") *value = ctx->opt_wgs_per_cu;
+        else if (k == "grid_limit") *value = ctx->opt_grid_limit;
         else if (k == "depth") *value = ctx->opt_depth;
         else if (k == "roomy") *value = ctx->opt_roomy;
         else if (k == "direct") *value = ctx->opt_direct;

@@ -202,6 +202,8 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
     static_assert(!kOne || (NCOLS == 1 && (FLAGS & (FF_VALIDITY | FF_BOOL | FF_XS)) == 0), "single-term fast path");
     constexpr int kNarrow = (FLAGS & FF_NARROW16) ? 2 : ((FLAGS & FF_NARROW32) ? 4 : 0);  // bytes of a code; 0: the 8-byte rows
     static_assert(!kNarrow || ((FLAGS & FF_ONE_I64) != 0 && VEC == 2 && (FLAGS & (FF_NARROW16 | FF_NARROW32)) != (FF_NARROW16 | FF_NARROW32)), "narrow codes: lean Int64 form");
+    using Raw = typename NarrowRaw<kNarrow == 4 ? 4 : 2>::type;  // a lane's pair of codes, as loaded
+    constexpr int NRAW = kNarrow != 0 ? R / 2 : 1;
     // selector masks of term 0 (all ones / all zeros), fixed for the launch
     const DevTerm term0 = p.in.terms[0];
     const uint64_t SLT = term0.sel_lt() ? ~0ull : 0, SEQ = term0.sel_eq() ? ~0ull : 0, SGT = term0.sel_gt() ? ~0ull : 0,
@@ -240,7 +242,8 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
 #pragma unroll
         for (int c = 0; c < NV; ++c) {
             off_v[c] = cur;
-            if (c < NCOLS && (kAll || p.out_values[c])) cur += cap * 8;
+            // (a pass over codes stages the survivors' CODES: the same `cap` rows in a quarter or half of the bytes)
+            if (c < NCOLS && (kAll || p.out_values[c])) cur += cap * (kNarrow != 0 ? static_cast<uint32_t>(kNarrow) : 8u);
         }
 #pragma unroll
         for (int c = 0; c < NV; ++c) {
@@ -269,6 +272,14 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
         for (int c = 0; c < NCOLS; ++c) {
             if (!p.out_values[c]) continue;
             uint64_t *dst = p.out_values[c] + g0;
+            if constexpr (kNarrow != 0) {  // staged codes -> value = base + code, widened here: one addition per survivor
+                using Code = typename std::conditional<kNarrow == 2, uint16_t, uint32_t>::type;
+                const Code *sc = reinterpret_cast<const Code *>(smem + sb + off_v[c]);
+                const uint64_t base = static_cast<uint64_t>(p.narrow.base);
+                if (!(kStamp && (p.debug & 1)))
+                    for (uint32_t k = fl; k < cnt; k += 64) __builtin_nontemporal_store(base + sc[k], &dst[k]);
+                continue;
+            }
             const uint64_t *sv = reinterpret_cast<const uint64_t *>(smem + sb + off_v[c]);
             if (!(kStamp && (p.debug & 1)))
                 for (uint32_t k = fl; k < cnt; k += 64) __builtin_nontemporal_store(sv[k], &dst[k]);
@@ -321,12 +332,21 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
     if (threadIdx.x == 0) *s_redo = 0;
     __syncthreads();
     uint32_t tile = uniform32(s_tick[0]);
-    uint64_t v[NV][R];
+    uint64_t v[NV][kNarrow != 0 ? 1 : R];
     auto load_tile_rows = [&](uint64_t first_row) {  // of this wave
-        if constexpr (kNarrow != 0) load_rows_narrow<R, kNarrow>(p.narrow, p.in.cols[0].offset + first_row, lane, v[0]);
-        else load_rows<NCOLS, R, VEC>(p.in, first_row, lane, v);
+        if constexpr (kNarrow == 0) load_rows<NCOLS, R, VEC>(p.in, first_row, lane, v);
     };
-    if (tile < p.ntiles) load_tile_rows(static_cast<uint64_t>(tile) * TILE + static_cast<uint64_t>(wave) * ROWS_PER_WAVE);
+    // A pass over codes keeps the tile's raw pairs instead (R / 2 registers of 2-byte codes per lane, R of 4-byte codes), requested
+    // where the plain form requests its rows: behind the staging of the tile before.  (Three sets of pairs, the tile two ahead
+    // requested at the top of an iteration with the ids drawn four ahead, measured SLOWER: fused_narrow.hip.)
+    Raw codes[NRAW];
+    auto load_tile_codes = [&](uint32_t t) {  // of this wave; a tile id >= ntiles (the ticket counter ran out) issues no load
+        if constexpr (kNarrow != 0)
+            if (t < p.ntiles)
+                load_rows_narrow<R, kNarrow>(p.narrow, p.in.cols[0].offset + static_cast<uint64_t>(t) * TILE + static_cast<uint64_t>(wave) * ROWS_PER_WAVE, lane, codes);
+    };
+    if constexpr (kNarrow != 0) load_tile_codes(tile);
+    else if (tile < p.ntiles) load_tile_rows(static_cast<uint64_t>(tile) * TILE + static_cast<uint64_t>(wave) * ROWS_PER_WAVE);
     uint64_t vw[NV];  // validity words of the loaded rows (generic shapes with null bitmaps)
     // words of the Boolean predicate columns (values, validity) and of the Boolean columns travelling with
     // the rows (source, mask): fetched with the row prefetch, like vw
@@ -399,6 +419,18 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
         n_redo += 1;
     };
 
+    // The launch's compare term in code space (a pass over codes): an interval of codes, or the complement of one (narrow_term.hpp).
+    // It travels in the term slot behind the launch's one term (launch_pass: terms[1].lit = lo | span << 32, .packed = negate; nterms
+    // stays 1, so nothing else reads that slot) -- the kernel's parameter block is the parent's, byte for byte.
+    static_assert(!kNarrow || !kSel, "the forms that write the selection bitmap read the 8-byte values (choose_launch)");
+    uint32_t TLO = 0, TSPAN = 0;
+    uint64_t TNEG = 0;
+    if constexpr (kNarrow != 0) {
+        const DevTerm ct = p.in.terms[1];
+        TLO = static_cast<uint32_t>(static_cast<uint64_t>(ct.lit));
+        TSPAN = static_cast<uint32_t>(static_cast<uint64_t>(ct.lit) >> 32);
+        TNEG = ct.packed ? ~0ull : 0;
+    }
     for (uint32_t it = 0; tile < p.ntiles; ++it) {
         // ---- ticket for three iterations ahead: issued now, stored at the end of the iteration and read
         //      at the top of iteration it + 2 (the barrier of it + 1 lies in between) --------------------
@@ -457,14 +489,28 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
                     if constexpr (kSel) if (want_sel) sel_collect<1>(selw, j, m, 0, lane);
                     wave_total += static_cast<uint32_t>(__popcll(m));
                 }
+            } else if constexpr (kNarrow != 0) {
+                // ---- a pass over codes: the term is an interval of codes or the complement of one, so a row costs one 32-bit
+                //      subtract and one unsigned compare (the compare is the ballot; `negate` is a scalar XOR with a launch constant).
+                //      No 64-bit value is formed here: survivors are staged as codes and widened where they are written out (flush).
+                using Code = typename std::conditional<kNarrow == 2, uint16_t, uint32_t>::type;
+                Code *sc = reinterpret_cast<Code *>(smem + sb + off_v[0]);
+#pragma unroll
+                for (int j = 0; j < R / 2; ++j) {
+                    uint32_t c0, c1;
+                    unpack_pair<kNarrow>(codes[j], c0, c1);
+                    uint64_t m0 = ballot64(c0 - TLO <= TSPAN) ^ TNEG, m1 = ballot64(c1 - TLO <= TSPAN) ^ TNEG;
+                    if (!full) m0 &= ballot64(2 * lane < rem - j * 128), m1 &= ballot64(2 * lane + 1 < rem - j * 128);
+                    const bool p0 = lane_of(m0), p1 = lane_of(m1);
+                    const uint32_t r0 = wave_total + mbcnt(m0) + mbcnt(m1), r1 = r0 + (p0 ? 1u : 0u);
+                    if (project && p0 && r0 < cap) sc[r0] = static_cast<Code>(c0);
+                    if (project && p1 && r1 < cap) sc[r1] = static_cast<Code>(c1);
+                    wave_total += static_cast<uint32_t>(__popcll(m0) + __popcll(m1));
+                }
             } else {
 #pragma unroll
                 for (int j = 0; j < R / 2; ++j) {
-                    // the pair's rows: registers of the 16-byte load, or -- a pass over codes -- widened here, pair by pair (value =
-                    // base + code), so that only the raw codes occupy registers while the tile is in flight
-                    uint64_t a, b;
-                    if constexpr (kNarrow != 0) widen_pair<kNarrow>(p.narrow.base, v[0][j], a, b);
-                    else a = v[0][2 * j], b = v[0][2 * j + 1];
+                    const uint64_t a = v[0][2 * j], b = v[0][2 * j + 1];  // the pair's rows: registers of the 16-byte load
                     const uint64_t m0 = row_mask(a, j * 128, 2 * lane), m1 = row_mask(b, j * 128, 2 * lane + 1);
                     const bool p0 = lane_of(m0), p1 = lane_of(m1);
                     const uint32_t r0 = wave_total + mbcnt(m0) + mbcnt(m1), r1 = r0 + (p0 ? 1u : 0u);
@@ -781,7 +827,8 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
         uint32_t *const s_wtot = s_wtot_of(it & 1);
         if (wave == 0 && ret.have)
             resolve(ret, Desc{uniform32(static_cast<uint32_t>(prev_desc)), uniform32(static_cast<uint32_t>(prev_desc >> 32))}, s_excl);
-        if (more) {
+        if constexpr (kNarrow != 0) load_tile_codes(next_tile);
+        else if (more) {
             load_tile_rows(ntb + static_cast<uint64_t>(wave) * ROWS_PER_WAVE);
             prefetch_bits(ntb + static_cast<uint64_t>(wave) * ROWS_PER_WAVE);
         }

@@ -2,6 +2,7 @@
 // One unit of the backend library behind include/rivulus_gpu.h (gfx950 only; compiled with hipcc).  Shared helpers and the
 // functions the units call across each other are declared in launch.hpp (namespace rvl).
 #include "launch.hpp"
+#include "narrow_term.hpp"
 
 #include <cmath>
 
@@ -75,14 +76,25 @@ const rvk::FusedEntry &pick_fused(rv_ctx *ctx, int ncols, int vec, int need, int
     return *best;
 }
 
-// The plain lean Int64 instantiation of a narrow one's geometry: what re-runs a pass over codes after an output overflow.
+// Does the narrow table hold an instantiation with exactly these flags -- and, for a forced geometry (option "rows_per_lane" =
+// R | waves << 8, waves 0: any), at exactly that geometry?
+static bool narrow_instantiated(int flags, int64_t forced) {
+    size_t n = 0;
+    const rvk::FusedEntry *t = rvk::fused_entries_narrow(&n);
+    const int want_r = static_cast<int>(forced & 0xFF), want_w = static_cast<int>((forced >> 8) & 0xFF);
+    for (size_t i = 0; i < n; ++i)
+        if (t[i].flags == flags && (forced <= 0 || (t[i].r == want_r && (want_w == 0 || t[i].waves == want_w)))) return true;
+    return false;
+}
+// The plain lean Int64 instantiation of a narrow one's geometry (a diagnostic one's: without the stamps): what re-runs a pass over
+// codes after an output overflow.
 static void (*plain_twin(const rvk::FusedEntry &e))(const rvk::FusedParams) {
     size_t n = 0;
     const rvk::FusedEntry *t = rvk::fused_entries_lean1(&n);
     for (size_t i = 0; i < n; ++i)
-        if (t[i].ncols == e.ncols && t[i].r == e.r && t[i].vec == e.vec && t[i].waves == e.waves && t[i].flags == (e.flags & ~kNarrowFlags)) return t[i].fn;
+        if (t[i].ncols == e.ncols && t[i].r == e.r && t[i].vec == e.vec && t[i].waves == e.waves && t[i].flags == (e.flags & ~(kNarrowFlags | rvk::FF_STAMP))) return t[i].fn;
     const rvk::FusedEntry tall = rvk::narrow_tall_plain();  // (not a geometry of the lean table)
-    if (tall.ncols == e.ncols && tall.r == e.r && tall.vec == e.vec && tall.waves == e.waves && tall.flags == (e.flags & ~kNarrowFlags)) return tall.fn;
+    if (tall.ncols == e.ncols && tall.r == e.r && tall.vec == e.vec && tall.waves == e.waves && tall.flags == (e.flags & ~(kNarrowFlags | rvk::FF_STAMP))) return tall.fn;
     return nullptr;
 }
 // (costs several microseconds: once per (kernel, LDS size) and context)
@@ -395,6 +407,7 @@ struct LaunchChoice {
     void (*fn)(const rvk::FusedParams) = nullptr;
     int need = 0;
     size_t stages = 3, lds = 0, stage_row_bytes = 0;
+    size_t lds_plain = 0;  // a pass over codes: what its plain twin needs for the same slots (the re-run after an output overflow)
     uint32_t cap = 0, ntiles = 0;
     uint64_t tile_rows = 0;
     bool make_selection = false;  // the selection bitmap deferred for per-batch counts is wanted after all (the pass cannot count them)
@@ -505,18 +518,23 @@ static void size_staged(rv_ctx *ctx, LaunchChoice &c, const rvk::FusedEntry &e, 
     c.cap = std::max<uint32_t>(c.cap, 64u * static_cast<uint32_t>(e.vec));  // a slot holds at least one chunk
     require(c.cap >= 64, RV_ERR_INTERNAL, "LDS stage too small");
     // bit streams of a lane-form launch are staged as R + 1 words of bits, whatever the slot's row capacity
-    auto lds_for = [&](size_t st, uint32_t rows) {
+    // (a pass over codes stages the survivors' codes: `cap` is sized above from the 8 bytes of a row's value, like the plain form's
+    // -- the redo rule, its memory and the walk through the geometries see the same slots -- and only the bytes of the launch shrink)
+    const size_t code_bytes = (e.flags & rvk::FF_NARROW16) ? 2 : ((e.flags & rvk::FF_NARROW32) ? 4 : 0);
+    auto lds_at = [&](size_t st, uint32_t rows, size_t row_bytes_staged) {
         const size_t xs_words = (e.vec == 1 && rows < (static_cast<uint32_t>(e.r) + 2) * 8u) ? static_cast<size_t>(nxs) * ((e.r + 2) * 8 - rows) : 0;
-        const size_t slot = (static_cast<size_t>(rows) * c.stage_row_bytes + xs_words + 15) & ~size_t(15);
+        const size_t slot = (static_cast<size_t>(rows) * row_bytes_staged + xs_words + 15) & ~size_t(15);
         return rvk::kLdsHeader + st * e.waves * slot + static_cast<size_t>(e.waves) * rvk::kLdsDumpBytes;
     };
+    auto lds_for = [&](size_t st, uint32_t rows) { return lds_at(st, rows, c.stage_row_bytes); };
     // the minimum slot of a wide row (several columns with validity bytes) times three stages can pass the CU's 160 KiB
     // (a forced "depth" = 2 on such a shape): two stages then
     constexpr size_t kLdsPerCu = 160 * 1024;
     if (c.stages == 3 && lds_for(3, c.cap) > kLdsPerCu) c.stages = 2;
     require(lds_for(c.stages, c.cap) <= kLdsPerCu, RV_ERR_UNSUPPORTED,
             fmt("fused pass: %zu bytes of LDS for %d columns at %u rows per slot", lds_for(c.stages, c.cap), nvals, c.cap));
-    c.lds = lds_for(c.stages, c.cap);
+    c.lds = c.lds_plain = lds_for(c.stages, c.cap);
+    if (code_bytes && c.stage_row_bytes == 8) c.lds = lds_at(c.stages, c.cap, code_bytes);
 }
 
 // Survivors that come in RUNS (a table sorted or clustered on the predicate's column: ids, timestamps): a wave of the staged
@@ -570,11 +588,18 @@ static LaunchChoice choose_launch(rv_ctx *ctx, const FusedLaunch &L, const Bound
     if (!expr && (c.need & ~rvk::FF_SEL) == 0 && nvals == 1 && p.in.nterms == 1 && !p.in.terms[0].is_bool() && p.in.terms[0].code() != rvk::TC_CONST)
         c.need |= p.in.terms[0].is_float() ? rvk::FF_ONE_F64 : rvk::FF_ONE_I64;
     // the lean Int64 form over a column whose buffer has a narrow companion (narrow.hip: built, covering this view, first element even)
-    // reads the codes: the default row mapping only (16-byte loads, no forced geometry), no diagnostics
-    if (narrow && c.need == rvk::FF_ONE_I64 && vec == 2 && !L.place && ctx->opt_rows_per_lane <= 0 && !ctx->opt_stamp && !ctx->opt_debug)
-        c.need |= narrow->code_bytes == 2 ? rvk::FF_NARROW16 : rvk::FF_NARROW32;
+    // reads the codes: the default row mapping only (16-byte loads).  A forced geometry ("rows_per_lane") or a diagnostic ("stamp",
+    // "debug") takes the codes only in a context that packs on request ("narrow_codes" = 1: tools/narrow_stamp.py; the older tools
+    // keep measuring the plain kernel) AND where the narrow table holds EXACTLY that instantiation -- the geometry asked for, with
+    // FF_STAMP for a diagnostic (2-byte codes at 32 and 16 rows per lane, fused_narrow.hip).  Otherwise the launch reads the 8-byte
+    // values as it always did: a forced geometry is never swapped for another one (include/rivulus_gpu.h, "narrow_codes")
+    const bool diag = ctx->opt_stamp || ctx->opt_debug;
+    if (narrow && c.need == rvk::FF_ONE_I64 && vec == 2 && !L.place && ((ctx->opt_rows_per_lane <= 0 && !diag) || ctx->opt_narrow_codes > 0)) {
+        const int codes = narrow->code_bytes == 2 ? rvk::FF_NARROW16 : rvk::FF_NARROW32;
+        if (narrow_instantiated(c.need | codes | (diag ? rvk::FF_STAMP : 0), ctx->opt_rows_per_lane)) c.need |= codes;
+    }
     // diagnostics (per-phase stamps, ablations) exist in the FF_STAMP instantiations only; "debug" implies them
-    if ((ctx->opt_stamp || ctx->opt_debug) && (c.need == rvk::FF_ONE_I64 || (nvals == 2 && c.need == rvk::FF_VALIDITY))) c.need |= rvk::FF_STAMP;
+    if (diag && ((c.need & ~kNarrowFlags) == rvk::FF_ONE_I64 || (nvals == 2 && c.need == rvk::FF_VALIDITY))) c.need |= rvk::FF_STAMP;
     // every loaded column projected, output bitmap exactly where there is an input bitmap?
     // ... or no output bitmap at all (FF_NONULL: every nullable column is tested by a null-dropping term)
     int projected = 0, nv_out = 0;  // loaded columns projected; ... whose output keeps a bitmap
@@ -698,7 +723,16 @@ static void launch_pass(rv_ctx *ctx, FusedLaunch &L, const LaunchChoice &c, int 
         p.narrow.codes = c.narrow->codes->ptr;
         p.narrow.bytes = c.narrow->codes->bytes;
         p.narrow.base = c.narrow->base;
+        // the pass compares codes: the term, lowered to an interval of codes (or the complement of one) once per launch
+        const rvk::DevTerm &t0 = p.in.terms[0];
+        const rvn::CodeTerm ct = rvn::lower_term(t0.sel_lt(), t0.sel_eq(), t0.sel_gt(), t0.lit, c.narrow->base);
+        // (in the term slot behind the launch's one term, which no other reader of `p` looks at: nterms stays 1.  truth(code) =
+        // ((code - lo) as uint32 <= span) != negate, fused_kernel.hpp)
+        p.in.terms[1].lit = static_cast<int64_t>(static_cast<uint64_t>(ct.lo) | (static_cast<uint64_t>(ct.span) << 32));
+        p.in.terms[1].packed = ct.negate ? 1u : 0u;
+        p.in.terms[1].pad = 0;
         L.fn_plain = plain_twin(*c.staged);
+        L.lds_plain = c.lds_plain;
         require(L.fn_plain != nullptr, RV_ERR_INTERNAL, "narrow pass without a plain instantiation of its geometry");
         ctx->narrow_passes += 1;
     }
@@ -713,7 +747,9 @@ static void launch_pass(rv_ctx *ctx, FusedLaunch &L, const LaunchChoice &c, int 
     int per_cu = occ->second;
     if (ctx->opt_wgs_per_cu > 0) per_cu = static_cast<int>(ctx->opt_wgs_per_cu);
     // + 1: workgroup 0 is the scanner (lookback.hpp, scanner_wave)
-    const uint32_t grid = 1 + static_cast<uint32_t>(std::min<uint64_t>(p.ntiles, static_cast<uint64_t>(ctx->props.multiProcessorCount) * per_cu - 1));
+    uint64_t workers = std::min<uint64_t>(p.ntiles, static_cast<uint64_t>(ctx->props.multiProcessorCount) * per_cu - 1);
+    if (ctx->opt_grid_limit > 0 && !c.direct) workers = std::min<uint64_t>(workers, static_cast<uint64_t>(ctx->opt_grid_limit));  // (tests: one workgroup, many tiles)
+    const uint32_t grid = 1 + static_cast<uint32_t>(workers);
     p.overflow = &ctrl->overflow;
     if (ranges) {
         ranges->range_rows = 64u * static_cast<uint32_t>(c.r);
@@ -907,8 +943,9 @@ uint64_t fused_finish(rv_ctx *ctx, FusedLaunch &L) {
         alloc_outputs(ctx, L, exact);
         const size_t zeroed = kCtrlBytes + (static_cast<size_t>(p.ntiles) + L.nranges) * 8;
         RV_HIP(hipMemsetAsync(L.ctrl.dev, 0, (zeroed + 15) & ~size_t(15), ctx->stream));
-        if (L.fn_plain) enable_lds(ctx, reinterpret_cast<const void *>(L.fn_plain), L.lds);  // a pass over codes: re-run over the 8-byte values
-        hipLaunchKernelGGL(L.fn_plain ? L.fn_plain : L.fn, dim3(L.grid), dim3(L.block), L.lds, ctx->stream, p);
+        // a pass over codes: re-run over the 8-byte values, whose slots of the same rows take 8 bytes per row
+        if (L.fn_plain) enable_lds(ctx, reinterpret_cast<const void *>(L.fn_plain), L.lds_plain);
+        hipLaunchKernelGGL(L.fn_plain ? L.fn_plain : L.fn, dim3(L.grid), dim3(L.block), L.fn_plain ? L.lds_plain : L.lds, ctx->stream, p);
         RV_HIP(hipGetLastError());
         RV_HIP(hipMemcpyAsync(L.ctrl.host, L.ctrl.dev, kCtrlBytes, hipMemcpyDeviceToHost, ctx->stream));
         RV_HIP(hipStreamSynchronize(ctx->stream));

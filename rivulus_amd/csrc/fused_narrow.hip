@@ -1,17 +1,33 @@
 #include "fused_table.hpp"
 namespace rvk {
 // The lean Int64 form (one column, no null bitmap, one compare term) reading the column's narrow companion: 2-byte (FF_NARROW16) or
-// 4-byte (FF_NARROW32) frame-of-reference codes instead of the 8-byte rows (scan_frontend.hpp, load_rows_narrow).
+// 4-byte (FF_NARROW32) frame-of-reference codes instead of the 8-byte rows (scan_frontend.hpp, load_rows_narrow).  What these
+// instantiations do differently from the plain form (fused_kernel.hpp, the `kNarrow != 0` branches):
+//   - a lane holds the tile as raw code pairs (one register per pair of 2-byte codes), requested one tile ahead like the plain form's rows;
+//   - the compare term runs in code space: the host lowers it to an interval of codes or the complement of one (narrow_term.hpp), a row
+//     costs one 32-bit subtract and one unsigned compare;
+//   - survivors are staged as codes and widened (value = base + code) where they are written out; the slots hold the same ROWS as the
+//     plain form's (fused_launch.hip, size_staged), in a quarter or half of the LDS bytes.
+// Same values, same order, same counts and redo list as the plain form, bit for bit.
+// The pass is bound by the vector instructions of its waves, not by HBM latency (tools/narrow_stamp.py, profiles/narrow2_stamps_*.txt:
+// a wave waits ~50 of 11 000-15 000 cycles per tile for its codes; evaluating them and waiting at the barrier for the other waves on the
+// SIMD to evaluate theirs is 80-87 %).  Tried on top of the above and taken out again: THREE sets of pairs per lane, the tile two
+// ahead requested at the top of an iteration (ids drawn four ahead, loop unrolled by three) -- 128 VGPRs, and the headline kernel
+// took 0.612 ms against 0.576 ms with one set (1e9 rows, same box, alternating processes; profiles/narrow2_steps.txt).  The two kept
+// steps one by one: compare in code space 0.772 -> 0.603 ms, codes in the slots 0.603 -> 0.564 ms.
 // The first entry of a flags class is the default geometry; kNarrowTallRows rows per lane is what a launch without per-batch counts
-// takes (fused_launch.hip): a tile's codes are a quarter or half of its rows' bytes, and a workgroup that keeps ONE tile of 16 rows per
-// lane in flight has too few bytes on their way to cover HBM's latency -- twice the rows per lane, twice the bytes.  The geometries
-// with fewer rows per lane are the ones the plain lean form walks down through for denser selections.
+// takes (fused_launch.hip): a tile's codes are a quarter or half of its rows' bytes, so twice the rows per lane put twice the bytes
+// on their way per request and halve the per-tile costs (barrier, ticket, descriptor) per row.  The geometries with fewer rows per lane
+// are the ones the plain lean form walks down through for denser selections.
 const FusedEntry *fused_entries_narrow(size_t *n) {
     static const FusedEntry t[] = {
         RV_FUSED(1, 16, 2, 16, FF_ONE_I64 | FF_NARROW16), RV_FUSED(1, 32, 2, 16, FF_ONE_I64 | FF_NARROW16),
         RV_FUSED(1, 8, 2, 16, FF_ONE_I64 | FF_NARROW16),  RV_FUSED(1, 4, 2, 16, FF_ONE_I64 | FF_NARROW16),
-        // (4-byte codes: 32 rows per lane do not fit 128 VGPRs without spills; the class has no tall geometry)
+        // (4-byte codes: no tall geometry yet.  32 rows per lane compile to 108 VGPRs without scratch in this form -- the parent's widened
+        //  form spilled -- but the geometry has not been measured, and the class keeps what has been)
         RV_FUSED(1, 16, 2, 16, FF_ONE_I64 | FF_NARROW32), RV_FUSED(1, 8, 2, 16, FF_ONE_I64 | FF_NARROW32), RV_FUSED(1, 4, 2, 16, FF_ONE_I64 | FF_NARROW32),
+        // diagnostic (options "stamp" / "debug": phase cycle sums and the ablations of a pass over 2-byte codes, tools/narrow_stamp.py)
+        RV_FUSED(1, 16, 2, 16, FF_STAMP | FF_ONE_I64 | FF_NARROW16), RV_FUSED(1, 32, 2, 16, FF_STAMP | FF_ONE_I64 | FF_NARROW16),
     };
     *n = sizeof(t) / sizeof(t[0]);
     return t;

@@ -134,6 +134,7 @@ struct FusedLaunch {
     DevBufRef lean_values;
     uint64_t lean_offset = 0;
     void (*fn_plain)(const rvk::FusedParams) = nullptr;
+    size_t lds_plain = 0;  // its dynamic LDS: the same slot rows at 8 bytes each (the pass over codes stages 2 or 4)
 };
 struct SegmentOverflow {};  // thrown by run_segmented_pass's callee chain: the shared outputs were too small -- the caller falls back to one pass
 

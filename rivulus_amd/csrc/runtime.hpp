@@ -196,6 +196,7 @@ struct rv_ctx {
     int64_t opt_vec = 0;            // 0 auto, 1 force 8-byte loads, 2 force 16-byte loads
     int64_t opt_cap_rows = 0;       // 0 = as many as LDS allows
     int64_t opt_wgs_per_cu = 0;     // 0 = occupancy query
+    int64_t opt_grid_limit = 0;     // tests: at most this many worker workgroups in a staged launch (0 = what the device keeps resident)
     double last_redo_fraction = 0.0;  // share of tiles the last fused launch left to the redo kernel
     int64_t opt_stamp = 0;          // diagnostic: run the FF_STAMP instantiation
     int64_t opt_direct = 0;         // 0 auto (dense selections of plain value columns), 1 whenever eligible, -1 never: the direct kernel

@@ -39,8 +39,8 @@ enum : int { FF_EXPR = 512 };
 // the rows (a byte per survivor next to its value in the LDS slot, packed to words on the way out)
 enum : int { FF_OUTVALID = 2048 };
 // Lean Int64 form only (FF_ONE_I64, one column, 16-byte row mapping): the rows are read as the 2- or 4-byte frame-of-reference codes
-// of the column's narrow companion (runtime.hpp, NarrowCodes; narrow.hip) and widened in registers, value = base + code.  Only the
-// load differs: everything behind it sees the same Int64 values.
+// of the column's narrow companion (runtime.hpp, NarrowCodes; narrow.hip).  The compare runs on the codes (narrow_term.hpp), survivors are staged as codes, and the
+// 8-byte value = base + code is formed where a survivor is written out: the outputs are those of the plain form, bit for bit.
 enum : int { FF_NARROW16 = 4096, FF_NARROW32 = 8192 };
 
 // A bit stream compacted with the rows: out bit = src bit (& mask bit).
@@ -167,8 +167,8 @@ __device__ __forceinline__ void load_rows(const ScanInputs &in, uint64_t wave_ba
 // ---- the same rows out of the column's narrow companion (FF_NARROW16 / FF_NARROW32) -------------------------------------------
 // codes[i] = uint(value[i] - base) for every element of the values buffer, 2 or 4 bytes each (narrow_kernel.hpp).  The row-to-lane
 // mapping is that of VEC == 2: lane l takes rows 2l, 2l + 1 of each 128-row group j -- ONE 4-byte (2-byte codes) or 8-byte (4-byte
-// codes) nontemporal buffer load per pair, kept RAW in v[j] until the tile is evaluated (widen_pair): an addition issued with the
-// prefetch would wait for it on the spot.  The descriptor is bounded by the code bytes left in the companion, not by the rows of
+// codes) nontemporal buffer load per pair, kept RAW (NarrowRaw) until the tile is evaluated: anything computed on a pair when it is
+// requested would wait for it on the spot.  The descriptor is bounded by the code bytes left in the companion, not by the rows of
 // the slice: a pair that straddles the slice's last row is still read whole (the ragged tile's row mask drops what lies past it), and
 // what lies past the companion reads 0.  `first` (element of the buffer) must be even: the pair's load is then aligned.
 struct NarrowView {
@@ -176,8 +176,16 @@ struct NarrowView {
     uint64_t bytes;     // readable bytes behind it
     int64_t base;       // the column minimum
 };
+template <int BYTES>
+struct NarrowRaw {
+    using type = uint32_t;  // two 2-byte codes
+};
+template <>
+struct NarrowRaw<4> {
+    using type = uint64_t;  // two 4-byte codes
+};
 template <int R, int BYTES>
-__device__ __forceinline__ void load_rows_narrow(const NarrowView &nv, uint64_t first, int lane, uint64_t (&v)[R]) {
+__device__ __forceinline__ void load_rows_narrow(const NarrowView &nv, uint64_t first, int lane, typename NarrowRaw<BYTES>::type (&c)[R / 2]) {
     static_assert((BYTES == 2 || BYTES == 4) && R % 2 == 0, "narrow codes");
     constexpr uint64_t WAVE_BYTES = 64u * R * BYTES;
     const uint64_t at = first * BYTES;
@@ -188,20 +196,18 @@ __device__ __forceinline__ void load_rows_narrow(const NarrowView &nv, uint64_t 
 #pragma unroll
     for (int j = 0; j < R / 2; ++j) {
         if constexpr (BYTES == 2) {
-            v[j] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, lane * 4, j * 256, kStreamPolicy);
+            c[j] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, lane * 4, j * 256, kStreamPolicy);
         } else {
             const rv_u32x2 t = __builtin_amdgcn_raw_buffer_load_b64(rsrc, lane * 8, j * 512, kStreamPolicy);
-            v[j] = (static_cast<uint64_t>(t.y) << 32) | t.x;
+            c[j] = (static_cast<uint64_t>(t.y) << 32) | t.x;
         }
     }
 }
-// a raw pair -> the Int64 values of its two rows (rows 2l, 2l + 1 of the pair's 128-row group)
+// a raw pair -> the codes of its two rows (rows 2l, 2l + 1 of the pair's 128-row group), zero-extended
 template <int BYTES>
-__device__ __forceinline__ void widen_pair(int64_t base, uint64_t raw, uint64_t &row0, uint64_t &row1) {
-    const uint32_t c0 = BYTES == 2 ? static_cast<uint32_t>(raw) & 0xFFFFu : static_cast<uint32_t>(raw);
-    const uint32_t c1 = BYTES == 2 ? static_cast<uint32_t>(raw) >> 16 : static_cast<uint32_t>(raw >> 32);
-    row0 = static_cast<uint64_t>(base) + c0;
-    row1 = static_cast<uint64_t>(base) + c1;
+__device__ __forceinline__ void unpack_pair(typename NarrowRaw<BYTES>::type raw, uint32_t &c0, uint32_t &c1) {
+    c0 = BYTES == 2 ? static_cast<uint32_t>(raw) & 0xFFFFu : static_cast<uint32_t>(raw);
+    c1 = BYTES == 2 ? static_cast<uint32_t>(raw) >> 16 : static_cast<uint32_t>(static_cast<uint64_t>(raw) >> 32);
 }
 
 // The validity words of a wave's rows travel with the row prefetch: lane k holds the aligned 64-bit
