@@ -271,7 +271,11 @@ rv_status rv_ctx_device_info(rv_ctx *ctx, int *compute_units, uint64_t *hbm_byte
  * table by min(rows, k); "agg_hash_bits" = b (tests): the key hash of group tables truncated to b low bits (see rv_hash_aggregate).
  * "sort_engine": 0, the default = rv_sort_indices runs its own radix passes; 1 (measurements and tests, never chosen by the library) = the
  * pair sort goes through rocprim::radix_sort_pairs over all 64 bits, everything around it unchanged (see rv_sort_indices).  The read-only
- * "sort_last_passes" is the number of scatter passes the last sort call of the context ran. */
+ * "sort_last_passes" is the number of scatter passes the last sort call of the context ran.
+ * "top_k_select_from_rows" = k > 0 (tests): rv_top_k_indices / rv_top_k run their radix select from k rows on (0: the built-in
+ * crossover); "top_k_refine_divisor" = d > 0 (tests): the select takes one more pass while its candidates number more than rows / d
+ * (0: the built-in 32).  The read-only "top_k_last_passes" is the number of passes over the key column the select of the last top-k
+ * call ran (0: it sorted the whole column), "top_k_last_candidates" the rows that call sorted (see rv_top_k_indices). */
 rv_status rv_ctx_set_option(rv_ctx *ctx, const char *key, int64_t value);
 /* current value of an option, or of the read-only counters "overflow_reruns" (launches re-run because speculatively sized
  * outputs were too small), "last_selectivity_ppm" (survivors per million rows of the last fused launch, -1: none yet),
@@ -858,6 +862,38 @@ rv_status rv_sort_indices(rv_ctx *ctx, const rv_dcolumn *key, uint32_t flags, co
  * ONE gather of the frame. */
 rv_status rv_sort(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, const uint32_t *key_cols, const uint32_t *key_flags,
                   uint32_t nkeys, rv_dcolumn **out);
+
+/* ---- top-k (K11) ------------------------------------------------------------ */
+/* ORDER BY ... LIMIT k without sorting the column.  This comment is the normative text, tests/topk_model.py the executable one;
+ * DESIGN.md section 4 K11 argues it.
+ *
+ * The result.  rv_top_k_indices(key, flags, k) is the first min(k, rows) rows of what rv_sort_indices(key, flags, NULL) returns: an
+ * Int64 column without nulls.  rv_top_k(cols, keys, k) is the first min(k, rows) rows of every column of rv_sort with the same
+ * arguments.  The sort is stable, so both are unique and the same on every run; rows whose keys compare equal come in ascending row
+ * order, and ties of the first key that straddle the cut are decided by the later keys, never by row order.  k == 0 gives zero-row
+ * columns of the input's dtypes, k >= rows the whole sort.  There is no `prior`.
+ *
+ * Everything else is the sort's, with the same statuses and texts under this function's name: the key dtypes (RV_INT64, RV_FLOAT64,
+ * RV_NULL; RV_BOOLEAN and RV_STRING keys are RV_ERR_UNSUPPORTED), RV_SORT_DESCENDING and RV_SORT_NULLS_LAST, slices at any offset,
+ * whatever lies under a null cell is never read as a value, keys of 2^32 rows or more are RV_ERR_UNSUPPORTED, unknown flag bits,
+ * nkeys == 0 and a key index out of range are RV_ERR_INVALID_ARG, columns of different lengths RV_ERR_LENGTH_MISMATCH.  Errors
+ * leave the context usable and create nothing.  Columns that are no key may be of any dtype rv_take_device gathers.
+ *
+ * The passes.  A radix SELECT over the 8-bit digits of the first key's mapped key, from the most significant digit at which two
+ * non-null keys differ: one pass over the key column counts every digit, each further pass the next differing digit among the rows
+ * that still tie with the cut; it stops when no differing digit is left or the candidates -- the rows at or before the cut, every
+ * tie of the cut included, the null rows when they come first -- number at most rows / 32.  The candidates' row ids are collected in
+ * ascending order, every key column is gathered at them, and rv_sort_indices' chain over those few rows settles the order.  The
+ * whole column is sorted instead (rv_sort_indices / rv_sort unchanged, then the first k rows) when k >= rows / 2, when the column
+ * is shorter than the built-in crossover, and when the candidates come out as more than half the rows (few distinct keys; nulls
+ * last with fewer than k values).  Context option "top_k_last_passes" reports the select's passes over the key column of the last
+ * call (0: the whole sort ran), "top_k_last_candidates" the rows it sorted; rv_ctx_last_kernel names "topk_collect" after a select
+ * and what the sort names otherwise; rv_ctx_kernel_stats (option "profile_kernels") times the select and the sort stage. */
+rv_status rv_top_k_indices(rv_ctx *ctx, const rv_dcolumn *key, uint32_t flags, uint64_t k, rv_dcolumn **out_indices);
+/* the whole operator: the first min(k, rows) rows of rv_sort(cols, key_cols, key_flags); out has room for ncols handles.  ONE gather
+ * of the frame, of k rows. */
+rv_status rv_top_k(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, const uint32_t *key_cols, const uint32_t *key_flags,
+                   uint32_t nkeys, uint64_t k, rv_dcolumn **out);
 
 /* ---- multi-GPU (one process per GPU) --------------------------------------- */
 /* Row-range shard of rank `rank` of `world`: [*begin, *end), boundaries at multiples of

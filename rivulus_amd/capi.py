@@ -209,6 +209,8 @@ PROTOTYPES = {
     "rv_hash_aggregate_keys": (C.c_int, [_P, _PP, C.c_uint32, _PP, C.c_uint32, C.POINTER(RvAggSpec), C.c_uint32, _PP, _PP, _U64P]),
     "rv_sort_indices": (C.c_int, [_P, _P, C.c_uint32, _P, _PP]),
     "rv_sort": (C.c_int, [_P, _PP, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, _PP]),
+    "rv_top_k_indices": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, _PP]),
+    "rv_top_k": (C.c_int, [_P, _PP, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint64, _PP]),
     "rv_hash_join_kind": (C.c_int, [_P, _PP, C.c_uint32, C.c_uint32, _PP, C.c_uint32, C.c_uint32, C.c_int, _PP, _U64P]),
     "rv_hash_join_chunked_kind": (C.c_int, [_P, _P, _PP, C.c_uint32, C.c_uint32, _PP, C.c_uint32, C.c_uint32, C.c_int, C.c_uint64, C.c_uint64,
                                             _PP, _U64P, C.c_uint64, C.POINTER(C.c_int64), _U64P, _U64P]),
@@ -922,6 +924,24 @@ class Context:
         kf = (C.c_uint32 * max(1, len(keys)))(*[k[1] for k in keys])
         out = (C.c_void_p * max(1, len(cols)))()
         _check(load().rv_sort(self.handle, _handles(cols), len(cols), kc, kf, len(keys), out))
+        return [DeviceColumn(self, C.c_void_p(out[i])) for i in range(len(cols))]
+
+    def top_k_indices(self, key: DeviceColumn, k: int, descending: bool = False, nulls_last: bool = False, flags: Optional[int] = None) -> DeviceColumn:
+        """rv_top_k_indices: the first min(k, rows) rows of sort_indices(key) as an Int64 column; `flags` overrides the two booleans with
+        a raw flag word."""
+        if flags is None:
+            flags = (RV_SORT_DESCENDING if descending else 0) | (RV_SORT_NULLS_LAST if nulls_last else 0)
+        out = C.c_void_p()
+        _check(load().rv_top_k_indices(self.handle, key.handle, flags, k, C.byref(out)))
+        return DeviceColumn(self, out)
+
+    def top_k(self, cols: Sequence[DeviceColumn], keys, k: int):
+        """rv_top_k: the first min(k, rows) rows of sort(cols, keys); `keys` as sort takes them."""
+        keys = [(key, 0) if isinstance(key, int) else tuple(key) for key in keys]
+        kc = (C.c_uint32 * max(1, len(keys)))(*[key[0] for key in keys])
+        kf = (C.c_uint32 * max(1, len(keys)))(*[key[1] for key in keys])
+        out = (C.c_void_p * max(1, len(cols)))()
+        _check(load().rv_top_k(self.handle, _handles(cols), len(cols), kc, kf, len(keys), k, out))
         return [DeviceColumn(self, C.c_void_p(out[i])) for i in range(len(cols))]
 
     def hash_join(self, build_cols: Sequence[DeviceColumn], build_key: int, probe_cols: Sequence[DeviceColumn], probe_key: int,

@@ -424,6 +424,10 @@ rv_status rv_ctx_set_option(rv_ctx *ctx, const char *key, int64_t value) {
             require(value == 0 || value == 1, RV_ERR_INVALID_ARG, "sort_engine: 0 (the sort's own passes) or 1 (rocprim::radix_sort_pairs)");
             ctx->opt_sort_engine = value;
         }
+        else if (k == "top_k_select_from_rows" || k == "top_k_refine_divisor") {
+            require(value >= 0, RV_ERR_INVALID_ARG, k + ": 0 (the built-in value) or a positive number");
+            (k == "top_k_select_from_rows" ? ctx->opt_top_k_select_from_rows : ctx->opt_top_k_refine_divisor) = value;
+        }
         else if (k == "out_sizing") {
             require(value >= -1 && value <= 1000000, RV_ERR_INVALID_ARG, "out_sizing: -1, 0, 1 or a bound in rows per million");
             ctx->opt_out_sizing = value;
@@ -481,6 +485,10 @@ rv_status rv_ctx_get_option(rv_ctx *ctx, const char *key, int64_t *value) {
         else if (k == "agg_max_groups") *value = ctx->opt_agg_max_groups;
         else if (k == "sort_engine") *value = ctx->opt_sort_engine;
         else if (k == "sort_last_passes") *value = static_cast<int64_t>(ctx->sort_last_passes);  // read-only
+        else if (k == "top_k_select_from_rows") *value = ctx->opt_top_k_select_from_rows;
+        else if (k == "top_k_refine_divisor") *value = ctx->opt_top_k_refine_divisor;
+        else if (k == "top_k_last_passes") *value = static_cast<int64_t>(ctx->top_k_last_passes);  // read-only
+        else if (k == "top_k_last_candidates") *value = static_cast<int64_t>(ctx->top_k_last_candidates);  // read-only
         else if (k == "out_sizing") *value = ctx->opt_out_sizing;
         else if (k == "overflow_reruns") *value = static_cast<int64_t>(ctx->overflow_reruns);  // read-only counter
         else if (k == "batch_counts_in_pass") *value = static_cast<int64_t>(ctx->batch_counts_in_pass);  // read-only counter

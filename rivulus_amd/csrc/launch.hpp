@@ -1,5 +1,5 @@
 // Internal interface between the translation units of librivulus_gpu.so (core / fused_launch / narrow / strings / predicate / arrays /
-// query / take_concat / host_table / aggregate / join / string_dict / csv / group / group_agg / sort .hip): the control block, the request / launch
+// query / take_concat / host_table / aggregate / join / string_dict / csv / group / group_agg / sort / topk .hip): the control block, the request / launch
 // records that travel with a fused pass, and the functions the units call across each other.  Nothing here is part of the C ABI.
 #pragma once
 
@@ -268,6 +268,14 @@ inline void drop_outputs(rv_dcolumn **out, uint32_t n) {
 // RecordBatch::take with the index list in HBM (bounds pre-pass unless check_bounds is false), one gather per column
 void take_on_device(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, const uint64_t *d_idx, uint64_t n_indices, rv_dcolumn **out,
                     bool check_bounds = true);
+
+// ---- sort.hip ----------------------------------------------------------------------------------------------
+// flags, dtype and row limit of a sort key, refused under the caller's name `what`
+void check_sort_key(const rv_dcolumn *key, uint32_t flags, const char *what);
+// the stable permutation of `key` (of `prior`, n device-resident indices, reordered by it) as key->length Int64 rows
+DevBufRef sort_indices(rv_ctx *ctx, const rv_dcolumn *key, uint32_t flags, const uint64_t *prior);
+// an Int64 column without nulls over the first `rows` rows of `buf`
+rv_dcolumn *sort_index_column(const DevBufRef &buf, uint64_t rows);
 
 // ---- take_nullable.hip -------------------------------------------------------------------------------------
 // A nullable index list of the gathers: a null index yields a null cell of the column's dtype.  validity: the list's bitmap, read

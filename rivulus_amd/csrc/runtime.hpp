@@ -278,6 +278,10 @@ struct rv_ctx {
     int64_t opt_agg_max_groups = 0; // rv_hash_aggregate / rv_group_ids refuse more distinct keys than this; 0: rvt::kGroupAggGroupsMostDefault
     int64_t opt_sort_engine = 0;    // 0: the sort's own radix passes; 1 (measurements, tests): the pair sort by rocprim::radix_sort_pairs over all 64 bits
     uint64_t sort_last_passes = 0;  // scatter passes the last sort call ran (the null pass included)
+    int64_t opt_top_k_select_from_rows = 0;  // tests: top-k selects from this many rows on; 0: rvt::kTopKSelectFromRows
+    int64_t opt_top_k_refine_divisor = 0;    // tests: the select refines while candidates > rows / this; 0: rvt::kTopKRefineDivisor
+    uint64_t top_k_last_passes = 0;      // passes over the key column the last top-k call's select ran (hist + refine); 0: it sorted the whole column
+    uint64_t top_k_last_candidates = 0;  // rows the last top-k call sorted
     int64_t opt_bools_in_pass = 0;  // 1: projected Boolean columns are compacted inside the fused pass (lane-form PEXT)
     int64_t opt_narrow_codes = 0;   // narrow companions of Int64 columns (NarrowCodes): 0 auto, -1 never, 1 at the first whole scan at any size (tests)
     uint64_t narrow_builds = 0;     // companions built by this context

@@ -15,12 +15,17 @@ namespace {
 constexpr uint32_t kSortFlagsKnown = RV_SORT_DESCENDING | RV_SORT_NULLS_LAST;
 static_assert(rvk::kSortTileRows == 256 * rvt::kSortRowsPerLane, "a tile is one workgroup x rvt::kSortRowsPerLane rows per lane");
 
+}  // namespace
+
+// what every entry point that orders rows by a key column checks of it (rv_sort_indices, rv_sort, rv_top_k_indices, rv_top_k)
 void check_sort_key(const rv_dcolumn *key, uint32_t flags, const char *what) {
     require((flags & ~kSortFlagsKnown) == 0, RV_ERR_INVALID_ARG, fmt("%s: unknown flag bits 0x%x", what, flags & ~kSortFlagsKnown));
     require(key->dtype == RV_INT64 || key->dtype == RV_FLOAT64 || key->dtype == RV_NULL, RV_ERR_UNSUPPORTED,
             fmt("%s: only Int64, Float64 (and Null) key columns are supported; Boolean and String sort keys are not built", what));
     require(key->length < (uint64_t{1} << 32), RV_ERR_UNSUPPORTED, fmt("%s: keys of 2^32 rows or more are not supported (32-bit row ids inside)", what));
 }
+
+namespace {
 
 template <bool NULLS>
 void launch_pass(rv_ctx *ctx, rvk::SortPassParams &p, bool last, DevBufRef &hist_total) {
@@ -35,6 +40,8 @@ void launch_pass(rv_ctx *ctx, rvk::SortPassParams &p, bool last, DevBufRef &hist
     RV_HIP(hipGetLastError());
     // (`bases` goes back to the pool; its next user runs behind the scatter on the stream)
 }
+
+}  // namespace
 
 // The permutation as n Int64 rows.  `prior`: n device-resident indices, or nullptr.  Two waits: the plan (which passes run; a bad index
 // of `prior`) and the end, after which the working buffers go back to the pool.
@@ -143,6 +150,8 @@ DevBufRef sort_indices(rv_ctx *ctx, const rv_dcolumn *key, uint32_t flags, const
     return out;
 }
 
+namespace {
+
 // `prior` as rv_take_device takes its index list
 const uint64_t *check_prior(rv_ctx *ctx, const rv_dcolumn *key, const rv_dcolumn *prior) {
     if (!prior) return nullptr;
@@ -156,7 +165,9 @@ const uint64_t *check_prior(rv_ctx *ctx, const rv_dcolumn *key, const rv_dcolumn
     return static_cast<const uint64_t *>(prior->values->ptr) + prior->offset;
 }
 
-rv_dcolumn *index_column(const DevBufRef &buf, uint64_t rows) {
+}  // namespace
+
+rv_dcolumn *sort_index_column(const DevBufRef &buf, uint64_t rows) {
     auto o = std::make_unique<rv_dcolumn>();
     o->dtype = RV_INT64;
     o->length = rows;
@@ -165,7 +176,6 @@ rv_dcolumn *index_column(const DevBufRef &buf, uint64_t rows) {
     return o.release();
 }
 
-}  // namespace
 }  // namespace rvl
 
 extern "C" {
@@ -179,7 +189,7 @@ rv_status rv_sort_indices(rv_ctx *ctx, const rv_dcolumn *key, uint32_t flags, co
         const uint64_t *d_prior = check_prior(ctx, key, prior);
         try {
             DevBufRef idx = sort_indices(ctx, key, flags, d_prior);
-            *out_indices = index_column(idx, key->length);
+            *out_indices = sort_index_column(idx, key->length);
         } catch (...) {
             (void)hipStreamSynchronize(ctx->stream);  // whatever was queued has run before its buffers go back to the pool
             throw;

@@ -135,4 +135,26 @@ constexpr uint64_t kGroupAggGroupsMostDefault = uint64_t{1} << 26;
 // a pass scans (256 per 2048 rows: 1 byte per row through the scan against the 32 a pass moves).  Not a crossover; set by that reasoning,
 // NOT by a sweep -- 16 rows per lane would halve the counts and leave two workgroups per CU.                       tools/sort_bench.py
 constexpr uint32_t kSortRowsPerLane = 8;
+
+// ---- top-k (topk.hip) -------------------------------------------------------------------------------------------------------------------------
+// The radix select refines its cut by one more pass over the key column while differing digit positions remain and the candidates
+// number more than rows / kTopKRefineDivisor.  By bytes: a refine pass reads 8 bytes per ROW of the table; it saves at most the sort of
+// the candidates it sheds, about 296 derived bytes per CANDIDATE -- so a pass pays while candidates > rows x 8 /
+// 296 = rows / 37, rounded to the power of two below.  The value is that reasoning.  The sweep over {8, 32, 128} at 2^28 rows agrees with it
+// where the candidates are full-width (3.1 % of the rows, six bytes left to sort: 3.75 ms unrefined against 3.72 refined -- the break-even)
+// and shows it conservative where they differ in one byte only, whose sort is one pass (8.5 % of the rows: 2.82 ms unrefined against
+// 2.88; 2.1 %: 2.33 against 2.75).  32 is within 2.5 % of the best divisor on every shape at k = 100 (DESIGN.md section 4 K11 has the
+// table).  Option "top_k_refine_divisor" overrides it (tests).
+//                                                                                tools/topk_bench.py --sweep, profiles/topk_bench.txt
+constexpr uint64_t kTopKRefineDivisor = 32;
+// Below this many rows rv_top_k_indices / rv_top_k sort the whole column and keep the first k: the select is a dozen launches and two or
+// three read-backs whatever the size, the sort of a short column a few more launches and one read-back.  A launch-bound crossover: k = 100
+// over random Int64, select / sort 2^19 0.366 / 0.348 ms, 2^20 0.393 / 0.382, 2^21 0.395 / 0.459, 2^22 0.411 / 0.626 (below 2^12 rows the
+// select refines to the last digit and is 2.4 x behind).  Option "top_k_select_from_rows" overrides it (tests).
+//                                                                                tools/topk_bench.py --sweep, profiles/topk_bench.txt
+constexpr uint64_t kTopKSelectFromRows = uint64_t{1} << 21;
+// Rows per lane of a tile of the collect (topk_tile_count, topk_collect: one workgroup of 256 lanes per tile, so 2048 rows): one count per
+// tile goes through the scan, 4 bytes per 2048 rows, and a wave keeps one ballot per step in registers.  Not a crossover; the sort's tile,
+// by the sort's reasoning, NOT a sweep.
+constexpr uint32_t kTopKCollectRowsPerLane = 8;
 }  // namespace rvt

@@ -2033,26 +2033,37 @@ inline SchemaRef sort_schema(const Schema &in, const std::vector<SortKey> &keys)
     return std::make_shared<const Schema>(in);
 }
 
+// What rv_sort and rv_top_k take of a frame (`columns` in the order of `schema`) and a key list: the handles, and per key the column's index
+// and its flag word.
+struct SortCall {
+    std::vector<const rv_dcolumn *> handles;
+    std::vector<uint32_t> key_cols, key_flags;
+    SortCall(const Schema &schema, const std::vector<ArrayRef> &columns, const std::vector<SortKey> &keys) {
+        for (auto &c : columns) {
+            if (!c->on_device()) throw Error(RV_ERR_UNSUPPORTED, "columns off the device are outside the device path");
+            handles.push_back(c->handle());
+        }
+        for (auto &k : keys) {
+            key_cols.push_back(static_cast<uint32_t>(*schema.index_of(k.column)));
+            key_flags.push_back((k.descending ? RV_SORT_DESCENDING : 0u) | (k.nulls_last ? RV_SORT_NULLS_LAST : 0u));
+        }
+    }
+};
+inline std::vector<ArrayRef> adopt_columns(const ContextRef &ctx, const std::vector<rv_dcolumn *> &out) {
+    std::vector<ArrayRef> res;
+    for (auto *h : out) res.push_back(Array::adopt(ctx, h));
+    return res;
+}
+
 // One rv_sort over one frame (`columns` in the order of `schema`): every column reordered, the first key the most significant.  Columns
 // that are no key ride along whatever their dtype.
 inline std::vector<ArrayRef> sort_columns(const ContextRef &ctx, const Schema &schema, const std::vector<ArrayRef> &columns, const std::vector<SortKey> &keys) {
     (void)sort_schema(schema, keys);
-    std::vector<const rv_dcolumn *> handles;
-    for (auto &c : columns) {
-        if (!c->on_device()) throw Error(RV_ERR_UNSUPPORTED, "columns off the device are outside the device path");
-        handles.push_back(c->handle());
-    }
-    std::vector<uint32_t> key_cols, key_flags;
-    for (auto &k : keys) {
-        key_cols.push_back(static_cast<uint32_t>(*schema.index_of(k.column)));
-        key_flags.push_back((k.descending ? RV_SORT_DESCENDING : 0u) | (k.nulls_last ? RV_SORT_NULLS_LAST : 0u));
-    }
-    std::vector<rv_dcolumn *> out(handles.size(), nullptr);
-    check(rv_sort(ctx->raw(), handles.data(), static_cast<uint32_t>(handles.size()), key_cols.data(), key_flags.data(), static_cast<uint32_t>(keys.size()),
-                  out.data()));
-    std::vector<ArrayRef> res;
-    for (auto *h : out) res.push_back(Array::adopt(ctx, h));
-    return res;
+    const SortCall call(schema, columns, keys);
+    std::vector<rv_dcolumn *> out(call.handles.size(), nullptr);
+    check(rv_sort(ctx->raw(), call.handles.data(), static_cast<uint32_t>(call.handles.size()), call.key_cols.data(), call.key_flags.data(),
+                  static_cast<uint32_t>(keys.size()), out.data()));
+    return adopt_columns(ctx, out);
 }
 
 // sort as a stream: a PIPELINE BREAKER like GpuGroupByStream.  It drains its input the same way -- a resident frame is taken as it is,
@@ -2091,6 +2102,88 @@ class GpuSortStream : public DataStream {
   private:
     JoinSide input_;
     std::vector<SortKey> keys_;
+    ContextRef ctx_;
+    SchemaRef schema_;
+    bool done_ = false;
+};
+
+// ---------------------------------------------------------------------------------------
+// top_k(keys, k) -- ORDER BY ... LIMIT k: the first k rows of sort(keys); include/rivulus_gpu.h, rv_top_k_indices
+// ---------------------------------------------------------------------------------------
+// Checks `keys` against `in` as sort_schema does -- the same SortPlanError, the same texts -- and returns the output schema, the input's.
+inline SchemaRef top_k_schema(const Schema &in, const std::vector<SortKey> &keys, size_t /*k*/) { return sort_schema(in, keys); }
+
+// One rv_top_k over one frame: the first min(k, rows) rows of sort_columns, every column.
+inline std::vector<ArrayRef> top_k_columns(const ContextRef &ctx, const Schema &schema, const std::vector<ArrayRef> &columns, const std::vector<SortKey> &keys,
+                                           size_t k) {
+    (void)top_k_schema(schema, keys, k);
+    const SortCall call(schema, columns, keys);
+    std::vector<rv_dcolumn *> out(call.handles.size(), nullptr);
+    check(rv_top_k(ctx->raw(), call.handles.data(), static_cast<uint32_t>(call.handles.size()), call.key_cols.data(), call.key_flags.data(),
+                   static_cast<uint32_t>(keys.size()), static_cast<uint64_t>(k), out.data()));
+    return adopt_columns(ctx, out);
+}
+
+// Rows a GpuTopKStream gathers before it folds them into its best k.  Set by reasoning, not by a sweep: a fold is one rv_top_k -- a dozen
+// launches and a few read-backs, a few hundred microseconds whatever the size -- so it is amortised over millions of rows (a pass over
+// 4 Mi rows of a key is about 10 us of HBM time per read), while 4 Mi rows of a handful of 8-byte columns stay in the low hundreds of MiB.
+constexpr size_t kTopKFoldRows = size_t{1} << 22;
+
+// top_k as a stream: a PIPELINE BREAKER that emits EXACTLY ONE batch of min(k, rows) rows.  A resident frame is taken whole.  The batches
+// of any other stream are NOT concatenated: they are gathered until they hold at least `fold_rows` rows and then folded,
+//     best = top_k(concat(best, gathered...)),
+// so no more than fold_rows + k rows (and the batch that crossed the line) are held at once.  The fold is exact: `best` comes before
+// the later rows in the concatenation and the sort is stable, so rows with equal keys come out in input order, whatever batches they
+// arrived in.  An input without rows gives one zero-row batch with the schema.
+class GpuTopKStream : public DataStream {
+  public:
+    // `fallback_ctx`: where the zero-row batch of an input that yields no batch at all is created
+    GpuTopKStream(JoinSide input, std::vector<SortKey> keys, size_t k, ContextRef fallback_ctx, size_t fold_rows = kTopKFoldRows)
+        : input_(std::move(input)), keys_(std::move(keys)), k_(k), fold_rows_(std::max<size_t>(fold_rows, 1)), ctx_(std::move(fallback_ctx)) {
+        schema_ = top_k_schema(*input_.schema(), keys_, k_);
+    }
+    SchemaRef schema() const override { return schema_; }
+    size_t folds() const { return folds_; }  // rv_top_k calls so far (tests)
+    std::optional<RecordBatch> next_batch() override {
+        if (done_) return std::nullopt;
+        done_ = true;
+        if (!input_.stream) return stream_call([&] { return best_of(input_.columns); });
+        std::optional<RecordBatch> best;
+        std::vector<RecordBatch> gathered;
+        size_t gathered_rows = 0;
+        auto fold = [&] {
+            std::vector<RecordBatch> all;
+            if (best) all.push_back(*best);
+            for (auto &b : gathered) all.push_back(std::move(b));
+            gathered.clear();
+            gathered_rows = 0;
+            best = stream_call([&] { return best_of((all.size() == 1 ? all[0] : RecordBatch::concat(all)).columns()); });
+        };
+        while (auto b = input_.stream->next_batch()) {
+            if (!ctx_ && b->num_columns() > 0) ctx_ = b->column(0)->context();
+            if (b->num_rows() == 0) continue;
+            gathered_rows += b->num_rows();
+            gathered.push_back(std::move(*b));
+            if (gathered_rows >= fold_rows_) fold();
+        }
+        if (!gathered.empty()) fold();
+        if (best) return best;
+        if (!ctx_) throw StreamError::execution("top_k: the input yielded no batch and the plan holds no device context");
+        return RecordBatch::empty(ctx_, schema_);
+    }
+
+  private:
+    RecordBatch best_of(const std::vector<ArrayRef> &columns) {
+        const ContextRef ctx = columns.empty() ? ctx_ : columns[0]->context();
+        if (columns.empty() || columns[0]->len() == 0) return RecordBatch::empty(ctx, schema_);
+        ++folds_;
+        std::vector<ArrayRef> out = top_k_columns(ctx, *schema_, columns, keys_, k_);
+        const size_t rows = out[0]->len();
+        return RecordBatch::new_unchecked(schema_, std::move(out), rows);
+    }
+    JoinSide input_;
+    std::vector<SortKey> keys_;
+    size_t k_, fold_rows_, folds_ = 0;
     ContextRef ctx_;
     SchemaRef schema_;
     bool done_ = false;
@@ -2446,7 +2539,7 @@ class StreamingPhysicalPlan;
 using StreamingPlanPtr = std::shared_ptr<const StreamingPhysicalPlan>;
 class StreamingPhysicalPlan {
   public:
-    enum Kind { MemorySource, DataFrameSource, CsvFileSource, Filter, GpuFilterProject, Select, Limit, HashJoin, Project, ComputedFilterProject, GroupBy, Sort } kind = MemorySource;
+    enum Kind { MemorySource, DataFrameSource, CsvFileSource, Filter, GpuFilterProject, Select, Limit, HashJoin, Project, ComputedFilterProject, GroupBy, Sort, TopK } kind = MemorySource;
     std::vector<Expr> exprs;  // Project: select expressions, arithmetic included
     Expr predicate_expr;      // ComputedFilterProject: a filter with `<arith> <cmp> <literal>` terms
     // DataFrameSource (streaming.rs:85-94)
@@ -2473,7 +2566,8 @@ class StreamingPhysicalPlan {
     std::vector<std::string> group_keys;  // GroupBy { input, group_keys, aggs } when group_by_list: the key-list form
     bool group_by_list = false;
     std::vector<execution::AggSpec> aggs;
-    std::vector<execution::SortKey> sort_keys;  // Sort { input, sort_keys }
+    std::vector<execution::SortKey> sort_keys;  // Sort { input, sort_keys }, TopK { input, sort_keys, top_k_rows, top_k_fold_rows }
+    size_t top_k_rows = 0, top_k_fold_rows = execution::kTopKFoldRows;
 
     static StreamingPlanPtr memory_source(std::vector<execution::RecordBatch> b) {
         auto p = std::make_shared<StreamingPhysicalPlan>();
@@ -2603,6 +2697,17 @@ class StreamingPhysicalPlan {
         p->sort_keys = std::move(keys);
         return p;
     }
+    // top_k(keys, k): the first k rows of sort(keys) without sorting the input; a pipeline breaker that emits exactly one batch
+    // (GpuTopKStream, which folds the input every `fold_rows` rows).  What a planner makes of Limit(Sort(x)).
+    static StreamingPlanPtr top_k(StreamingPlanPtr in, std::vector<execution::SortKey> keys, size_t k, size_t fold_rows = execution::kTopKFoldRows) {
+        auto p = std::make_shared<StreamingPhysicalPlan>();
+        p->kind = TopK;
+        p->input = std::move(in);
+        p->sort_keys = std::move(keys);
+        p->top_k_rows = k;
+        p->top_k_fold_rows = fold_rows;
+        return p;
+    }
     // a device context some source of the plan holds (nullptr: none does)
     ContextRef any_context() const {
         if (csv_ctx) return csv_ctx;
@@ -2684,7 +2789,8 @@ class StreamingPhysicalPlan {
                     if (group_by_list) return std::make_unique<GpuGroupByStream>(std::move(s), group_keys, aggs, any_context());
                     return std::make_unique<GpuGroupByStream>(std::move(s), group_key, aggs, any_context());
                 }
-                case Sort: {  // drains its input as GroupBy does
+                case Sort:
+                case TopK: {  // drain their input as GroupBy does
                     JoinSide s;
                     if (input->kind == DataFrameSource && !input->df.columns.empty() && input->df_batch_size > 0) {
                         s.names = input->df.names;
@@ -2693,6 +2799,7 @@ class StreamingPhysicalPlan {
                     } else {
                         s.stream = input->execute();
                     }
+                    if (kind == TopK) return std::make_unique<GpuTopKStream>(std::move(s), sort_keys, top_k_rows, any_context(), top_k_fold_rows);
                     return std::make_unique<GpuSortStream>(std::move(s), sort_keys, any_context());
                 }
             }
@@ -2747,7 +2854,7 @@ class PhysicalPlan;
 using PhysicalPlanPtr = std::shared_ptr<const PhysicalPlan>;
 class PhysicalPlan {
   public:
-    enum Kind { DataFrameSource, Select, Filter, HashJoin, Project, ComputedFilter, GroupBy, Sort } kind = DataFrameSource;
+    enum Kind { DataFrameSource, Select, Filter, HashJoin, Project, ComputedFilter, GroupBy, Sort, TopK } kind = DataFrameSource;
     DeviceFrame df;
     std::vector<Expr> exprs;  // Project: select expressions, arithmetic included
     Expr predicate_expr;      // ComputedFilter: `<arith> <cmp> <literal>` terms, alone or under AND / OR
@@ -2761,7 +2868,8 @@ class PhysicalPlan {
     std::vector<std::string> group_keys;  // GroupBy { input, group_keys, aggs } when group_by_list: the key-list form
     bool group_by_list = false;
     std::vector<execution::AggSpec> aggs;
-    std::vector<execution::SortKey> sort_keys;  // Sort { input, sort_keys }
+    std::vector<execution::SortKey> sort_keys;  // Sort { input, sort_keys }, TopK { input, sort_keys, top_k_rows }
+    size_t top_k_rows = 0;
 
     static PhysicalPlanPtr source(DeviceFrame f) {
         auto p = std::make_shared<PhysicalPlan>();
@@ -2850,9 +2958,28 @@ class PhysicalPlan {
         p->sort_keys = std::move(keys);
         return p;
     }
+    // top_k(keys, k), eager: one rv_top_k -- the first min(k, rows) rows of sort(keys), without sorting the frame
+    static PhysicalPlanPtr top_k(PhysicalPlanPtr in, std::vector<execution::SortKey> keys, size_t k) {
+        auto p = std::make_shared<PhysicalPlan>();
+        p->kind = TopK;
+        p->input = std::move(in);
+        p->sort_keys = std::move(keys);
+        p->top_k_rows = k;
+        return p;
+    }
     DeviceFrame execute() const {
         switch (kind) {
             case DataFrameSource: return df;  // plan.rs:67
+            case TopK: {
+                DeviceFrame in = input->execute();
+                const execution::Schema schema = frame_schema(in);
+                (void)execution::top_k_schema(schema, sort_keys, top_k_rows);  // the planning errors
+                if (in.height() == 0) return in;
+                DeviceFrame out;
+                out.names = in.names;
+                out.columns = execution::top_k_columns((*in.column(sort_keys[0].column))->context(), schema, in.columns, sort_keys, top_k_rows);
+                return out;
+            }
             case Sort: {
                 DeviceFrame in = input->execute();
                 const execution::Schema schema = frame_schema(in);
