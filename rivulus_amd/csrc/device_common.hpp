@@ -115,6 +115,11 @@ __device__ __forceinline__ uint32_t opaque(uint32_t x) {
     asm volatile("" : "+v"(x));
     return x;
 }
+// the same for a wave-uniform value: it stays in ONE scalar register, and no constant is split off it into a later vector addition
+__device__ __forceinline__ uint32_t opaque_uniform(uint32_t x) {
+    asm volatile("" : "+s"(x));
+    return x;
+}
 
 // ---- counters of set bits etc. that many waves add to ------------------------------------------------------------
 // Atomics on ONE address are served one at a time, 12 ns each: 8192 waves adding their partial count to the same word at

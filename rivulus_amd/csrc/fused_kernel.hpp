@@ -209,8 +209,11 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
     const uint64_t SLT = term0.sel_lt() ? ~0ull : 0, SEQ = term0.sel_eq() ? ~0ull : 0, SGT = term0.sel_gt() ? ~0ull : 0,
                    SUN = term0.sel_un() ? ~0ull : 0;
     const int64_t lit0 = term0.lit;
-    unsigned long long st_wait = 0, st_stage = 0, tm = 0;
-    unsigned long long st_eval = 0, st_scatter = 0, st_look = 0, st_waitB = 0, st_flush = 0, st_tiles = 0, t0 = 0, t1 = 0;
+    // (the stamped narrow instantiations keep their cycle sums in VECTOR registers: as scalars they, a pair's masks and the staging
+    // loop's bases no longer fit the scalar file, and the spills cost the tall one a 32-byte stack frame)
+    const unsigned long long stz = (kStamp && kNarrow != 0) ? static_cast<unsigned long long>(opaque(0u)) : 0ull;
+    unsigned long long st_wait = stz, st_stage = 0, tm = 0;
+    unsigned long long st_eval = stz, st_scatter = stz, st_look = stz, st_waitB = 0, st_flush = stz, st_tiles = stz, t0 = 0, t1 = 0;
 
     unsigned char *const smem = rv_smem;
     uint32_t *s_tick = reinterpret_cast<uint32_t *>(smem);       // [4] ring of tile ids, drawn three iterations ahead
@@ -419,18 +422,26 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
         n_redo += 1;
     };
 
-    // The launch's compare term in code space (a pass over codes): an interval of codes, or the complement of one (narrow_term.hpp).
-    // It travels in the term slot behind the launch's one term (launch_pass: terms[1].lit = lo | span << 32, .packed = negate; nterms
-    // stays 1, so nothing else reads that slot) -- the kernel's parameter block is the parent's, byte for byte.
+    // The launch's compare term in code space (a pass over codes): ONE interval of codes -- the host folds a complement into the
+    // interval it is in wrap-around arithmetic (narrow_term.hpp, fold_negate).  It travels in the term slot behind the launch's one
+    // term (launch_pass: terms[1].lit = lo | span << 32, .packed = negate; nterms stays 1, so nothing else reads that slot) -- the
+    // kernel's parameter block is the parent's, byte for byte.
     static_assert(!kNarrow || !kSel, "the forms that write the selection bitmap read the 8-byte values (choose_launch)");
+    // `negate` is left on ONE term only, the empty set over 4-byte codes (the complement of all 2^32 of them is no interval).  It is
+    // tested once per tile, outside the row loop, and sends such a launch through the loop's second form, which still flips its
+    // masks: the form every whole tile of every other launch runs never hears of it.
     uint32_t TLO = 0, TSPAN = 0;
-    uint64_t TNEG = 0;
+    bool negated = false;
     if constexpr (kNarrow != 0) {
         const DevTerm ct = p.in.terms[1];
         TLO = static_cast<uint32_t>(static_cast<uint64_t>(ct.lit));
         TSPAN = static_cast<uint32_t>(static_cast<uint64_t>(ct.lit) >> 32);
-        TNEG = ct.packed ? ~0ull : 0;
+        negated = ct.packed != 0;
     }
+    // (the stamped instantiations carry the interval in VECTOR registers across the tile loop and read it once per tile, like the terms
+    // above: with the stamps beside the staging loop's masks and bases the scalar file is full, and one of them got a stack frame)
+    uint32_t tlo_v = 0, tspan_v = 0;
+    if constexpr (kStamp && kNarrow != 0) tlo_v = opaque(TLO), tspan_v = opaque(TSPAN);
     for (uint32_t it = 0; tile < p.ntiles; ++it) {
         // ---- ticket for three iterations ahead: issued now, stored at the end of the iteration and read
         //      at the top of iteration it + 2 (the barrier of it + 1 lies in between) --------------------
@@ -490,23 +501,64 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
                     wave_total += static_cast<uint32_t>(__popcll(m));
                 }
             } else if constexpr (kNarrow != 0) {
-                // ---- a pass over codes: the term is an interval of codes or the complement of one, so a row costs one 32-bit
-                //      subtract and one unsigned compare (the compare is the ballot; `negate` is a scalar XOR with a launch constant).
-                //      No 64-bit value is formed here: survivors are staged as codes and widened where they are written out (flush).
+                // ---- a pass over codes: the term is ONE interval of codes (the host folds a complement away, narrow_term.hpp), so a row
+                //      costs one 32-bit subtract and one unsigned compare, and the compare is the ballot.  No 64-bit value is formed
+                //      here: survivors are staged as codes and widened where they are written out (flush).
+                //      Everything below is in LDS BYTE ADDRESSES (of the hardware: the block's own address is part of the scalar base,
+                //      not a vector addition per store): the wave's running total moves a scalar base, the pair's ranks count from 0
+                //      (v_mbcnt's accumulator chains the four counts), and one v_lshl_add forms the cell's address.
                 using Code = typename std::conditional<kNarrow == 2, uint16_t, uint32_t>::type;
-                Code *sc = reinterpret_cast<Code *>(smem + sb + off_v[0]);
+                typedef __attribute__((address_space(3))) unsigned char LdsByte;
+                typedef __attribute__((address_space(3))) Code LdsCode;
+                const uint32_t slot0 = static_cast<uint32_t>(reinterpret_cast<uintptr_t>((LdsByte *)rv_smem)) + sb + off_v[0];
+                auto put = [&](uint32_t at, uint32_t code) { *reinterpret_cast<LdsCode *>(static_cast<uintptr_t>(at)) = static_cast<Code>(code); };
+                // An address is CLAMPED to the slot's last cell, not tested against `cap`: a wave whose survivors outgrow the slot is
+                // dense (wave_total > cap, below), its slot is never flushed and the redo kernel writes its range -- so the clamp can
+                // only overwrite a cell of a slot that is discarded.  A wave with exactly `cap` survivors writes cell cap - 1 last,
+                // which the clamp leaves alone.  (A launch that projects nothing has no slot and stores nothing.)
+                const uint32_t top = opaque_uniform(slot0 + (cap - 1u) * kNarrow);
+                // Branch-free stores, like the generic path's stage_slot: a lane without a survivor writes its code to its own cell of
+                // the wave's dump area behind the slots (kLdsDumpBytes, part of every launch's LDS), so the loop never writes the exec
+                // mask.  Two more vector instructions per pair than stores under an exec mask, and faster.
+                const uint32_t cell = opaque(slot0 - sb - off_v[0] + kLdsHeader + nstages * WAVES * slot_bytes + wave * kLdsDumpBytes + static_cast<uint32_t>(lane) * 8u);
+                uint32_t next = slot0;  // the cell of the wave's next survivor, wave-uniform
+                auto cells = [&](uint64_t m0, uint64_t m1, uint32_t &a0, uint32_t &a1) {
+                    const uint32_t below0 = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m0 >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m0), 0u));
+                    const uint32_t below = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m1 >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m1), below0));
+                    a0 = opaque_uniform(next) + below * kNarrow;  // (opaque: the base stays ONE scalar operand)
+                    a1 = a0 + (lane_of(m0) ? static_cast<uint32_t>(kNarrow) : 0u);
+                    a0 = a0 < top ? a0 : top;
+                    a1 = a1 < top ? a1 : top;
+                    next += static_cast<uint32_t>(__popcll(m0) + __popcll(m1)) * kNarrow;
+                };
+                if constexpr (kStamp) TLO = uniform32(tlo_v), TSPAN = uniform32(tspan_v);
+                if (full && project && !negated) {
+                    // ---- every tile but a launch's last: no test in the loop that comes out the same for every row of the tile ----
 #pragma unroll
-                for (int j = 0; j < R / 2; ++j) {
-                    uint32_t c0, c1;
-                    unpack_pair<kNarrow>(codes[j], c0, c1);
-                    uint64_t m0 = ballot64(c0 - TLO <= TSPAN) ^ TNEG, m1 = ballot64(c1 - TLO <= TSPAN) ^ TNEG;
-                    if (!full) m0 &= ballot64(2 * lane < rem - j * 128), m1 &= ballot64(2 * lane + 1 < rem - j * 128);
-                    const bool p0 = lane_of(m0), p1 = lane_of(m1);
-                    const uint32_t r0 = wave_total + mbcnt(m0) + mbcnt(m1), r1 = r0 + (p0 ? 1u : 0u);
-                    if (project && p0 && r0 < cap) sc[r0] = static_cast<Code>(c0);
-                    if (project && p1 && r1 < cap) sc[r1] = static_cast<Code>(c1);
-                    wave_total += static_cast<uint32_t>(__popcll(m0) + __popcll(m1));
+                    for (int j = 0; j < R / 2; ++j) {
+                        uint32_t c0, c1, a0, a1;
+                        unpack_pair<kNarrow>(codes[j], c0, c1);
+                        const uint64_t m0 = ballot64(c0 - TLO <= TSPAN), m1 = ballot64(c1 - TLO <= TSPAN);
+                        cells(m0, m1, a0, a1);
+                        put(lane_of(m0) ? a0 : cell, c0);
+                        put(lane_of(m1) ? a1 : cell, c1);
+                    }
+                } else {
+                    // ---- the ragged last tile, a launch that projects nothing and the one term that kept its `negate` (the empty
+                    //      set over 4-byte codes): the same with the tests and the flip in the loop ----
+                    const uint64_t TNEG = negated ? ~0ull : 0;
+#pragma unroll
+                    for (int j = 0; j < R / 2; ++j) {
+                        uint32_t c0, c1, a0, a1;
+                        unpack_pair<kNarrow>(codes[j], c0, c1);
+                        uint64_t m0 = ballot64(c0 - TLO <= TSPAN) ^ TNEG, m1 = ballot64(c1 - TLO <= TSPAN) ^ TNEG;
+                        if (!full) m0 &= ballot64(2 * lane < rem - j * 128), m1 &= ballot64(2 * lane + 1 < rem - j * 128);
+                        cells(m0, m1, a0, a1);
+                        if (project && lane_of(m0)) put(a0, c0);
+                        if (project && lane_of(m1)) put(a1, c1);
+                    }
                 }
+                wave_total = (next - slot0) / kNarrow;
             } else {
 #pragma unroll
                 for (int j = 0; j < R / 2; ++j) {

@@ -723,9 +723,14 @@ static void launch_pass(rv_ctx *ctx, FusedLaunch &L, const LaunchChoice &c, int 
         p.narrow.codes = c.narrow->codes->ptr;
         p.narrow.bytes = c.narrow->codes->bytes;
         p.narrow.base = c.narrow->base;
-        // the pass compares codes: the term, lowered to an interval of codes (or the complement of one) once per launch
+        // the pass compares codes: the term, lowered to ONE interval of codes once per launch -- a complement is folded into the
+        // interval it is in wrap-around arithmetic.  The one term without an interval, the empty set over 4-byte codes, comes back
+        // as it went in, `negate` set: the kernel tests the flag once per tile, outside its row loop, and runs such a launch through
+        // the form of the loop that still flips its masks
         const rvk::DevTerm &t0 = p.in.terms[0];
-        const rvn::CodeTerm ct = rvn::lower_term(t0.sel_lt(), t0.sel_eq(), t0.sel_gt(), t0.lit, c.narrow->base);
+        bool interval = false;
+        const rvn::CodeTerm ct = rvn::fold_negate(rvn::lower_term(t0.sel_lt(), t0.sel_eq(), t0.sel_gt(), t0.lit, c.narrow->base), c.narrow->code_bytes, &interval);
+        require(interval != ct.negate, RV_ERR_INTERNAL, "narrow pass: a folded term is an interval, and only an unfolded one is negated");
         // (in the term slot behind the launch's one term, which no other reader of `p` looks at: nterms stays 1.  truth(code) =
         // ((code - lo) as uint32 <= span) != negate, fused_kernel.hpp)
         p.in.terms[1].lit = static_cast<int64_t>(static_cast<uint64_t>(ct.lo) | (static_cast<uint64_t>(ct.span) << 32));

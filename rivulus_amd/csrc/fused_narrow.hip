@@ -4,8 +4,14 @@ namespace rvk {
 // 4-byte (FF_NARROW32) frame-of-reference codes instead of the 8-byte rows (scan_frontend.hpp, load_rows_narrow).  What these
 // instantiations do differently from the plain form (fused_kernel.hpp, the `kNarrow != 0` branches):
 //   - a lane holds the tile as raw code pairs (one register per pair of 2-byte codes), requested one tile ahead like the plain form's rows;
-//   - the compare term runs in code space: the host lowers it to an interval of codes or the complement of one (narrow_term.hpp), a row
-//     costs one 32-bit subtract and one unsigned compare;
+//   - the compare term runs in code space: the host lowers it to ONE interval of codes (narrow_term.hpp: a complement is folded into the
+//     interval it is in wrap-around arithmetic; the empty set over 4-byte codes, which is none, keeps its negate flag, tested once per
+//     tile), a row costs one 32-bit subtract and one unsigned compare;
+//   - the staging loop of a whole tile carries nothing that is the same for every row of it: no negate flag, no `full` / `project`
+//     test, ranks formed as LDS addresses from a scalar base and CLAMPED to the slot's last cell instead of compared with its capacity
+//     (a wave that outgrows its slot goes to the redo kernel anyway), and branch-free stores -- a lane without a survivor writes to
+//     its cell of the wave's dump area.  24 instructions per pair of rows (15 vector, 2 LDS, 6 scalar, one wait; no branch, no exec
+//     write) where the form before had 35; the ragged last tile, a launch that projects nothing and the one negated term run a second form with the tests and the flip;
 //   - survivors are staged as codes and widened (value = base + code) where they are written out; the slots hold the same ROWS as the
 //     plain form's (fused_launch.hip, size_staged), in a quarter or half of the LDS bytes.
 // Same values, same order, same counts and redo list as the plain form, bit for bit.
@@ -14,7 +20,10 @@ namespace rvk {
 // SIMD to evaluate theirs is 80-87 %).  Tried on top of the above and taken out again: THREE sets of pairs per lane, the tile two
 // ahead requested at the top of an iteration (ids drawn four ahead, loop unrolled by three) -- 128 VGPRs, and the headline kernel
 // took 0.612 ms against 0.576 ms with one set (1e9 rows, same box, alternating processes; profiles/narrow2_steps.txt).  The two kept
-// steps one by one: compare in code space 0.772 -> 0.603 ms, codes in the slots 0.603 -> 0.564 ms.
+// steps one by one: compare in code space 0.772 -> 0.603 ms, codes in the slots 0.603 -> 0.564 ms.  The staging loop above:
+// 0.564 -> 0.478 ms with the branch-free stores, 0.495 ms with stores under an exec mask (two vector instructions fewer per pair, four
+// exec writes more: taken out; profiles/narrow3_steps.txt).  At 0.478 ms the pass moves its 2.93 GB at 6.1 TB/s: what a streaming
+// kernel reaches on this part.
 // The first entry of a flags class is the default geometry; kNarrowTallRows rows per lane is what a launch without per-batch counts
 // takes (fused_launch.hip): a tile's codes are a quarter or half of its rows' bytes, so twice the rows per lane put twice the bytes
 // on their way per request and halve the per-tile costs (barrier, ticket, descriptor) per row.  The geometries with fewer rows per lane

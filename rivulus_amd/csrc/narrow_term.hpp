@@ -40,4 +40,19 @@ inline CodeTerm lower_term(bool sel_lt, bool sel_eq, bool sel_gt, int64_t lit, i
     }
 }
 
+// The same term without `negate`, wherever one exists: in 32-bit wrap-around arithmetic the complement of the cyclic interval
+// [lo, lo + span] is the cyclic interval [lo + span + 1, lo - 1], so the kernel tests one interval and never flips a mask.  The one
+// complement that is no interval is the EMPTY set (the complement of all 2^32 codes).  Over 2-byte codes, which reach the compare
+// zero-extended, an interval above them stands for it; over 4-byte codes nothing does: `*ok` comes back false, the term unchanged,
+// `negate` still set, and the launch hands it on as it is (fused_launch.hip, launch_pass): the kernel tests the flag once per tile
+// and runs such a launch through the form of its loop that still flips the masks (fused_kernel.hpp).
+inline CodeTerm fold_negate(const CodeTerm &t, int code_bytes, bool *ok) {
+    *ok = true;
+    if (!t.negate) return t;
+    if (t.span != 0xFFFFFFFFu) return CodeTerm{t.lo + t.span + 1u, 0xFFFFFFFEu - t.span, false};
+    if (code_bytes == 2) return CodeTerm{0x10000u, 0u, false};
+    *ok = false;
+    return t;
+}
+
 }  // namespace rvn
