@@ -895,6 +895,74 @@ rv_status rv_top_k_indices(rv_ctx *ctx, const rv_dcolumn *key, uint32_t flags, u
 rv_status rv_top_k(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, const uint32_t *key_cols, const uint32_t *key_flags,
                    uint32_t nkeys, uint64_t k, rv_dcolumn **out);
 
+/* ---- window functions (K12) -------------------------------------------------- */
+/* f(...) OVER (PARTITION BY p_0 .. ORDER BY o_0 ..): one new column per expression, out[j] of the frame's row count and in the
+ * INPUT'S ROW ORDER -- a window function adds columns and reorders nothing.  The reference has no window expression; this comment is the
+ * normative text, tests/window_model.py the executable one; DESIGN.md section 4 K12 argues it.
+ *
+ * Partition.  The partition of a row is the set of rows whose tuple of partition-key cells is equal under rv_group_ids_keys' equality
+ * (K9a): a null equals a null of the same column, all NaNs are equal, -0.0 != +0.0.  npart == 0: the whole frame is one partition.
+ * Partition-key dtypes are what rv_group_ids_keys takes (RV_INT64, RV_FLOAT64, RV_BOOLEAN, RV_NULL), at most 8 columns; an RV_STRING key is
+ * RV_ERR_UNSUPPORTED -- the host layer handles String keys through rv_string_dict_build ids.
+ *
+ * Order.  Within a partition the rows stand in the order rv_sort over (order_cols, order_flags) would give them.  That order is stable, so
+ * ties stand in row order and every row has a unique 1-based position `pos` in its partition.  Order-key dtypes and flags are exactly
+ * rv_sort_indices' (RV_INT64, RV_FLOAT64, RV_NULL; RV_SORT_DESCENDING, RV_SORT_NULLS_LAST); Boolean and String order keys are refused with
+ * its text.  At most 8 order keys.  norder == 0: the order is row order.  Two rows of a partition are PEERS when no order key tells them
+ * apart (both cells null, or both values with the same sort key: all NaNs are peers, -0.0 and +0.0 are not); with norder == 0 all rows of a
+ * partition are peers.
+ *
+ * Numbering.  RV_WIN_ROW_NUMBER = pos.  RV_WIN_RANK = pos of the row's first peer.  RV_WIN_DENSE_RANK = the number of peer groups up to and
+ * including the row's own.  `col` is ignored (but must be a column index).
+ *
+ * Running aggregates.  The frame is ROWS UNBOUNDED PRECEDING .. CURRENT ROW: the partition's rows with position <= pos.
+ * RV_WIN_CUM_COUNT counts the frame's non-null cells of `col`, any dtype.  RV_WIN_CUM_SUM / CUM_MIN / CUM_MAX take an RV_INT64 or RV_FLOAT64
+ * column (any other dtype: RV_ERR_TYPE_MISMATCH), and every numeric rule is rv_hash_aggregate's, applied to the frame instead of the group:
+ * Int64 SUM wraps and is exact; SUM over a frame without a non-null cell is 0 / +0.0, no bitmap; MIN / MAX over such a frame is null;
+ * Float64 MIN / MAX go through the same order map (-0.0 below +0.0; one NaN in the frame makes the result NaN, payload unspecified);
+ * NaN or inf under a null cell never reaches a result.
+ *   Float64 CUM_SUM uses no floating-point atomic.  With a (+) b = b when b holds a partition head, else a + b (one IEEE addition; a null
+ *   cell and a zero of either sign enter as +0.0, so no result is -0.0), over the rows in sequence order (partitions side by side, each in
+ *   its order), tiles of 2048 positions, 256 threads of 8 consecutive positions, 4 waves:
+ *     T_t  thread t's left fold of its 8 elements, ((e_0 (+) e_1) (+) ..) (+) e_7;
+ *     L_l  what lane l - 1 holds after the steps d = 1, 2, 4, 8, 16, 32 of x_l <- x_{l-d} (+) x_l (l >= d) over the wave's T; identity for lane 0;
+ *     W_w  the left fold, from the identity, of the last lanes' x of the waves before wave w;
+ *     C_i  the carry into tile i: the same construction over the tile aggregates, 2048 tiles to a round, R (+) (W (+) L) with R the left
+ *          fold of the totals of the rounds before;
+ *   the result at a thread's k-th position is ((C_i (+) (W_w (+) L_l)) (+) e_0) (+) .. (+) e_k.  Only the row's position in the sequence,
+ *   the positions of the partition heads and this fixed geometry enter it: the same call over the same buffers gives the same bits run to
+ *   run.  The result is bit exact whenever every partial sum is representable, and otherwise |got - exact| <= gamma_{m-1} x sum|x| over
+ *   the frame (m = its non-null cells, gamma as at rv_hash_aggregate: the bound of any summation order).
+ *
+ * LAG and LEAD.  RV_WIN_LAG(col, offset = k) is the cell of `col` at the partition's row with position pos - k, RV_WIN_LEAD at pos + k;
+ * null when there is no such row or that cell is null.  Any dtype rv_take_device_nullable gathers, String and Boolean included.  k == 0
+ * copies the column.  `offset` is ignored by every other op.
+ *
+ * Outputs.  Counts and numbers are Int64 without a bitmap; SUM / MIN / MAX and LAG / LEAD have the column's dtype.  A bitmap is attached
+ * iff some output cell is null; null_count is known; values under nulls are 0.  A zero-row frame gives zero-row outputs of the right
+ * dtypes.  Slices at any element offset are fine, each column its own.
+ *
+ * Errors leave the context usable and create nothing: NULL arguments, ncols == 0, nspecs == 0, an unknown op, a column index out of range,
+ * unknown flag bits, more than 8 partition or order keys RV_ERR_INVALID_ARG; columns of different lengths RV_ERR_LENGTH_MISMATCH; frames
+ * of 2^32 rows or more, and more partitions than context option "agg_max_groups", RV_ERR_UNSUPPORTED.
+ *
+ * The passes.  (1) The partition ids (rv_group_ids_keys' passes; skipped when npart == 0) and the sequence: rv_sort_indices' chain over
+ * the order keys from the last to the first, then over the id column -- with npart == 0 and norder == 0 no sort runs and every kernel reads
+ * and writes in place.  All expressions of a call share it.  (2) window_heads: one lane per position, two bitmaps (partition head, peer
+ * head).  (3) window_scan, per numbering or aggregate: three launches over the fixed tiles (tile aggregates; their scan by one workgroup;
+ * the apply, which stores at out[perm[j]]).  (4) window_shift, per LAG / LEAD: a nullable index list in row order, then
+ * rv_take_device_nullable's gather.  No kernel waits for another workgroup.  rv_ctx_last_kernel names "window_scan", or "window_shift" when
+ * only LAG / LEAD ran; rv_ctx_kernel_stats (option "profile_kernels") times the sorts (as rv_sort_indices does) and passes (2) - (4). */
+typedef enum rv_window_op { RV_WIN_ROW_NUMBER = 0, RV_WIN_RANK = 1, RV_WIN_DENSE_RANK = 2, RV_WIN_CUM_COUNT = 3, RV_WIN_CUM_SUM = 4, RV_WIN_CUM_MIN = 5, RV_WIN_CUM_MAX = 6, RV_WIN_LAG = 7, RV_WIN_LEAD = 8 } rv_window_op;
+typedef struct rv_window_spec {
+    uint32_t op;     /* rv_window_op */
+    uint32_t col;    /* index into cols */
+    uint64_t offset; /* RV_WIN_LAG / RV_WIN_LEAD only */
+} rv_window_spec;
+rv_status rv_window(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, const uint32_t *partition_cols, uint32_t npart,
+                    const uint32_t *order_cols, const uint32_t *order_flags, uint32_t norder, const rv_window_spec *specs,
+                    uint32_t nspecs, rv_dcolumn **out);
+
 /* ---- multi-GPU (one process per GPU) --------------------------------------- */
 /* Row-range shard of rank `rank` of `world`: [*begin, *end), boundaries at multiples of
  * 64 rows so selection-bitmap words never straddle ranks. */

@@ -135,6 +135,17 @@ class RvAggSpec(C.Structure):
     _fields_ = [("op", C.c_uint32), ("col", C.c_uint32)]
 
 
+# rv_window_op
+(RV_WIN_ROW_NUMBER, RV_WIN_RANK, RV_WIN_DENSE_RANK, RV_WIN_CUM_COUNT, RV_WIN_CUM_SUM, RV_WIN_CUM_MIN, RV_WIN_CUM_MAX, RV_WIN_LAG,
+ RV_WIN_LEAD) = range(9)
+WINDOW_OPS = {"row_number": RV_WIN_ROW_NUMBER, "rank": RV_WIN_RANK, "dense_rank": RV_WIN_DENSE_RANK, "cum_count": RV_WIN_CUM_COUNT,
+              "cum_sum": RV_WIN_CUM_SUM, "cum_min": RV_WIN_CUM_MIN, "cum_max": RV_WIN_CUM_MAX, "lag": RV_WIN_LAG, "lead": RV_WIN_LEAD}
+
+
+class RvWindowSpec(C.Structure):
+    _fields_ = [("op", C.c_uint32), ("col", C.c_uint32), ("offset", C.c_uint64)]
+
+
 class RvSynthSpec(C.Structure):
     _fields_ = [("dtype", C.c_int), ("seed", C.c_uint64), ("first_row", C.c_uint64), ("length", C.c_uint64),
                 ("modulus", C.c_uint64), ("true_percent", C.c_uint32), ("with_validity", C.c_int32),
@@ -211,6 +222,8 @@ PROTOTYPES = {
     "rv_sort": (C.c_int, [_P, _PP, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, _PP]),
     "rv_top_k_indices": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, _PP]),
     "rv_top_k": (C.c_int, [_P, _PP, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint64, _PP]),
+    "rv_window": (C.c_int, [_P, _PP, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32,
+                            C.POINTER(RvWindowSpec), C.c_uint32, _PP]),
     "rv_hash_join_kind": (C.c_int, [_P, _PP, C.c_uint32, C.c_uint32, _PP, C.c_uint32, C.c_uint32, C.c_int, _PP, _U64P]),
     "rv_hash_join_chunked_kind": (C.c_int, [_P, _P, _PP, C.c_uint32, C.c_uint32, _PP, C.c_uint32, C.c_uint32, C.c_int, C.c_uint64, C.c_uint64,
                                             _PP, _U64P, C.c_uint64, C.POINTER(C.c_int64), _U64P, _U64P]),
@@ -943,6 +956,23 @@ class Context:
         out = (C.c_void_p * max(1, len(cols)))()
         _check(load().rv_top_k(self.handle, _handles(cols), len(cols), kc, kf, len(keys), k, out))
         return [DeviceColumn(self, C.c_void_p(out[i])) for i in range(len(cols))]
+
+    def window(self, cols: Sequence[DeviceColumn], partition_by: Sequence[int], order_by, exprs):
+        """rv_window: one new column per expression, in the input's row order.  partition_by: column indices; order_by: column indices or
+        (column index, flags) pairs, the first key the most significant; exprs: (op, column index) or (op, column index, offset) with op a
+        name of WINDOW_OPS or an rv_window_op number."""
+        order = [(k, 0) if isinstance(k, int) else tuple(k) for k in order_by]
+        pc = (C.c_uint32 * max(1, len(partition_by)))(*partition_by)
+        oc = (C.c_uint32 * max(1, len(order)))(*[k[0] for k in order])
+        of = (C.c_uint32 * max(1, len(order)))(*[k[1] for k in order])
+        specs = (RvWindowSpec * max(1, len(exprs)))()
+        for j, e in enumerate(exprs):
+            specs[j].op = WINDOW_OPS[e[0]] if isinstance(e[0], str) else int(e[0])
+            specs[j].col = int(e[1])
+            specs[j].offset = int(e[2]) if len(e) > 2 else 0
+        out = (C.c_void_p * max(1, len(exprs)))()
+        _check(load().rv_window(self.handle, _handles(cols), len(cols), pc, len(partition_by), oc, of, len(order), specs, len(exprs), out))
+        return [DeviceColumn(self, C.c_void_p(out[j])) for j in range(len(exprs))]
 
     def hash_join(self, build_cols: Sequence[DeviceColumn], build_key: int, probe_cols: Sequence[DeviceColumn], probe_key: int,
                   kind: Optional[int] = None):

@@ -425,6 +425,14 @@ void hash_aggregate(rv_ctx *ctx, const KeyCols &keys, const char *what, const rv
 }
 
 }  // namespace
+
+// ---- the window operator's way in (window.hip): rv_group_ids_keys' checks and its dense Int64 ids, without the handles
+void check_partition_keys(const rv_dcolumn *const *keys, uint32_t nkeys, const char *what) { check_group_keys(keys, nkeys, what); }
+DevBufRef partition_ids(rv_ctx *ctx, const rv_dcolumn *const *keys, uint32_t nkeys, const char *what) {
+    GroupIds ids = group_ids_of(ctx, key_cols(keys, nkeys), what, true);
+    require(fetch_ctrl(ctx)->err == 0, RV_ERR_INTERNAL, fmt("%s: a row's key was not found in the group table", what));
+    return ids.gids;
+}
 }  // namespace rvl
 
 extern "C" {

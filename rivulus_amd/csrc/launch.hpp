@@ -1,5 +1,5 @@
 // Internal interface between the translation units of librivulus_gpu.so (core / fused_launch / narrow / strings / predicate / arrays /
-// query / take_concat / host_table / aggregate / join / string_dict / csv / group / group_agg / sort / topk .hip): the control block, the request / launch
+// query / take_concat / host_table / aggregate / join / string_dict / csv / group / group_agg / sort / topk / window .hip): the control block, the request / launch
 // records that travel with a fused pass, and the functions the units call across each other.  Nothing here is part of the C ABI.
 #pragma once
 
@@ -276,6 +276,12 @@ void check_sort_key(const rv_dcolumn *key, uint32_t flags, const char *what);
 DevBufRef sort_indices(rv_ctx *ctx, const rv_dcolumn *key, uint32_t flags, const uint64_t *prior);
 // an Int64 column without nulls over the first `rows` rows of `buf`
 rv_dcolumn *sort_index_column(const DevBufRef &buf, uint64_t rows);
+
+// ---- group_agg.hip -----------------------------------------------------------------------------------------
+// what rv_group_ids_keys checks of its key list, under the caller's name `what`, and the dense Int64 group id of every row (n cells, no
+// nulls; equal tuples -- K9a's equality -- get equal ids)
+void check_partition_keys(const rv_dcolumn *const *keys, uint32_t nkeys, const char *what);
+DevBufRef partition_ids(rv_ctx *ctx, const rv_dcolumn *const *keys, uint32_t nkeys, const char *what);
 
 // ---- take_nullable.hip -------------------------------------------------------------------------------------
 // A nullable index list of the gathers: a null index yields a null cell of the column's dtype.  validity: the list's bitmap, read

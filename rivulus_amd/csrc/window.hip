@@ -1,0 +1,275 @@
+// Window functions on the device: rv_window -- rank, running aggregates and lag / lead over PARTITION BY ... ORDER BY.  One unit of the
+// backend library behind include/rivulus_gpu.h (gfx950 only; compiled with hipcc).  Shared helpers are declared in launch.hpp (namespace
+// rvl); the kernels, the shape of the passes and the bracketing of the scan are in window_kernel.hpp, the combine in window_combine.hpp.
+// The partition ids are rv_group_ids_keys' (group_agg.hip), the sequence is the sort's chain (sort.hip), LAG / LEAD gather through
+// take_nullable_on_device (take_nullable.hip): what is new here is the heads pass, the segmented scan and the shift.
+#include "launch.hpp"
+#include "window_kernel.hpp"
+
+using namespace rvh;
+using namespace rvl;
+
+namespace rvl {
+namespace {
+
+static_assert(rvk::kWinTileRows == rvk::kWinThreads * rvk::kWinItems, "a tile is one workgroup x kWinItems positions per thread");
+static_assert(sizeof(rvk::WinTriple) == 24, "tile aggregates and carries are 24-byte records");
+
+// the rows of a call in window order, and where its partitions and peer groups begin
+struct Sequence {
+    uint64_t n = 0;
+    DevBufRef ids;   // Int64 partition id per row; null: one partition
+    DevBufRef perm;  // null: the identity
+    DevBufRef part_heads, peer_heads;
+    const uint64_t *d_perm() const { return perm ? static_cast<const uint64_t *>(perm->ptr) : nullptr; }
+    const int64_t *d_ids() const { return ids ? static_cast<const int64_t *>(ids->ptr) : nullptr; }
+};
+
+template <uint32_t OP>
+void launch_scan(rv_ctx *ctx, const rvk::WinScanParams &p) {
+    const dim3 grid(static_cast<uint32_t>(p.ntiles)), block(rvk::kWinThreads);
+    hipLaunchKernelGGL(rvk::window_tile_agg<OP>, grid, block, 0, ctx->stream, p);
+    RV_HIP(hipGetLastError());
+    hipLaunchKernelGGL(rvk::window_carry_scan<OP>, dim3(1), block, 0, ctx->stream, static_cast<const rvk::WinTriple *>(p.tile_agg), p.ntiles, p.carry);
+    RV_HIP(hipGetLastError());
+    hipLaunchKernelGGL(rvk::window_apply<OP>, grid, block, 0, ctx->stream, p);
+    RV_HIP(hipGetLastError());
+}
+
+bool is_shift(uint32_t op) { return op == RV_WIN_LAG || op == RV_WIN_LEAD; }
+
+// events around the window's own passes (option profile_kernels); the sorts before them time themselves
+struct PassTimer {
+    rv_ctx *ctx;
+    uint64_t launches = 0;
+    bool open = false;
+    explicit PassTimer(rv_ctx *c) : ctx(c) {}
+    void start() {
+        if (ctx->opt_profile) RV_HIP(hipEventRecord(ctx->evk0, ctx->stream));
+        open = true;
+    }
+    void stop_after_wait_for(hipStream_t s) {
+        if (!open) return;
+        open = false;
+        if (!ctx->opt_profile) return;
+        RV_HIP(hipEventRecord(ctx->evk1, s));
+        RV_HIP(hipEventSynchronize(ctx->evk1));
+        float ms = 0.f;
+        RV_HIP(hipEventElapsedTime(&ms, ctx->evk0, ctx->evk1));
+        ctx->kernel_ms += ms;
+        ctx->kernel_launches += launches;
+        launches = 0;
+    }
+};
+
+void window(rv_ctx *ctx, const rv_dcolumn *const *cols, const uint32_t *partition_cols, uint32_t npart, const uint32_t *order_cols,
+            const uint32_t *order_flags, uint32_t norder, const rv_window_spec *specs, uint32_t nspecs, rv_dcolumn **out) {
+    Sequence q;
+    q.n = cols[0]->length;
+    const uint64_t n = q.n;
+    std::vector<std::unique_ptr<rv_dcolumn>> outs(nspecs);
+    if (n == 0) {  // zero-row outputs of the right dtypes
+        for (uint32_t j = 0; j < nspecs; ++j) {
+            const rv_dcolumn *col = cols[specs[j].col];
+            if (is_shift(specs[j].op)) {
+                rv_dcolumn *o = nullptr;
+                take_nullable_on_device(ctx, &col, 1, nullptr, 0, &o, false, IndexNulls{});
+                outs[j].reset(o);
+            } else {
+                outs[j] = new_value_column(ctx, specs[j].op >= RV_WIN_CUM_SUM ? col->dtype : RV_INT64, 0);
+            }
+        }
+        RV_HIP(hipStreamSynchronize(ctx->stream));
+        for (uint32_t j = 0; j < nspecs; ++j) out[j] = outs[j].release();
+        ctx->last_kernel.clear();
+        return;
+    }
+
+    // 1. the sequence: partition ids, then the sort's chain from the last order key to the first and over the ids last
+    if (npart) {
+        std::vector<const rv_dcolumn *> keys(npart);
+        for (uint32_t k = 0; k < npart; ++k) keys[k] = cols[partition_cols[k]];
+        q.ids = partition_ids(ctx, keys.data(), npart, "rv_window");
+    }
+    for (uint32_t k = norder; k-- > 0;) q.perm = sort_indices(ctx, cols[order_cols[k]], order_flags[k], q.d_perm());
+    if (npart) {
+        rv_dcolumn id_col;
+        id_col.dtype = RV_INT64;
+        id_col.values = q.ids;
+        id_col.length = n;
+        id_col.null_count = 0;
+        q.perm = sort_indices(ctx, &id_col, 0, q.d_perm());
+    }
+
+    PassTimer timer(ctx);
+    timer.start();
+    bool scanned = false, shifted = false;
+
+    // 2. the heads (needed by the scans only: the shift compares the ids themselves)
+    bool any_scan = false;
+    for (uint32_t j = 0; j < nspecs; ++j) any_scan = any_scan || !is_shift(specs[j].op);
+    const uint64_t nwords = (n + 63) / 64, ntiles = (n + rvk::kWinTileRows - 1) / rvk::kWinTileRows;
+    DevBufRef tile_agg, carry;
+    if (any_scan) {
+        q.part_heads = pool_alloc(ctx, nwords * 8 + 16);
+        q.peer_heads = pool_alloc(ctx, nwords * 8 + 16);
+        rvk::WinHeadsParams h{};
+        h.perm = q.d_perm();
+        h.ids = q.d_ids();
+        h.n = n;
+        h.norder = norder;
+        for (uint32_t k = 0; k < norder; ++k) h.order[k] = dev_view(cols[order_cols[k]]);
+        h.part_heads = static_cast<uint64_t *>(q.part_heads->ptr);
+        h.peer_heads = static_cast<uint64_t *>(q.peer_heads->ptr);
+        hipLaunchKernelGGL(rvk::window_heads, dim3(static_cast<uint32_t>((n + rvk::kWinThreads - 1) / rvk::kWinThreads)), dim3(rvk::kWinThreads), 0, ctx->stream, h);
+        RV_HIP(hipGetLastError());
+        ++timer.launches;
+        tile_agg = pool_alloc(ctx, ntiles * sizeof(rvk::WinTriple) + 16);
+        carry = pool_alloc(ctx, ntiles * sizeof(rvk::WinTriple) + 16);
+    }
+
+    // 3. the scans, one spec after the other over the one sequence
+    struct Pending {  // a MIN / MAX whose null count the next read-back brings
+        uint32_t j;
+        int slot;
+    };
+    std::vector<Pending> pending;
+    Ctrl *ctrl = nullptr;
+    auto settle = [&] {  // read the null counts of the MIN / MAX outputs queued so far
+        if (pending.empty()) return;
+        const Ctrl *hc = fetch_ctrl(ctx);
+        for (const Pending &w : pending) {
+            outs[w.j]->null_count = static_cast<int64_t>(hc->valid_pop[w.slot]);
+            if (outs[w.j]->null_count == 0) outs[w.j]->validity.reset();  // attached iff some cell is null
+        }
+        pending.clear();
+        ctrl = nullptr;
+    };
+    for (uint32_t j = 0; j < nspecs; ++j) {
+        const uint32_t op = specs[j].op;
+        if (is_shift(op)) continue;
+        const rv_dcolumn *col = cols[specs[j].col];
+        rvk::WinScanParams p{};
+        p.perm = q.d_perm();
+        p.part_heads = static_cast<const uint64_t *>(q.part_heads->ptr);
+        p.peer_heads = static_cast<const uint64_t *>(q.peer_heads->ptr);
+        p.n = n;
+        p.ntiles = ntiles;
+        p.tile_agg = static_cast<rvk::WinTriple *>(tile_agg->ptr);
+        p.carry = static_cast<rvk::WinTriple *>(carry->ptr);
+        const bool numeric = op >= RV_WIN_CUM_SUM;
+        outs[j] = new_value_column(ctx, numeric ? col->dtype : RV_INT64, n);
+        p.out = static_cast<uint64_t *>(outs[j]->values->ptr);
+        p.is_float = numeric && col->dtype == RV_FLOAT64;
+        p.is_max = op == RV_WIN_CUM_MAX;
+        switch (op) {
+            case RV_WIN_ROW_NUMBER: p.src = rvk::WS_ONE; break;
+            case RV_WIN_DENSE_RANK: p.src = rvk::WS_PEER; break;
+            case RV_WIN_RANK: p.src = rvk::WS_PEER_POS, p.fin = rvk::WF_RANK; break;
+            case RV_WIN_CUM_COUNT: p.src = rvk::WS_VALID, p.col = dev_view(col); break;
+            default: p.src = rvk::WS_CELL, p.col = dev_view(col); break;
+        }
+        if (op == RV_WIN_CUM_MIN || op == RV_WIN_CUM_MAX) {
+            if (pending.size() == 8) settle();
+            if (!ctrl) ctrl = prepare_ctrl(ctx, 0);
+            const int slot = static_cast<int>(pending.size());
+            outs[j]->validity = pool_alloc(ctx, zeroed_bitmap_bytes(n));
+            RV_HIP(hipMemsetAsync(outs[j]->validity->ptr, 0, zeroed_bitmap_bytes(n), ctx->stream));
+            p.fin = rvk::WF_MINMAX;
+            p.out_validity = static_cast<uint64_t *>(outs[j]->validity->ptr);
+            p.nulls = striped(ctx, &ctrl->valid_pop[slot]);
+            pending.push_back(Pending{j, slot});
+            if (op == RV_WIN_CUM_MIN) launch_scan<rvwin::WC_MIN_U64>(ctx, p);
+            else launch_scan<rvwin::WC_MAX_U64>(ctx, p);
+        }
+        else if (op == RV_WIN_RANK) launch_scan<rvwin::WC_MAX_U64>(ctx, p);
+        else if (op == RV_WIN_CUM_SUM && col->dtype == RV_FLOAT64) launch_scan<rvwin::WC_ADD_F64>(ctx, p);
+        else launch_scan<rvwin::WC_ADD_I64>(ctx, p);
+        timer.launches += 3;
+        scanned = true;
+    }
+
+    // 4. the shifts: a nullable index list in row order, gathered like any other
+    struct Shift {
+        uint32_t j;
+        DevBufRef idx;
+    };
+    std::vector<Shift> shifts;
+    for (uint32_t j = 0; j < nspecs; ++j) {
+        if (!is_shift(specs[j].op)) continue;
+        rvk::WinShiftParams s{};
+        s.perm = q.d_perm();
+        s.ids = q.d_ids();
+        s.n = n;
+        s.k = specs[j].offset;
+        s.lead = specs[j].op == RV_WIN_LEAD;
+        shifts.push_back(Shift{j, pool_alloc(ctx, n * 8 + 16)});
+        s.idx = static_cast<uint64_t *>(shifts.back().idx->ptr);
+        hipLaunchKernelGGL(rvk::window_shift, dim3(grid_for_words(ctx, n, rvk::kWinThreads)), dim3(rvk::kWinThreads), 0, ctx->stream, s);
+        RV_HIP(hipGetLastError());
+        ++timer.launches;
+        shifted = true;
+    }
+    timer.stop_after_wait_for(ctx->stream);
+    settle();
+    for (const Shift &s : shifts) {
+        const rv_dcolumn *col = cols[specs[s.j].col];
+        rv_dcolumn *o = nullptr;
+        take_nullable_on_device(ctx, &col, 1, static_cast<const uint64_t *>(s.idx->ptr), n, &o, false, IndexNulls{});
+        outs[s.j].reset(o);
+    }
+    RV_HIP(hipStreamSynchronize(ctx->stream));  // the sequence and the working buffers go back to the pool
+    for (uint32_t j = 0; j < nspecs; ++j) out[j] = outs[j].release();
+    ctx->last_kernel = scanned ? "window_scan" : shifted ? "window_shift" : "";
+}
+
+}  // namespace
+}  // namespace rvl
+
+extern "C" {
+
+rv_status rv_window(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, const uint32_t *partition_cols, uint32_t npart,
+                    const uint32_t *order_cols, const uint32_t *order_flags, uint32_t norder, const rv_window_spec *specs, uint32_t nspecs,
+                    rv_dcolumn **out) {
+    return guarded([&] {
+        require(ctx && cols && specs && out && (npart == 0 || partition_cols) && (norder == 0 || (order_cols && order_flags)), RV_ERR_INVALID_ARG,
+                "rv_window: NULL argument");
+        require(ncols >= 1, RV_ERR_INVALID_ARG, "rv_window: no columns");
+        require(nspecs >= 1, RV_ERR_INVALID_ARG, "rv_window: no window expressions");
+        check_batch(cols, ncols);
+        for (uint32_t k = 0; k < npart; ++k)
+            require(partition_cols[k] < ncols, RV_ERR_INVALID_ARG, fmt("rv_window: partition key %u is column %u of %u", k, partition_cols[k], ncols));
+        for (uint32_t k = 0; k < norder; ++k)
+            require(order_cols[k] < ncols, RV_ERR_INVALID_ARG, fmt("rv_window: order key %u is column %u of %u", k, order_cols[k], ncols));
+        require(norder <= static_cast<uint32_t>(rvk::kWinOrderKeysMost), RV_ERR_INVALID_ARG,
+                fmt("rv_window: %u order keys; at most %d are taken", norder, rvk::kWinOrderKeysMost));
+        for (uint32_t j = 0; j < nspecs; ++j) {
+            require(specs[j].op <= static_cast<uint32_t>(RV_WIN_LEAD), RV_ERR_INVALID_ARG, fmt("rv_window: expression %u has the unknown op %u", j, specs[j].op));
+            require(specs[j].col < ncols, RV_ERR_INVALID_ARG, fmt("rv_window: expression %u reads column %u of %u", j, specs[j].col, ncols));
+        }
+        require(cols[0]->length < (uint64_t{1} << 32), RV_ERR_UNSUPPORTED, "rv_window: frames of 2^32 rows or more are not supported (32-bit row ids inside, as the sort)");
+        if (npart) {
+            std::vector<const rv_dcolumn *> keys(npart);
+            for (uint32_t k = 0; k < npart; ++k) keys[k] = cols[partition_cols[k]];
+            check_partition_keys(keys.data(), npart, "rv_window");
+        }
+        for (uint32_t k = 0; k < norder; ++k) check_sort_key(cols[order_cols[k]], order_flags[k], "rv_window");
+        for (uint32_t j = 0; j < nspecs; ++j) {
+            const rv_dtype d = cols[specs[j].col]->dtype;
+            if (specs[j].op >= RV_WIN_CUM_SUM && specs[j].op <= RV_WIN_CUM_MAX)
+                require(is_value_type(d), RV_ERR_TYPE_MISMATCH, fmt("rv_window: expression %u: CUM_SUM / CUM_MIN / CUM_MAX take an Int64 or Float64 column", j));
+            else if (specs[j].op == RV_WIN_CUM_COUNT || is_shift(specs[j].op))
+                require(is_value_type(d) || d == RV_BOOLEAN || d == RV_STRING || d == RV_NULL, RV_ERR_UNSUPPORTED, fmt("rv_window: expression %u: unsupported dtype", j));
+        }
+        for (uint32_t j = 0; j < nspecs; ++j) out[j] = nullptr;
+        set_device(ctx);
+        try {
+            window(ctx, cols, partition_cols, npart, order_cols, order_flags, norder, specs, nspecs, out);
+        } catch (...) {
+            (void)hipStreamSynchronize(ctx->stream);  // whatever was queued has run before its buffers go back to the pool
+            throw;
+        }
+    });
+}
+
+}  // extern "C"

@@ -2108,6 +2108,148 @@ class GpuSortStream : public DataStream {
 };
 
 // ---------------------------------------------------------------------------------------
+// window(partition_by, order_by, exprs) -- f(...) OVER (PARTITION BY .. ORDER BY ..); the reference has no window expression:
+// include/rivulus_gpu.h, rv_window
+// ---------------------------------------------------------------------------------------
+enum class WindowOp { RowNumber, Rank, DenseRank, CumCount, CumSum, CumMin, CumMax, Lag, Lead };  // rv_window_op, in its order
+inline const char *to_string(WindowOp op) {
+    static const char *n[] = {"ROW_NUMBER", "RANK", "DENSE_RANK", "CUM_COUNT", "CUM_SUM", "CUM_MIN", "CUM_MAX", "LAG", "LEAD"};
+    return n[static_cast<int>(op)];
+}
+inline bool window_op_reads_a_column(WindowOp op) { return op != WindowOp::RowNumber && op != WindowOp::Rank && op != WindowOp::DenseRank; }
+// One window expression: `op` over `column` (ignored by the three numberings), `offset` rows back or ahead (Lag / Lead only), under the
+// output name `alias`.
+struct WindowExpr {
+    WindowOp op;
+    std::string column;
+    uint64_t offset = 0;
+    std::string alias;
+};
+struct WindowPlanError : std::runtime_error {  // what planning a window refuses, with the column it refuses it for
+    using std::runtime_error::runtime_error;
+};
+constexpr size_t kWindowKeysMost = 8;
+
+// Checks the window against `in` and returns the output schema: the input's fields, then one field per expression under its alias --
+// numbers and counts Int64, CUM_SUM / CUM_MIN / CUM_MAX and LAG / LEAD of the column's dtype; MIN / MAX and LAG / LEAD are nullable.
+// Partition keys may be of any dtype (String keys go through the dictionary); order keys are what the sort takes.  Throws WindowPlanError
+// for an empty expression list, an unknown column, more than 8 partition or order keys, a String / Boolean order key (with the sort's
+// words), SUM / MIN / MAX over a column that is not Int64 or Float64, and an empty or duplicate alias.
+inline SchemaRef window_schema(const Schema &in, const std::vector<std::string> &partition_by, const std::vector<SortKey> &order_by,
+                               const std::vector<WindowExpr> &exprs) {
+    if (exprs.empty()) throw WindowPlanError("window: no window expressions");
+    if (partition_by.size() > kWindowKeysMost)
+        throw WindowPlanError("window: " + std::to_string(partition_by.size()) + " partition columns; at most " + std::to_string(kWindowKeysMost) + " are taken");
+    if (order_by.size() > kWindowKeysMost)
+        throw WindowPlanError("window: " + std::to_string(order_by.size()) + " order columns; at most " + std::to_string(kWindowKeysMost) + " are taken");
+    for (auto &p : partition_by)
+        if (!in.field_by_name(p)) throw WindowPlanError("window: unknown partition column '" + p + "'");
+    for (auto &k : order_by) {
+        const Field *f = in.field_by_name(k.column);
+        if (!f) throw WindowPlanError("window: unknown order column '" + k.column + "'");
+        if (f->data_type() == DataType::String || f->data_type() == DataType::Boolean)
+            throw WindowPlanError("window: order column '" + k.column + "' is " + to_string(f->data_type()) + "; only Int64 and Float64 keys are sorted");
+    }
+    std::vector<Field> out = in.fields();
+    for (auto &e : exprs) {
+        DataType t = DataType::Int64;
+        if (window_op_reads_a_column(e.op)) {
+            const Field *f = in.field_by_name(e.column);
+            if (!f) throw WindowPlanError("window: expression '" + e.alias + "' reads the unknown column '" + e.column + "'");
+            if (e.op != WindowOp::CumCount) t = f->data_type();
+            if ((e.op == WindowOp::CumSum || e.op == WindowOp::CumMin || e.op == WindowOp::CumMax) && t != DataType::Int64 && t != DataType::Float64)
+                throw WindowPlanError(std::string("window: ") + to_string(e.op) + " over column '" + e.column + "' of dtype " + to_string(t));
+        }
+        if (e.alias.empty()) throw WindowPlanError(std::string("window: the ") + to_string(e.op) + " expression over column '" + e.column + "' has no alias");
+        for (auto &f : out)
+            if (f.name() == e.alias) throw WindowPlanError("window: duplicate output name '" + e.alias + "'");
+        out.push_back(Field{e.alias, t, e.op == WindowOp::CumMin || e.op == WindowOp::CumMax || e.op == WindowOp::Lag || e.op == WindowOp::Lead});
+    }
+    return std::make_shared<const Schema>(out);
+}
+
+// One rv_window over one frame (`columns` in the order of `schema`): the NEW columns, one per expression, in the frame's row order.
+// Every String partition key goes through the string dictionary on its own, as group_by's do: its ids (a null string is a null id; "" is
+// a value) stand in the tuple.
+inline std::vector<ArrayRef> window_columns(const ContextRef &ctx, const Schema &schema, const std::vector<ArrayRef> &columns,
+                                            const std::vector<std::string> &partition_by, const std::vector<SortKey> &order_by,
+                                            const std::vector<WindowExpr> &exprs) {
+    (void)window_schema(schema, partition_by, order_by, exprs);
+    const SortCall call(schema, columns, order_by);
+    std::vector<const rv_dcolumn *> handles = call.handles;
+    std::vector<ArrayRef> ids;  // keeps the ids of the String keys alive over the call
+    std::vector<uint32_t> part_cols;
+    for (auto &p : partition_by) {
+        const size_t at = *schema.index_of(p);
+        if (schema.field_by_name(p)->data_type() != DataType::String) {
+            part_cols.push_back(static_cast<uint32_t>(at));
+            continue;
+        }
+        rv_string_dict *dict = nullptr;
+        rv_dcolumn *h = nullptr;
+        check(rv_string_dict_build(ctx->raw(), call.handles[at], &dict, &h));
+        ids.push_back(Array::adopt(ctx, h));
+        check(rv_string_dict_free(ctx->raw(), dict));  // only the ids are needed: equal strings share an id
+        part_cols.push_back(static_cast<uint32_t>(handles.size()));
+        handles.push_back(ids.back()->handle());
+    }
+    std::vector<rv_window_spec> specs;
+    for (auto &e : exprs)
+        specs.push_back(rv_window_spec{static_cast<uint32_t>(e.op), window_op_reads_a_column(e.op) ? static_cast<uint32_t>(*schema.index_of(e.column)) : 0u, e.offset});
+    std::vector<rv_dcolumn *> out(specs.size(), nullptr);
+    check(rv_window(ctx->raw(), handles.data(), static_cast<uint32_t>(handles.size()), part_cols.data(), static_cast<uint32_t>(part_cols.size()),
+                    call.key_cols.data(), call.key_flags.data(), static_cast<uint32_t>(order_by.size()), specs.data(), static_cast<uint32_t>(specs.size()),
+                    out.data()));
+    return adopt_columns(ctx, out);
+}
+
+// window as a stream: a PIPELINE BREAKER like GpuSortStream.  It drains its input the same way -- a resident frame is taken as it is, the
+// batches of any other stream are concatenated (RecordBatch::concat) -- and emits EXACTLY ONE batch: every row in input order, the new
+// columns appended.  An input without rows gives one zero-row batch with the schema.  (Windows over input that arrives partitioned,
+// batch by batch, are not built.)
+class GpuWindowStream : public DataStream {
+  public:
+    // `fallback_ctx`: where the zero-row batch of an input that yields no batch at all is created
+    GpuWindowStream(JoinSide input, std::vector<std::string> partition_by, std::vector<SortKey> order_by, std::vector<WindowExpr> exprs, ContextRef fallback_ctx)
+        : input_(std::move(input)), partition_by_(std::move(partition_by)), order_by_(std::move(order_by)), exprs_(std::move(exprs)), ctx_(std::move(fallback_ctx)) {
+        input_schema_ = input_.schema();
+        schema_ = window_schema(*input_schema_, partition_by_, order_by_, exprs_);
+    }
+    SchemaRef schema() const override { return schema_; }
+    std::optional<RecordBatch> next_batch() override {
+        if (done_) return std::nullopt;
+        done_ = true;
+        std::vector<ArrayRef> columns = input_.columns;
+        if (input_.stream) {
+            std::vector<RecordBatch> all;
+            while (auto b = input_.stream->next_batch()) all.push_back(std::move(*b));
+            if (all.empty()) {
+                if (!ctx_) throw StreamError::execution("window: the input yielded no batch and the plan holds no device context");
+                return RecordBatch::empty(ctx_, schema_);
+            }
+            RecordBatch whole = all.size() == 1 ? all[0] : stream_call([&] { return RecordBatch::concat(all); });
+            columns = whole.columns();
+        }
+        return stream_call([&] {
+            const ContextRef ctx = columns.empty() ? ctx_ : columns[0]->context();
+            if (columns.empty() || columns[0]->len() == 0) return RecordBatch::empty(ctx, schema_);
+            const size_t rows = columns[0]->len();
+            for (auto &c : window_columns(ctx, *input_schema_, columns, partition_by_, order_by_, exprs_)) columns.push_back(c);
+            return RecordBatch::new_unchecked(schema_, std::move(columns), rows);
+        });
+    }
+
+  private:
+    JoinSide input_;
+    std::vector<std::string> partition_by_;
+    std::vector<SortKey> order_by_;
+    std::vector<WindowExpr> exprs_;
+    ContextRef ctx_;
+    SchemaRef input_schema_, schema_;
+    bool done_ = false;
+};
+
+// ---------------------------------------------------------------------------------------
 // top_k(keys, k) -- ORDER BY ... LIMIT k: the first k rows of sort(keys); include/rivulus_gpu.h, rv_top_k_indices
 // ---------------------------------------------------------------------------------------
 // Checks `keys` against `in` as sort_schema does -- the same SortPlanError, the same texts -- and returns the output schema, the input's.
@@ -2539,7 +2681,7 @@ class StreamingPhysicalPlan;
 using StreamingPlanPtr = std::shared_ptr<const StreamingPhysicalPlan>;
 class StreamingPhysicalPlan {
   public:
-    enum Kind { MemorySource, DataFrameSource, CsvFileSource, Filter, GpuFilterProject, Select, Limit, HashJoin, Project, ComputedFilterProject, GroupBy, Sort, TopK } kind = MemorySource;
+    enum Kind { MemorySource, DataFrameSource, CsvFileSource, Filter, GpuFilterProject, Select, Limit, HashJoin, Project, ComputedFilterProject, GroupBy, Sort, TopK, Window } kind = MemorySource;
     std::vector<Expr> exprs;  // Project: select expressions, arithmetic included
     Expr predicate_expr;      // ComputedFilterProject: a filter with `<arith> <cmp> <literal>` terms
     // DataFrameSource (streaming.rs:85-94)
@@ -2568,6 +2710,8 @@ class StreamingPhysicalPlan {
     std::vector<execution::AggSpec> aggs;
     std::vector<execution::SortKey> sort_keys;  // Sort { input, sort_keys }, TopK { input, sort_keys, top_k_rows, top_k_fold_rows }
     size_t top_k_rows = 0, top_k_fold_rows = execution::kTopKFoldRows;
+    std::vector<std::string> partition_keys;  // Window { input, partition_keys, sort_keys (the window order), window_exprs }
+    std::vector<execution::WindowExpr> window_exprs;
 
     static StreamingPlanPtr memory_source(std::vector<execution::RecordBatch> b) {
         auto p = std::make_shared<StreamingPhysicalPlan>();
@@ -2708,6 +2852,18 @@ class StreamingPhysicalPlan {
         p->top_k_fold_rows = fold_rows;
         return p;
     }
+    // window(partition_by, order_by, exprs): the input's rows in input order with one new column per expression; a pipeline breaker that
+    // emits exactly one batch (GpuWindowStream); the reference has no such operator
+    static StreamingPlanPtr window(StreamingPlanPtr in, std::vector<std::string> partition_by, std::vector<execution::SortKey> order_by,
+                                   std::vector<execution::WindowExpr> exprs) {
+        auto p = std::make_shared<StreamingPhysicalPlan>();
+        p->kind = Window;
+        p->input = std::move(in);
+        p->partition_keys = std::move(partition_by);
+        p->sort_keys = std::move(order_by);
+        p->window_exprs = std::move(exprs);
+        return p;
+    }
     // a device context some source of the plan holds (nullptr: none does)
     ContextRef any_context() const {
         if (csv_ctx) return csv_ctx;
@@ -2790,6 +2946,7 @@ class StreamingPhysicalPlan {
                     return std::make_unique<GpuGroupByStream>(std::move(s), group_key, aggs, any_context());
                 }
                 case Sort:
+                case Window:
                 case TopK: {  // drain their input as GroupBy does
                     JoinSide s;
                     if (input->kind == DataFrameSource && !input->df.columns.empty() && input->df_batch_size > 0) {
@@ -2800,6 +2957,7 @@ class StreamingPhysicalPlan {
                         s.stream = input->execute();
                     }
                     if (kind == TopK) return std::make_unique<GpuTopKStream>(std::move(s), sort_keys, top_k_rows, any_context(), top_k_fold_rows);
+                    if (kind == Window) return std::make_unique<GpuWindowStream>(std::move(s), partition_keys, sort_keys, window_exprs, any_context());
                     return std::make_unique<GpuSortStream>(std::move(s), sort_keys, any_context());
                 }
             }
@@ -2854,7 +3012,7 @@ class PhysicalPlan;
 using PhysicalPlanPtr = std::shared_ptr<const PhysicalPlan>;
 class PhysicalPlan {
   public:
-    enum Kind { DataFrameSource, Select, Filter, HashJoin, Project, ComputedFilter, GroupBy, Sort, TopK } kind = DataFrameSource;
+    enum Kind { DataFrameSource, Select, Filter, HashJoin, Project, ComputedFilter, GroupBy, Sort, TopK, Window } kind = DataFrameSource;
     DeviceFrame df;
     std::vector<Expr> exprs;  // Project: select expressions, arithmetic included
     Expr predicate_expr;      // ComputedFilter: `<arith> <cmp> <literal>` terms, alone or under AND / OR
@@ -2870,6 +3028,8 @@ class PhysicalPlan {
     std::vector<execution::AggSpec> aggs;
     std::vector<execution::SortKey> sort_keys;  // Sort { input, sort_keys }, TopK { input, sort_keys, top_k_rows }
     size_t top_k_rows = 0;
+    std::vector<std::string> partition_keys;  // Window { input, partition_keys, sort_keys (the window order), window_exprs }
+    std::vector<execution::WindowExpr> window_exprs;
 
     static PhysicalPlanPtr source(DeviceFrame f) {
         auto p = std::make_shared<PhysicalPlan>();
@@ -2967,9 +3127,32 @@ class PhysicalPlan {
         p->top_k_rows = k;
         return p;
     }
+    // window(partition_by, order_by, exprs), eager: one rv_window -- the frame as it is, rows in place, with one new column per expression
+    // appended under its alias.  The nulls of the frame stay nulls (no fill: this is not a stream).
+    static PhysicalPlanPtr window(PhysicalPlanPtr in, std::vector<std::string> partition_by, std::vector<execution::SortKey> order_by,
+                                  std::vector<execution::WindowExpr> exprs) {
+        auto p = std::make_shared<PhysicalPlan>();
+        p->kind = Window;
+        p->input = std::move(in);
+        p->partition_keys = std::move(partition_by);
+        p->sort_keys = std::move(order_by);
+        p->window_exprs = std::move(exprs);
+        return p;
+    }
     DeviceFrame execute() const {
         switch (kind) {
             case DataFrameSource: return df;  // plan.rs:67
+            case Window: {
+                DeviceFrame in = input->execute();
+                const execution::Schema schema = frame_schema(in);
+                const execution::SchemaRef out_schema = execution::window_schema(schema, partition_keys, sort_keys, window_exprs);  // the planning errors
+                if (in.columns.empty()) throw Error(RV_ERR_INVALID_ARG, "window: the frame has no columns");
+                DeviceFrame out = in;
+                for (auto &c : execution::window_columns(in.columns[0]->context(), schema, in.columns, partition_keys, sort_keys, window_exprs)) out.columns.push_back(c);
+                out.names.clear();
+                for (auto &f : out_schema->fields()) out.names.push_back(f.name());
+                return out;
+            }
             case TopK: {
                 DeviceFrame in = input->execute();
                 const execution::Schema schema = frame_schema(in);
