@@ -14,6 +14,7 @@ A schema is one dict per column:
   fresh    full, and rv_eval_arith wrote it: arith operands and group keys / arguments lean towards these, so that the state "bitmap
            attached, zero nulls" reaches consumers on columns an operator made
 """
+import collections
 import math
 
 import numpy as np
@@ -381,6 +382,294 @@ def case(seed):
     return {"seed": seed, "n": n, "source": source, "steps": steps, "builds": builds}
 
 
+# ---- the second generator: window, top-k, outer / semi / anti joins and multi-key grouping among the older kinds ---------------------
+# case() above and everything it calls stay as they are (tests/golden/pipeline_cases_digest.json pins the 200 default cases); the makers
+# below read three more schema hints, set by them alone:
+#   padded  an "outer" / "full" join may have put nulls into the column (the side that can lack a partner)
+#   holes   an operator wrote the column and it may hold nulls (a quotient, a padded column, a MIN / MAX, a LAG / LEAD): top-k first
+#           keys lean towards these
+#   far     a LAG / LEAD beyond every partition wrote the column: every cell is null
+NEW_KINDS = pipeline_model.NEW_KINDS
+KINDS_ALL = pipeline_model.KINDS_ALL
+PAIRS_OPS = [(a, b) for a in KINDS_ALL for b in KINDS_ALL if a in NEW_KINDS or b in NEW_KINDS]  # 72 ordered pairs
+HOWS = ("outer", "full", "semi", "anti")
+FAR = 1 << 20  # a LAG / LEAD offset larger than any partition (the largest frame is LARGE rows times two joins)
+TOPK_K = (["abs", 1], ["abs", 7], ["of", 1, 8, 1], ["of", 1, 2, -1], ["of", 1, 2], ["of", 1, 1], ["of", 1, 1, 5])  # (rows / 8 + 1: a small frame keeps a row)
+TOPK_K_P = (0.17, 0.2, 0.25, 0.1, 0.08, 0.1, 0.1)
+
+
+def _lean(rng, cand, schema, hints, p=0.85):
+    """cand, or with probability p those of it that carry one of `hints` (if any does)"""
+    if rng.random() < p:
+        for h in hints:
+            sub = [j for j in cand if schema[j].get(h)]
+            if sub:
+                return sub
+    return cand
+
+
+def _passed_on(c, **hints):
+    out = dict(c)
+    out.update({"full": False, "fresh": False}, **hints)
+    return out
+
+
+def _step_window(rng, schema):
+    hints = ("padded", "fresh", "full")
+    parts = [j for j, c in enumerate(schema) if c["dtype"] in ("i64", "f64", "bool", "null", "str")]
+    order = _sortable(schema)
+    small = [j for j in parts if schema[j]["dtype"] != "i64" or (schema[j]["dom"] is not None and schema[j]["dom"][1] - schema[j]["dom"][0] <= 100)]
+    partition_by = [_pick(rng, _lean(rng, small or parts, schema, hints, 0.6)) for _ in range(int(rng.choice([0, 1, 1, 1, 2])))]
+    order_by = [(_pick(rng, _lean(rng, order, schema, hints, 0.6)), int(rng.integers(0, 4))) for _ in range(int(rng.choice([0, 1, 1, 2])))]
+    options = [("row_number", 0), ("rank", 0), ("dense_rank", 0)]
+    for j, c in enumerate(schema):
+        options.append(("cum_count", j))
+        options += [(_pick(rng, ["lag", "lead"]), j, int(rng.choice([0, 1, 2, FAR])))]
+        if c["dtype"] == "i64" or (c["dtype"] == "f64" and c["sum"]):
+            options.append(("cum_sum", j))
+        if c["dtype"] in ("i64", "f64"):
+            options += [("cum_min", j), ("cum_max", j)]
+    exprs = [_pick(rng, options) for _ in range(int(rng.integers(1, 5)))]
+    reads = _lean(rng, list(range(len(schema))), schema, hints, 1.0)
+    if reads != list(range(len(schema))):  # one expression over a column in a state worth meeting
+        j = _pick(rng, reads)
+        ops = ["cum_count", "lag", "lead"] + (["cum_min", "cum_max", "cum_sum"] if schema[j]["dtype"] == "i64" else ["cum_min", "cum_max"] if schema[j]["dtype"] == "f64" else [])
+        op = _pick(rng, ops)
+        exprs[0] = (op, j, int(rng.choice([0, 1, 2, FAR]))) if op in ("lag", "lead") else (op, j)
+    out = [dict(c) for c in schema]  # the frame's columns are passed on untouched
+    for e in exprs:
+        src = schema[e[1]]
+        if e[0] in ("row_number", "rank", "dense_rank", "cum_count"):
+            out.append(_col("i64"))
+        elif e[0] == "cum_sum":
+            out.append(_col(src["dtype"]))  # not summable: no later SUM or CUM_SUM reads it
+        else:
+            out.append(_passed_on(src, sum=False, holes=True, padded=False, far=len(e) > 2 and e[2] == FAR))
+    return {"kind": "window", "partition_by": partition_by, "order_by": order_by, "exprs": exprs}, out
+
+
+def _step_topk(rng, schema, tiny=False, none=False, holes=False):
+    """tiny: the source has at most two rows -- no k that rounds to 0; none: k = 0 (two of the default seeds); holes: the select, forced,
+    over a first key an operator wrote nulls into if the frame has one -- nulls last and a small k, so that it runs whatever their number"""
+    cand = _sortable(schema)
+    wide = [j for j in cand if schema[j]["dtype"] == "f64" or (schema[j]["dtype"] == "i64" and (schema[j]["dom"] is None or schema[j]["dom"][1] - schema[j]["dom"][0] >= 100))]
+    first = _pick(rng, _lean(rng, _lean(rng, cand, schema, ("holes",), 0.7), schema, ("padded", "fresh", "full"), 0.5)) if rng.random() < 0.6 else _pick(rng, wide or cand)
+    keys = [(first, int(rng.integers(0, 4)))]
+    via = "indices" if rng.random() < 0.3 else "frame"
+    if via == "frame" and rng.random() < 0.5:
+        keys.append((_pick(rng, cand), int(rng.integers(0, 4))))
+    k = list(TOPK_K[int(rng.choice(len(TOPK_K), p=TOPK_K_P))])
+    if tiny and k[0] == "of" and k[2] == 2:
+        k = ["abs", 1]
+    if none:
+        k = ["abs", 0]
+    made = [j for j in cand if schema[j].get("holes")]
+    if holes and made and not none:
+        keys[0] = (_pick(rng, made), 2 + int(rng.integers(0, 2)))
+        first, k = keys[0][0], [["abs", 1], ["abs", 7]][int(rng.integers(0, 2))]
+    step = {"kind": "topk", "keys": keys, "k": k, "via": via, "select": bool(rng.random() < 0.7) or (holes and bool(made))}
+    out = [_passed_on(c) for c in schema]
+    out[first]["dom"] = None  # the rows that stay are one end of the key's domain
+    return step, out
+
+
+def _step_outer_join(rng, schema, how=None, side=None, least=0):
+    """_step_join for the other kinds.  The second frame's keys cover the upper half of the probe key's domain and as much again above it:
+    whatever `how`, some probe rows find a partner and some do not, and some rows of the second frame meet nobody (what FULL appends)."""
+    how = how or str(rng.choice(HOWS))
+    keys = [j for j, c in enumerate(schema) if c["dtype"] == "i64"]
+    keys = [j for j in keys if schema[j]["dom"] is not None] or keys
+    if rng.random() < 0.9:
+        keys = [j for j in keys if not schema[j]["dead"]] or keys
+        keys = [j for j in keys if schema[j]["dom"] is not None and schema[j]["dom"][1] - schema[j]["dom"][0] >= 2] or keys  # one value: every row matches
+    pk = _pick(rng, _lean(rng, keys, schema, ("padded", "fresh"), 0.5))
+    lo, hi = schema[pk]["dom"] or (0, 8)
+    card = max(1, hi - lo)
+    side = side or ("build" if rng.random() < 0.3 else "probe")
+    m = min(int(rng.choice([0, 1, 5, 64, 300], p=(0.02, 0.04, 0.1, 0.34, 0.5))), 3 * card)
+    m = max(m, min(least, 3 * card))
+    if side == "build":
+        m = min(max(m, 2), 5)
+    dts = ["i64", str(rng.choice(["i64", "f64"]))] + [str(rng.choice(["i64", "f64", "bool", "str", "null"])) for _ in range(int(rng.integers(0, 3)))]
+    src, bschema = _source(rng, dts, m, "slice" if rng.random() < 0.3 else "upload")
+    first = hi - (m + 1) // 2 if side == "build" else lo + card // 2  # (the few rows that probe the frame straddle its domain's end)
+    keyvals = first + rng.permutation(m) % card
+    valid = None
+    if m >= 3 and rng.random() < 0.4:
+        valid = np.ones(m, bool)
+        valid[rng.integers(0, m, 2)] = False
+    kfull = np.array(src["padded"][0][1])
+    kfull[src["pad"]:src["pad"] + m] = keyvals
+    vfull = None
+    if valid is not None:
+        vfull = np.ones(len(kfull), bool)
+        vfull[src["pad"]:src["pad"] + m] = valid
+    src["padded"][0] = ("i64", kfull, vfull)
+    src["frame"][0] = _cut(src["padded"][0], src["pad"], m)
+    bschema[0] = _col("i64", (first, first + card))
+    bsteps = []
+    r = rng.random()
+    if r < 0.15:
+        step, bschema = _step_sort(rng, bschema)
+        bsteps.append(step)
+    elif r < 0.3:
+        step, bschema = _step_arith(rng, bschema)
+        bsteps.append(step)
+    step = {"kind": "outer_join", "how": how, "probe_key": pk, "build_key": 0, "chunked": bool(how != "full" and rng.random() < 0.4), "side": side}
+    mine, other = [dict(c) for c in schema], [dict(c) for c in bschema]
+    probe, build, bk = (other, mine, pk) if side == "build" else (mine, other, 0)
+    if how in ("semi", "anti"):
+        return step, [_passed_on(c) for c in probe], {"source": src, "steps": bsteps}
+    pads = how in ("outer", "full")
+    out = [_passed_on(c, padded=c.get("padded", False) or how == "full", holes=c.get("holes", False) or how == "full") for c in probe]
+    out += [_passed_on(c, padded=pads, holes=pads) for j, c in enumerate(build) if j != bk or how == "full"]
+    if how == "full":
+        for c in out:
+            if c["dtype"] == "i64" and c["dom"] is not None:
+                c["dom"] = (min(c["dom"][0], lo, first), max(c["dom"][1], first + card))
+    return step, out, {"source": src, "steps": bsteps}
+
+
+def _step_group_keys(rng, schema):
+    hints = ("padded", "fresh", "full")
+    cand = [j for j, c in enumerate(schema) if c["dtype"] in ("i64", "f64", "bool", "null", "str")]
+    nkeys = min(len(cand), int(rng.choice([2, 2, 3])))
+    keys = []
+    while len(keys) < nkeys:
+        j = _pick(rng, _lean(rng, [c for c in cand if c not in keys], schema, hints, 0.7))
+        keys.append(j)
+    if len(keys) == 1:  # a frame of one column: the tuple of the same column twice
+        keys.append(keys[0])
+    options = [("count_rows", None)] + [("count", j) for j in range(len(schema))]
+    for j, c in enumerate(schema):
+        if c["dtype"] == "i64" or (c["dtype"] == "f64" and c["sum"]):
+            options.append(("sum", j))
+        if c["dtype"] in ("i64", "f64"):
+            options += [("min", j), ("max", j)] * 2
+    specs = [_pick(rng, options) for _ in range(int(rng.integers(1, 4)))]
+    numeric = _lean(rng, [j for j, c in enumerate(schema) if c["dtype"] in ("i64", "f64")], schema, hints, 1.0)
+    if any(schema[j].get(h) for j in numeric for h in hints):
+        j = _pick(rng, numeric)
+        specs[0] = (_pick(rng, ["min", "max"] + (["sum"] if schema[j]["dtype"] == "i64" else [])), j)
+    if not any(schema[j]["dtype"] == "i64" for j in keys):
+        specs = [("count_rows", None)] + specs[:2]  # every frame keeps an Int64 column
+    out = [_passed_on(schema[j]) for j in keys]
+    for op, j in specs:
+        if op in ("count_rows", "count"):
+            out.append(_col("i64"))
+        elif op == "sum":
+            out.append(_col(schema[j]["dtype"], None, schema[j]["sum"]))
+        else:
+            out.append(_passed_on(schema[j], holes=True, padded=False))
+    return {"kind": "group_keys", "keys": keys, "specs": specs}, out
+
+
+def _step_arith_ops(rng, schema, plain=False):
+    """_step_arith; over a frame with padded numeric columns mostly an expression that reads one (a sum or a quotient, as the nulls an
+    outer join wrote meet the operators)."""
+    padded = [j for j, c in enumerate(schema) if c.get("padded") and c["dtype"] in ("i64", "f64")]
+    if plain or not padded or rng.random() < 0.1:
+        step, out = _step_arith(rng, schema, plain)
+    else:
+        num = [j for j, c in enumerate(schema) if c["dtype"] in ("i64", "f64")]
+        a, b = ("col", _pick(rng, padded)), ("col", _pick(rng, num))
+        tree = (_pick(rng, ["+", "/", "*"]), a, b) if rng.random() < 0.5 else ("/", b, a)
+        dtype = {v: k for k, v in RV.items()}[arith_model.tree_dtype(tree, [RV[c["dtype"]] for c in schema])]
+        step, out = {"kind": "arith", "tree": tree}, [dict(c) for c in schema] + [_col(dtype, None, False, dtype == "f64")]
+    out[-1]["holes"] = True
+    return step, out
+
+
+def _step_group_ops(rng, schema):
+    """_step_group; over a frame with padded numeric columns the last aggregate is mostly a MIN / MAX of one"""
+    step, out = _step_group(rng, schema)
+    padded = [j for j, c in enumerate(schema) if c.get("padded") and c["dtype"] in ("i64", "f64")]
+    if padded and rng.random() < 0.9:
+        j = _pick(rng, padded)
+        step["specs"][-1] = (_pick(rng, ["min", "max"]), j)
+        out[-1] = dict(schema[j])
+    for c, (op, _) in zip(out[1:], step["specs"]):
+        if op in ("min", "max"):
+            c["holes"], c["padded"] = True, False
+    return step, out
+
+
+MAKERS_OPS = dict(MAKERS, window=_step_window, group_keys=_step_group_keys)  # (case_ops calls the makers of joins, arith, group and topk itself)
+EMPTY_SEEDS_OPS = (4, 5, 7)  # mask -> a new kind over a table without rows, then the other three new kinds
+TOPK_NONE_SEEDS = (25, 72 + 58)  # reshape -> topk and outer_join -> topk with k = 0
+JOIN_CONSUMERS = [i for i, (_, b) in enumerate(PAIRS_OPS) if b == "outer_join"]
+N_CASES_OPS = 216  # three walks through PAIRS_OPS
+
+
+def case_ops(seed):
+    """case() over KINDS_ALL: the first two kinds walk through PAIRS_OPS (seed % 72), then 0 to 3 drawn steps; sizes, sources and null
+    shares as case() has them."""
+    rng = np.random.default_rng(848_400 + seed)
+    how = "csv" if seed % 10 == 3 else "slice" if seed % 10 in (1, 5, 8) else "upload"
+    n = int(rng.choice(SIZES, p=SIZE_P))
+    if seed % 40 == 7:
+        n = LARGE
+    if how == "csv":
+        n = int(rng.choice([257, 300, 511]))
+    a, b = PAIRS_OPS[seed % len(PAIRS_OPS)]
+    steer = a == "arith"
+    if steer and how == "csv":
+        how = "upload"
+    if seed in EMPTY_SEEDS_OPS:
+        n = 0
+    elif "outer_join" in (a, b) and n < 63:
+        n = 65  # the walk's consumer is to meet padded cells, every kind of join rows with and rows without a partner
+    walk = seed // len(PAIRS_OPS)
+    pool = ["i64", "f64", "bool", "str"] + ([] if how == "csv" else ["null"])
+    dts = ["i64"] + [str(rng.choice(pool)) for _ in range(int(rng.integers(1, 6)))]
+    if steer:
+        dts[1] = ("i64", "f64")[seed % 2]
+    source, schema = _source(rng, dts, n, how, (0, 1) if steer else ())
+    kinds = [a, b] + [str(rng.choice(KINDS_ALL)) for _ in range(int(rng.integers(0, 4)))]
+    if seed in EMPTY_SEEDS_OPS:
+        kinds = [a, b] + sorted((k for k in NEW_KINDS if k != b), key=lambda k: k == "outer_join")  # (a FULL join brings rows back: last)
+    steps, builds, joins = [], {}, 0
+    for pos, kind in enumerate(kinds):
+        if kind in ("join", "outer_join") and joins == 2:
+            kind = "sort"
+        if kind == "arith" and n == LARGE and any(s["kind"] == "arith" for s in steps):
+            kind = "sort"
+        if kind in ("filter", "mask", "join"):
+            # predicates and inner-join keys mostly look past the columns that may well be all null by now (what `dead` is for)
+            for c in schema:
+                c["was_dead"], c["dead"] = c["dead"], c["dead"] or c.get("padded", False) or c.get("far", False)
+        if kind == "join":
+            joins += 1
+            step, schema, build = _step_join(rng, schema)
+            builds[len(steps)] = build
+        elif kind == "outer_join":
+            joins += 1
+            # as a walk's producer the join pads (its consumer is to meet the padded columns); as its consumer every kind takes its turn
+            how_join = str(rng.choice(HOWS[:2]))  # (a drawn join sits late, over what is often a small frame: "semi" / "anti" are the walk's)
+            if pos == 0:
+                how_join = HOWS[(walk + seed) % 2]
+            elif pos == 1:
+                how_join = HOWS[(walk + JOIN_CONSUMERS.index(seed % len(PAIRS_OPS))) % 4]
+            step, schema, build = _step_outer_join(rng, schema, how_join, "probe" if pos == 0 else None, 5 if pos == 0 else 0)
+            builds[len(steps)] = build
+        elif kind == "arith":
+            step, schema = _step_arith_ops(rng, schema, steer and not steps)
+        elif kind == "group":
+            step, schema = _step_group_ops(rng, schema)
+        elif kind == "topk":
+            step, schema = _step_topk(rng, schema, n <= 2, seed in TOPK_NONE_SEEDS and pos == 1, pos == 1 and a in ("outer_join", "window"))
+        else:
+            step, schema = MAKERS_OPS[kind](rng, schema)
+        for c in schema:
+            if "was_dead" in c:
+                c["dead"] = c.pop("was_dead")
+        if kind not in ("arith", "window") and not (kind == "reshape" and step["how"] == "slice"):
+            for c in schema:  # every other producer gathers: a bitmap without nulls is dropped
+                c["full"] = c["fresh"] = False
+        steps.append(step)
+    return {"seed": seed, "n": n, "source": source, "steps": steps, "builds": builds}
+
+
 # ---- directed pipelines: the edges by name, at any size (tests/golden/pipeline_cases.json holds each at toy size) --------------------------
 def upload_of(frame):
     return {"how": "upload", "frame": frame, "padded": frame, "pad": 0, "ref": False, "text": None}
@@ -498,7 +787,195 @@ def assert_consumer_met_bitmap_without_nulls(case):
     assert read == [2, 3], read
     for j in read:
         assert meta[j]["made"] and "bitmap_no_nulls" in pipeline_model.column_states(frame[j], meta[j]), f"{step['kind']} input column {j}: {meta[j]}"
-    if step["kind"] == "join":
+    if step["kind"] in pipeline_model.JOINS:
         bframe, bmeta = builds[k][-1]
         j = step["build_key"]
         assert bmeta[j]["made"] and "bitmap_no_nulls" in pipeline_model.column_states(bframe[j], bmeta[j]), f"join, other side's key: {bmeta[j]}"
+
+
+# ---- directed pipelines over the newer operators (tests/golden/pipeline_ops_cases.json holds a hand-written toy version of each) -------
+SLICE_AT = (1, 63, 65)
+NOTHING = {"kind": "filter", "terms": [(0, "<", -1)], "nulls": "drops", "expr": None, "via": "project"}
+
+
+def _outer_frames(n, rng, seed):
+    """Probe keys in [0, 10) and build keys in [3, 13), a null key on each side, payloads of every dtype: a FULL join pads both sides.
+    Output columns of the FULL join: probe 0 key, 1 Float64, 2 String, 3 Boolean, 4 Null; build 5 key, 6 Float64, 7 String, 8 Boolean."""
+    m = max(4, n // 8)
+    probe = [("i64", rng.integers(0, 10, n, dtype=np.int64), rng.random(n) > 0.1), ("f64", dyadic_cells(seed, n, SCALE)[1], rng.random(n) > 0.2),
+             ("str", [WORDS[i % 5] for i in range(n)], None), ("bool", rng.random(n) > 0.5, rng.random(n) > 0.1), ("null", np.zeros(n, np.int64), None)]
+    bvalid = np.ones(m, bool)
+    bvalid[m // 2] = False
+    build = [("i64", 3 + np.arange(m, dtype=np.int64) % 10, bvalid), ("f64", dyadic_cells(seed + 1, m, SCALE)[1], rng.random(m) > 0.2),
+             ("str", [WORDS[(i + 2) % 6] for i in range(m)], None), ("bool", rng.random(m) > 0.5, None)]
+    if n:
+        probe[0][2][0] = False  # a null key on the probe side whatever the draw
+        probe[0][1][-1] = 1     # and a key no build row holds
+    return probe, build
+
+
+FULL = {"kind": "outer_join", "how": "full", "probe_key": 0, "build_key": 0, "chunked": False, "side": "probe"}
+
+
+def _minmax_frame(n, rng, seed, nulls):
+    """key k in [0, max(6, n / 8)) and an Int64 x whose first cells in every partition are null (nulls: else none is): CUM_MIN / CUM_MAX over the
+    partitions in row order are null at every partition's start."""
+    k = rng.integers(0, max(6, n // 8), n, dtype=np.int64)  # (partitions start all along the frame: a slice keeps null cells)
+    x = rng.integers(-40, 40, n, dtype=np.int64)
+    valid = np.ones(n, bool)
+    if nulls:
+        seen = collections.Counter()
+        for i, key in enumerate(k.tolist()):
+            seen[key] += 1
+            valid[i] = seen[key] > 2 and rng.random() > 0.1
+    return [("i64", k, None), ("i64", x, valid if nulls else None), ("f64", dyadic_cells(seed, n, SCALE)[1], None)]
+
+
+def directed_ops(name, n, seed=5):
+    """(frame, steps, {step index: (second frame, its steps)}) of the directed pipeline `name` over n rows."""
+    rng = np.random.default_rng(seed)
+    if name.startswith("full_outer_then_"):
+        # The consumer reads the columns FULL_OUTER padded -- value 0 under the null -- as keys and operands.
+        probe, build = _outer_frames(n, rng, seed)
+        c = name[len("full_outer_then_"):]
+        builds = {0: (build, [])}
+        if c == "window":  # partitions by the padded probe key, ordered by the padded build payload
+            tail = [{"kind": "window", "partition_by": [0], "order_by": [(6, 2)],
+                     "exprs": [("row_number", 0), ("dense_rank", 0), ("cum_count", 6), ("cum_min", 6), ("cum_max", 0), ("lag", 7, 1), ("lead", 3, 1), ("cum_sum", 5)]}]
+        elif c.startswith("topk_"):  # the padded Float64 payload under flag word f, k below / above its null count, the select forced
+            tail = [{"kind": "topk", "keys": [(6, int(c[5]))], "k": ["of", 1, 8] if c.endswith("lo") else ["of", 9, 20], "via": "frame", "select": True}]
+        elif c == "group_keys":
+            tail = [{"kind": "group_keys", "keys": [0, 5], "specs": [("count_rows", None), ("sum", 1), ("min", 6), ("count", 7)]}]
+        elif c == "sort":
+            tail = [{"kind": "sort", "keys": [(5, 0), (0, 3)], "via": "sort"}]
+        elif c == "group":
+            tail = [{"kind": "group", "key": 5, "specs": [("count", 0), ("min", 6), ("sum", 1)]}]
+        elif c == "arith":
+            tail = [{"kind": "arith", "tree": ("+", ("col", 0), ("col", 5))}, {"kind": "arith", "tree": ("/", ("col", 0), ("col", 5))}]
+        else:  # the padded build key probes a second join whose build side holds key 0 (and a null key: the padded rows meet that one)
+            assert c == "join", name
+            second = [("i64", np.array([0, 4, 0, 7, 12], np.int64), np.array([1, 1, 1, 1, 0], bool)), ("str", ["zero", "four", "zero2", "seven", "null"], None)]
+            tail = [{"kind": "join", "probe_key": 5, "build_key": 0, "chunked": False}]
+            builds[1] = (second, [])
+        return probe, [dict(FULL)] + tail, builds
+    if name.startswith("window_minmax_"):  # window_minmax_<bitmap | plain>_then_<c>_<offset>
+        _, _, state, _, c, off = name.split("_", 5)
+        if c == "group":
+            c, off = "group_keys", off.split("_")[-1]
+        if c == "outer":
+            c, off = "outer_join", off.split("_")[-1]
+        frame = _minmax_frame(n, rng, seed, state == "bitmap")
+        steps = [{"kind": "window", "partition_by": [0], "order_by": [], "exprs": [("cum_min", 1), ("cum_max", 1)]},
+                 {"kind": "reshape", "how": "slice", "offset": int(off), "tail": 1}]
+        second = [("i64", np.array([-5, 3, -5, 30, 0], np.int64), np.array([1, 1, 1, 1, 0], bool)), ("f64", np.array([0.5, 1.5, 2.5, 3.5, 4.5]), None)]
+        tail = {"sort": {"kind": "sort", "keys": [(3, 1), (4, 2)], "via": "sort"},
+                "topk": {"kind": "topk", "keys": [(3, 0), (4, 1)], "k": ["of", 1, 4], "via": "frame", "select": True},
+                "group_keys": {"kind": "group_keys", "keys": [3, 0], "specs": [("count_rows", None), ("max", 4), ("sum", 2)]},
+                "filter": {"kind": "filter", "terms": [(3, "<", 0)], "nulls": "least", "expr": None, "via": "project"},
+                "outer_join": {"kind": "outer_join", "how": "outer", "probe_key": 3, "build_key": 0, "chunked": True, "side": "probe"}}[c]
+        return frame, steps + [tail], ({2: (second, [])} if c == "outer_join" else {})
+    if name.startswith("topk_indices_as_index_"):  # top_k_indices over a / b, select forced; take_device by it; a window over the k rows
+        steps = [DIV, {"kind": "topk", "keys": [(3, int(name[-1]))], "k": ["of", 1, 4], "via": "indices", "select": True},
+                 {"kind": "window", "partition_by": [1], "order_by": [(3, 0)], "exprs": [("rank", 0), ("cum_sum", 2), ("lag", 3, 1)]}]
+        return _div_frame(n, seed), steps, {}
+    if name.startswith("empty_then_"):
+        frame = directed("empty_then_sort", n, seed)[0]
+        build = [("i64", np.array([0, 1, 2], np.int64), None), ("str", ["a", "b", "c"], None)]
+        c = name[len("empty_then_"):]
+        if c in HOWS:
+            return frame, [NOTHING, {"kind": "outer_join", "how": c, "probe_key": 0, "build_key": 0, "chunked": c == "semi", "side": "probe"}], {1: (build, [])}
+        tail = {"window": {"kind": "window", "partition_by": [0, 3], "order_by": [(1, 1)], "exprs": [("row_number", 0), ("cum_sum", 1), ("cum_min", 0), ("lag", 2, 1), ("lead", 4, 0)]},
+                "topk": {"kind": "topk", "keys": [(1, 0), (0, 3)], "k": ["abs", 7], "via": "frame", "select": True},
+                "group_keys": {"kind": "group_keys", "keys": [0, 3, 2], "specs": [("count_rows", None), ("sum", 1), ("min", 1)]}}[c]
+        return frame, [NOTHING, tail], {}
+    if name.startswith("empty_build_side_") or name == "empty_probe_side_full":
+        frame = [("i64", rng.integers(0, 3, n, dtype=np.int64), rng.random(n) > 0.1), ("f64", dyadic_cells(seed, n, SCALE)[1], None), ("str", [WORDS[i % 4] for i in range(n)], None)]
+        other = [("i64", np.array([0, 1, 2], np.int64), None), ("str", ["a", "b", "c"], None), ("null", np.zeros(3, np.int64), None), ("bool", np.array([1, 0, 1], bool), None),
+                 ("f64", np.array([0.5, -1.0, 2.0]), None)]
+        nothing = {"kind": "filter", "terms": [(0, ">", 99)], "nulls": "least", "expr": None, "via": "selection"}
+        if name == "empty_probe_side_full":
+            return frame, [NOTHING, dict(FULL)], {1: (other, [])}
+        return frame, [{"kind": "outer_join", "how": name.split("_")[-1], "probe_key": 0, "build_key": 0, "chunked": False, "side": "probe"}], {0: (other, [nothing])}
+    if name.startswith("bitmap_without_nulls_"):
+        frame, made, builds = directed("bitmap_without_nulls_join_probe", n, seed)
+        made, other = made[:2], builds[2]
+        tail = {"window": {"kind": "window", "partition_by": [2], "order_by": [(3, 0)], "exprs": [("cum_sum", 3), ("cum_max", 2), ("lag", 3, 1), ("rank", 0)]},
+                "topk": {"kind": "topk", "keys": [(3, 1), (2, 0)], "k": ["of", 1, 8], "via": "frame", "select": True},
+                "group_keys": {"kind": "group_keys", "keys": [2, 3], "specs": [("sum", 3), ("min", 2), ("count_rows", None)]},
+                "outer_join_probe": {"kind": "outer_join", "how": "outer", "probe_key": 2, "build_key": 2, "chunked": True, "side": "probe"},
+                "outer_join_build": {"kind": "outer_join", "how": "full", "probe_key": 2, "build_key": 2, "chunked": False, "side": "build"}}[name[len("bitmap_without_nulls_"):]]
+        return frame, made + [tail], ({2: other} if tail["kind"] == "outer_join" else {})
+    if name == "null_columns_ride_along_ops":
+        # Null-dtype columns as window partition key and order key, LAG source, CUM_COUNT argument, top-k key, group_keys key and
+        # FULL_OUTER payload (column 1 on the probe side, the second frame's column 1)
+        frame = [("i64", rng.integers(0, 4, n, dtype=np.int64), rng.random(n) > 0.1), ("null", np.zeros(n, np.int64), None),
+                 ("f64", dyadic_cells(seed, n, SCALE)[1], rng.random(n) > 0.2)]
+        build = [("i64", np.array([3, 1, 1, 8], np.int64), None), ("null", np.zeros(4, np.int64), None), ("bool", np.array([1, 0, 1, 1], bool), None)]
+        steps = [{"kind": "window", "partition_by": [1, 0], "order_by": [(1, 3), (2, 0)], "exprs": [("lag", 1, 1), ("cum_count", 1), ("row_number", 1)]},
+                 dict(FULL),
+                 {"kind": "topk", "keys": [(1, 1), (5, 0)], "k": ["of", 3, 4], "via": "frame", "select": True},
+                 {"kind": "group_keys", "keys": [1, 0, 3], "specs": [("count", 7), ("count_rows", None), ("max", 5)]}]
+        return frame, steps, {1: (build, [])}
+    raise KeyError(name)
+
+
+DIRECTED_OPS = ([f"full_outer_then_{c}" for c in ("window", "group_keys", "sort", "group", "arith", "join")]
+                + [f"full_outer_then_topk_{f}_{side}" for f in range(4) for side in ("lo", "hi")]
+                + [f"window_minmax_bitmap_then_{c}_{o}" for c in ("sort", "topk", "group_keys", "filter", "outer_join") for o in SLICE_AT]
+                + [f"window_minmax_plain_then_{c}_1" for c in ("sort", "topk", "group_keys", "filter", "outer_join")]
+                + [f"topk_indices_as_index_{f}" for f in range(4)]
+                + [f"empty_then_{c}" for c in ("window", "topk", "group_keys") + HOWS]
+                + [f"empty_build_side_{c}" for c in HOWS] + ["empty_probe_side_full"]
+                + [f"bitmap_without_nulls_{c}" for c in ("window", "topk", "group_keys", "outer_join_probe", "outer_join_build")]
+                + ["null_columns_ride_along_ops"])
+
+
+def directed_ops_case(name, n, seed=5):
+    """directed_ops() in the shape of case_ops(): sources are plain uploads."""
+    frame, steps, builds = directed_ops(name, n, seed)
+    return {"seed": name, "n": n, "source": upload_of(frame), "steps": steps,
+            "builds": {k: {"source": upload_of(b), "steps": s} for k, (b, s) in builds.items()}}
+
+
+def assert_point(name, case):
+    """Where data could lose the point of a directed pipeline: assert that it is there (on the model alone)."""
+    pm = pipeline_model
+    model, builds = pm.run_case(case)
+    pads = pm.padded_run(case, model, builds)
+    steps = case["steps"]
+    if name.startswith("full_outer_then_"):
+        frame = model[1][0]
+        for j in (0, 5, 6):  # both keys and the build payload hold padded nulls, and the probe key a genuine 0 beside them
+            assert pads[1][j].any(), f"{name}: FULL_OUTER padded nothing into column {j}"
+        assert (frame[0][1][pm.valid_of(frame[0])] == 0).any() and pm.null_count(frame[0]) > int(pads[1][0].sum()), name
+        if "_topk_" in name and case["n"] >= 64:
+            k, nulls = pm.topk_k(steps[1], pm.rows(frame)), pm.null_count(frame[6])
+            assert (k < nulls) == name.endswith("lo"), f"{name}: k {k} against {nulls} nulls"
+            assert pm.topk_select(steps[1], frame, 1, const("kTopKRefineDivisor")).passes >= 1, f"{name}: the select does not run"
+    if name.startswith("window_minmax_"):
+        frame, meta = model[2]  # what the consumer reads: the sliced window outputs
+        for j in (3, 4):
+            nulls = pm.null_count(frame[j])
+            assert meta[j]["made"] and meta[j]["offset"] == min(steps[1]["offset"], pm.rows(model[1][0]) // 2) and meta[j]["bitmap"] == ("_bitmap_" in name)
+            assert (nulls > 0) == ("_bitmap_" in name), f"{name}: {nulls} nulls in column {j}"
+    if name.startswith("topk_indices_as_index_"):
+        q = model[1][0][3]
+        assert pm.null_count(q) > 0 and (q[1][pm.valid_of(q)] == 0).any(), "the case lost its point: no null quotient beside a genuine 0"
+        if case["n"] >= 64:
+            assert pm.topk_select(steps[1], model[1][0], 1, const("kTopKRefineDivisor")).passes >= 1, f"{name}: the select does not run"
+    if name.startswith("empty_then_") or name == "empty_probe_side_full":
+        assert pm.rows(model[1][0]) == 0
+        assert pm.rows(model[-1][0]) == (3 if name.endswith("full") else 0)
+    if name.startswith("empty_build_side_"):
+        how = name.split("_")[-1]
+        assert pm.rows(builds[0][-1][0]) == 0
+        assert pm.rows(model[-1][0]) == (0 if how == "semi" else case["n"])
+        if how == "anti":
+            assert pm.frame_diff(model[-1][0], model[0][0]) is None
+        if how in ("outer", "full"):
+            assert pm.dtypes(model[-1][0])[3:] == (["i64"] if how == "full" else []) + ["str", "null", "bool", "f64"]
+            assert all(pm.null_count(c) == case["n"] for c in model[-1][0][3:])
+    if name.startswith("bitmap_without_nulls_"):
+        assert_consumer_met_bitmap_without_nulls(case)
+    if name == "null_columns_ride_along_ops":
+        assert [model[k][0][j][0] for k, j in ((0, 1), (1, 3), (2, 1), (2, 7))] == ["null"] * 4

@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 
 import pipeline_model as pm
+from helpers import const
 from rivulus_amd import capi
 from rivulus_amd.capi import DeviceColumn, Predicate, Term, pack_bits
 
@@ -41,17 +42,24 @@ def compare(ctx, col, op, literal):
     return DeviceColumn(ctx, out)
 
 
-def join_chunked(ctx, build, bk, probe, pk, n, chunk):
-    """rv_hash_join_chunked over the whole probe frame of n rows: (output columns, rows)."""
+JOIN_KIND = {"outer": capi.RV_JOIN_PROBE_OUTER, "full": capi.RV_JOIN_FULL_OUTER, "semi": capi.RV_JOIN_PROBE_SEMI, "anti": capi.RV_JOIN_PROBE_ANTI}
+
+
+def join_chunked(ctx, build, bk, probe, pk, n, chunk, kind=None):
+    """rv_hash_join_chunked (kind: rv_hash_join_chunked_kind) over the whole probe frame of n rows: (output columns, rows)."""
     k = (n + chunk - 1) // chunk
-    nout = len(probe) + len(build) - 1
+    nout = capi.join_output_columns(kind or capi.RV_JOIN_INNER, len(probe), len(build))
     table = ctx.join_build(build[bk])
     out = (C.c_void_p * max(1, nout))()
     per_batch = np.zeros(max(1, k), np.uint64)
     total, taken = C.c_uint64(), C.c_uint64()
+    head = (ctx.handle, table.handle, capi._handles(build), len(build), bk, capi._handles(probe), len(probe), pk)
+    tail = (chunk, 0, out, per_batch.ctypes.data_as(capi._U64P), k, None, C.byref(total), C.byref(taken))
     try:
-        capi._check(capi.load().rv_hash_join_chunked(ctx.handle, table.handle, capi._handles(build), len(build), bk, capi._handles(probe), len(probe), pk,
-                                                     chunk, 0, out, per_batch.ctypes.data_as(capi._U64P), k, None, C.byref(total), C.byref(taken)))
+        if kind is None:
+            capi._check(capi.load().rv_hash_join_chunked(*head, *tail))
+        else:
+            capi._check(capi.load().rv_hash_join_chunked_kind(*head, kind, *tail))
     finally:
         table.free()
     assert taken.value == k and int(per_batch[:k].sum()) == total.value
@@ -77,9 +85,73 @@ def _mask(ctx, frame, step):
     return ev(pm.tup(expr) if expr is not None else ("and", *range(len(masks))) if len(masks) > 1 else 0)
 
 
-def run_step(ctx, step, frame, n, dtypes, build=None):
-    """(output columns, rows) of one step over the device columns `frame` of n rows and model dtypes `dtypes`."""
+def _top_k(ctx, step, frame, n, model_frame):
+    """rv_top_k, or rv_top_k_indices over the first key and take_device; then the context's account of the call against
+    topk_model.select over the model's key column (tests/test_topk_gpu.py, assert_path): the proof that the select ran, or did not."""
+    k = pm.topk_k(step, n)
+    keys = pm.topk_keys(step)
+    if step.get("select"):
+        ctx.set_option("top_k_select_from_rows", 1)
+    try:
+        want = None if model_frame is None else pm.topk_select(step, model_frame, ctx.get_option("top_k_select_from_rows") or const("kTopKSelectFromRows"),
+                                                               ctx.get_option("top_k_refine_divisor") or const("kTopKRefineDivisor"))
+        if step.get("via") == "indices":
+            outs = ctx.take_device(frame, ctx.top_k_indices(frame[keys[0][0]], k, flags=keys[0][1]))
+        else:
+            outs = ctx.top_k(frame, keys, k)
+        got = (ctx.get_option("top_k_last_passes"), ctx.get_option("top_k_last_candidates"))
+    finally:
+        if step.get("select"):
+            ctx.set_option("top_k_select_from_rows", 0)
+    assert want is None or got == (want.passes, want.count), f"top-k over {n} rows, k {k}, keys {keys}: (passes, candidates) {got}, the model's select says {(want.passes, want.count)}"
+    return outs, min(k, n)
+
+
+def run_step(ctx, step, frame, n, dtypes, build=None, model_frame=None):
+    """(output columns, rows) of one step over the device columns `frame` of n rows and model dtypes `dtypes`.  model_frame: the model's
+    input frame of the step, which a top-k step's path check reads (None: the check is left out)."""
     kind = step["kind"]
+    if kind == "window":
+        cols, part, dicts = list(frame), [], []
+        try:  # (the context is shared: a call that raises leaves no dictionary behind)
+            for c in step["partition_by"]:
+                if dtypes[c] == "str":
+                    sdict, ids = ctx.string_dict_build(frame[c])
+                    dicts.append(sdict)
+                    cols.append(ids)
+                    c = len(cols) - 1
+                part.append(c)
+            outs = ctx.window(cols, part, [(int(c), int(f)) for c, f in step["order_by"]], [tuple(e) for e in step["exprs"]])
+        finally:
+            for sdict in dicts:
+                sdict.free()
+        return list(frame) + outs, n
+    if kind == "topk":
+        return _top_k(ctx, step, frame, n, model_frame)
+    if kind == "outer_join":
+        cols, m = build
+        probe, pk, bcols, bk = pm.join_sides(frame, step, cols)
+        if step.get("chunked"):
+            return join_chunked(ctx, bcols, bk, probe, pk, m if step.get("side") == "build" else n, pm.JOIN_CHUNK, JOIN_KIND[step["how"]])
+        return ctx.hash_join(bcols, bk, probe, pk, kind=JOIN_KIND[step["how"]])
+    if kind == "group_keys":
+        keys, dicts = [], []
+        try:
+            for c in step["keys"]:
+                if dtypes[c] == "str":
+                    sdict, ids = ctx.string_dict_build(frame[c])
+                    dicts.append(sdict)
+                    keys.append(ids)
+                else:
+                    keys.append(frame[c])
+            outs, first, groups = ctx.hash_aggregate_keys(keys, frame, [(op, c) for op, c in step["specs"]])
+        finally:
+            for sdict in dicts:
+                sdict.free()
+        for j, c in enumerate(step["keys"]):
+            if dtypes[c] == "str":
+                outs[j] = ctx.take_device([frame[c]], first)[0]
+        return outs, groups
     if kind == "filter":
         outs, rows, sel = ctx.filter_project(frame, pm.predicate_of(step), list(range(len(frame))), step.get("via") == "selection")
         if sel is not None:
@@ -101,8 +173,10 @@ def run_step(ctx, step, frame, n, dtypes, build=None):
             outs, _, groups = ctx.hash_aggregate(key, frame, specs, want_first_row=False)
             return outs, groups
         sdict, ids = ctx.string_dict_build(key)
-        outs, first, groups = ctx.hash_aggregate(ids, frame, specs)
-        sdict.free()
+        try:
+            outs, first, groups = ctx.hash_aggregate(ids, frame, specs)
+        finally:
+            sdict.free()
         return ctx.take_device([key], first) + outs[1:], groups
     if kind == "sort":
         keys = [(int(c), int(f)) for c, f in step["keys"]]
@@ -163,7 +237,7 @@ def run_pipeline(ctx, source, steps, builds, model, build_models, look, what, tm
             closers.append(closer)
             inter = build_models[k]
             for s, bstep in enumerate(b["steps"]):
-                cols, m = run_step(ctx, bstep, cols, m, pm.dtypes(inter[s][0]))
+                cols, m = run_step(ctx, bstep, cols, m, pm.dtypes(inter[s][0]), None, inter[s][0])
                 if look:
                     inspect(cols, inter[s + 1][0], inter[s + 1][1], f"{what} join step {k}, build side step {s} ({bstep['kind']})")
             built[k] = (cols, m)
@@ -174,7 +248,7 @@ def run_pipeline(ctx, source, steps, builds, model, build_models, look, what, tm
         for k, step in enumerate(steps):
             where = f"{what} step {k} ({step['kind']}{' ' + step['how'] if 'how' in step else ''})"
             try:
-                frame, n = run_step(ctx, step, frame, n, pm.dtypes(model[k][0]), built.get(k))
+                frame, n = run_step(ctx, step, frame, n, pm.dtypes(model[k][0]), built.get(k), model[k][0])
             except capi.RvError as e:
                 raise AssertionError(f"{where}: {e}") from e
             assert n == pm.rows(model[k + 1][0]), f"{where}: {n} rows != {pm.rows(model[k + 1][0])}"

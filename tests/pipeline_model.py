@@ -19,6 +19,13 @@ A step is a dict (JSON can hold it; trees may arrive as lists):
   {"kind": "reshape", "how": "concat", "eighths": e}                                            rows [h, n) then [0, h), h = n * e // 8
   {"kind": "reshape", "how": "take_first", "col": c}                                            take by the group first rows of column c
   {"kind": "reshape", "how": "take_sorted", "col": c, "flags": f}                               take by the sort indices of column c
+and, adapters over window_model, topk_model / sort_model, outer_join_model and group_keys_model (KINDS_ALL; KINDS is the older set):
+  {"kind": "window",  "partition_by": [c], "order_by": [(c, flags)], "exprs": [(op, c[, k])]}   the results are appended, as arith's is
+  {"kind": "topk",    "keys": [(c, flags)], "k": ["abs", K] | ["of", num, den[, add]], "via": "frame" | "indices", "select": bool}
+                      k = K, or max(0, rows * num // den + add) of the rows the step receives; "indices": rv_top_k_indices over the first
+                      key alone, then take_device; "select": option top_k_select_from_rows = 1 around the call
+  {"kind": "outer_join", "how": "outer" | "full" | "semi" | "anti", and the fields of "join"}   rv_hash_join_kind's columns
+  {"kind": "group_keys", "keys": [c1, c2[, c3]], "specs": [(op, col | None)]}                   -> [key cells of every key, aggregate 0, ...]
 
 Beside every frame runs its `meta`, one dict per column: what include/rivulus_gpu.h lets a caller expect of the device column --
   bitmap  a validity bitmap is attached (None: the header states no rule)
@@ -30,14 +37,22 @@ import numpy as np
 
 import arith_model
 import group_agg_model
+import group_keys_model
 import join_model
+import outer_join_model
 import sort_model
+import topk_model
+import window_model
 from helpers import host_survivors
 from rivulus_amd.capi import RV_BOOLEAN, RV_FLOAT64, RV_INT64, RV_NULL, RV_STRING, Column, Predicate, Term
 
 RV = {"i64": RV_INT64, "f64": RV_FLOAT64, "bool": RV_BOOLEAN, "str": RV_STRING, "null": RV_NULL}
 DTYPE_OF_RV = {v: k for k, v in RV.items()}
 KINDS = ("filter", "mask", "arith", "join", "group", "sort", "reshape")
+NEW_KINDS = ("window", "topk", "outer_join", "group_keys")
+KINDS_ALL = KINDS + NEW_KINDS
+JOINS = ("join", "outer_join")  # the kinds that read a second frame
+HOW = {"outer": outer_join_model.PROBE_OUTER, "full": outer_join_model.FULL_OUTER, "semi": outer_join_model.PROBE_SEMI, "anti": outer_join_model.PROBE_ANTI}
 CANONICAL_NAN = np.uint64(group_agg_model.CANONICAL_NAN)
 JOIN_CHUNK = 1024
 
@@ -299,8 +314,123 @@ def step_reshape(frame, step):
     return take_frame(frame, reshape_indices(frame, step))
 
 
+def window_args(frame, step):
+    """(columns, partition_by) as window_model.window takes them: a String partition key stands as its dictionary ids in an extra
+    column behind the frame (the device runner appends the same column), every other column as it is."""
+    cols = [(c[0], c[1], c[2]) for c in frame]
+    part = []
+    for c in step["partition_by"]:
+        if frame[c][0] == "str":
+            cols.append(string_ids(frame[c]))
+            c = len(cols) - 1
+        part.append(c)
+    return cols, part
+
+
+def model_column(dtype, values, valid):
+    """A result column of window_model (Float64 as bit patterns, None for a Null column) as a frame column."""
+    n = len(valid)
+    if dtype == "null":
+        return "null", np.zeros(n, np.int64), None
+    if dtype == "f64":
+        values = np.ascontiguousarray(values, np.uint64).view(np.float64)
+    return dtype, values, (None if valid.all() else np.asarray(valid, bool))
+
+
+def step_window(frame, step):
+    cols, part = window_args(frame, step)
+    out = window_model.window(cols, part, [(int(c), int(f)) for c, f in step["order_by"]], [tuple(e) for e in step["exprs"]], exact_float=True)
+    return list(frame) + [model_column(*c) for c in out]
+
+
+def topk_k(step, n):
+    k = step["k"]
+    if k[0] == "abs":
+        return int(k[1])
+    return max(0, n * k[1] // k[2] + (k[3] if len(k) > 3 else 0))
+
+
+def topk_keys(step):
+    keys = [(int(c), int(f)) for c, f in step["keys"]]
+    return keys[:1] if step.get("via") == "indices" else keys
+
+
+def topk_select(step, frame, select_from_rows, divisor):
+    """topk_model.Select of the step's call: which path it takes over the first key, its passes and candidates."""
+    c, flags = topk_keys(step)[0]
+    return topk_model.select(sort_columns(frame)[c], flags, topk_k(step, rows(frame)), 1 if step.get("select") else select_from_rows, divisor)
+
+
+def step_topk(frame, step):
+    return take_frame(frame, topk_model.top_k_frame(sort_columns(frame), topk_keys(step), topk_k(step, rows(frame))))
+
+
+def take_col_nullable(col, idx):
+    """take_col with -1 for "no row": a null cell (rv_take_device_nullable)."""
+    idx = np.asarray(idx, np.int64)
+    there = idx >= 0
+    if col[0] == "null":
+        return "null", np.zeros(len(idx), np.int64), None
+    if there.all():
+        return take_col(col, idx)
+    if len(col[1]) == 0:
+        return column_of(col[0], [None] * len(idx))
+    dtype, values, _ = take_col(col, np.where(there, idx, 0))
+    return dtype, values, valid_of(col)[np.where(there, idx, 0)] & there
+
+
+def outer_join_indices(probe, pk, build, bk, how):
+    """outer_join_model.join_pairs as two index arrays, -1 for "no partner" """
+    pairs = outer_join_model.join_pairs(HOW[how], RV[build[bk][0]], cells(build[bk]), RV[probe[pk][0]], cells(probe[pk]))
+    pi = np.array([-1 if p is None else p for p, _ in pairs], np.int64)
+    bi = np.array([-1 if b is None else b for _, b in pairs], np.int64)
+    return pi, bi
+
+
+def step_outer_join(frame, step, other):
+    probe, pk, build, bk = join_sides(frame, step, other)
+    how = step["how"]
+    pi, bi = outer_join_indices(probe, pk, build, bk, how)
+    out = [take_col_nullable(c, pi) for c in probe]
+    if how in ("semi", "anti"):
+        return out
+    return out + [take_col_nullable(c, bi) for j, c in enumerate(build) if j != bk or how == "full"]
+
+
+def group_keys_result(frame, step):
+    """group_keys_model.aggregate's dict for the step"""
+    n = rows(frame)
+    keys = []
+    for c in step["keys"]:
+        col = string_ids(frame[c]) if frame[c][0] == "str" else frame[c]
+        keys.append(("null", None, n) if col[0] == "null" else (col[0], col[1], col[2]))
+    columns = [(c[0] if c[0] in ("i64", "f64") else "other", c[1] if c[0] in ("i64", "f64") else None, valid_of(c)) for c in frame]
+    return group_keys_model.aggregate(keys, columns, [(op, c) for op, c in step["specs"]], exact_float=True)
+
+
+def agg_columns(aggs):
+    out = []
+    for dtype, bits, valid, _ in aggs:
+        raw = np.array(bits, np.uint64) if len(bits) else np.zeros(0, np.uint64)
+        out.append((dtype, raw.view(np.int64 if dtype == "i64" else np.float64), None if valid is None else np.array(valid, bool)))
+    return out
+
+
+def step_group_keys(frame, step):
+    res = group_keys_result(frame, step)
+    return [take_col(frame[c], res["first_row"]) for c in step["keys"]] + agg_columns(res["aggs"])
+
+
 def apply(step, frame, build=None):
     kind = step["kind"]
+    if kind == "window":
+        return step_window(frame, step)
+    if kind == "topk":
+        return step_topk(frame, step)
+    if kind == "outer_join":
+        return step_outer_join(frame, step, build)
+    if kind == "group_keys":
+        return step_group_keys(frame, step)
     if kind in ("filter", "mask"):
         return step_filter(frame, step)
     if kind == "arith":
@@ -355,9 +485,12 @@ def meta_after(step, frame_in, meta_in, frame_out):
                 out.append({"bitmap": m["bitmap"], "known": None if m["bitmap"] is None else not m["bitmap"],
                             "offset": None if m["offset"] is None else m["offset"] + off, "made": m["made"]})
         return out
-    if kind == "group":
-        out = [gathered_meta(frame_out[0])]
-        for (op, _), col in zip(step["specs"], frame_out[1:]):
+    if kind == "window":  # rv_window, "Outputs": a bitmap iff some output cell is null, null_count known; passed-on columns as they were
+        return list(meta_in) + [gathered_meta(c) for c in frame_out[len(meta_in):]]
+    if kind in ("group", "group_keys"):
+        nkeys = len(step["keys"]) if kind == "group_keys" else 1
+        out = [gathered_meta(c) for c in frame_out[:nkeys]]
+        for (op, _), col in zip(step["specs"], frame_out[nkeys:]):
             out.append({"bitmap": op in ("min", "max") and null_count(col) > 0, "known": True, "offset": 0, "made": True})  # attached iff some cell is null
         return out
     return [gathered_meta(c) for c in frame_out]
@@ -370,7 +503,65 @@ def touched(step, frame):
         return sorted(arith_model.columns_read(tup(step["tree"])))
     if kind == "group":
         return sorted({step["key"]} | {c for _, c in step["specs"] if c is not None})
+    if kind == "group_keys":
+        return sorted(set(step["keys"]) | {c for _, c in step["specs"] if c is not None})
+    if kind == "window":  # (the numbering ops ignore their column)
+        read = {e[1] for e in step["exprs"] if e[0] not in ("row_number", "rank", "dense_rank")}
+        return sorted(set(step["partition_by"]) | {c for c, _ in step["order_by"]} | read)
     return list(range(len(frame)))
+
+
+def padded_after(step, frame, pads, build=None, build_pads=None):
+    """Per output column the cells that are null because an "outer" / "full" join found no partner for the row, carried through every
+    step that moves cells (a computed column starts without any).  pads: one bool array per input column; the index lists are the ones
+    the step functions above use."""
+    kind = step["kind"]
+    n = rows(frame)
+    none = lambda m: np.zeros(m, bool)
+    if kind in ("arith", "window"):
+        return list(pads) + [none(n) for _ in range(len(step["exprs"]) if kind == "window" else 1)]
+    if kind == "group":
+        first = group_result(frame, step)["first_row"]
+        return [pads[step["key"]][first]] + [none(len(first)) for _ in step["specs"]]
+    if kind == "group_keys":
+        first = group_keys_result(frame, step)["first_row"]
+        return [pads[c][first] for c in step["keys"]] + [none(len(first)) for _ in step["specs"]]
+    if kind in JOINS:
+        other = build_pads if build_pads is not None else [none(rows(build)) for _ in build]
+        probe, pk, bcols, bk = join_sides(frame, step, build)
+        ppads, bpads = (other, pads) if step.get("side") == "build" else (pads, other)
+        how = step.get("how", "inner")
+        pi, bi = join_pairs(probe, pk, bcols, bk) if kind == "join" else outer_join_indices(probe, pk, bcols, bk, how)
+        pad = how in ("outer", "full")
+        gather = lambda p, idx: np.where(idx >= 0, p[np.maximum(idx, 0)] if len(p) else False, pad)
+        out = [gather(p, pi) for p in ppads]
+        if how in ("semi", "anti"):
+            return out
+        return out + [gather(p, bi) for j, p in enumerate(bpads) if j != bk or how == "full"]
+    if kind in ("filter", "mask"):
+        idx = np.flatnonzero(survivors(frame, step))
+    elif kind == "sort":
+        idx = sort_model.sort_frame(sort_columns(frame), [(int(c), int(f)) for c, f in step["keys"]])
+    elif kind == "topk":
+        idx = topk_model.top_k_frame(sort_columns(frame), topk_keys(step), topk_k(step, n))
+    else:
+        idx = reshape_indices(frame, step)
+    return [p[idx] for p in pads]
+
+
+def padded_run(case, inter, builds):
+    """[pads of every intermediate] of a case whose model intermediates are (inter, builds); the sources hold no padded cell."""
+    def walk(steps, frames, seconds):
+        pads = [np.zeros(rows(frames[0][0]), bool) for _ in frames[0][0]]
+        out = [pads]
+        for k, step in enumerate(steps):
+            b = seconds.get(k) if step["kind"] in JOINS else None
+            pads = padded_after(step, frames[k][0], pads, None if b is None else b[0], None if b is None else b[1])
+            assert [len(p) for p in pads] == [rows(frames[k + 1][0])] * len(frames[k + 1][0])
+            out.append(pads)
+        return out
+    seconds = {k: (builds[k][-1][0], walk(case["builds"][k]["steps"], builds[k], {})[-1]) for k in builds}
+    return walk(case["steps"], inter, seconds)
 
 
 def column_states(col, meta):
@@ -394,9 +585,9 @@ def run(sources, steps, builds=None):
     frame, meta = sources
     out = [(frame, meta)]
     for k, step in enumerate(steps):
-        build = builds[k][-1][0] if step["kind"] == "join" else None
+        build = builds[k][-1][0] if step["kind"] in JOINS else None
         nxt = apply(step, frame, build)
-        if step["kind"] == "join":
+        if step["kind"] in JOINS:
             meta = [gathered_meta(c) for c in nxt]
         else:
             meta = meta_after(step, frame, meta, nxt)

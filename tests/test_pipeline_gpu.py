@@ -198,12 +198,18 @@ def test_looking_at_a_column_changes_nothing(gpu_ctx, offset):
                           ([{"kind": "group", "key": 2, "specs": [("count_rows", None), ("count", 0)]}], {}),
                           ([{"kind": "sort", "keys": [(0, 3), (1, 0)], "via": "chain"}], {}),
                           ([{"kind": "arith", "tree": ("/", ("col", 1), ("col", 0))}, {"kind": "mask", "terms": [(3, "<", 0.0)], "expr": ("not", 0)}], {}),
-                          ([{"kind": "join", "probe_key": 0, "build_key": 0, "chunked": True}], {0: build})):
+                          ([{"kind": "join", "probe_key": 0, "build_key": 0, "chunked": True}], {0: build}),
+                          ([{"kind": "window", "partition_by": [0, 2], "order_by": [(1, 2)], "exprs": [("cum_count", 2), ("cum_sum", 1), ("cum_max", 0), ("lag", 2, 1)]}], {}),
+                          ([{"kind": "topk", "keys": [(1, 0), (0, 3)], "k": ["of", 1, 8], "via": "frame", "select": True}], {}),
+                          ([{"kind": "topk", "keys": [(0, 2)], "k": ["abs", 7], "via": "indices", "select": True}], {}),
+                          ([{"kind": "outer_join", "how": "full", "probe_key": 0, "build_key": 0, "chunked": False, "side": "probe"}], {0: build}),
+                          ([{"kind": "outer_join", "how": "anti", "probe_key": 0, "build_key": 0, "chunked": True, "side": "probe"}], {0: build}),
+                          ([{"kind": "group_keys", "keys": [0, 2, 1], "specs": [("count_rows", None), ("sum", 1), ("min", 0), ("count", 2)]}], {})):
         want = frame
         got, rows = d, n
         for k, step in enumerate(steps):
             b = builds.get(k)
-            got, rows = pd.run_step(gpu_ctx, step, got, rows, pm.dtypes(want), None if b is None else ([gpu_ctx.upload(pd.to_host(c)) for c in b], pm.rows(b)))
+            got, rows = pd.run_step(gpu_ctx, step, got, rows, pm.dtypes(want), None if b is None else ([gpu_ctx.upload(pd.to_host(c)) for c in b], pm.rows(b)), want)
             want = pm.apply(step, want, b)
         diff = pm.frame_diff(pd.download(got), want)
         assert diff is None, f"{[s['kind'] for s in steps]} over inspected columns: {diff}"
