@@ -963,6 +963,73 @@ rv_status rv_window(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, 
                     const uint32_t *order_cols, const uint32_t *order_flags, uint32_t norder, const rv_window_spec *specs,
                     uint32_t nspecs, rv_dcolumn **out);
 
+/* ---- window frames (K12a) ---------------------------------------------------- */
+/* The general form of rv_window: the same partition, order, peers, sequence, output rules (row order; a bitmap iff some cell is null; a
+ * known null_count; zeros under nulls), limits and error texts, under its own name.  Ops 0 .. 8 are rv_window_op's with the same values and
+ * meaning, ignore preceding / following and give what rv_window gives, so one call computes old and new expressions over ONE sequence.
+ * The reference has no window expression; this comment is the normative text, tests/window_frame_model.py the executable one; DESIGN.md
+ * section 4 K12a argues it.
+ *
+ * Frame.  For a row at the 1-based position pos of a partition of len rows, the positions [max(1, pos - preceding), min(len, pos +
+ * following)] of that partition; EMPTY when that interval is empty.  Offsets are signed: preceding = 3, following = -1 is "the three rows
+ * before this one", preceding = -1, following = RV_FRAME_UNBOUNDED is "everything after this row".  RV_FRAME_UNBOUNDED on either side
+ * means the partition's edge.  A finite offset has a magnitude of at most 2^62, and preceding + following >= 0 when both are finite;
+ * anything else is RV_ERR_INVALID_ARG naming the expression.  (Offsets are clamped before anything is added: no signed overflow.)
+ *
+ * RV_WINF_COUNT: the non-null cells of `col` in the frame.  Any dtype.  Int64, no bitmap, 0 for an empty frame.
+ *
+ * RV_WINF_SUM / MIN / MAX take an RV_INT64 or RV_FLOAT64 column (any other dtype: RV_ERR_TYPE_MISMATCH); every numeric rule is
+ * rv_hash_aggregate's applied to the frame, as at rv_window: Int64 SUM wraps and is exact; SUM over a frame without a non-null cell (an
+ * empty one included) is 0 / +0.0, no bitmap; MIN / MAX over such a frame is null; Float64 MIN / MAX go through the same order map (-0.0
+ * below +0.0; one NaN in the frame makes the result NaN, payload unspecified); nothing under a null cell reaches a result.
+ *
+ * RV_WINF_AVG: Float64; null when the frame has no non-null cell, otherwise RV_WINF_SUM's result divided by RV_WINF_COUNT's with one IEEE
+ * division -- for an Int64 column the wrapped Int64 sum is converted to double first.
+ *
+ * RV_WINF_FIRST_VALUE / LAST_VALUE: the cell of `col` at the frame's first / last position; null when the frame is empty or that cell is
+ * null (there is no IGNORE NULLS).  Any dtype rv_take_device_nullable gathers, String and Boolean included: the route of LAG / LEAD, a
+ * nullable index list in row order and then the gather.
+ *
+ * RV_WINF_NTILE(n = offset): with q = len / n and r = len % n the partition's first r buckets hold q + 1 rows and the rest q, in window
+ * order; the result is the row's 1-based bucket (n > len: the bucket is pos).  Int64, no bitmap.  n == 0: RV_ERR_INVALID_ARG.  `col`
+ * is ignored (but must be a column index), as are preceding / following.
+ *
+ * Float64 SUM uses no floating-point atomic.  A frame of the finite width w = preceding + following + 1 cuts every partition into blocks
+ * of w positions anchored at the partition's head (with an unbounded side, or w >= len, the block is the partition).  prefix[j] is the
+ * sum of j's block up to j, bracketed exactly as rv_window's CUM_SUM with the block heads in the place of the partition heads (T, L, W, C
+ * above); suffix[j], the sum of j's block from j on, is the mirror image: the same construction over the positions counted from the
+ * sequence's end, so a thread folds its 8 positions from the highest down and a (+) b stands for a AFTER b.  A frame [lo, hi] within one
+ * block is prefix[hi] (lo starts the block) or suffix[lo] (hi ends it, or the partition); across two blocks it is the one final addition
+ * suffix[lo] + prefix[hi].  The result depends only on the row's position in the sequence, the partition heads, the frame and this fixed
+ * geometry: the same call over the same buffers gives the same bits run to run.  It is bit exact whenever every partial sum is
+ * representable, and otherwise |got - exact| <= gamma_{m-1} x sum|x| over the frame (m its non-null cells): every result is a summation
+ * tree over exactly the frame's cells -- no difference of prefix sums -- and additions of the +0.0 that stands for a null are exact.  A
+ * zero of either sign enters as +0.0, so no sum is -0.0.  MIN / MAX / COUNT / Int64 SUM are made the same way and are exact.
+ *
+ * Errors: rv_window's, and those named above; an op above RV_WINF_NTILE is unknown.
+ *
+ * The passes.  (1) rv_window's sequence, shared by all expressions.  (2) When a frame op is asked for: head_pos / tail_pos of every
+ * position (two scans over the partition-head bitmap; npart == 0: one partition, nothing to scan), and per distinct value column one
+ * gather into sequence order (skipped in place).
+ * (3) Per distinct finite width the block-head bitmap; per (column, SUM-COUNT-AVG | MIN | MAX, width) the block prefix and / or suffix
+ * scan, three launches each, value and non-null count per position (an unbounded preceding side needs the prefix only, an unbounded
+ * following side the suffix only).  (4) window_frame, per expression: one lane per position picks the case, combines, finishes and stores
+ * at out[perm[j]].  FIRST / LAST / NTILE need (2)'s geometry only.  No kernel waits for another workgroup; the cost does not depend on the
+ * frame's width.  rv_ctx_last_kernel names "window_frame" when an op from RV_WINF_COUNT on ran, and what rv_window names otherwise;
+ * rv_ctx_kernel_stats (option "profile_kernels") times these passes along with rv_window's. */
+#define RV_FRAME_UNBOUNDED INT64_MAX
+typedef enum rv_window_frame_op { RV_WINF_COUNT = 9, RV_WINF_SUM = 10, RV_WINF_MIN = 11, RV_WINF_MAX = 12, RV_WINF_AVG = 13, RV_WINF_FIRST_VALUE = 14, RV_WINF_LAST_VALUE = 15, RV_WINF_NTILE = 16 } rv_window_frame_op;
+typedef struct rv_window_frame_spec {
+    uint32_t op;       /* rv_window_op (0 .. 8) or rv_window_frame_op */
+    uint32_t col;      /* index into cols */
+    uint64_t offset;   /* RV_WIN_LAG / RV_WIN_LEAD: k; RV_WINF_NTILE: the number of buckets */
+    int64_t preceding; /* frame ops only */
+    int64_t following;
+} rv_window_frame_spec;
+rv_status rv_window_frames(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, const uint32_t *partition_cols, uint32_t npart,
+                           const uint32_t *order_cols, const uint32_t *order_flags, uint32_t norder, const rv_window_frame_spec *specs,
+                           uint32_t nspecs, rv_dcolumn **out);
+
 /* ---- multi-GPU (one process per GPU) --------------------------------------- */
 /* Row-range shard of rank `rank` of `world`: [*begin, *end), boundaries at multiples of
  * 64 rows so selection-bitmap words never straddle ranks. */

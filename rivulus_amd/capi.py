@@ -146,6 +146,17 @@ class RvWindowSpec(C.Structure):
     _fields_ = [("op", C.c_uint32), ("col", C.c_uint32), ("offset", C.c_uint64)]
 
 
+# rv_window_frame_op (rv_window_frames takes these and every rv_window_op)
+RV_FRAME_UNBOUNDED = (1 << 63) - 1
+(RV_WINF_COUNT, RV_WINF_SUM, RV_WINF_MIN, RV_WINF_MAX, RV_WINF_AVG, RV_WINF_FIRST_VALUE, RV_WINF_LAST_VALUE, RV_WINF_NTILE) = range(9, 17)
+WINDOW_FRAME_OPS = {"count": RV_WINF_COUNT, "sum": RV_WINF_SUM, "min": RV_WINF_MIN, "max": RV_WINF_MAX, "avg": RV_WINF_AVG,
+                    "first_value": RV_WINF_FIRST_VALUE, "last_value": RV_WINF_LAST_VALUE, "ntile": RV_WINF_NTILE}
+
+
+class RvWindowFrameSpec(C.Structure):
+    _fields_ = [("op", C.c_uint32), ("col", C.c_uint32), ("offset", C.c_uint64), ("preceding", C.c_int64), ("following", C.c_int64)]
+
+
 class RvSynthSpec(C.Structure):
     _fields_ = [("dtype", C.c_int), ("seed", C.c_uint64), ("first_row", C.c_uint64), ("length", C.c_uint64),
                 ("modulus", C.c_uint64), ("true_percent", C.c_uint32), ("with_validity", C.c_int32),
@@ -224,6 +235,8 @@ PROTOTYPES = {
     "rv_top_k": (C.c_int, [_P, _PP, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint64, _PP]),
     "rv_window": (C.c_int, [_P, _PP, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32,
                             C.POINTER(RvWindowSpec), C.c_uint32, _PP]),
+    "rv_window_frames": (C.c_int, [_P, _PP, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32,
+                                   C.POINTER(RvWindowFrameSpec), C.c_uint32, _PP]),
     "rv_hash_join_kind": (C.c_int, [_P, _PP, C.c_uint32, C.c_uint32, _PP, C.c_uint32, C.c_uint32, C.c_int, _PP, _U64P]),
     "rv_hash_join_chunked_kind": (C.c_int, [_P, _P, _PP, C.c_uint32, C.c_uint32, _PP, C.c_uint32, C.c_uint32, C.c_int, C.c_uint64, C.c_uint64,
                                             _PP, _U64P, C.c_uint64, C.POINTER(C.c_int64), _U64P, _U64P]),
@@ -972,6 +985,33 @@ class Context:
             specs[j].offset = int(e[2]) if len(e) > 2 else 0
         out = (C.c_void_p * max(1, len(exprs)))()
         _check(load().rv_window(self.handle, _handles(cols), len(cols), pc, len(partition_by), oc, of, len(order), specs, len(exprs), out))
+        return [DeviceColumn(self, C.c_void_p(out[j])) for j in range(len(exprs))]
+
+    def window_frames(self, cols: Sequence[DeviceColumn], partition_by: Sequence[int], order_by, exprs):
+        """rv_window_frames: as window(), and an expression may also be (op, column index, preceding, following) with op "count", "sum",
+        "min", "max", "avg", "first_value" or "last_value" (offsets signed, RV_FRAME_UNBOUNDED or None for the partition's edge), or
+        ("ntile", column index, buckets).  Ops may be rv_window_op / rv_window_frame_op numbers: (number, column index, offset,
+        preceding, following)."""
+        order = [(k, 0) if isinstance(k, int) else tuple(k) for k in order_by]
+        pc = (C.c_uint32 * max(1, len(partition_by)))(*partition_by)
+        oc = (C.c_uint32 * max(1, len(order)))(*[k[0] for k in order])
+        of = (C.c_uint32 * max(1, len(order)))(*[k[1] for k in order])
+        specs = (RvWindowFrameSpec * max(1, len(exprs)))()
+        edge = lambda v: RV_FRAME_UNBOUNDED if v is None else int(v)
+        for j, e in enumerate(exprs):
+            name = e[0] if isinstance(e[0], str) else None
+            specs[j].op = int(e[0]) if name is None else WINDOW_OPS[name] if name in WINDOW_OPS else WINDOW_FRAME_OPS[name]
+            specs[j].col = int(e[1])
+            specs[j].preceding, specs[j].following = RV_FRAME_UNBOUNDED, 0
+            if name is not None and name in WINDOW_FRAME_OPS and name != "ntile":
+                specs[j].offset = 0
+                specs[j].preceding, specs[j].following = edge(e[2]), edge(e[3])
+            else:
+                specs[j].offset = int(e[2]) if len(e) > 2 else 0
+                if len(e) > 4:
+                    specs[j].preceding, specs[j].following = edge(e[3]), edge(e[4])
+        out = (C.c_void_p * max(1, len(exprs)))()
+        _check(load().rv_window_frames(self.handle, _handles(cols), len(cols), pc, len(partition_by), oc, of, len(order), specs, len(exprs), out))
         return [DeviceColumn(self, C.c_void_p(out[j])) for j in range(len(exprs))]
 
     def hash_join(self, build_cols: Sequence[DeviceColumn], build_key: int, probe_cols: Sequence[DeviceColumn], probe_key: int,

@@ -1,5 +1,5 @@
 // Internal interface between the translation units of librivulus_gpu.so (core / fused_launch / narrow / strings / predicate / arrays /
-// query / take_concat / host_table / aggregate / join / string_dict / csv / group / group_agg / sort / topk / window .hip): the control block, the request / launch
+// query / take_concat / host_table / aggregate / join / string_dict / csv / group / group_agg / sort / topk / window / window_frame .hip): the control block, the request / launch
 // records that travel with a fused pass, and the functions the units call across each other.  Nothing here is part of the C ABI.
 #pragma once
 

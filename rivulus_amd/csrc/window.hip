@@ -3,8 +3,7 @@
 // rvl); the kernels, the shape of the passes and the bracketing of the scan are in window_kernel.hpp, the combine in window_combine.hpp.
 // The partition ids are rv_group_ids_keys' (group_agg.hip), the sequence is the sort's chain (sort.hip), LAG / LEAD gather through
 // take_nullable_on_device (take_nullable.hip): what is new here is the heads pass, the segmented scan and the shift.
-#include "launch.hpp"
-#include "window_kernel.hpp"
+#include "window_passes.hpp"
 
 using namespace rvh;
 using namespace rvl;
@@ -14,16 +13,6 @@ namespace {
 
 static_assert(rvk::kWinTileRows == rvk::kWinThreads * rvk::kWinItems, "a tile is one workgroup x kWinItems positions per thread");
 static_assert(sizeof(rvk::WinTriple) == 24, "tile aggregates and carries are 24-byte records");
-
-// the rows of a call in window order, and where its partitions and peer groups begin
-struct Sequence {
-    uint64_t n = 0;
-    DevBufRef ids;   // Int64 partition id per row; null: one partition
-    DevBufRef perm;  // null: the identity
-    DevBufRef part_heads, peer_heads;
-    const uint64_t *d_perm() const { return perm ? static_cast<const uint64_t *>(perm->ptr) : nullptr; }
-    const int64_t *d_ids() const { return ids ? static_cast<const int64_t *>(ids->ptr) : nullptr; }
-};
 
 template <uint32_t OP>
 void launch_scan(rv_ctx *ctx, const rvk::WinScanParams &p) {
@@ -36,34 +25,8 @@ void launch_scan(rv_ctx *ctx, const rvk::WinScanParams &p) {
     RV_HIP(hipGetLastError());
 }
 
-bool is_shift(uint32_t op) { return op == RV_WIN_LAG || op == RV_WIN_LEAD; }
-
-// events around the window's own passes (option profile_kernels); the sorts before them time themselves
-struct PassTimer {
-    rv_ctx *ctx;
-    uint64_t launches = 0;
-    bool open = false;
-    explicit PassTimer(rv_ctx *c) : ctx(c) {}
-    void start() {
-        if (ctx->opt_profile) RV_HIP(hipEventRecord(ctx->evk0, ctx->stream));
-        open = true;
-    }
-    void stop_after_wait_for(hipStream_t s) {
-        if (!open) return;
-        open = false;
-        if (!ctx->opt_profile) return;
-        RV_HIP(hipEventRecord(ctx->evk1, s));
-        RV_HIP(hipEventSynchronize(ctx->evk1));
-        float ms = 0.f;
-        RV_HIP(hipEventElapsedTime(&ms, ctx->evk0, ctx->evk1));
-        ctx->kernel_ms += ms;
-        ctx->kernel_launches += launches;
-        launches = 0;
-    }
-};
-
-void window(rv_ctx *ctx, const rv_dcolumn *const *cols, const uint32_t *partition_cols, uint32_t npart, const uint32_t *order_cols,
-            const uint32_t *order_flags, uint32_t norder, const rv_window_spec *specs, uint32_t nspecs, rv_dcolumn **out) {
+void window(const char *who, rv_ctx *ctx, const rv_dcolumn *const *cols, const uint32_t *partition_cols, uint32_t npart, const uint32_t *order_cols,
+            const uint32_t *order_flags, uint32_t norder, const rv_window_frame_spec *specs, uint32_t nspecs, rv_dcolumn **out) {
     Sequence q;
     q.n = cols[0]->length;
     const uint64_t n = q.n;
@@ -71,10 +34,12 @@ void window(rv_ctx *ctx, const rv_dcolumn *const *cols, const uint32_t *partitio
     if (n == 0) {  // zero-row outputs of the right dtypes
         for (uint32_t j = 0; j < nspecs; ++j) {
             const rv_dcolumn *col = cols[specs[j].col];
-            if (is_shift(specs[j].op)) {
+            if (is_window_shift(specs[j].op) || specs[j].op == RV_WINF_FIRST_VALUE || specs[j].op == RV_WINF_LAST_VALUE) {
                 rv_dcolumn *o = nullptr;
                 take_nullable_on_device(ctx, &col, 1, nullptr, 0, &o, false, IndexNulls{});
                 outs[j].reset(o);
+            } else if (is_window_frame_op(specs[j].op)) {
+                outs[j] = new_value_column(ctx, window_frame_dtype(specs[j].op, col), 0);
             } else {
                 outs[j] = new_value_column(ctx, specs[j].op >= RV_WIN_CUM_SUM ? col->dtype : RV_INT64, 0);
             }
@@ -89,7 +54,7 @@ void window(rv_ctx *ctx, const rv_dcolumn *const *cols, const uint32_t *partitio
     if (npart) {
         std::vector<const rv_dcolumn *> keys(npart);
         for (uint32_t k = 0; k < npart; ++k) keys[k] = cols[partition_cols[k]];
-        q.ids = partition_ids(ctx, keys.data(), npart, "rv_window");
+        q.ids = partition_ids(ctx, keys.data(), npart, who);
     }
     for (uint32_t k = norder; k-- > 0;) q.perm = sort_indices(ctx, cols[order_cols[k]], order_flags[k], q.d_perm());
     if (npart) {
@@ -103,11 +68,11 @@ void window(rv_ctx *ctx, const rv_dcolumn *const *cols, const uint32_t *partitio
 
     PassTimer timer(ctx);
     timer.start();
-    bool scanned = false, shifted = false;
+    bool scanned = false, shifted = false, framed = false;
 
-    // 2. the heads (needed by the scans only: the shift compares the ids themselves)
+    // 2. the heads (needed by the scans and the frames only: the shift compares the ids themselves)
     bool any_scan = false;
-    for (uint32_t j = 0; j < nspecs; ++j) any_scan = any_scan || !is_shift(specs[j].op);
+    for (uint32_t j = 0; j < nspecs; ++j) any_scan = any_scan || !is_window_shift(specs[j].op);
     const uint64_t nwords = (n + 63) / 64, ntiles = (n + rvk::kWinTileRows - 1) / rvk::kWinTileRows;
     DevBufRef tile_agg, carry;
     if (any_scan) {
@@ -129,25 +94,10 @@ void window(rv_ctx *ctx, const rv_dcolumn *const *cols, const uint32_t *partitio
     }
 
     // 3. the scans, one spec after the other over the one sequence
-    struct Pending {  // a MIN / MAX whose null count the next read-back brings
-        uint32_t j;
-        int slot;
-    };
-    std::vector<Pending> pending;
-    Ctrl *ctrl = nullptr;
-    auto settle = [&] {  // read the null counts of the MIN / MAX outputs queued so far
-        if (pending.empty()) return;
-        const Ctrl *hc = fetch_ctrl(ctx);
-        for (const Pending &w : pending) {
-            outs[w.j]->null_count = static_cast<int64_t>(hc->valid_pop[w.slot]);
-            if (outs[w.j]->null_count == 0) outs[w.j]->validity.reset();  // attached iff some cell is null
-        }
-        pending.clear();
-        ctrl = nullptr;
-    };
+    NullCounts nulls(ctx, outs);  // of the MIN / MAX outputs: the next read-back brings them
     for (uint32_t j = 0; j < nspecs; ++j) {
         const uint32_t op = specs[j].op;
-        if (is_shift(op)) continue;
+        if (is_window_shift(op) || is_window_frame_op(op)) continue;
         const rv_dcolumn *col = cols[specs[j].col];
         rvk::WinScanParams p{};
         p.perm = q.d_perm();
@@ -170,15 +120,9 @@ void window(rv_ctx *ctx, const rv_dcolumn *const *cols, const uint32_t *partitio
             default: p.src = rvk::WS_CELL, p.col = dev_view(col); break;
         }
         if (op == RV_WIN_CUM_MIN || op == RV_WIN_CUM_MAX) {
-            if (pending.size() == 8) settle();
-            if (!ctrl) ctrl = prepare_ctrl(ctx, 0);
-            const int slot = static_cast<int>(pending.size());
-            outs[j]->validity = pool_alloc(ctx, zeroed_bitmap_bytes(n));
-            RV_HIP(hipMemsetAsync(outs[j]->validity->ptr, 0, zeroed_bitmap_bytes(n), ctx->stream));
             p.fin = rvk::WF_MINMAX;
+            p.nulls = nulls.attach(j, n);
             p.out_validity = static_cast<uint64_t *>(outs[j]->validity->ptr);
-            p.nulls = striped(ctx, &ctrl->valid_pop[slot]);
-            pending.push_back(Pending{j, slot});
             if (op == RV_WIN_CUM_MIN) launch_scan<rvwin::WC_MIN_U64>(ctx, p);
             else launch_scan<rvwin::WC_MAX_U64>(ctx, p);
         }
@@ -190,29 +134,28 @@ void window(rv_ctx *ctx, const rv_dcolumn *const *cols, const uint32_t *partitio
     }
 
     // 4. the shifts: a nullable index list in row order, gathered like any other
-    struct Shift {
-        uint32_t j;
-        DevBufRef idx;
-    };
-    std::vector<Shift> shifts;
+    std::vector<IndexGather> shifts;
     for (uint32_t j = 0; j < nspecs; ++j) {
-        if (!is_shift(specs[j].op)) continue;
+        if (!is_window_shift(specs[j].op)) continue;
         rvk::WinShiftParams s{};
         s.perm = q.d_perm();
         s.ids = q.d_ids();
         s.n = n;
         s.k = specs[j].offset;
         s.lead = specs[j].op == RV_WIN_LEAD;
-        shifts.push_back(Shift{j, pool_alloc(ctx, n * 8 + 16)});
+        shifts.push_back(IndexGather{j, pool_alloc(ctx, n * 8 + 16)});
         s.idx = static_cast<uint64_t *>(shifts.back().idx->ptr);
         hipLaunchKernelGGL(rvk::window_shift, dim3(grid_for_words(ctx, n, rvk::kWinThreads)), dim3(rvk::kWinThreads), 0, ctx->stream, s);
         RV_HIP(hipGetLastError());
         ++timer.launches;
         shifted = true;
     }
+    // 5. the frames, first / last value and ntile, over the same sequence
+    for (uint32_t j = 0; j < nspecs; ++j) framed = framed || is_window_frame_op(specs[j].op);
+    if (framed) window_frame_passes(ctx, q, cols, specs, nspecs, outs, nulls, shifts, timer);
     timer.stop_after_wait_for(ctx->stream);
-    settle();
-    for (const Shift &s : shifts) {
+    nulls.settle();
+    for (const IndexGather &s : shifts) {
         const rv_dcolumn *col = cols[specs[s.j].col];
         rv_dcolumn *o = nullptr;
         take_nullable_on_device(ctx, &col, 1, static_cast<const uint64_t *>(s.idx->ptr), n, &o, false, IndexNulls{});
@@ -220,10 +163,61 @@ void window(rv_ctx *ctx, const rv_dcolumn *const *cols, const uint32_t *partitio
     }
     RV_HIP(hipStreamSynchronize(ctx->stream));  // the sequence and the working buffers go back to the pool
     for (uint32_t j = 0; j < nspecs; ++j) out[j] = outs[j].release();
-    ctx->last_kernel = scanned ? "window_scan" : shifted ? "window_shift" : "";
+    ctx->last_kernel = framed ? "window_frame" : scanned ? "window_scan" : shifted ? "window_shift" : "";
 }
 
 }  // namespace
+
+void window_call(const char *who, uint32_t op_most, rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, const uint32_t *partition_cols,
+                 uint32_t npart, const uint32_t *order_cols, const uint32_t *order_flags, uint32_t norder, const rv_window_frame_spec *specs,
+                 uint32_t nspecs, rv_dcolumn **out) {
+    const std::string w = who;
+    require(ctx && cols && specs && out && (npart == 0 || partition_cols) && (norder == 0 || (order_cols && order_flags)), RV_ERR_INVALID_ARG,
+            w + ": NULL argument");
+    require(ncols >= 1, RV_ERR_INVALID_ARG, w + ": no columns");
+    require(nspecs >= 1, RV_ERR_INVALID_ARG, w + ": no window expressions");
+    check_batch(cols, ncols);
+    for (uint32_t k = 0; k < npart; ++k)
+        require(partition_cols[k] < ncols, RV_ERR_INVALID_ARG, fmt("%s: partition key %u is column %u of %u", who, k, partition_cols[k], ncols));
+    for (uint32_t k = 0; k < norder; ++k)
+        require(order_cols[k] < ncols, RV_ERR_INVALID_ARG, fmt("%s: order key %u is column %u of %u", who, k, order_cols[k], ncols));
+    require(norder <= static_cast<uint32_t>(rvk::kWinOrderKeysMost), RV_ERR_INVALID_ARG,
+            fmt("%s: %u order keys; at most %d are taken", who, norder, rvk::kWinOrderKeysMost));
+    for (uint32_t j = 0; j < nspecs; ++j) {
+        require(specs[j].op <= op_most, RV_ERR_INVALID_ARG, fmt("%s: expression %u has the unknown op %u", who, j, specs[j].op));
+        require(specs[j].col < ncols, RV_ERR_INVALID_ARG, fmt("%s: expression %u reads column %u of %u", who, j, specs[j].col, ncols));
+        if (specs[j].op >= RV_WINF_COUNT && specs[j].op <= RV_WINF_LAST_VALUE)
+            require(rvframe::frame_ok(specs[j].preceding, specs[j].following), RV_ERR_INVALID_ARG,
+                    fmt("%s: expression %u: a frame's finite offsets are at most 2^62 in magnitude and preceding + following >= 0", who, j));
+        if (specs[j].op == RV_WINF_NTILE) require(specs[j].offset >= 1, RV_ERR_INVALID_ARG, fmt("%s: expression %u: NTILE of 0 buckets", who, j));
+    }
+    require(cols[0]->length < (uint64_t{1} << 32), RV_ERR_UNSUPPORTED, w + ": frames of 2^32 rows or more are not supported (32-bit row ids inside, as the sort)");
+    if (npart) {
+        std::vector<const rv_dcolumn *> keys(npart);
+        for (uint32_t k = 0; k < npart; ++k) keys[k] = cols[partition_cols[k]];
+        check_partition_keys(keys.data(), npart, who);
+    }
+    for (uint32_t k = 0; k < norder; ++k) check_sort_key(cols[order_cols[k]], order_flags[k], who);
+    for (uint32_t j = 0; j < nspecs; ++j) {
+        const rv_dtype d = cols[specs[j].col]->dtype;
+        const uint32_t op = specs[j].op;
+        if (op >= RV_WIN_CUM_SUM && op <= RV_WIN_CUM_MAX)
+            require(is_value_type(d), RV_ERR_TYPE_MISMATCH, fmt("%s: expression %u: CUM_SUM / CUM_MIN / CUM_MAX take an Int64 or Float64 column", who, j));
+        else if (op >= RV_WINF_SUM && op <= RV_WINF_AVG)
+            require(is_value_type(d), RV_ERR_TYPE_MISMATCH, fmt("%s: expression %u: SUM / MIN / MAX / AVG take an Int64 or Float64 column", who, j));
+        else if (op == RV_WIN_CUM_COUNT || is_window_shift(op) || op == RV_WINF_COUNT || op == RV_WINF_FIRST_VALUE || op == RV_WINF_LAST_VALUE)
+            require(is_value_type(d) || d == RV_BOOLEAN || d == RV_STRING || d == RV_NULL, RV_ERR_UNSUPPORTED, fmt("%s: expression %u: unsupported dtype", who, j));
+    }
+    for (uint32_t j = 0; j < nspecs; ++j) out[j] = nullptr;
+    set_device(ctx);
+    try {
+        window(who, ctx, cols, partition_cols, npart, order_cols, order_flags, norder, specs, nspecs, out);
+    } catch (...) {
+        (void)hipStreamSynchronize(ctx->stream);  // whatever was queued has run before its buffers go back to the pool
+        throw;
+    }
+}
+
 }  // namespace rvl
 
 extern "C" {
@@ -232,43 +226,11 @@ rv_status rv_window(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, 
                     const uint32_t *order_cols, const uint32_t *order_flags, uint32_t norder, const rv_window_spec *specs, uint32_t nspecs,
                     rv_dcolumn **out) {
     return guarded([&] {
-        require(ctx && cols && specs && out && (npart == 0 || partition_cols) && (norder == 0 || (order_cols && order_flags)), RV_ERR_INVALID_ARG,
-                "rv_window: NULL argument");
-        require(ncols >= 1, RV_ERR_INVALID_ARG, "rv_window: no columns");
-        require(nspecs >= 1, RV_ERR_INVALID_ARG, "rv_window: no window expressions");
-        check_batch(cols, ncols);
-        for (uint32_t k = 0; k < npart; ++k)
-            require(partition_cols[k] < ncols, RV_ERR_INVALID_ARG, fmt("rv_window: partition key %u is column %u of %u", k, partition_cols[k], ncols));
-        for (uint32_t k = 0; k < norder; ++k)
-            require(order_cols[k] < ncols, RV_ERR_INVALID_ARG, fmt("rv_window: order key %u is column %u of %u", k, order_cols[k], ncols));
-        require(norder <= static_cast<uint32_t>(rvk::kWinOrderKeysMost), RV_ERR_INVALID_ARG,
-                fmt("rv_window: %u order keys; at most %d are taken", norder, rvk::kWinOrderKeysMost));
-        for (uint32_t j = 0; j < nspecs; ++j) {
-            require(specs[j].op <= static_cast<uint32_t>(RV_WIN_LEAD), RV_ERR_INVALID_ARG, fmt("rv_window: expression %u has the unknown op %u", j, specs[j].op));
-            require(specs[j].col < ncols, RV_ERR_INVALID_ARG, fmt("rv_window: expression %u reads column %u of %u", j, specs[j].col, ncols));
-        }
-        require(cols[0]->length < (uint64_t{1} << 32), RV_ERR_UNSUPPORTED, "rv_window: frames of 2^32 rows or more are not supported (32-bit row ids inside, as the sort)");
-        if (npart) {
-            std::vector<const rv_dcolumn *> keys(npart);
-            for (uint32_t k = 0; k < npart; ++k) keys[k] = cols[partition_cols[k]];
-            check_partition_keys(keys.data(), npart, "rv_window");
-        }
-        for (uint32_t k = 0; k < norder; ++k) check_sort_key(cols[order_cols[k]], order_flags[k], "rv_window");
-        for (uint32_t j = 0; j < nspecs; ++j) {
-            const rv_dtype d = cols[specs[j].col]->dtype;
-            if (specs[j].op >= RV_WIN_CUM_SUM && specs[j].op <= RV_WIN_CUM_MAX)
-                require(is_value_type(d), RV_ERR_TYPE_MISMATCH, fmt("rv_window: expression %u: CUM_SUM / CUM_MIN / CUM_MAX take an Int64 or Float64 column", j));
-            else if (specs[j].op == RV_WIN_CUM_COUNT || is_shift(specs[j].op))
-                require(is_value_type(d) || d == RV_BOOLEAN || d == RV_STRING || d == RV_NULL, RV_ERR_UNSUPPORTED, fmt("rv_window: expression %u: unsupported dtype", j));
-        }
-        for (uint32_t j = 0; j < nspecs; ++j) out[j] = nullptr;
-        set_device(ctx);
-        try {
-            window(ctx, cols, partition_cols, npart, order_cols, order_flags, norder, specs, nspecs, out);
-        } catch (...) {
-            (void)hipStreamSynchronize(ctx->stream);  // whatever was queued has run before its buffers go back to the pool
-            throw;
-        }
+        // the general form's specs: rv_window's one frame is ROWS UNBOUNDED PRECEDING .. CURRENT ROW, and its ops end at RV_WIN_LEAD
+        std::vector<rv_window_frame_spec> general(specs ? size_t{nspecs} + 1 : 0);  // + 1: not NULL when nspecs == 0, which has its own text
+        for (uint32_t j = 0; specs && j < nspecs; ++j) general[j] = rv_window_frame_spec{specs[j].op, specs[j].col, specs[j].offset, RV_FRAME_UNBOUNDED, 0};
+        window_call("rv_window", RV_WIN_LEAD, ctx, cols, ncols, partition_cols, npart, order_cols, order_flags, norder,
+                    specs ? general.data() : nullptr, nspecs, out);
     });
 }
 

@@ -2109,21 +2109,30 @@ class GpuSortStream : public DataStream {
 
 // ---------------------------------------------------------------------------------------
 // window(partition_by, order_by, exprs) -- f(...) OVER (PARTITION BY .. ORDER BY ..); the reference has no window expression:
-// include/rivulus_gpu.h, rv_window
+// include/rivulus_gpu.h, rv_window and rv_window_frames
 // ---------------------------------------------------------------------------------------
-enum class WindowOp { RowNumber, Rank, DenseRank, CumCount, CumSum, CumMin, CumMax, Lag, Lead };  // rv_window_op, in its order
+// rv_window_op and then rv_window_frame_op, in their order
+enum class WindowOp { RowNumber, Rank, DenseRank, CumCount, CumSum, CumMin, CumMax, Lag, Lead, Count, Sum, Min, Max, Avg, FirstValue, LastValue, Ntile };
 inline const char *to_string(WindowOp op) {
-    static const char *n[] = {"ROW_NUMBER", "RANK", "DENSE_RANK", "CUM_COUNT", "CUM_SUM", "CUM_MIN", "CUM_MAX", "LAG", "LEAD"};
+    static const char *n[] = {"ROW_NUMBER", "RANK", "DENSE_RANK", "CUM_COUNT", "CUM_SUM", "CUM_MIN", "CUM_MAX", "LAG", "LEAD",
+                              "COUNT", "SUM", "MIN", "MAX", "AVG", "FIRST_VALUE", "LAST_VALUE", "NTILE"};
     return n[static_cast<int>(op)];
 }
-inline bool window_op_reads_a_column(WindowOp op) { return op != WindowOp::RowNumber && op != WindowOp::Rank && op != WindowOp::DenseRank; }
-// One window expression: `op` over `column` (ignored by the three numberings), `offset` rows back or ahead (Lag / Lead only), under the
-// output name `alias`.
+inline bool window_op_reads_a_column(WindowOp op) {
+    return op != WindowOp::RowNumber && op != WindowOp::Rank && op != WindowOp::DenseRank && op != WindowOp::Ntile;
+}
+// Count .. LastValue: the ops that aggregate or pick over the frame [preceding, following]
+inline bool window_op_has_a_frame(WindowOp op) { return op >= WindowOp::Count && op <= WindowOp::LastValue; }
+// One window expression: `op` over `column` (ignored by the three numberings and Ntile), `offset` rows back or ahead (Lag / Lead) or the
+// number of buckets (Ntile), under the output name `alias`.  Count .. LastValue work over the ROWS frame of `preceding` rows before the
+// current one to `following` after it: signed, RV_FRAME_UNBOUNDED for the partition's edge (the default is the running frame); the
+// other ops ignore the two.
 struct WindowExpr {
     WindowOp op;
     std::string column;
     uint64_t offset = 0;
     std::string alias;
+    int64_t preceding = RV_FRAME_UNBOUNDED, following = 0;
 };
 struct WindowPlanError : std::runtime_error {  // what planning a window refuses, with the column it refuses it for
     using std::runtime_error::runtime_error;
@@ -2131,10 +2140,12 @@ struct WindowPlanError : std::runtime_error {  // what planning a window refuses
 constexpr size_t kWindowKeysMost = 8;
 
 // Checks the window against `in` and returns the output schema: the input's fields, then one field per expression under its alias --
-// numbers and counts Int64, CUM_SUM / CUM_MIN / CUM_MAX and LAG / LEAD of the column's dtype; MIN / MAX and LAG / LEAD are nullable.
+// numbers, counts and NTILE Int64, SUM / MIN / MAX, LAG / LEAD and FIRST / LAST_VALUE of the column's dtype, AVG Float64; MIN / MAX, AVG,
+// LAG / LEAD and FIRST / LAST_VALUE are nullable.
 // Partition keys may be of any dtype (String keys go through the dictionary); order keys are what the sort takes.  Throws WindowPlanError
 // for an empty expression list, an unknown column, more than 8 partition or order keys, a String / Boolean order key (with the sort's
-// words), SUM / MIN / MAX over a column that is not Int64 or Float64, and an empty or duplicate alias.
+// words), SUM / MIN / MAX / AVG over a column that is not Int64 or Float64, NTILE with 0 buckets, a frame with preceding + following < 0
+// or a finite offset beyond 2^62 (these three name the column and the alias), and an empty or duplicate alias.
 inline SchemaRef window_schema(const Schema &in, const std::vector<std::string> &partition_by, const std::vector<SortKey> &order_by,
                                const std::vector<WindowExpr> &exprs) {
     if (exprs.empty()) throw WindowPlanError("window: no window expressions");
@@ -2156,19 +2167,34 @@ inline SchemaRef window_schema(const Schema &in, const std::vector<std::string> 
         if (window_op_reads_a_column(e.op)) {
             const Field *f = in.field_by_name(e.column);
             if (!f) throw WindowPlanError("window: expression '" + e.alias + "' reads the unknown column '" + e.column + "'");
-            if (e.op != WindowOp::CumCount) t = f->data_type();
+            if (e.op != WindowOp::CumCount && e.op != WindowOp::Count) t = f->data_type();
             if ((e.op == WindowOp::CumSum || e.op == WindowOp::CumMin || e.op == WindowOp::CumMax) && t != DataType::Int64 && t != DataType::Float64)
                 throw WindowPlanError(std::string("window: ") + to_string(e.op) + " over column '" + e.column + "' of dtype " + to_string(t));
+            if (e.op >= WindowOp::Sum && e.op <= WindowOp::Avg && t != DataType::Int64 && t != DataType::Float64)
+                throw WindowPlanError(std::string("window: ") + to_string(e.op) + " over column '" + e.column + "' of dtype " + to_string(t) + " (expression '" +
+                                      e.alias + "')");
+            if (e.op == WindowOp::Avg) t = DataType::Float64;
+        }
+        if (e.op == WindowOp::Ntile && e.offset == 0) throw WindowPlanError("window: NTILE expression '" + e.alias + "' has 0 buckets");
+        if (window_op_has_a_frame(e.op)) {
+            const int64_t most = int64_t{1} << 62;
+            const bool pu = e.preceding == RV_FRAME_UNBOUNDED, fu = e.following == RV_FRAME_UNBOUNDED;
+            const std::string what = std::string("window: the frame of the ") + to_string(e.op) + " expression '" + e.alias + "' over column '" + e.column + "' ";
+            if ((!pu && (e.preceding < -most || e.preceding > most)) || (!fu && (e.following < -most || e.following > most)))
+                throw WindowPlanError(what + "has a finite offset beyond 2^62");
+            if (!pu && !fu && e.preceding < -e.following) throw WindowPlanError(what + "has preceding + following < 0");
         }
         if (e.alias.empty()) throw WindowPlanError(std::string("window: the ") + to_string(e.op) + " expression over column '" + e.column + "' has no alias");
         for (auto &f : out)
             if (f.name() == e.alias) throw WindowPlanError("window: duplicate output name '" + e.alias + "'");
-        out.push_back(Field{e.alias, t, e.op == WindowOp::CumMin || e.op == WindowOp::CumMax || e.op == WindowOp::Lag || e.op == WindowOp::Lead});
+        const bool nullable = e.op == WindowOp::CumMin || e.op == WindowOp::CumMax || e.op == WindowOp::Lag || e.op == WindowOp::Lead || e.op == WindowOp::Min ||
+                              e.op == WindowOp::Max || e.op == WindowOp::Avg || e.op == WindowOp::FirstValue || e.op == WindowOp::LastValue;
+        out.push_back(Field{e.alias, t, nullable});
     }
     return std::make_shared<const Schema>(out);
 }
 
-// One rv_window over one frame (`columns` in the order of `schema`): the NEW columns, one per expression, in the frame's row order.
+// One rv_window_frames over one frame (`columns` in the order of `schema`): the NEW columns, one per expression, in the frame's row order.
 // Every String partition key goes through the string dictionary on its own, as group_by's do: its ids (a null string is a null id; "" is
 // a value) stand in the tuple.
 inline std::vector<ArrayRef> window_columns(const ContextRef &ctx, const Schema &schema, const std::vector<ArrayRef> &columns,
@@ -2193,11 +2219,12 @@ inline std::vector<ArrayRef> window_columns(const ContextRef &ctx, const Schema 
         part_cols.push_back(static_cast<uint32_t>(handles.size()));
         handles.push_back(ids.back()->handle());
     }
-    std::vector<rv_window_spec> specs;
+    std::vector<rv_window_frame_spec> specs;
     for (auto &e : exprs)
-        specs.push_back(rv_window_spec{static_cast<uint32_t>(e.op), window_op_reads_a_column(e.op) ? static_cast<uint32_t>(*schema.index_of(e.column)) : 0u, e.offset});
+        specs.push_back(rv_window_frame_spec{static_cast<uint32_t>(e.op), window_op_reads_a_column(e.op) ? static_cast<uint32_t>(*schema.index_of(e.column)) : 0u,
+                                             e.offset, e.preceding, e.following});
     std::vector<rv_dcolumn *> out(specs.size(), nullptr);
-    check(rv_window(ctx->raw(), handles.data(), static_cast<uint32_t>(handles.size()), part_cols.data(), static_cast<uint32_t>(part_cols.size()),
+    check(rv_window_frames(ctx->raw(), handles.data(), static_cast<uint32_t>(handles.size()), part_cols.data(), static_cast<uint32_t>(part_cols.size()),
                     call.key_cols.data(), call.key_flags.data(), static_cast<uint32_t>(order_by.size()), specs.data(), static_cast<uint32_t>(specs.size()),
                     out.data()));
     return adopt_columns(ctx, out);
