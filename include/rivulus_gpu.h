@@ -249,10 +249,17 @@ rv_status rv_ctx_device_info(rv_ctx *ctx, int *compute_units, uint64_t *hbm_byte
  * the 8-byte values; same rows, same order, same bits.  MEMORY: + 25 % of the column for 2-byte codes, + 50 % for 4-byte codes, held
  * until the column's buffer is freed; a range of 2^32 and more, or no memory for the codes, means no companion and never a failed
  * query.  Only buffers the library allocated qualify -- columns are immutable once their handle is out; rv_wrap memory is the caller's
- * to write and is never packed.  0 = as described, -1 = never, 1 = at the first whole scan whatever the size (tests) -- and only with 1 does a launch with a
+ * to write and is never packed.  A column whose value range is 1023 and less, and whose triggering scan was a launch over the whole
+ * column -- no per-batch counts, first element a multiple of 384 -- gets its codes PACKED instead: 10 bits each, six per 8-byte word,
+ * + 16.7 % of the column; launches without per-batch counts over views that start at a multiple of 384 read them, every other launch
+ * over the buffer reads the 8-byte values, and when such launches complete two whole scans of their own the 2-byte codes are built
+ * beside the packed ones (+ 25 % more; likewise the packed ones beside 2-byte codes that whole-column launches cannot read).
+ * 0 = as described, -1 = never, 1 = at the first whole scan whatever the size and never the packed layout (tests), 2 = at the first
+ * whole scan whatever the size, packed where the rule above allows, else as 1 (tests, tools/narrow_stamp.py) -- and only with 1 or 2
+ * does a launch with a
  * forced "rows_per_lane" geometry or the "stamp" / "debug" diagnostics read the codes, and only where exactly that instantiation exists
- * over codes (the forced geometry; for the diagnostics 2-byte codes at 32 or 16 rows per lane): every other such launch reads the
- * 8-byte values at the geometry asked for, a 4-byte companion under the diagnostics included; read-only
+ * over codes (the forced geometry; for the diagnostics 2-byte codes at 32 or 16 rows per lane, packed codes at 48 or 24): every other
+ * such launch reads the 8-byte values at the geometry asked for, a 4-byte companion under the diagnostics included; read-only
  * counters "narrow_builds", "narrow_passes", "narrow_bytes").  Diagnostics only, never for results: "stamp" (per-phase cycle
  * counters, printed to stderr) and "debug" (bit 0 skip the value stores, bit 1 skip the
  * output-offset lookup -- both make the output WRONG, timing shares only -- bit 2 print

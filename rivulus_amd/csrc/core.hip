@@ -396,7 +396,7 @@ rv_status rv_ctx_set_option(rv_ctx *ctx, const char *key, int64_t value) {
         else if (k == "agg_grid") ctx->opt_agg_grid = value;
         else if (k == "bools_in_pass") ctx->opt_bools_in_pass = value;
         else if (k == "narrow_codes") {
-            require(value >= -1 && value <= 1, RV_ERR_INVALID_ARG, "narrow_codes: 0 (auto), -1 (never) or 1 (at the first whole scan)");
+            require(value >= -1 && value <= 2, RV_ERR_INVALID_ARG, "narrow_codes: 0 (auto), -1 (never), 1 (at the first whole scan, never packed) or 2 (at the first whole scan, packed where the rule allows)");
             ctx->opt_narrow_codes = value;
         }
         else if (k == "inject_failure") ctx->opt_inject_failure = value;

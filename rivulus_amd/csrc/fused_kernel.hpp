@@ -202,8 +202,12 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
     static_assert(!kOne || (NCOLS == 1 && (FLAGS & (FF_VALIDITY | FF_BOOL | FF_XS)) == 0), "single-term fast path");
     constexpr int kNarrow = (FLAGS & FF_NARROW16) ? 2 : ((FLAGS & FF_NARROW32) ? 4 : 0);  // bytes of a code; 0: the 8-byte rows
     static_assert(!kNarrow || ((FLAGS & FF_ONE_I64) != 0 && VEC == 2 && (FLAGS & (FF_NARROW16 | FF_NARROW32)) != (FF_NARROW16 | FF_NARROW32)), "narrow codes: lean Int64 form");
-    using Raw = typename NarrowRaw<kNarrow == 4 ? 4 : 2>::type;  // a lane's pair of codes, as loaded
-    constexpr int NRAW = kNarrow != 0 ? R / 2 : 1;
+    // FF_PACK10: the 2-byte cells' codes lie packed in memory, six per 8-byte word (scan_frontend.hpp, load_rows_packed); it changes how
+    // a tile's codes are loaded and unpacked, nothing behind the unpack
+    constexpr bool kPack10 = (FLAGS & FF_PACK10) != 0;
+    static_assert(!kPack10 || (kNarrow == 2 && R % 6 == 0), "packed codes: 2-byte cells, three pairs per word");
+    using Raw = typename NarrowRaw<(kNarrow == 4 || kPack10) ? 4 : 2>::type;  // a lane's pair of codes (packed: three pairs), as loaded
+    constexpr int NRAW = kNarrow != 0 ? (kPack10 ? R / 6 : R / 2) : 1;
     // selector masks of term 0 (all ones / all zeros), fixed for the launch
     const DevTerm term0 = p.in.terms[0];
     const uint64_t SLT = term0.sel_lt() ? ~0ull : 0, SEQ = term0.sel_eq() ? ~0ull : 0, SGT = term0.sel_gt() ? ~0ull : 0,
@@ -339,14 +343,17 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
     auto load_tile_rows = [&](uint64_t first_row) {  // of this wave
         if constexpr (kNarrow == 0) load_rows<NCOLS, R, VEC>(p.in, first_row, lane, v);
     };
-    // A pass over codes keeps the tile's raw pairs instead (R / 2 registers of 2-byte codes per lane, R of 4-byte codes), requested
+    // A pass over codes keeps the tile's raw pairs instead (R / 2 registers of 2-byte codes per lane, R of 4-byte codes, R / 3 of packed ones), requested
     // where the plain form requests its rows: behind the staging of the tile before.  (Three sets of pairs, the tile two ahead
     // requested at the top of an iteration with the ids drawn four ahead, measured SLOWER: fused_narrow.hip.)
     Raw codes[NRAW];
     auto load_tile_codes = [&](uint32_t t) {  // of this wave; a tile id >= ntiles (the ticket counter ran out) issues no load
         if constexpr (kNarrow != 0)
-            if (t < p.ntiles)
-                load_rows_narrow<R, kNarrow>(p.narrow, p.in.cols[0].offset + static_cast<uint64_t>(t) * TILE + static_cast<uint64_t>(wave) * ROWS_PER_WAVE, lane, codes);
+            if (t < p.ntiles) {
+                const uint64_t first = p.in.cols[0].offset + static_cast<uint64_t>(t) * TILE + static_cast<uint64_t>(wave) * ROWS_PER_WAVE;
+                if constexpr (kPack10) load_rows_packed<R>(p.narrow, first, lane, codes);
+                else load_rows_narrow<R, kNarrow>(p.narrow, first, lane, codes);
+            }
     };
     if constexpr (kNarrow != 0) load_tile_codes(tile);
     else if (tile < p.ntiles) load_tile_rows(static_cast<uint64_t>(tile) * TILE + static_cast<uint64_t>(wave) * ROWS_PER_WAVE);
@@ -531,13 +538,18 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
                     a1 = a1 < top ? a1 : top;
                     next += static_cast<uint32_t>(__popcll(m0) + __popcll(m1)) * kNarrow;
                 };
+                // pair j of the tile: a register of its own, or -- packed -- fields 2 (j % 3), 2 (j % 3) + 1 of word j / 3
+                auto unpack = [&](int j, uint32_t &c0, uint32_t &c1) {
+                    if constexpr (kPack10) unpack_packed_pair(codes[j / 3], j % 3, c0, c1);
+                    else unpack_pair<kNarrow>(codes[j], c0, c1);
+                };
                 if constexpr (kStamp) TLO = uniform32(tlo_v), TSPAN = uniform32(tspan_v);
                 if (full && project && !negated) {
                     // ---- every tile but a launch's last: no test in the loop that comes out the same for every row of the tile ----
 #pragma unroll
                     for (int j = 0; j < R / 2; ++j) {
                         uint32_t c0, c1, a0, a1;
-                        unpack_pair<kNarrow>(codes[j], c0, c1);
+                        unpack(j, c0, c1);
                         const uint64_t m0 = ballot64(c0 - TLO <= TSPAN), m1 = ballot64(c1 - TLO <= TSPAN);
                         cells(m0, m1, a0, a1);
                         put(lane_of(m0) ? a0 : cell, c0);
@@ -550,7 +562,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
 #pragma unroll
                     for (int j = 0; j < R / 2; ++j) {
                         uint32_t c0, c1, a0, a1;
-                        unpack_pair<kNarrow>(codes[j], c0, c1);
+                        unpack(j, c0, c1);
                         uint64_t m0 = ballot64(c0 - TLO <= TSPAN) ^ TNEG, m1 = ballot64(c1 - TLO <= TSPAN) ^ TNEG;
                         if (!full) m0 &= ballot64(2 * lane < rem - j * 128), m1 &= ballot64(2 * lane + 1 < rem - j * 128);
                         cells(m0, m1, a0, a1);

@@ -16,7 +16,7 @@ namespace rvl {
 // ---------------------------------------------------------------------------------------
 // Smallest instantiation whose feature flags cover `need`; for one-column lean/validity
 // launches the geometry can be steered with rv_ctx_set_option("rows_per_lane", R | waves << 8).
-constexpr int kNarrowFlags = rvk::FF_NARROW16 | rvk::FF_NARROW32;
+constexpr int kNarrowFlags = rvk::FF_NARROW16 | rvk::FF_NARROW32 | rvk::FF_PACK10;
 // `prefer_r` > 0: that many rows per lane among the default level's geometries, when the class has one
 const rvk::FusedEntry *find_fused(rv_ctx *ctx, int ncols, int vec, int need, int roomy = 0, int below_r = 1 << 30, int prefer_r = 0) {
     const rvk::FusedEntry *best = nullptr;
@@ -95,6 +95,9 @@ static void (*plain_twin(const rvk::FusedEntry &e))(const rvk::FusedParams) {
         if (t[i].ncols == e.ncols && t[i].r == e.r && t[i].vec == e.vec && t[i].waves == e.waves && t[i].flags == (e.flags & ~(kNarrowFlags | rvk::FF_STAMP))) return t[i].fn;
     const rvk::FusedEntry tall = rvk::narrow_tall_plain();  // (not a geometry of the lean table)
     if (tall.ncols == e.ncols && tall.r == e.r && tall.vec == e.vec && tall.waves == e.waves && tall.flags == (e.flags & ~(kNarrowFlags | rvk::FF_STAMP))) return tall.fn;
+    t = rvk::narrow_packed_plain(&n);  // (nor are the packed geometries, but for 24 rows per lane)
+    for (size_t i = 0; i < n; ++i)
+        if (t[i].ncols == e.ncols && t[i].r == e.r && t[i].vec == e.vec && t[i].waves == e.waves && t[i].flags == (e.flags & ~(kNarrowFlags | rvk::FF_STAMP))) return t[i].fn;
     return nullptr;
 }
 // (costs several microseconds: once per (kernel, LDS size) and context)
@@ -408,6 +411,7 @@ struct LaunchChoice {
     int need = 0;
     size_t stages = 3, lds = 0, stage_row_bytes = 0;
     size_t lds_plain = 0;  // a pass over codes: what its plain twin needs for the same slots (the re-run after an output overflow)
+    size_t stages_plain = 3;  // ... and the stages it runs them with (two behind a three-stage pass over packed codes: size_staged)
     uint32_t cap = 0, ntiles = 0;
     uint64_t tile_rows = 0;
     bool make_selection = false;  // the selection bitmap deferred for per-batch counts is wanted after all (the pass cannot count them)
@@ -507,8 +511,15 @@ static void size_staged(rv_ctx *ctx, LaunchChoice &c, const rvk::FusedEntry &e, 
     const size_t budget = (roomy || e.waves >= 16) ? 144 * 1024 : 72 * 1024;
     // Three stages (write-out two iterations after the aggregate went out, so the scanner's prefix is
     // there when it is needed) when a slot still holds 3/16 of a wave's rows; two otherwise.
+    // (a pass over PACKED codes sizes its three stages of slots as the plain form sizes TWO: its re-run after an output overflow, the
+    // plain instantiation of its geometry over the 8-byte values, then runs two-staged in the same slots -- the rare second pass pays the
+    // exposed look-back, and the pass itself keeps three stages at 48 rows per lane, where a slot sized for three plain stages holds
+    // 384 of a wave's 3072 rows, less than the 3/16 below; with two stages it took 0.57 ms against 0.47 ms of the pass over 2-byte
+    // codes, profiles/narrow4_steps.txt)
+    const bool packed = (e.flags & rvk::FF_PACK10) != 0;
     auto cap_for = [&](size_t st) -> uint32_t {
         if (!c.stage_row_bytes) return rows_per_wave;
+        if (packed && st == 3) st = 2;
         return static_cast<uint32_t>(std::min<uint64_t>(rows_per_wave, (budget / (st * e.waves * c.stage_row_bytes)) & ~size_t(63)));
     };
     c.stages = 3;
@@ -530,10 +541,13 @@ static void size_staged(rv_ctx *ctx, LaunchChoice &c, const rvk::FusedEntry &e, 
     // the minimum slot of a wide row (several columns with validity bytes) times three stages can pass the CU's 160 KiB
     // (a forced "depth" = 2 on such a shape): two stages then
     constexpr size_t kLdsPerCu = 160 * 1024;
-    if (c.stages == 3 && lds_for(3, c.cap) > kLdsPerCu) c.stages = 2;
-    require(lds_for(c.stages, c.cap) <= kLdsPerCu, RV_ERR_UNSUPPORTED,
-            fmt("fused pass: %zu bytes of LDS for %d columns at %u rows per slot", lds_for(c.stages, c.cap), nvals, c.cap));
-    c.lds = c.lds_plain = lds_for(c.stages, c.cap);
+    // (the plain twin of a pass over packed codes never runs three stages: see cap_for)
+    auto plain_stages = [&](size_t st) { return (packed && st == 3) ? size_t(2) : st; };
+    if (c.stages == 3 && lds_for(plain_stages(3), c.cap) > kLdsPerCu) c.stages = 2;
+    require(lds_for(plain_stages(c.stages), c.cap) <= kLdsPerCu, RV_ERR_UNSUPPORTED,
+            fmt("fused pass: %zu bytes of LDS for %d columns at %u rows per slot", lds_for(plain_stages(c.stages), c.cap), nvals, c.cap));
+    c.stages_plain = plain_stages(c.stages);
+    c.lds = c.lds_plain = lds_for(c.stages_plain, c.cap);
     if (code_bytes && c.stage_row_bytes == 8) c.lds = lds_at(c.stages, c.cap, code_bytes);
 }
 
@@ -591,11 +605,13 @@ static LaunchChoice choose_launch(rv_ctx *ctx, const FusedLaunch &L, const Bound
     // reads the codes: the default row mapping only (16-byte loads).  A forced geometry ("rows_per_lane") or a diagnostic ("stamp",
     // "debug") takes the codes only in a context that packs on request ("narrow_codes" = 1: tools/narrow_stamp.py; the older tools
     // keep measuring the plain kernel) AND where the narrow table holds EXACTLY that instantiation -- the geometry asked for, with
-    // FF_STAMP for a diagnostic (2-byte codes at 32 and 16 rows per lane, fused_narrow.hip).  Otherwise the launch reads the 8-byte
-    // values as it always did: a forced geometry is never swapped for another one (include/rivulus_gpu.h, "narrow_codes")
+    // FF_STAMP for a diagnostic (2-byte codes at 32 and 16 rows per lane, packed ones at 48 and 24, fused_narrow.hip).  Otherwise the
+    // launch reads the 8-byte values as it always did: a forced geometry is never swapped for another one (include/rivulus_gpu.h,
+    // "narrow_codes").  A packed companion (narrow.hip hands one out only to a launch without per-batch counts whose view starts on a
+    // super-group) sets FF_PACK10 beside FF_NARROW16: the cells the pass stages are 2-byte codes whatever their layout in memory
     const bool diag = ctx->opt_stamp || ctx->opt_debug;
     if (narrow && c.need == rvk::FF_ONE_I64 && vec == 2 && !L.place && ((ctx->opt_rows_per_lane <= 0 && !diag) || ctx->opt_narrow_codes > 0)) {
-        const int codes = narrow->code_bytes == 2 ? rvk::FF_NARROW16 : rvk::FF_NARROW32;
+        const int codes = narrow->layout == rvn::Layout::kPacked ? (rvk::FF_NARROW16 | rvk::FF_PACK10) : (narrow->code_bytes == 2 ? rvk::FF_NARROW16 : rvk::FF_NARROW32);
         if (narrow_instantiated(c.need | codes | (diag ? rvk::FF_STAMP : 0), ctx->opt_rows_per_lane)) c.need |= codes;
     }
     // diagnostics (per-phase stamps, ablations) exist in the FF_STAMP instantiations only; "debug" implies them
@@ -648,12 +664,17 @@ static LaunchChoice choose_launch(rv_ctx *ctx, const FusedLaunch &L, const Bound
     while (!c.direct) {
         // (a pass over codes without per-batch counts: the tall geometry, fused_narrow.hip -- a 1024-row batch is no whole number of its
         // 2048-row wave ranges)
-        const int tall_r = ((c.need & kNarrowFlags) && !(req && req->counts)) ? rvk::kNarrowTallRows : 0;
+        const int tall_r = (c.need & rvk::FF_PACK10) ? rvk::kPackedTallRows : (((c.need & kNarrowFlags) && !(req && req->counts)) ? rvk::kNarrowTallRows : 0);
         c.staged = &pick_fused(ctx, nvals, vec, c.need, prefer, min_r, below_r, tall_r);
         if (min_r == 1 && (c.staged->waves != 16 || c.staged->r >= below_r)) {  // no 16-wave geometry below that many rows per lane left
             if (!dense_sizing) {  // the walk again, sized for a dense selection
                 dense_sizing = true;
                 below_r = 1 << 30;
+            } else if (c.need & rvk::FF_PACK10) {
+                // denser than the packed class's last geometry (12 rows per lane) admits: the plain lean pass over the 8-byte values,
+                // from the top of ITS walk, as over a buffer without a companion
+                c.need &= ~kNarrowFlags;
+                min_r = 0, below_r = 1 << 30, dense_sizing = false;
             } else {
                 min_r = 2;
             }
@@ -721,7 +742,7 @@ static void launch_pass(rv_ctx *ctx, FusedLaunch &L, const LaunchChoice &c, int 
     enable_lds(ctx, fn, c.lds);
     if (c.narrow) {
         p.narrow.codes = c.narrow->codes->ptr;
-        p.narrow.bytes = c.narrow->codes->bytes;
+        p.narrow.bytes = c.narrow->layout == rvn::Layout::kPacked ? std::min<uint64_t>(c.narrow->codes->bytes, rvn::packed_bytes(c.narrow->count)) : c.narrow->codes->bytes;
         p.narrow.base = c.narrow->base;
         // the pass compares codes: the term, lowered to ONE interval of codes once per launch -- a complement is folded into the
         // interval it is in wrap-around arithmetic.  The one term without an interval, the empty set over 4-byte codes, comes back
@@ -738,6 +759,7 @@ static void launch_pass(rv_ctx *ctx, FusedLaunch &L, const LaunchChoice &c, int 
         p.in.terms[1].pad = 0;
         L.fn_plain = plain_twin(*c.staged);
         L.lds_plain = c.lds_plain;
+        L.depth_plain = static_cast<int32_t>(c.stages_plain) - 1;
         require(L.fn_plain != nullptr, RV_ERR_INTERNAL, "narrow pass without a plain instantiation of its geometry");
         ctx->narrow_passes += 1;
     }
@@ -887,10 +909,12 @@ void fused_begin(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, con
     // the lean one-column Int64 pass: the buffer's narrow companion, when it has one this view can read (narrow.hip)
     const rv_dcolumn *lean = (b.nvals == 1 && nterms == 1 && !ex && !L.place && cols[terms[0].column]->dtype == RV_INT64) ? cols[terms[0].column] : nullptr;
     narrow_note_extent(ctx, lean);
-    const LaunchChoice c = choose_launch(ctx, L, b, row_bytes, ex != nullptr, sel_deferred, seen, sampled_now, req, ranges, lean ? narrow_codes_for(ctx, lean) : nullptr);
+    const bool lean_counts = req && req->counts;
+    const LaunchChoice c = choose_launch(ctx, L, b, row_bytes, ex != nullptr, sel_deferred, seen, sampled_now, req, ranges, lean ? narrow_codes_for(ctx, lean, lean_counts) : nullptr);
     if (lean && c.staged && !c.direct && (c.flags & rvk::FF_ONE_I64)) {  // counted towards the buffer's whole scans by fused_finish
         L.lean_values = lean->values;
         L.lean_offset = lean->offset;
+        L.lean_counts = lean_counts;
     }
     launch_pass(ctx, L, c, b.nvals, sel_out, req, ranges, seen);
 }
@@ -949,7 +973,10 @@ uint64_t fused_finish(rv_ctx *ctx, FusedLaunch &L) {
         const size_t zeroed = kCtrlBytes + (static_cast<size_t>(p.ntiles) + L.nranges) * 8;
         RV_HIP(hipMemsetAsync(L.ctrl.dev, 0, (zeroed + 15) & ~size_t(15), ctx->stream));
         // a pass over codes: re-run over the 8-byte values, whose slots of the same rows take 8 bytes per row
-        if (L.fn_plain) enable_lds(ctx, reinterpret_cast<const void *>(L.fn_plain), L.lds_plain);
+        if (L.fn_plain) {
+            enable_lds(ctx, reinterpret_cast<const void *>(L.fn_plain), L.lds_plain);
+            p.depth = L.depth_plain;  // (the stages lds_plain holds: size_staged)
+        }
         hipLaunchKernelGGL(L.fn_plain ? L.fn_plain : L.fn, dim3(L.grid), dim3(L.block), L.fn_plain ? L.lds_plain : L.lds, ctx->stream, p);
         RV_HIP(hipGetLastError());
         RV_HIP(hipMemcpyAsync(L.ctrl.host, L.ctrl.dev, kCtrlBytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -1019,7 +1046,7 @@ uint64_t fused_finish(rv_ctx *ctx, FusedLaunch &L) {
     if (L.lean_values) {  // a whole scan more of the column's buffer?  Its narrow companion is queued behind this pass then (narrow.hip)
         const DevBufRef values = std::move(L.lean_values);
         L.lean_values.reset();
-        narrow_after_pass(ctx, *values, L.lean_offset, L.n);
+        narrow_after_pass(ctx, *values, L.lean_offset, L.n, L.lean_counts);
     }
     return rows;
 }

@@ -15,6 +15,18 @@ namespace rvk {
 //   - survivors are staged as codes and widened (value = base + code) where they are written out; the slots hold the same ROWS as the
 //     plain form's (fused_launch.hip, size_staged), in a quarter or half of the LDS bytes.
 // Same values, same order, same counts and redo list as the plain form, bit for bit.
+// PACKED codes (FF_PACK10 beside FF_NARROW16; narrow_rule.hpp): a column whose values need 10 bits keeps them six per 8-byte word, in a
+// layout whose word l of a 384-element super-group holds rows 2l, 2l + 1 of its three 128-row groups -- the pair loads' row-to-lane
+// mapping, so ranks, masks, write-out order, wave totals and the redo list are the 2-byte form's.  A lane loads one 8-byte word per
+// three pairs (scan_frontend.hpp, load_rows_packed) and unpacks a row with one bit-field extract where the 2-byte form has an `and` or a
+// shift; everything behind the unpack is the same instruction stream, the cells staged in LDS are 2-byte codes.  48 rows per lane
+// occupy the 16 code registers per lane that 32 rows of 2-byte codes do: the pass reads 1.33 GB instead of 2.00 GB per 1e9 rows and
+// pays a tile's fixed part once per 49 152 rows.  Measured (profiles/narrow4_*): 0.470 -> 0.438 ms; 12 040 cycles per 48-row tile of
+// wave 1 against 9 085 per 32-row tile (8 027 per 32 rows, -12 %), which is what the per-tile cost model predicted (11 460) and far
+// from what the byte model did (0.353 ms): the pass stands at the instruction issue of its waves, not at HBM.  It needs THREE stages
+// of slots: with two (what the plain form's LDS rule gives 3072-row wave ranges) the look-back is exposed, 15 280 cycles per tile and
+// 0.57 ms -- so its slots are sized as the plain form sizes two stages, and its plain re-run runs two-staged (fused_launch.hip,
+// size_staged).
 // The pass is bound by the vector instructions of its waves, not by HBM latency (tools/narrow_stamp.py, profiles/narrow2_stamps_*.txt:
 // a wave waits ~50 of 11 000-15 000 cycles per tile for its codes; evaluating them and waiting at the barrier for the other waves on the
 // SIMD to evaluate theirs is 80-87 %).  Tried on top of the above and taken out again: THREE sets of pairs per lane, the tile two
@@ -37,6 +49,14 @@ const FusedEntry *fused_entries_narrow(size_t *n) {
         RV_FUSED(1, 16, 2, 16, FF_ONE_I64 | FF_NARROW32), RV_FUSED(1, 8, 2, 16, FF_ONE_I64 | FF_NARROW32), RV_FUSED(1, 4, 2, 16, FF_ONE_I64 | FF_NARROW32),
         // diagnostic (options "stamp" / "debug": phase cycle sums and the ablations of a pass over 2-byte codes, tools/narrow_stamp.py)
         RV_FUSED(1, 16, 2, 16, FF_STAMP | FF_ONE_I64 | FF_NARROW16), RV_FUSED(1, 32, 2, 16, FF_STAMP | FF_ONE_I64 | FF_NARROW16),
+        // packed codes (FF_PACK10, always with FF_NARROW16: the cells staged in LDS stay 2-byte codes): kPackedTallRows rows per lane
+        // first, then the geometries the walk down at denser selections takes; a selection denser than the 12-row one admits reads the
+        // 8-byte values through the plain lean pass (fused_launch.hip, choose_launch)
+        // (1e9 rows, x > 899, kernel ms by events, same box, alternating processes: 48 rows per lane 0.438, 36 0.489, 24 0.589, against
+        //  0.470 of the 2-byte codes at 32; 36 was instantiated for the experiment only: profiles/narrow4_steps.txt)
+        RV_FUSED(1, 48, 2, 16, FF_ONE_I64 | FF_NARROW16 | FF_PACK10), RV_FUSED(1, 24, 2, 16, FF_ONE_I64 | FF_NARROW16 | FF_PACK10),
+        RV_FUSED(1, 12, 2, 16, FF_ONE_I64 | FF_NARROW16 | FF_PACK10),
+        RV_FUSED(1, 48, 2, 16, FF_STAMP | FF_ONE_I64 | FF_NARROW16 | FF_PACK10), RV_FUSED(1, 24, 2, 16, FF_STAMP | FF_ONE_I64 | FF_NARROW16 | FF_PACK10),
     };
     *n = sizeof(t) / sizeof(t[0]);
     return t;
@@ -45,4 +65,11 @@ const FusedEntry *fused_entries_narrow(size_t *n) {
 // codes after an output overflow, over the 8-byte values.  (Its 64 value registers per lane spill at 128 VGPRs: a rare second pass,
 // never the launch a query is sized for.)
 FusedEntry narrow_tall_plain() { return RV_FUSED(1, kNarrowTallRows, 2, 16, FF_ONE_I64); }
+// ... and of the packed geometries (24 rows per lane is in the lean table): 96 value registers per lane at 48 rows, which spill like
+// the tall one's; profiles/narrow4_resources.txt has their scratch
+const FusedEntry *narrow_packed_plain(size_t *n) {
+    static const FusedEntry t[] = {RV_FUSED(1, 48, 2, 16, FF_ONE_I64), RV_FUSED(1, 12, 2, 16, FF_ONE_I64)};
+    *n = sizeof(t) / sizeof(t[0]);
+    return t;
+}
 }  // namespace rvk

@@ -28,7 +28,9 @@ const FusedEntry *fused_entries_expr(size_t *n);    // OR / NOT expressions (con
 const FusedEntry *fused_entries_roomy(size_t *n);   // 2..4 columns, slots that hold every row of a wave (dense selections)
 const FusedEntry *fused_entries_narrow(size_t *n);  // 1 Int64 column read as 2- / 4-byte codes of its narrow companion
 constexpr int kNarrowTallRows = 32;                 // rows per lane of a narrow pass without per-batch counts (fused_narrow.hip)
+constexpr int kPackedTallRows = 48;                 // ... of a pass over packed codes (FF_PACK10): the same 16 code registers per lane
 FusedEntry narrow_tall_plain();                     // the plain lean Int64 form of that geometry
+const FusedEntry *narrow_packed_plain(size_t *n);   // ... of the packed geometries the lean table does not hold
 // the direct (register-staged) kernel for dense selections (direct_kernel.hpp): np 8-byte columns the predicate reads, nq more
 // that are only projected; flags: FF_VALIDITY / FF_BOOL of the predicate's inputs
 struct DirectEntry {

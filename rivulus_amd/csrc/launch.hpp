@@ -133,8 +133,10 @@ struct FusedLaunch {
     //      geometry over the 8-byte values
     DevBufRef lean_values;
     uint64_t lean_offset = 0;
+    bool lean_counts = false;  // the launch asked for per-batch counts (a stream's window): such launches read no packed companion
     void (*fn_plain)(const rvk::FusedParams) = nullptr;
     size_t lds_plain = 0;  // its dynamic LDS: the same slot rows at 8 bytes each (the pass over codes stages 2 or 4)
+    int32_t depth_plain = 2;  // FusedParams::depth of that re-run (stages - 1)
 };
 struct SegmentOverflow {};  // thrown by run_segmented_pass's callee chain: the shared outputs were too small -- the caller falls back to one pass
 
@@ -193,8 +195,8 @@ struct BoolCompactLaunch {
 
 // ---- narrow.hip --------------------------------------------------------------------------------------------
 void narrow_note_extent(rv_ctx *ctx, const rv_dcolumn *col);
-const NarrowCodes *narrow_codes_for(rv_ctx *ctx, const rv_dcolumn *col);
-void narrow_after_pass(rv_ctx *ctx, DevBuf &buf, uint64_t offset, uint64_t rows);
+const NarrowCodes *narrow_codes_for(rv_ctx *ctx, const rv_dcolumn *col, bool batch_counts);
+void narrow_after_pass(rv_ctx *ctx, DevBuf &buf, uint64_t offset, uint64_t rows, bool batch_counts);
 
 // ---- strings.hip -------------------------------------------------------------------------------------------
 // total_dst (device, zeroed by the caller): where the scan leaves its total instead of the context's control block -- nothing of the

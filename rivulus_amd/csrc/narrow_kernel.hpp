@@ -1,11 +1,13 @@
-// The two kernels that build a narrow companion of an Int64 values buffer (runtime.hpp, NarrowCodes; narrow.hip): the column's
-// minimum and maximum, then codes[i] = uint(value[i] - min) in 2 or 4 bytes.  Both are plain streaming passes over the 8-byte values
-// (ordinary vector loads and stores, every index checked against `count`), run once per buffer.
+// The kernels that build a narrow companion of an Int64 values buffer (runtime.hpp, NarrowCodes; narrow.hip): the column's
+// minimum and maximum, then codes[i] = uint(value[i] - min) in 2 or 4 bytes, or packed at 10 bits (narrow_pack10_kernel).  All are
+// plain streaming passes over the 8-byte values (ordinary vector loads and stores, every index checked against `count`), run once per
+// buffer and layout.
 #pragma once
 
 #include <type_traits>
 
 #include "device_common.hpp"
+#include "narrow_rule.hpp"
 
 namespace rvk {
 
@@ -67,6 +69,35 @@ __global__ __launch_bounds__(256) void narrow_pack_kernel(const long long *value
     }
     const uint64_t tail = nquads * 4 + me;  // the last count % 4 elements
     if (me < 4 && tail < count) static_cast<Code *>(codes)[tail] = static_cast<Code>(static_cast<uint64_t>(values[tail]) - ub);
+}
+
+// The packed layout (narrow_rule.hpp: 10-bit codes, six per 8-byte word, super-groups of 384 elements in 64 words).  One thread per
+// output word: word l of super-group g takes elements 384 g + 128 s + 2 l + {0, 1}, s = 0, 1, 2 -- three 16-byte loads, each
+// coalesced over the 64 threads of a super-group like a pass's pair loads -- and stores one 8-byte word.  `words` = 64 x the
+// super-groups of `count`; an element past `count` packs as code 0 (the tail super-group is padded).  The codes buffer holds at
+// least words x 8 bytes.
+__global__ __launch_bounds__(256) void narrow_pack10_kernel(const long long *values, uint64_t count, long long base, uint64_t words, rv_u32x2 *codes) {
+    const rv_i64x2 *pairs = reinterpret_cast<const rv_i64x2 *>(values);
+    const uint64_t ub = static_cast<uint64_t>(base);
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+    for (uint64_t w = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; w < words; w += stride) {
+        const uint64_t first = (w >> 6) * rvn::kPackGroup + 2 * (w & 63);  // the word's first element
+        uint32_t c[6];
+#pragma unroll
+        for (int s = 0; s < 3; ++s) {
+            const uint64_t e = first + 128u * s;
+            long long a = base, b = base;  // (code 0)
+            if (e + 1 < count) {
+                const rv_i64x2 t = __builtin_nontemporal_load(&pairs[e >> 1]);
+                a = t.x, b = t.y;
+            } else if (e < count) {
+                a = values[e];
+            }
+            c[2 * s] = static_cast<uint32_t>(static_cast<uint64_t>(a) - ub) & rvn::kPackMask;
+            c[2 * s + 1] = static_cast<uint32_t>(static_cast<uint64_t>(b) - ub) & rvn::kPackMask;
+        }
+        codes[w] = rv_u32x2{c[0] | (c[1] << 10) | (c[2] << 20), c[3] | (c[4] << 10) | (c[5] << 20)};
+    }
 }
 
 }  // namespace rvk

@@ -46,6 +46,9 @@ inline CodeTerm lower_term(bool sel_lt, bool sel_eq, bool sel_gt, int64_t lit, i
 // zero-extended, an interval above them stands for it; over 4-byte codes nothing does: `*ok` comes back false, the term unchanged,
 // `negate` still set, and the launch hands it on as it is (fused_launch.hip, launch_pass): the kernel tests the flag once per tile
 // and runs such a launch through the form of its loop that still flips the masks (fused_kernel.hpp).
+// A pass over PACKED codes (10 bits each, narrow_rule.hpp) calls this with code_bytes == 2, like the 2-byte cells it stages: its
+// codes reach the compare zero-extended from 10 bits, so the interval {0x10000, 0} lies above every one of them as well, and every
+// other folded interval is exact over 0..1023 because it is exact over 0..65535.
 inline CodeTerm fold_negate(const CodeTerm &t, int code_bytes, bool *ok) {
     *ok = true;
     if (!t.negate) return t;

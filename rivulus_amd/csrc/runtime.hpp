@@ -130,9 +130,12 @@ struct DevBuf {
     // The narrow companion of an Int64 values buffer (below), what the lean passes have read of the buffer so far, and whether a
     // companion was refused (a value range of 2^32 and more, or no memory for it: not tried again).  They live and die with THIS
     // record, which pool_alloc makes anew for every allocation: a freed table's block handed out again starts without codes.
-    std::shared_ptr<NarrowCodes> narrow;
-    rvn::ScanCover scan;
-    bool narrow_refused = false;
+    // A buffer holds at most one companion of each layout (narrow_rule.hpp): `narrow` 2- or 4-byte codes, `narrow_packed` 10-bit codes.
+    // Until the first of them is built every lean pass is counted in `scan`; after that the launches that cannot read it are counted in
+    // `scan_other`, whose trigger builds the other layout beside it (`other_refused`: it could not be, not tried again).
+    std::shared_ptr<NarrowCodes> narrow, narrow_packed;
+    rvn::ScanCover scan, scan_other;
+    bool narrow_refused = false, other_refused = false;
     ~DevBuf() {
         if (pool && ptr) pool->give_back(ptr, bytes);
     }
@@ -145,12 +148,15 @@ using DevBufRef = std::shared_ptr<DevBuf>;
 // reading 64, so it reads the codes instead (scan_frontend.hpp, FF_NARROW16 / FF_NARROW32) and widens them in registers.  The codes
 // depend on the column alone: every predicate over it uses them, and so does every slice of it -- they hang off the values buffer.
 // The 8-byte original always stays (the redo kernel, the sampler, every other shape read it).
-// MEMORY: + 25 % of the column for 2-byte codes, + 50 % for 4-byte codes, held until the buffer is freed (option "narrow_codes" = -1:
-// never built).  Built by narrow.hip when the buffer has been scanned often enough (narrow_rule.hpp, thresholds.hpp).
+// MEMORY: + 25 % of the column for 2-byte codes, + 50 % for 4-byte codes, + 16.7 % for packed 10-bit codes (six per 8-byte word; a
+// column scanned whole AND streamed can end with both the packed and the 2-byte form: + 41.7 %), held until the buffer is freed (option
+// "narrow_codes" = -1: never built).  Built by narrow.hip when the buffer has been scanned often enough (narrow_rule.hpp, thresholds.hpp).
 struct NarrowCodes {
     DevBufRef codes;
+    rvn::Layout layout = rvn::Layout::kPlain;  // kPacked: 10-bit codes in super-groups (narrow_rule.hpp); code_bytes is then 2, the cell a pass stages
     int code_bytes = 0;  // 2 or 4
     int64_t base = 0;
+    uint64_t range = 0;  // max - min of the covered elements (narrow_rule.hpp, value_range)
     uint64_t count = 0;  // elements covered, from element 0 of the values buffer
 };
 

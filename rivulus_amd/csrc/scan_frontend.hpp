@@ -42,6 +42,9 @@ enum : int { FF_OUTVALID = 2048 };
 // of the column's narrow companion (runtime.hpp, NarrowCodes; narrow.hip).  The compare runs on the codes (narrow_term.hpp), survivors are staged as codes, and the
 // 8-byte value = base + code is formed where a survivor is written out: the outputs are those of the plain form, bit for bit.
 enum : int { FF_NARROW16 = 4096, FF_NARROW32 = 8192 };
+// With FF_NARROW16 only: the codes lie PACKED in memory, 10 bits each, six per 8-byte word (narrow_rule.hpp, the packed layout).  It
+// says how a tile's codes are loaded and unpacked and nothing else: survivors are still staged and flushed as 2-byte cells.
+enum : int { FF_PACK10 = 16384 };
 
 // A bit stream compacted with the rows: out bit = src bit (& mask bit).
 struct BitStream {
@@ -208,6 +211,36 @@ template <int BYTES>
 __device__ __forceinline__ void unpack_pair(typename NarrowRaw<BYTES>::type raw, uint32_t &c0, uint32_t &c1) {
     c0 = BYTES == 2 ? static_cast<uint32_t>(raw) & 0xFFFFu : static_cast<uint32_t>(raw);
     c1 = BYTES == 2 ? static_cast<uint32_t>(raw) >> 16 : static_cast<uint32_t>(static_cast<uint64_t>(raw) >> 32);
+}
+
+// ---- the same rows out of a PACKED companion (FF_NARROW16 | FF_PACK10; narrow_rule.hpp, the packed layout) -------------------------
+// 10-bit codes, six per 8-byte word: word l of a 384-element super-group (64 words, 512 bytes) holds rows 2l, 2l + 1 of its three
+// 128-row groups, so lane l reads word l and owns the rows it owns with the pair loads above -- ONE 8-byte nontemporal buffer load per
+// THREE pairs, kept raw like them.  `first` (element of the buffer) must be a multiple of 384: the view's first element is (the host's
+// rule, narrow_rule.hpp packed_view_aligned) and a wave range is 64 R rows with R a multiple of 6.  The descriptor is bounded by the
+// companion bytes left, as above: the companion ends on a whole super-group whose padding is code 0.
+template <int R>
+__device__ __forceinline__ void load_rows_packed(const NarrowView &nv, uint64_t first, int lane, uint64_t (&c)[R / 6]) {
+    static_assert(R % 6 == 0, "packed codes: three pairs per word");
+    constexpr uint64_t WAVE_BYTES = 512u * (R / 6);
+    const uint64_t at = first / 384u * 512u;
+    const uint64_t left = nv.bytes > at ? nv.bytes - at : 0;
+    const uint32_t nbytes = uniform32(static_cast<uint32_t>(left < WAVE_BYTES ? left : WAVE_BYTES));
+    const uint64_t base = uniform64(reinterpret_cast<uint64_t>(nv.codes) + at);
+    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void *>(base), 0, nbytes, 0x00020000);
+#pragma unroll
+    for (int t = 0; t < R / 6; ++t) {
+        const rv_u32x2 w = __builtin_amdgcn_raw_buffer_load_b64(rsrc, lane * 8, t * 512, kStreamPolicy);
+        c[t] = (static_cast<uint64_t>(w.y) << 32) | w.x;
+    }
+}
+// pair s (0, 1, 2: the word's 128-row group; a constant once the staging loop is unrolled) of a raw word -> the codes of its two
+// rows: fields 2s, 2s + 1, one bit-field extract each
+__device__ __forceinline__ void unpack_packed_pair(uint64_t raw, int s, uint32_t &c0, uint32_t &c1) {
+    const uint32_t lo = static_cast<uint32_t>(raw), hi = static_cast<uint32_t>(raw >> 32);
+    const int k0 = 2 * s, k1 = 2 * s + 1;
+    c0 = __builtin_amdgcn_ubfe(k0 < 3 ? lo : hi, 10u * static_cast<uint32_t>(k0 % 3), 10u);
+    c1 = __builtin_amdgcn_ubfe(k1 < 3 ? lo : hi, 10u * static_cast<uint32_t>(k1 % 3), 10u);
 }
 
 // The validity words of a wave's rows travel with the row prefetch: lane k holds the aligned 64-bit

@@ -1,8 +1,8 @@
 """Diagnostic: per-phase cycle shares of the pass over narrow codes (the FF_STAMP | FF_NARROW16 instantiations, fused_narrow.hip) on
 the headline shape, x > 899 -> [x] over 1e9 resident Int64 rows.  Shares only: a stamped build's run time is never quoted.
-    python3 tools/narrow_stamp.py [rows]            (RIVULUS_GPU_LIB=<other build> for a before / after on one box)
-Per geometry (32 and 16 rows per lane, 16 waves) and ablation (option "debug": 1 = no output stores, 2 = no look-back) it prints wave 1's
-cycles per tile by phase and their shares:
+    python3 tools/narrow_stamp.py [rows] [--packed]   (RIVULUS_GPU_LIB=<other build> for a before / after on one box)
+Per geometry (32 and 16 rows per lane, 16 waves; --packed: the packed 10-bit codes under option narrow_codes = 2, 48 and 24 rows per lane)
+and ablation (option "debug": 1 = no output stores, 2 = no look-back) it prints wave 1's cycles per tile by phase and their shares:
     wait     the tile's codes are not there yet when the wave wants to evaluate them (part of eval)
     eval     unpack, compare, rank, stage (without the wait)
     barrier  from the end of the wave's own work to behind the tile's one barrier: waiting for the slowest wave
@@ -20,9 +20,9 @@ if len(sys.argv) > 1 and sys.argv[1] == "--child":
     sys.path.insert(0, ROOT)
     from rivulus_amd import capi
     from rivulus_amd.capi import RV_INT64, Predicate, Term, synth_spec
-    n, r, debug = int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4])
+    n, r, debug, mode = int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), int(sys.argv[5])
     ctx = capi.Context(0)
-    ctx.set_option("narrow_codes", 1)
+    ctx.set_option("narrow_codes", mode)
     x = ctx.generate(synth_spec(RV_INT64, seed=42, length=n))
     pred = Predicate([Term(0, ">", 899)])
     for _ in range(3):  # the scan that packs, then passes over codes
@@ -36,13 +36,15 @@ if len(sys.argv) > 1 and sys.argv[1] == "--child":
     print("kernel", ctx.last_kernel(), flush=True)
     sys.exit(0)
 
-n = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000_000
-print(f"library: {os.environ.get('RIVULUS_GPU_LIB', 'the tree')}; {n} rows, x > 899 -> [x]")
-for r in (32, 16):
+args = [a for a in sys.argv[1:] if a != "--packed"]
+packed = "--packed" in sys.argv[1:]
+n = int(args[0]) if args else 1_000_000_000
+print(f"library: {os.environ.get('RIVULUS_GPU_LIB', 'the tree')}; {n} rows, x > 899 -> [x]; {'packed 10-bit codes' if packed else '2-byte codes'}")
+for r in ((48, 24) if packed else (32, 16)):
     for debug, label in ((0, "as it runs"), (1, "no output stores"), (2, "no look-back")):
         # one form per process, each under its own time limit; the first that fails ends the run: nothing more is started on that card
         try:
-            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", str(n), str(r), str(debug)], capture_output=True, text=True, timeout=120)
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", str(n), str(r), str(debug), "2" if packed else "1"], capture_output=True, text=True, timeout=120)
         except subprocess.TimeoutExpired:
             sys.exit(f"R={r} debug={debug}: no answer within 120 s; stopped")
         kernel = [q for q in p.stdout.splitlines() if q.startswith("kernel ")]
