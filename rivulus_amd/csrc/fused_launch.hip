@@ -1,6 +1,7 @@
 // The fused filter + compact launch: shape -> instantiation, LDS and output sizing, launch, read-back, redo and overflow re-run.
 // One unit of the backend library behind include/rivulus_gpu.h (gfx950 only; compiled with hipcc).  Shared helpers and the
 // functions the units call across each other are declared in launch.hpp (namespace rvl).
+#include "fused_rule.hpp"
 #include "launch.hpp"
 #include "narrow_term.hpp"
 
@@ -9,96 +10,38 @@
 using namespace rvh;
 using namespace rvl;
 
+namespace rvk {
+// first match wins among equals, so the preferred default geometry is listed first in each table
+const FusedEntry *fused_entries(size_t *n) {
+    static const std::vector<FusedEntry> all = [] {
+        std::vector<FusedEntry> v;
+        for (auto *source : {fused_entries_lean1, fused_entries_valid1, fused_entries_multi, fused_entries_bool, fused_entries_full, fused_entries_expr,
+                             fused_entries_roomy, fused_entries_narrow}) {
+            size_t k = 0;
+            const FusedEntry *t = source(&k);
+            v.insert(v.end(), t, t + k);
+        }
+        return v;
+    }();
+    *n = all.size();
+    return all.data();
+}
+}  // namespace rvk
+
 namespace rvl {
 
 // ---------------------------------------------------------------------------------------
 // fused launch
 // ---------------------------------------------------------------------------------------
-// Smallest instantiation whose feature flags cover `need`; for one-column lean/validity
-// launches the geometry can be steered with rv_ctx_set_option("rows_per_lane", R | waves << 8).
+// The staged instantiation of a launch and the geometries it walks down through are chosen by fused_rule.hpp, over every staged entry in
+// one array; for one-column lean/validity launches the geometry can be steered with rv_ctx_set_option("rows_per_lane", R | waves << 8).
 constexpr int kNarrowFlags = rvk::FF_NARROW16 | rvk::FF_NARROW32 | rvk::FF_PACK10;
-// `prefer_r` > 0: that many rows per lane among the default level's geometries, when the class has one
-const rvk::FusedEntry *find_fused(rv_ctx *ctx, int ncols, int vec, int need, int roomy = 0, int below_r = 1 << 30, int prefer_r = 0) {
-    const rvk::FusedEntry *best = nullptr;
-    auto scan = [&](const rvk::FusedEntry *t, size_t n) {
-        for (size_t i = 0; i < n; ++i) {
-            const rvk::FusedEntry &e = t[i];
-            constexpr int kShape = rvk::FF_ONE_I64 | rvk::FF_ONE_F64 | rvk::FF_STAMP | rvk::FF_PROJALL | rvk::FF_NONULL | rvk::FF_EXPR | kNarrowFlags;  // must match exactly
-            // the generic FF_PROJALL instantiations write the selection bitmap on request (fused_kernel.hpp, kSel)
-            const int has = e.flags | (((e.flags & rvk::FF_PROJALL) && !(e.flags & (rvk::FF_ONE_I64 | rvk::FF_ONE_F64))) ? rvk::FF_SEL : 0);
-            if (e.ncols != ncols || (ncols > 0 && e.vec != vec) || (has & need) != need) continue;
-            if ((e.flags & kShape) != (need & kShape)) continue;
-            bool wanted = false;
-            if (ctx->opt_rows_per_lane > 0) {
-                const int want_r = static_cast<int>(ctx->opt_rows_per_lane & 0xFF);
-                const int want_w = static_cast<int>((ctx->opt_rows_per_lane >> 8) & 0xFF);
-                wanted = e.r == want_r && (want_w == 0 || e.waves == want_w);
-            } else if (prefer_r > 0 && roomy == 0) {
-                wanted = e.r == prefer_r;
-            }
-            // roomy 1: a 16-wave geometry with fewer rows per lane -- its LDS slots hold a larger share of a wave's
-            // rows; roomy 2: the 8-wave geometries of fused_roomy.hip, whose slots hold every row of a wave
-            if (roomy == 1 && ctx->opt_rows_per_lane <= 0 && ncols >= 1)  // ... among those with fewer than below_r rows per lane, the largest
-                wanted = best && e.waves == 16 && e.r < below_r && (best->waves != 16 || best->r >= below_r || e.r > best->r);
-            if (roomy == 2 && ctx->opt_rows_per_lane <= 0 && ncols >= 1) wanted = best && (e.waves < best->waves || (e.waves == best->waves && e.r < best->r));
-            if (!best || __builtin_popcount(e.flags) < __builtin_popcount(best->flags) ||
-                (wanted && e.flags == best->flags))
-                best = &e;
-        }
-    };
+constexpr rvf::Flags kRuleFlags = {rvk::FF_ONE_I64 | rvk::FF_ONE_F64 | rvk::FF_STAMP | rvk::FF_PROJALL | rvk::FF_NONULL | rvk::FF_EXPR | kNarrowFlags,
+                                   rvk::FF_ONE_I64 | rvk::FF_ONE_F64, rvk::FF_PROJALL, rvk::FF_NONULL, rvk::FF_SEL, kNarrowFlags, rvk::FF_PACK10};
+static rvf::Table<rvk::FusedEntry> staged_table() {
     size_t n = 0;
-    const rvk::FusedEntry *t;
-    // first match wins among equals, so list the preferred default geometry first in each table
-    for (int pass = 0; pass < 2 && !best; ++pass) {
-        t = rvk::fused_entries_lean1(&n), scan(t, n);
-        t = rvk::fused_entries_valid1(&n), scan(t, n);
-        t = rvk::fused_entries_multi(&n), scan(t, n);
-        t = rvk::fused_entries_bool(&n), scan(t, n);
-        t = rvk::fused_entries_full(&n), scan(t, n);
-        t = rvk::fused_entries_expr(&n), scan(t, n);
-        t = rvk::fused_entries_roomy(&n), scan(t, n);
-        t = rvk::fused_entries_narrow(&n), scan(t, n);
-        vec = 1;  // every feature set exists with 8-byte loads
-    }
-    return best;
-}
-// `prefer`: shape flags worth having when an instantiation exists (FF_PROJALL)
-const rvk::FusedEntry &pick_fused(rv_ctx *ctx, int ncols, int vec, int need, int prefer = 0, int roomy = 0, int below_r = 1 << 30, int prefer_r = 0) {
-    // the refinements the launch qualifies for, dropped one by one (FF_NONULL first) until an instantiation exists
-    const rvk::FusedEntry *best = nullptr;
-    for (const int pf : {prefer, prefer & ~rvk::FF_NONULL}) {
-        if (best || !pf) continue;
-        best = find_fused(ctx, ncols, vec, need | pf, roomy, below_r, prefer_r);
-        if (best && (best->flags & ~(need | pf)) != 0) best = nullptr;  // not at the price of features the launch does not need
-    }
-    if (!best) best = find_fused(ctx, ncols, vec, need, roomy, below_r, prefer_r);
-    require(best != nullptr, RV_ERR_INTERNAL, fmt("no fused kernel variant for %d columns, flags %d", ncols, need));
-    return *best;
-}
-
-// Does the narrow table hold an instantiation with exactly these flags -- and, for a forced geometry (option "rows_per_lane" =
-// R | waves << 8, waves 0: any), at exactly that geometry?
-static bool narrow_instantiated(int flags, int64_t forced) {
-    size_t n = 0;
-    const rvk::FusedEntry *t = rvk::fused_entries_narrow(&n);
-    const int want_r = static_cast<int>(forced & 0xFF), want_w = static_cast<int>((forced >> 8) & 0xFF);
-    for (size_t i = 0; i < n; ++i)
-        if (t[i].flags == flags && (forced <= 0 || (t[i].r == want_r && (want_w == 0 || t[i].waves == want_w)))) return true;
-    return false;
-}
-// The plain lean Int64 instantiation of a narrow one's geometry (a diagnostic one's: without the stamps): what re-runs a pass over
-// codes after an output overflow.
-static void (*plain_twin(const rvk::FusedEntry &e))(const rvk::FusedParams) {
-    size_t n = 0;
-    const rvk::FusedEntry *t = rvk::fused_entries_lean1(&n);
-    for (size_t i = 0; i < n; ++i)
-        if (t[i].ncols == e.ncols && t[i].r == e.r && t[i].vec == e.vec && t[i].waves == e.waves && t[i].flags == (e.flags & ~(kNarrowFlags | rvk::FF_STAMP))) return t[i].fn;
-    const rvk::FusedEntry tall = rvk::narrow_tall_plain();  // (not a geometry of the lean table)
-    if (tall.ncols == e.ncols && tall.r == e.r && tall.vec == e.vec && tall.waves == e.waves && tall.flags == (e.flags & ~(kNarrowFlags | rvk::FF_STAMP))) return tall.fn;
-    t = rvk::narrow_packed_plain(&n);  // (nor are the packed geometries, but for 24 rows per lane)
-    for (size_t i = 0; i < n; ++i)
-        if (t[i].ncols == e.ncols && t[i].r == e.r && t[i].vec == e.vec && t[i].waves == e.waves && t[i].flags == (e.flags & ~(kNarrowFlags | rvk::FF_STAMP))) return t[i].fn;
-    return nullptr;
+    const rvk::FusedEntry *t = rvk::fused_entries(&n);
+    return {t, n};
 }
 // (costs several microseconds: once per (kernel, LDS size) and context)
 static void enable_lds(rv_ctx *ctx, const void *fn, size_t lds) {
@@ -420,7 +363,10 @@ struct LaunchChoice {
 };
 
 // per-batch counts out of the pass: a batch must be a whole number of the geometry's wave ranges (64 x rows per lane)
-static bool counts_in_pass(const BatchReq *req, int r) { return req && req->counts && req->chunk_rows % (64u * static_cast<uint64_t>(r)) == 0; }
+static bool counts_in_pass(const BatchReq *req, int r) { return req && req->counts && rvf::whole_ranges(req->chunk_rows, r); }
+// The direct kernel's LDS bytes: one slot per wave, its rows of every loaded column (+ a validity byte per row for each of the nv_out
+// columns with an output bitmap).
+static size_t direct_lds(const rvk::DirectEntry &g, int nvals, int nv_out) { return static_cast<size_t>(g.waves) * 64 * g.r * (8 * static_cast<size_t>(nvals) + nv_out); }
 
 // The direct instantiation for this launch's columns and features, or none.
 static const rvk::DirectEntry *find_direct(rv_ctx *ctx, const Bound &b, int nv_out, double seen, const BatchReq *req, const RangeOffsets *ranges) {
@@ -436,8 +382,6 @@ static const rvk::DirectEntry *find_direct(rv_ctx *ctx, const Bound &b, int nv_o
     // counts a batch that is a whole number of ranges
     const rvk::DirectEntry *fallback = nullptr;
     bool tall_tried = false;
-    // (columns with an output bitmap: a validity byte per row each in the LDS slot)
-    auto direct_lds = [&](const rvk::DirectEntry &g) { return static_cast<size_t>(g.waves) * 64 * g.r * (8 * static_cast<size_t>(nvals) + nv_out); };
     constexpr size_t kDirectLdsBudget = (160 * 1024) / 2 - 512;
     for (int t = 0; t < 2 && !found; ++t) {
         size_t cnt = 0;
@@ -449,7 +393,7 @@ static const rvk::DirectEntry *find_direct(rv_ctx *ctx, const Bound &b, int nv_o
                 if ((ctx->opt_direct_r <= 0 || g.r == ctx->opt_direct_r) && (ctx->opt_direct_waves <= 0 || g.waves == ctx->opt_direct_waves)) found = &g;
                 continue;
             }
-            if (g.waves != 8 || direct_lds(g) > kDirectLdsBudget) continue;  // two workgroups per CU have to fit
+            if (g.waves != 8 || direct_lds(g, nvals, nv_out) > kDirectLdsBudget) continue;  // two workgroups per CU have to fit
             const bool serves = (!ranges || 4096u % (64u * static_cast<uint32_t>(g.r)) == 0) && (!(req && req->counts) || counts_in_pass(req, g.r));
             // one loaded column while fewer than kDirectTallBelow survive (a table of runs at 30-50 %, a selection just past
             // kDirectFromOneColumn): the 16-row geometry -- what the launch keeps in registers and LDS behind a tile's aggregate
@@ -457,7 +401,7 @@ static const rvk::DirectEntry *find_direct(rv_ctx *ctx, const Bound &b, int nv_o
             if (serves && npred == 1 && nvals == 1 && !nv_out && seen >= 0.0 && seen < rvt::kDirectTallBelow && g.r != 16 && !tall_tried) {
                 tall_tried = true;
                 for (size_t k = i + 1; k < cnt; ++k)
-                    if (tab[k].np == 1 && tab[k].nq == 0 && tab[k].r == 16 && tab[k].waves == 8 && tab[k].flags == g.flags && direct_lds(tab[k]) <= kDirectLdsBudget &&
+                    if (tab[k].np == 1 && tab[k].nq == 0 && tab[k].r == 16 && tab[k].waves == 8 && tab[k].flags == g.flags && direct_lds(tab[k], nvals, nv_out) <= kDirectLdsBudget &&
                         (!(req && req->counts) || counts_in_pass(req, 16))) {
                         found = &tab[k];
                         break;
@@ -472,8 +416,8 @@ static const rvk::DirectEntry *find_direct(rv_ctx *ctx, const Bound &b, int nv_o
     return found;
 }
 
-// The direct kernel for the launch, when an instantiation serves it (find_direct), with its tiles and LDS: one slot per wave, its rows of
-// every loaded column (+ a validity byte per row and column when nulls can survive).  A staged geometry's cap and stage_row_bytes stay.
+// The direct kernel for the launch, when an instantiation serves it (find_direct), with its tiles and LDS (direct_lds).  A staged
+// geometry's cap and stage_row_bytes stay.
 static bool use_direct(rv_ctx *ctx, LaunchChoice &c, const Bound &b, int nv_out, double seen, const BatchReq *req, const RangeOffsets *ranges,
                        bool sel_deferred) {
     const rvk::DirectEntry *d = find_direct(ctx, b, nv_out, seen, req, ranges);
@@ -487,7 +431,7 @@ static bool use_direct(rv_ctx *ctx, LaunchChoice &c, const Bound &b, int nv_out,
     require(ntiles64 < (1ull << 31) - 1, RV_ERR_UNSUPPORTED, "batch too large for one launch");
     c.ntiles = static_cast<uint32_t>(ntiles64);
     c.stages = 2;
-    c.lds = static_cast<size_t>(d->waves) * 64 * d->r * (8 * static_cast<size_t>(b.nvals) + nv_out);
+    c.lds = direct_lds(*d, b.nvals, nv_out);
     return true;
 }
 
@@ -612,7 +556,7 @@ static LaunchChoice choose_launch(rv_ctx *ctx, const FusedLaunch &L, const Bound
     const bool diag = ctx->opt_stamp || ctx->opt_debug;
     if (narrow && c.need == rvk::FF_ONE_I64 && vec == 2 && !L.place && ((ctx->opt_rows_per_lane <= 0 && !diag) || ctx->opt_narrow_codes > 0)) {
         const int codes = narrow->layout == rvn::Layout::kPacked ? (rvk::FF_NARROW16 | rvk::FF_PACK10) : (narrow->code_bytes == 2 ? rvk::FF_NARROW16 : rvk::FF_NARROW32);
-        if (narrow_instantiated(c.need | codes | (diag ? rvk::FF_STAMP : 0), ctx->opt_rows_per_lane)) c.need |= codes;
+        if (rvf::holds_exactly(staged_table(), c.need | codes | (diag ? rvk::FF_STAMP : 0), ctx->opt_rows_per_lane)) c.need |= codes;
     }
     // diagnostics (per-phase stamps, ablations) exist in the FF_STAMP instantiations only; "debug" implies them
     if (diag && ((c.need & ~kNarrowFlags) == rvk::FF_ONE_I64 || (nvals == 2 && c.need == rvk::FF_VALIDITY))) c.need |= rvk::FF_STAMP;
@@ -659,41 +603,25 @@ static LaunchChoice choose_launch(rv_ctx *ctx, const FusedLaunch &L, const Bound
     // on the share of redone tiles did: the dense geometry redoes none).  x > lit -> [x, y, fn], 5e8 rows, ms per call at
     // 10 / 20 / 30 / 50 / 90 %: default geometry + redo kernel 2.4 / 8.1 / 8.7 / 9.8 / 12.4; walked down 2.4 / 3.7 / 3.8 / 6.5 / 6.9
     // (tools/roomy_ab.py; one column: tools/dense_one.py).
-    int min_r = 0, below_r = 1 << 30;  // pick_fused's `roomy` level (0 default, 1 walk down the 16-wave geometries, 2 fewest waves)
-    bool dense_sizing = false;
-    while (!c.direct) {
-        // (a pass over codes without per-batch counts: the tall geometry, fused_narrow.hip -- a 1024-row batch is no whole number of its
-        // 2048-row wave ranges)
-        const int tall_r = (c.need & rvk::FF_PACK10) ? rvk::kPackedTallRows : (((c.need & kNarrowFlags) && !(req && req->counts)) ? rvk::kNarrowTallRows : 0);
-        c.staged = &pick_fused(ctx, nvals, vec, c.need, prefer, min_r, below_r, tall_r);
-        if (min_r == 1 && (c.staged->waves != 16 || c.staged->r >= below_r)) {  // no 16-wave geometry below that many rows per lane left
-            if (!dense_sizing) {  // the walk again, sized for a dense selection
-                dense_sizing = true;
-                below_r = 1 << 30;
-            } else if (c.need & rvk::FF_PACK10) {
-                // denser than the packed class's last geometry (12 rows per lane) admits: the plain lean pass over the 8-byte values,
-                // from the top of ITS walk, as over a buffer without a companion
-                c.need &= ~kNarrowFlags;
-                min_r = 0, below_r = 1 << 30, dense_sizing = false;
-            } else {
-                min_r = 2;
-            }
-            continue;
-        }
-        if (sel_deferred && !c.make_selection && !counts_in_pass(req, c.staged->r)) {  // the caller will count the selection bitmap instead
+    // (a pass over packed codes goes on with the plain lean class from its top instead of 3.)  The candidates and their order are the
+    // rule's (fused_rule.hpp, Walk); here each one is sized, and the walk ends at the first whose slots are not crowded.
+    rvf::Walk<rvk::FusedEntry> walk{staged_table(), kRuleFlags, {rvk::kNarrowTallRows, rvk::kPackedTallRows}, nvals, vec, c.need, prefer, ctx->opt_rows_per_lane, req && req->counts};
+    for (c.staged = c.direct ? nullptr : walk.first(); !c.direct; c.staged = walk.next()) {
+        // the caller will count the selection bitmap instead (a batch is no whole number of this candidate's wave ranges): the class that
+        // writes it, at this step of the walk (the forms that write the selection bitmap read the 8-byte values)
+        if (c.staged && sel_deferred && !c.make_selection && !counts_in_pass(req, c.staged->r)) {
             c.make_selection = true;
-            c.need = (c.need | rvk::FF_SEL) & ~kNarrowFlags;  // (the forms that write the selection bitmap read the 8-byte values)
-            c.staged = &pick_fused(ctx, nvals, vec, c.need, prefer, min_r, below_r);
+            c.staged = walk.reclass((walk.need | rvk::FF_SEL) & ~kNarrowFlags);
         }
-        size_staged(ctx, c, *c.staged, n, nvals, nxs, row_bytes, dense_sizing);
+        require(c.staged != nullptr, RV_ERR_INTERNAL, fmt("no fused kernel variant for %d columns, flags %d", nvals, walk.need));
+        c.need = walk.need;
+        size_staged(ctx, c, *c.staged, n, nvals, nxs, row_bytes, walk.dense_sizing());
         // expected survivors of a wave (+ 10 % and three standard deviations of a binomial) against the slot
         const uint32_t rows_per_wave = 64u * static_cast<uint32_t>(c.staged->r);
         const double expect = seen * rows_per_wave;
-        const bool crowded = min_r < 2 && ctx->opt_rows_per_lane <= 0 && nvals >= 1 && c.stage_row_bytes && c.cap < rows_per_wave &&
-                             seen > 0.0 && expect * rvt::kCrowdedMargin + rvt::kCrowdedSigmas * std::sqrt(expect) > static_cast<double>(c.cap);
-        if (!crowded) break;
-        below_r = c.staged->r;  // the next 16-wave geometry with fewer rows per lane
-        min_r = 1;
+        const bool crowded = c.stage_row_bytes && c.cap < rows_per_wave && seen > 0.0 &&
+                             expect * rvt::kCrowdedMargin + rvt::kCrowdedSigmas * std::sqrt(expect) > static_cast<double>(c.cap);
+        if (!crowded || walk.last()) break;
     }
     if (!c.direct && seen >= 0.0 && c.stage_row_bytes) {
         c.redo_expected = redo_estimate(ctx, L, seen, sampled_now, c.cap, 64u * static_cast<uint32_t>(c.staged->r));
@@ -757,10 +685,7 @@ static void launch_pass(rv_ctx *ctx, FusedLaunch &L, const LaunchChoice &c, int 
         p.in.terms[1].lit = static_cast<int64_t>(static_cast<uint64_t>(ct.lo) | (static_cast<uint64_t>(ct.span) << 32));
         p.in.terms[1].packed = ct.negate ? 1u : 0u;
         p.in.terms[1].pad = 0;
-        L.fn_plain = plain_twin(*c.staged);
-        L.lds_plain = c.lds_plain;
-        L.depth_plain = static_cast<int32_t>(c.stages_plain) - 1;
-        require(L.fn_plain != nullptr, RV_ERR_INTERNAL, "narrow pass without a plain instantiation of its geometry");
+        L.plain = {c.staged->fn_plain, c.lds_plain, static_cast<int32_t>(c.stages_plain) - 1};
         ctx->narrow_passes += 1;
     }
     // persistent grid: as many workgroups as the device keeps resident (tiles are handed out
@@ -973,11 +898,11 @@ uint64_t fused_finish(rv_ctx *ctx, FusedLaunch &L) {
         const size_t zeroed = kCtrlBytes + (static_cast<size_t>(p.ntiles) + L.nranges) * 8;
         RV_HIP(hipMemsetAsync(L.ctrl.dev, 0, (zeroed + 15) & ~size_t(15), ctx->stream));
         // a pass over codes: re-run over the 8-byte values, whose slots of the same rows take 8 bytes per row
-        if (L.fn_plain) {
-            enable_lds(ctx, reinterpret_cast<const void *>(L.fn_plain), L.lds_plain);
-            p.depth = L.depth_plain;  // (the stages lds_plain holds: size_staged)
+        if (L.plain.fn) {
+            enable_lds(ctx, reinterpret_cast<const void *>(L.plain.fn), L.plain.lds);
+            p.depth = L.plain.depth;  // (the stages plain.lds holds: size_staged)
         }
-        hipLaunchKernelGGL(L.fn_plain ? L.fn_plain : L.fn, dim3(L.grid), dim3(L.block), L.fn_plain ? L.lds_plain : L.lds, ctx->stream, p);
+        hipLaunchKernelGGL(L.plain.fn ? L.plain.fn : L.fn, dim3(L.grid), dim3(L.block), L.plain.fn ? L.plain.lds : L.lds, ctx->stream, p);
         RV_HIP(hipGetLastError());
         RV_HIP(hipMemcpyAsync(L.ctrl.host, L.ctrl.dev, kCtrlBytes, hipMemcpyDeviceToHost, ctx->stream));
         RV_HIP(hipStreamSynchronize(ctx->stream));

@@ -36,39 +36,38 @@ namespace rvk {
 // 0.564 -> 0.478 ms with the branch-free stores, 0.495 ms with stores under an exec mask (two vector instructions fewer per pair, four
 // exec writes more: taken out; profiles/narrow3_steps.txt).  At 0.478 ms the pass moves its 2.93 GB at 6.1 TB/s: what a streaming
 // kernel reaches on this part.
+// An entry carries its PLAIN TWIN, the lean Int64 instantiation of its geometry over the 8-byte values (RV_NARROW below names both, so a
+// geometry without one cannot be listed): what re-runs a pass over codes after an output overflow.  16, 8, 4 and 24 rows per lane are
+// geometries of the lean table (fused_lean1.hip instantiates them: declared here, not built a second time); 32, 48 and 12 are built in
+// this unit only -- 64 and 96 value registers per lane at 32 and 48 rows spill at 128 VGPRs (profiles/narrow4_resources.txt has their
+// scratch): a rare second pass, never the launch a query is sized for.
 // The first entry of a flags class is the default geometry; kNarrowTallRows rows per lane is what a launch without per-batch counts
 // takes (fused_launch.hip): a tile's codes are a quarter or half of its rows' bytes, so twice the rows per lane put twice the bytes
 // on their way per request and halve the per-tile costs (barrier, ticket, descriptor) per row.  The geometries with fewer rows per lane
 // are the ones the plain lean form walks down through for denser selections.
+#define RV_NARROW(R, FLAGS) ::rvk::FusedEntry{1, R, 2, 16, FLAGS, &::rvk::fused_filter_compact<1, R, 2, 16, FLAGS>, &::rvk::fused_filter_compact<1, R, 2, 16, ::rvk::FF_ONE_I64>}
+extern template __global__ void fused_filter_compact<1, 16, 2, 16, FF_ONE_I64>(const FusedParams);
+extern template __global__ void fused_filter_compact<1, 8, 2, 16, FF_ONE_I64>(const FusedParams);
+extern template __global__ void fused_filter_compact<1, 4, 2, 16, FF_ONE_I64>(const FusedParams);
+extern template __global__ void fused_filter_compact<1, 24, 2, 16, FF_ONE_I64>(const FusedParams);
 const FusedEntry *fused_entries_narrow(size_t *n) {
     static const FusedEntry t[] = {
-        RV_FUSED(1, 16, 2, 16, FF_ONE_I64 | FF_NARROW16), RV_FUSED(1, 32, 2, 16, FF_ONE_I64 | FF_NARROW16),
-        RV_FUSED(1, 8, 2, 16, FF_ONE_I64 | FF_NARROW16),  RV_FUSED(1, 4, 2, 16, FF_ONE_I64 | FF_NARROW16),
+        RV_NARROW(16, FF_ONE_I64 | FF_NARROW16), RV_NARROW(32, FF_ONE_I64 | FF_NARROW16),
+        RV_NARROW(8, FF_ONE_I64 | FF_NARROW16),  RV_NARROW(4, FF_ONE_I64 | FF_NARROW16),
         // (4-byte codes: no tall geometry yet.  32 rows per lane compile to 108 VGPRs without scratch in this form -- the parent's widened
         //  form spilled -- but the geometry has not been measured, and the class keeps what has been)
-        RV_FUSED(1, 16, 2, 16, FF_ONE_I64 | FF_NARROW32), RV_FUSED(1, 8, 2, 16, FF_ONE_I64 | FF_NARROW32), RV_FUSED(1, 4, 2, 16, FF_ONE_I64 | FF_NARROW32),
+        RV_NARROW(16, FF_ONE_I64 | FF_NARROW32), RV_NARROW(8, FF_ONE_I64 | FF_NARROW32), RV_NARROW(4, FF_ONE_I64 | FF_NARROW32),
         // diagnostic (options "stamp" / "debug": phase cycle sums and the ablations of a pass over 2-byte codes, tools/narrow_stamp.py)
-        RV_FUSED(1, 16, 2, 16, FF_STAMP | FF_ONE_I64 | FF_NARROW16), RV_FUSED(1, 32, 2, 16, FF_STAMP | FF_ONE_I64 | FF_NARROW16),
+        RV_NARROW(16, FF_STAMP | FF_ONE_I64 | FF_NARROW16), RV_NARROW(32, FF_STAMP | FF_ONE_I64 | FF_NARROW16),
         // packed codes (FF_PACK10, always with FF_NARROW16: the cells staged in LDS stay 2-byte codes): kPackedTallRows rows per lane
         // first, then the geometries the walk down at denser selections takes; a selection denser than the 12-row one admits reads the
         // 8-byte values through the plain lean pass (fused_launch.hip, choose_launch)
         // (1e9 rows, x > 899, kernel ms by events, same box, alternating processes: 48 rows per lane 0.438, 36 0.489, 24 0.589, against
         //  0.470 of the 2-byte codes at 32; 36 was instantiated for the experiment only: profiles/narrow4_steps.txt)
-        RV_FUSED(1, 48, 2, 16, FF_ONE_I64 | FF_NARROW16 | FF_PACK10), RV_FUSED(1, 24, 2, 16, FF_ONE_I64 | FF_NARROW16 | FF_PACK10),
-        RV_FUSED(1, 12, 2, 16, FF_ONE_I64 | FF_NARROW16 | FF_PACK10),
-        RV_FUSED(1, 48, 2, 16, FF_STAMP | FF_ONE_I64 | FF_NARROW16 | FF_PACK10), RV_FUSED(1, 24, 2, 16, FF_STAMP | FF_ONE_I64 | FF_NARROW16 | FF_PACK10),
+        RV_NARROW(48, FF_ONE_I64 | FF_NARROW16 | FF_PACK10), RV_NARROW(24, FF_ONE_I64 | FF_NARROW16 | FF_PACK10),
+        RV_NARROW(12, FF_ONE_I64 | FF_NARROW16 | FF_PACK10),
+        RV_NARROW(48, FF_STAMP | FF_ONE_I64 | FF_NARROW16 | FF_PACK10), RV_NARROW(24, FF_STAMP | FF_ONE_I64 | FF_NARROW16 | FF_PACK10),
     };
-    *n = sizeof(t) / sizeof(t[0]);
-    return t;
-}
-// The plain lean Int64 instantiation of a narrow geometry the lean table (fused_lean1.hip) does not hold: what re-runs a pass over
-// codes after an output overflow, over the 8-byte values.  (Its 64 value registers per lane spill at 128 VGPRs: a rare second pass,
-// never the launch a query is sized for.)
-FusedEntry narrow_tall_plain() { return RV_FUSED(1, kNarrowTallRows, 2, 16, FF_ONE_I64); }
-// ... and of the packed geometries (24 rows per lane is in the lean table): 96 value registers per lane at 48 rows, which spill like
-// the tall one's; profiles/narrow4_resources.txt has their scratch
-const FusedEntry *narrow_packed_plain(size_t *n) {
-    static const FusedEntry t[] = {RV_FUSED(1, 48, 2, 16, FF_ONE_I64), RV_FUSED(1, 12, 2, 16, FF_ONE_I64)};
     *n = sizeof(t) / sizeof(t[0]);
     return t;
 }

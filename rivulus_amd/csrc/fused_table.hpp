@@ -1,5 +1,5 @@
-// Launch tables of the fused / aggregate kernel instantiations.  The instantiations are
-// spread over several translation units (fused_nc*.hip) so hipcc can build them in parallel.
+// Launch tables of the fused / aggregate kernel instantiations.  The instantiations are spread over several translation units (the
+// fused_*.hip table sources and agg_table.hip, one accessor each) so hipcc can build them in parallel.
 #pragma once
 
 #include "agg_kernel.hpp"
@@ -10,12 +10,15 @@ namespace rvk {
 struct FusedEntry {
     int ncols, r, vec, waves, flags;
     void (*fn)(const FusedParams);
+    // a pass over codes (fused_narrow.hip) only: the plain lean Int64 instantiation of its geometry, which re-runs it over the 8-byte
+    // values after an output overflow
+    void (*fn_plain)(const FusedParams);
 };
 struct AggEntry {
     int ncols, r, vec, waves, flags;
     void (*fn)(const AggParams);
 };
-#define RV_FUSED(NC, R, V, W, F) ::rvk::FusedEntry{NC, R, V, W, F, &::rvk::fused_filter_compact<NC, R, V, W, F>}
+#define RV_FUSED(NC, R, V, W, F) ::rvk::FusedEntry{NC, R, V, W, F, &::rvk::fused_filter_compact<NC, R, V, W, F>, nullptr}
 #define RV_AGG(NC, R, V, W, F) ::rvk::AggEntry{NC, R, V, W, F, &::rvk::filter_agg_kernel<NC, R, V, W, F>}
 
 // each returns a static array and its length
@@ -29,8 +32,8 @@ const FusedEntry *fused_entries_roomy(size_t *n);   // 2..4 columns, slots that 
 const FusedEntry *fused_entries_narrow(size_t *n);  // 1 Int64 column read as 2- / 4-byte codes of its narrow companion
 constexpr int kNarrowTallRows = 32;                 // rows per lane of a narrow pass without per-batch counts (fused_narrow.hip)
 constexpr int kPackedTallRows = 48;                 // ... of a pass over packed codes (FF_PACK10): the same 16 code registers per lane
-FusedEntry narrow_tall_plain();                     // the plain lean Int64 form of that geometry
-const FusedEntry *narrow_packed_plain(size_t *n);   // ... of the packed geometries the lean table does not hold
+// every staged entry as one array, in the order above (the first listed entry of a class is its default geometry: fused_rule.hpp)
+const FusedEntry *fused_entries(size_t *n);
 // the direct (register-staged) kernel for dense selections (direct_kernel.hpp): np 8-byte columns the predicate reads, nq more
 // that are only projected; flags: FF_VALIDITY / FF_BOOL of the predicate's inputs
 struct DirectEntry {

@@ -129,14 +129,16 @@ struct FusedLaunch {
     bool overflowed = false;
     uint32_t out_bias = 0;  // out: FusedParams::out_bias of the launch (place_base & 15)
     // ---- the lean one-column Int64 pass (FF_ONE_I64) and the narrow companion of the buffer it reads (narrow.hip): fused_finish counts
-    //      the pass towards the buffer's whole scans; a pass that read CODES is re-run after an output overflow by `fn_plain`, the same
+    //      the pass towards the buffer's whole scans; a pass that read CODES is re-run after an output overflow by `plain`, the same
     //      geometry over the 8-byte values
     DevBufRef lean_values;
     uint64_t lean_offset = 0;
     bool lean_counts = false;  // the launch asked for per-batch counts (a stream's window): such launches read no packed companion
-    void (*fn_plain)(const rvk::FusedParams) = nullptr;
-    size_t lds_plain = 0;  // its dynamic LDS: the same slot rows at 8 bytes each (the pass over codes stages 2 or 4)
-    int32_t depth_plain = 2;  // FusedParams::depth of that re-run (stages - 1)
+    struct PlainRerun {
+        void (*fn)(const rvk::FusedParams) = nullptr;  // the entry's plain twin (FusedEntry::fn_plain); null: the pass re-runs itself
+        size_t lds = 0;     // its dynamic LDS: the same slot rows at 8 bytes each (the pass over codes stages 2 or 4)
+        int32_t depth = 2;  // FusedParams::depth of that re-run (stages - 1)
+    } plain;
 };
 struct SegmentOverflow {};  // thrown by run_segmented_pass's callee chain: the shared outputs were too small -- the caller falls back to one pass
 

@@ -105,9 +105,10 @@ def same_float(got, want):
 # ---- the filter kernels' launch tables, read from the sources ---------------------------------------------------------------
 CSRC = os.path.join(os.path.dirname(THRESHOLDS))
 FUSED_SOURCES = ("fused_lean1.hip", "fused_valid1.hip", "fused_multi.hip", "fused_bool.hip", "fused_full.hip", "fused_expr.hip", "fused_roomy.hip")
+NARROW_SOURCE = "fused_narrow.hip"  # passes over codes: RV_NARROW(R, FLAGS) is fused_filter_compact<1,R,2,16,FLAGS> and its plain twin
 DIRECT_SOURCES = ("fused_direct.hip", "fused_direct2.hip")
 REDO_SOURCE = "fused_full.hip"
-_ENTRY = re.compile(r"\b(RV_FUSED|RV_DIRECT3|RV_DIRECT)\(([^()]*)\)")
+_ENTRY = re.compile(r"\b(RV_FUSED|RV_NARROW|RV_DIRECT3|RV_DIRECT)\(([^()]*)\)")
 
 
 def _table_text(name):
@@ -147,6 +148,8 @@ def table_entries(name):
         if macro == "RV_DIRECT3":
             a, b, c, d = (int(v) for v in args)
             out += [("fused_direct_compact", a, b, c, d, f) for f in (0, names["FF_VALIDITY"], names["FF_VALIDITY"] | names["FF_BOOL"])]
+        elif macro == "RV_NARROW":
+            out.append(("fused_filter_compact", 1, int(args[0]), 2, 16, _flag_value(args[1], names)))
         else:
             a, b, c, d = (int(v) for v in args[:4])
             out.append(("fused_filter_compact" if macro == "RV_FUSED" else "fused_direct_compact", a, b, c, d, _flag_value(args[4], names)))
