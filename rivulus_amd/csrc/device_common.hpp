@@ -120,6 +120,26 @@ __device__ __forceinline__ uint32_t opaque_uniform(uint32_t x) {
     asm volatile("" : "+s"(x));
     return x;
 }
+// A wave-uniform kernel parameter the tile loop uses, as scalars OF ITS OWN.  The parameter block arrives in 16-register tuples; a
+// field read inside the loop keeps its whole tuple alive, and at the scalar file's limit the tuple is spilled and reloaded whole -- 16
+// v_readlane in front of a single use.  Copied out before the loop, the field costs its own one or two registers and the tuple dies.
+// (An s_mov the compiler cannot fold: a tied "+s" operand is coalesced with the tuple's sub-register and keeps the tuple alive.
+//  readfirstlane: a value the compiler chose to form with vector instructions becomes a scalar first; of a scalar it is a copy.)
+__device__ __forceinline__ uint32_t own_scalar(uint32_t x) {
+    uint32_t y;
+    asm volatile("s_mov_b32 %0, %1" : "=s"(y) : "s"(uniform32(x)));
+    return y;
+}
+__device__ __forceinline__ uint64_t own_scalars(uint64_t x) {
+    return (static_cast<uint64_t>(own_scalar(static_cast<uint32_t>(x >> 32))) << 32) | own_scalar(static_cast<uint32_t>(x));
+}
+// ... of a pointer to GLOBAL memory (every pointer of a parameter block is): rebuilt from integers it would be a generic pointer, and
+// its loads and stores flat_ instructions
+template <class T>
+__device__ __forceinline__ T *own_scalars(T *ptr) {
+    typedef __attribute__((address_space(1))) T Global;
+    return (T *)(Global *)own_scalars(reinterpret_cast<uint64_t>(ptr));
+}
 
 // ---- counters of set bits etc. that many waves add to ------------------------------------------------------------
 // Atomics on ONE address are served one at a time, 12 ns each: 8192 waves adding their partial count to the same word at
@@ -155,6 +175,15 @@ __device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
         uint32_t hi = __shfl_xor(static_cast<uint32_t>(v >> 32), s, 64);
         v += (static_cast<uint64_t>(hi) << 32) | lo;
     }
+    return v;
+}
+// inclusive prefix sum over each ROW of 16 lanes (row_shr 1 / 2 / 4 / 8; gfx9 DPP controls, lanes without a source add 0): lane
+// 16 r + 15 holds row r's sum -- what sixteen wave totals, one per lane, need (fused_kernel.hpp, publish)
+__device__ __forceinline__ uint32_t row16_scan_u32(uint32_t v) {
+    v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x111, 0xf, 0xf, false));
+    v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x112, 0xf, 0xf, false));
+    v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x114, 0xf, 0xf, false));
+    v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x118, 0xf, 0xf, false));
     return v;
 }
 // inclusive prefix sum over the 64 lanes of a wave: row_shr 1 / 2 / 4 / 8 inside the rows of 16, then row_bcast 15 and 31 carry

@@ -30,6 +30,7 @@
 
 #include "lookback.hpp"
 #include "scan_frontend.hpp"
+#include "tile_addr.hpp"
 
 namespace rvk {
 
@@ -81,6 +82,31 @@ struct FusedParams {
     // 8-byte original, which the redo kernel and a re-run's plain kernel read
     NarrowView narrow;
 };
+
+// The per-launch constants of the tile loop (tile_addr.hpp: which tile is ragged and by how much; a pass over codes: where a tile's and a
+// wave's codes lie) of a launch with ONE term travel in the term slots 2 and 3, 32 bytes that nothing else reads (nterms stays 1; slot 1
+// holds a pass over codes' interval, see the kernel) -- like that interval they leave the kernel's parameter block as it was, byte for
+// byte: a field more moves the tuples the block is loaded in and with them the register allocation of every instantiation, those
+// that never read it included.
+static_assert(kMaxTerms >= 4, "term slots 1 to 3 carry a one-term launch's code interval and tile constants");
+__host__ __device__ inline void put_tile_walk(ScanInputs &in, const rvtile::TileWalk &w) {
+    in.terms[2].lit = static_cast<int64_t>(w.view_byte0);
+    in.terms[2].packed = w.tile_bytes;
+    in.terms[2].pad = w.wave_bytes;
+    in.terms[3].lit = static_cast<int64_t>(w.bytes);
+    in.terms[3].packed = w.first_ragged_tile;
+    in.terms[3].pad = w.ragged_rows;
+}
+__host__ __device__ inline rvtile::TileWalk get_tile_walk(const ScanInputs &in) {
+    rvtile::TileWalk w{};
+    w.view_byte0 = static_cast<uint64_t>(in.terms[2].lit);
+    w.tile_bytes = in.terms[2].packed;
+    w.wave_bytes = in.terms[2].pad;
+    w.bytes = static_cast<uint64_t>(in.terms[3].lit);
+    w.first_ragged_tile = in.terms[3].packed;
+    w.ragged_rows = in.terms[3].pad;
+    return w;
+}
 
 // The dynamic LDS block of the fused kernel.  Helpers address it by byte offset (generic
 // pointers into LDS handed to out-of-line functions trip a gfx950 codegen bug in ROCm 7.2).
@@ -176,6 +202,12 @@ __device__ __forceinline__ unsigned long long stamp_now() {
 // the scan like any other -- its output range is reserved -- but leaves ITS 64 R rows to the redo kernel
 // (fused_redo_waves), which re-reads that wave range alone and writes it at the reserved offset: the tile's
 // other waves flush as usual, and no wave of the redo kernel waits for another.
+// A parameter the tile loop reads: the kernel's own scalar copy where the loop's fixed part is cut (kLeanTile, `own`, below), else the
+// parameter block's field where it is used, as before.  Macros on purpose: the condition is a constant, so the compiler emits the one arm
+// and the forms that keep the old loop compile to the code they had.  (Lambdas that captured the parameter block by reference to make
+// this choice moved those forms' register allocation: fused_full's <3,4,1,16,15> gained 16 bytes of scratch.)
+#define RV_TILE_PARAM(field) (kLeanTile ? own.field : p.field)
+#define RV_TILE_WRITES(bit, field) (kLeanTile ? (own.side & bit) != 0 : p.field != nullptr)
 constexpr unsigned long long kRedoFlag = 1ull << 63;
 template <int NCOLS, int R, int VEC, int WAVES, int FLAGS>
 __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4))) void fused_filter_compact(const FusedParams p) {
@@ -240,6 +272,62 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
         return;
     }
 
+    // ---- the tile loop's fixed part, cut (kLeanTile) ------------------------------------------------------------------------------
+    // Outside its staging and flush loops a tile of the headline pass listed 363 instructions beside the staging's 602, 118 of them v_readlane
+    // reloads of spilled scalars (profiles/narrow5_loop_counts.txt).  Three things, all the same work for the same result:
+    //   own scalars   what the loop reads of `p` in every iteration is copied out before it (device_common.hpp, own_scalars): read through
+    //                 `p` a field kept its 16-register tuple alive, spilled and reloaded whole in front of single uses; the side arrays a
+    //                 launch may write (wave_counts, batch_counts, wave_offsets) are ONE launch-uniform bit word, a scalar bit test and a
+    //                 branch per tile, and their pointers are read behind the branch only;
+    //   publish       the wave prefix and the tile count are a DPP sum over one row of 16 lanes (below, behind the barrier);
+    //   tile_addr.hpp `full` is a 32-bit compare with the launch's first ragged tile, a wave's codes lie one 32 x 32 -> 64 multiply and
+    //                 an addition from the wave's codes of tile 0.
+    // In the passes over PACKED codes only.  The other instantiations keep the loop as it was and compile to the code they had:
+    //   - the generic shapes and the forms that collect the selection bitmap stand at 128 VGPRs, the plain forms at 32 and 48 rows per
+    //     lane beyond them, and what moves their register allocation moves their scratch (16 to 160 bytes per lane more in thirteen of
+    //     them with the cut applied to all, profiles/narrow5_resources.txt);
+    //   - the plain lean pass at 16 rows per lane, which stands at HBM and not at its instruction issue, measured 0.8 % SLOWER with it
+    //     (1.343-1.346 -> 1.355-1.357 ms per 1e9 rows), and a stream's windows over 2-byte codes at 16 rows per lane 0.9-1.2 % slower in
+    //     two sets of five alternating rounds, with and without own scalars for the side arrays' pointers (profiles/narrow5_steps.txt).
+    constexpr bool kLeanTile = kPack10;
+    // (the other forms read a field where they use it, as before: a read up here would move their register allocation as well)
+    struct {
+        uint64_t *state;
+        uint32_t *ticket;
+        uint64_t out_capacity;
+        uint32_t ntiles, out_bias, side;
+        uint64_t *out0;        // out_values[0]
+        uint64_t narrow_base;  // narrow.base: what the staged codes are widened with
+    } own{};
+    constexpr uint32_t kSideWaveCounts = 1u, kSideBatchCounts = 2u, kSideWaveOffsets = 4u;
+    if constexpr (kLeanTile) {
+        own.state = own_scalars(p.state);
+        own.ticket = own_scalars(p.ticket);
+        own.out_capacity = own_scalars(p.out_capacity);
+        own.ntiles = own_scalar(p.ntiles);
+        own.out_bias = own_scalar(p.out_bias);
+        own.side = own_scalar((p.wave_counts != nullptr ? kSideWaveCounts : 0u) | (p.batch_counts != nullptr ? kSideBatchCounts : 0u) |
+                              (p.wave_offsets != nullptr ? kSideWaveOffsets : 0u));
+        own.out0 = own_scalars(p.out_values[0]);
+        own.narrow_base = own_scalars(static_cast<uint64_t>(p.narrow.base));
+    }
+    // which tile is ragged and by how much (tile_addr.hpp); a pass over codes: where THIS WAVE's codes of tile 0 lie and what the
+    // companion holds
+    const rvtile::TileWalk pw = kLeanTile ? get_tile_walk(p.in) : rvtile::TileWalk{};  // (the other forms never read it)
+    rvtile::TileWalk walk{};
+    if constexpr (kLeanTile) {
+        walk.first_ragged_tile = own_scalar(pw.first_ragged_tile);
+        walk.ragged_rows = own_scalar(pw.ragged_rows);
+    }
+    const unsigned char *codes0 = nullptr;  // the companion
+    if constexpr (kLeanTile) {
+        walk.view_byte0 = own_scalars(rvtile::wave_byte_at(pw, 0u, wave));
+        walk.bytes = own_scalars(pw.bytes);
+        walk.tile_bytes = own_scalar(pw.tile_bytes);
+        walk.wave_bytes = own_scalar(pw.wave_bytes);
+        codes0 = own_scalars(static_cast<const unsigned char *>(p.narrow.codes));
+    }
+
     // ---- LDS carve: slot(stage, wave) of `cap` rows; byte offsets of the columns inside a slot ----
     const uint32_t cap = p.cap_rows;  // rows per wave slot
     uint32_t off_v[NV], off_b[NV], off_x[kMaxBitStreams];
@@ -270,19 +358,20 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
 
     // this wave's slot rows [0, cnt) -> out[g0 ...): one coalesced run per column
     auto flush = [&](uint32_t sb, uint32_t cnt, uint64_t g0) {
-        if (g0 + cnt > p.out_capacity) {  // wave-uniform; the counts stay exact, the host re-runs with buffers of that size
+        if (g0 + cnt > RV_TILE_PARAM(out_capacity)) {  // wave-uniform; the counts stay exact, the host re-runs with buffers of that size
             if (lane == 0) *p.overflow = 1u;
             return;
         }
         const uint32_t fl = opaque(static_cast<uint32_t>(lane));  // device_common.hpp: keeps the addresses below out of scratch
 #pragma unroll
         for (int c = 0; c < NCOLS; ++c) {
-            if (!p.out_values[c]) continue;
-            uint64_t *dst = p.out_values[c] + g0;
+            uint64_t *const out_c = kLeanTile ? own.out0 : p.out_values[c];  // (the lean forms have one column)
+            if (!out_c) continue;
+            uint64_t *dst = out_c + g0;
             if constexpr (kNarrow != 0) {  // staged codes -> value = base + code, widened here: one addition per survivor
                 using Code = typename std::conditional<kNarrow == 2, uint16_t, uint32_t>::type;
                 const Code *sc = reinterpret_cast<const Code *>(smem + sb + off_v[c]);
-                const uint64_t base = static_cast<uint64_t>(p.narrow.base);
+                const uint64_t base = kLeanTile ? own.narrow_base : static_cast<uint64_t>(p.narrow.base);
                 if (!(kStamp && (p.debug & 1)))
                     for (uint32_t k = fl; k < cnt; k += 64) __builtin_nontemporal_store(base + sc[k], &dst[k]);
                 continue;
@@ -329,9 +418,9 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
 
     // ---- prologue: three tickets, first loads -------------------------------------------------------
     if (threadIdx.x == 0) {
-        s_tick[0] = __hip_atomic_fetch_add(p.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_tick[1] = __hip_atomic_fetch_add(p.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_tick[2] = __hip_atomic_fetch_add(p.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_tick[0] = __hip_atomic_fetch_add(RV_TILE_PARAM(ticket), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_tick[1] = __hip_atomic_fetch_add(RV_TILE_PARAM(ticket), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_tick[2] = __hip_atomic_fetch_add(RV_TILE_PARAM(ticket), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if constexpr (kValidity || kXs)
         if (threadIdx.x < 8) reinterpret_cast<uint32_t *>(smem + 24)[threadIdx.x] = 0;
@@ -349,14 +438,20 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
     Raw codes[NRAW];
     auto load_tile_codes = [&](uint32_t t) {  // of this wave; a tile id >= ntiles (the ticket counter ran out) issues no load
         if constexpr (kNarrow != 0)
-            if (t < p.ntiles) {
-                const uint64_t first = p.in.cols[0].offset + static_cast<uint64_t>(t) * TILE + static_cast<uint64_t>(wave) * ROWS_PER_WAVE;
-                if constexpr (kPack10) load_rows_packed<R>(p.narrow, first, lane, codes);
-                else load_rows_narrow<R, kNarrow>(p.narrow, first, lane, codes);
+            if (t < RV_TILE_PARAM(ntiles)) {
+                if constexpr (kPack10) {
+                    // (`walk` counts from this wave's codes of tile 0: one 32 x 32 -> 64 multiply and an addition per tile where
+                    //  (offset + row) / 384 * 512 on 64-bit rows stood)
+                    const uint64_t at = rvtile::wave_byte_at(walk, t, 0u);
+                    load_rows_packed<R>(codes0, at, rvtile::wave_bytes_left(walk, at), lane, codes);
+                } else {
+                    const uint64_t first = p.in.cols[0].offset + static_cast<uint64_t>(t) * TILE + static_cast<uint64_t>(wave) * ROWS_PER_WAVE;
+                    load_rows_narrow<R, kNarrow>(p.narrow, first, lane, codes);
+                }
             }
     };
     if constexpr (kNarrow != 0) load_tile_codes(tile);
-    else if (tile < p.ntiles) load_tile_rows(static_cast<uint64_t>(tile) * TILE + static_cast<uint64_t>(wave) * ROWS_PER_WAVE);
+    else if (tile < RV_TILE_PARAM(ntiles)) load_tile_rows(static_cast<uint64_t>(tile) * TILE + static_cast<uint64_t>(wave) * ROWS_PER_WAVE);
     uint64_t vw[NV];  // validity words of the loaded rows (generic shapes with null bitmaps)
     // words of the Boolean predicate columns (values, validity) and of the Boolean columns travelling with
     // the rows (source, mask): fetched with the row prefetch, like vw
@@ -382,7 +477,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
             }
         }
     };
-    if (tile < p.ntiles) prefetch_bits(static_cast<uint64_t>(tile) * TILE + static_cast<uint64_t>(wave) * ROWS_PER_WAVE);
+    if (tile < RV_TILE_PARAM(ntiles)) prefetch_bits(static_cast<uint64_t>(tile) * TILE + static_cast<uint64_t>(wave) * ROWS_PER_WAVE);
 
     // Tiles whose survivors wait in their LDS slots for the output offset: `older` was staged two
     // iterations ago, `newer` one.  With p.depth == 2 (three slot stages) a tile is written out two
@@ -409,15 +504,15 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
     auto resolve = [&](const Pending &r, Desc prev, uint64_t *excl_out) {  // prev: the descriptor in front of r.tile, wave-uniform
         uint64_t e;
         if (kStamp && (p.debug & 2)) e = static_cast<uint64_t>(r.tile) * 1024;
-        else if (r.tile == 0) e = p.out_bias;
+        else if (r.tile == 0) e = RV_TILE_PARAM(out_bias);
         else if ((prev.hi >> 30) == 2u) e = (static_cast<uint64_t>(prev.hi & 0x3FFFFFFFu) << 32) | prev.lo;
         else {
             if (kStamp && (p.debug & 4) && lane == 0) atomicAdd(p.stamps + 31, 1ull);
-            e = lookback_exclusive(p.state, r.tile, r.count, p.err, p.spin_limit, kStamp ? p.stamps + 6 : nullptr);
+            e = lookback_exclusive(RV_TILE_PARAM(state), r.tile, r.count, p.err, p.spin_limit, kStamp ? p.stamps + 6 : nullptr);
         }
         if (lane == 0) {
             *excl_out = e;
-            if (r.tile == p.ntiles - 1) *p.out_count = e + r.count - p.out_bias;
+            if (r.tile == RV_TILE_PARAM(ntiles) - 1) *p.out_count = e + r.count - RV_TILE_PARAM(out_bias);
         }
     };
     uint32_t n_redo = 0;  // wave ranges this wave has left to the redo kernel
@@ -449,21 +544,21 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
     // above: with the stamps beside the staging loop's masks and bases the scalar file is full, and one of them got a stack frame)
     uint32_t tlo_v = 0, tspan_v = 0;
     if constexpr (kStamp && kNarrow != 0) tlo_v = opaque(TLO), tspan_v = opaque(TSPAN);
-    for (uint32_t it = 0; tile < p.ntiles; ++it) {
+    for (uint32_t it = 0; tile < RV_TILE_PARAM(ntiles); ++it) {
         // ---- ticket for three iterations ahead: issued now, stored at the end of the iteration and read
         //      at the top of iteration it + 2 (the barrier of it + 1 lies in between) --------------------
         uint32_t ticket3 = 0;
-        if (threadIdx.x == 0) ticket3 = __hip_atomic_fetch_add(p.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (threadIdx.x == 0) ticket3 = __hip_atomic_fetch_add(RV_TILE_PARAM(ticket), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         // the pending tile's predecessor descriptor: one 8-byte load whose round trip runs under this
         // tile's predicate + staging
         const Pending ret = deep ? older : newer;  // the tile to write out in this iteration
-        if (wave == 0 && ret.have && ret.tile != 0) prev_desc = ld_state(&p.state[ret.tile - 1]);
+        if (wave == 0 && ret.have && ret.tile != 0) prev_desc = ld_state(&RV_TILE_PARAM(state)[ret.tile - 1]);
         const uint32_t next_tile = uniform32(s_tick[(it + 1) & 3]);  // stored two iterations ago
         const uint64_t tile_base = static_cast<uint64_t>(tile) * TILE;
         const uint64_t wave_base = tile_base + static_cast<uint64_t>(wave) * ROWS_PER_WAVE;
-        const bool full = tile_base + TILE <= p.in.n;
+        const bool full = kLeanTile ? rvtile::tile_full(walk, tile) : tile_base + TILE <= p.in.n;  // (one 32-bit compare | a 64-bit multiply and compare)
         const uint64_t ntb = static_cast<uint64_t>(next_tile) * TILE;
-        const bool more = next_tile < p.ntiles;
+        const bool more = next_tile < RV_TILE_PARAM(ntiles);
 
         uint32_t wave_total = 0;
         uint64_t selw = 0;  // selection words of this wave's rows (FF_SEL), lane q = word q
@@ -477,13 +572,17 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
         if constexpr (kOne) {
             // ---- single-term fast path: compare -> lane masks -> rank -> own slot, row slot by row slot ----
             uint64_t *sv = reinterpret_cast<uint64_t *>(smem + sb + off_v[0]);
-            const bool project = p.out_values[0] != nullptr;
+            const bool project = (kLeanTile ? own.out0 : p.out_values[0]) != nullptr;
             // rows of this wave inside the batch (only the last tile is ragged); compared as scalar - lane
             // part so that no per-row-slot index is kept in registers
             int32_t rem = 0;
             if (!full) {
-                const int64_t left = static_cast<int64_t>(p.in.n) - static_cast<int64_t>(wave_base);
-                rem = static_cast<int32_t>(left < 0 ? 0 : (left > (1 << 30) ? (1 << 30) : left));
+                if constexpr (kLeanTile) {
+                    rem = rvtile::wave_rows_left(walk, tile, wave, ROWS_PER_WAVE);
+                } else {
+                    const int64_t left = static_cast<int64_t>(p.in.n) - static_cast<int64_t>(wave_base);
+                    rem = static_cast<int32_t>(left < 0 ? 0 : (left > (1 << 30) ? (1 << 30) : left));
+                }
             }
             auto row_mask = [&](uint64_t cell, int32_t srow, int32_t lrow) -> uint64_t {
                 uint64_t m;
@@ -910,21 +1009,35 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
         }
 
         uint32_t wave_prefix = 0, tile_count = 0;
+        if constexpr (kLeanTile) {
+            // The wave totals, one per lane of a row of 16 (lane l holds s_wtot[l & 15]: one LDS read per lane, every row the same
+            // words), summed inside the row by DPP: lane w of the inclusive scan holds the totals of waves 0..w.  About a dozen
+            // instructions where the loop below lists 88: WAVES selects under WAVES `w < wave` masks, 32 scalar registers that are
+            // spilled and reloaded in every tile.
+            const uint32_t l16 = static_cast<uint32_t>(lane) & 15u;
+            const uint32_t wtot = (WAVES == 16 || l16 < static_cast<uint32_t>(WAVES)) ? s_wtot[l16] : 0u;
+            const uint32_t wscan = row16_scan_u32(wtot);
+            wave_prefix = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(wscan - wtot), static_cast<int>(wave)));
+            tile_count = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(wscan), 15));
+        } else {
 #pragma unroll
-        for (int w = 0; w < WAVES; ++w) {
-            const uint32_t t = s_wtot[w];
-            wave_prefix += (static_cast<uint32_t>(w) < wave) ? t : 0;
-            tile_count += t;
+            for (int w = 0; w < WAVES; ++w) {
+                const uint32_t t = s_wtot[w];
+                wave_prefix += (static_cast<uint32_t>(w) < wave) ? t : 0;
+                tile_count += t;
+            }
+            wave_prefix = uniform32(wave_prefix);
+            tile_count = uniform32(tile_count);
         }
-        wave_prefix = uniform32(wave_prefix);
-        tile_count = uniform32(tile_count);
         // successors can sum this tile's count from here on
-        if (threadIdx.x == 0 && !(kStamp && (p.debug & 16) && tile == 1)) publish_aggregate(p.state, tile, tile_count, p.out_bias);
-        if (p.wave_counts != nullptr && threadIdx.x < WAVES)  // one 64-byte line per tile (batch counts of seam S1)
-            p.wave_counts[static_cast<uint64_t>(tile) * WAVES + threadIdx.x] = s_wtot[threadIdx.x];
-        if (p.batch_counts != nullptr && threadIdx.x < WAVES) {  // ... or straight to the caller's array: a batch is a wave range
-            const uint64_t b = static_cast<uint64_t>(tile) * WAVES + threadIdx.x;
-            if (b < p.nbatch_counts) p.batch_counts[b] = s_wtot[threadIdx.x];
+        if (threadIdx.x == 0 && !(kStamp && (p.debug & 16) && tile == 1)) publish_aggregate(RV_TILE_PARAM(state), tile, tile_count, RV_TILE_PARAM(out_bias));
+        if (!kLeanTile || (own.side & (kSideWaveCounts | kSideBatchCounts))) {
+            if (RV_TILE_WRITES(kSideWaveCounts, wave_counts) && threadIdx.x < WAVES)  // one 64-byte line per tile (batch counts of seam S1)
+                p.wave_counts[static_cast<uint64_t>(tile) * WAVES + threadIdx.x] = s_wtot[threadIdx.x];
+            if (RV_TILE_WRITES(kSideBatchCounts, batch_counts) && threadIdx.x < WAVES) {  // ... or straight to the caller's array: a batch is a wave range
+                const uint64_t b = static_cast<uint64_t>(tile) * WAVES + threadIdx.x;
+                if (b < p.nbatch_counts) p.batch_counts[b] = s_wtot[threadIdx.x];
+            }
         }
         if constexpr (kStamp) {
             t1 = stamp_now();
@@ -933,7 +1046,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
         }
 
         // ---- write out the pending tile's slots -------------------------------------------------------------
-        if (p.wave_offsets != nullptr && ret.have && lane == 0) p.wave_offsets[static_cast<uint64_t>(ret.tile) * WAVES + wave] = *s_excl + ret.wave_prefix;
+        if (RV_TILE_WRITES(kSideWaveOffsets, wave_offsets) && ret.have && lane == 0) p.wave_offsets[static_cast<uint64_t>(ret.tile) * WAVES + wave] = *s_excl + ret.wave_prefix;
         if (ret.have) write_out(ret, uniform64(*s_excl));
         older = newer;
         newer = Pending{tile, tile_count, cur_stage, wave_prefix, wave_total, wave_dense, true};
@@ -952,11 +1065,11 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
     auto retire = [&](const Pending &r) {
         if (!r.have) return;  // workgroup-uniform
         if (wave == 0) {
-            if (r.tile != 0) prev_desc = ld_state(&p.state[r.tile - 1]);
+            if (r.tile != 0) prev_desc = ld_state(&RV_TILE_PARAM(state)[r.tile - 1]);
             resolve(r, Desc{uniform32(static_cast<uint32_t>(prev_desc)), uniform32(static_cast<uint32_t>(prev_desc >> 32))}, s_excl_of(0));
         }
         __syncthreads();
-        if (p.wave_offsets != nullptr && lane == 0) p.wave_offsets[static_cast<uint64_t>(r.tile) * WAVES + wave] = *s_excl_of(0) + r.wave_prefix;
+        if (RV_TILE_WRITES(kSideWaveOffsets, wave_offsets) && lane == 0) p.wave_offsets[static_cast<uint64_t>(r.tile) * WAVES + wave] = *s_excl_of(0) + r.wave_prefix;
         write_out(r, uniform64(*s_excl_of(0)));
         __syncthreads();  // s_excl may be rewritten
     };
@@ -994,6 +1107,9 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
             atomicAdd(&p.out_valid_pop[threadIdx.x], static_cast<unsigned long long>(s_pop[threadIdx.x]));
     }
 }
+
+#undef RV_TILE_PARAM
+#undef RV_TILE_WRITES
 
 // ---- redo kernel ----------------------------------------------------------------------------------
 // Wave ranges (64 R consecutive rows: what ONE wave of the pass held of a tile) whose survivors outgrew the wave's LDS

@@ -4,6 +4,7 @@
 #include "fused_rule.hpp"
 #include "launch.hpp"
 #include "narrow_term.hpp"
+#include "tile_addr.hpp"
 
 #include <cmath>
 
@@ -669,9 +670,14 @@ static void launch_pass(rv_ctx *ctx, FusedLaunch &L, const LaunchChoice &c, int 
     const void *fn = reinterpret_cast<const void *>(c.fn);
     enable_lds(ctx, fn, c.lds);
     if (c.narrow) {
+        const bool packed = c.narrow->layout == rvn::Layout::kPacked;
         p.narrow.codes = c.narrow->codes->ptr;
-        p.narrow.bytes = c.narrow->layout == rvn::Layout::kPacked ? std::min<uint64_t>(c.narrow->codes->bytes, rvn::packed_bytes(c.narrow->count)) : c.narrow->codes->bytes;
+        p.narrow.bytes = packed ? std::min<uint64_t>(c.narrow->codes->bytes, rvn::packed_bytes(c.narrow->count)) : c.narrow->codes->bytes;
         p.narrow.base = c.narrow->base;
+        require(p.in.nterms == 1, RV_ERR_INTERNAL, "narrow pass: one term");
+        // a pass over packed codes: the tile loop's constants (tile_addr.hpp: the ragged tile, where a tile's and a wave's codes lie in the
+        // companion), in term slots 2 and 3, which a one-term launch leaves unused (fused_kernel.hpp, put_tile_walk)
+        if (packed) rvk::put_tile_walk(p.in, rvtile::codes_walk(p.in.n, c.r, c.waves, p.in.cols[0].offset, p.narrow.bytes, rvtile::kPackedCodes));
         // the pass compares codes: the term, lowered to ONE interval of codes once per launch -- a complement is folded into the
         // interval it is in wrap-around arithmetic.  The one term without an interval, the empty set over 4-byte codes, comes back
         // as it went in, `negate` set: the kernel tests the flag once per tile, outside its row loop, and runs such a launch through

@@ -61,6 +61,8 @@ struct BitStream {
 struct ScanInputs {
     DevCol cols[kMaxValueCols];
     DevCol bcols[kMaxBoolCols];
+    // (slots past nterms are NOT free in a one-term launch of a pass over codes: slot 1 holds the term's code interval, slots 2 and 3, `pad`
+    //  included, the launch's tile constants -- fused_kernel.hpp, put_tile_walk.  Read terms[t] for t < nterms only.)
     DevTerm terms[kMaxTerms];
     uint64_t n;  // rows
     int32_t nterms;
@@ -216,17 +218,14 @@ __device__ __forceinline__ void unpack_pair(typename NarrowRaw<BYTES>::type raw,
 // ---- the same rows out of a PACKED companion (FF_NARROW16 | FF_PACK10; narrow_rule.hpp, the packed layout) -------------------------
 // 10-bit codes, six per 8-byte word: word l of a 384-element super-group (64 words, 512 bytes) holds rows 2l, 2l + 1 of its three
 // 128-row groups, so lane l reads word l and owns the rows it owns with the pair loads above -- ONE 8-byte nontemporal buffer load per
-// THREE pairs, kept raw like them.  `first` (element of the buffer) must be a multiple of 384: the view's first element is (the host's
-// rule, narrow_rule.hpp packed_view_aligned) and a wave range is 64 R rows with R a multiple of 6.  The descriptor is bounded by the
-// companion bytes left, as above: the companion ends on a whole super-group whose padding is code 0.
+// THREE pairs, kept raw like them.  The wave range's first element must be a multiple of 384: the view's first element is (the host's
+// rule, narrow_rule.hpp packed_view_aligned) and a wave range is 64 R rows with R a multiple of 6 -- which also makes the range's byte
+// `at` linear in the tile and the wave (tile_addr.hpp).  The descriptor is bounded by the companion bytes left, as above: the companion
+// ends on a whole super-group whose padding is code 0.
 template <int R>
-__device__ __forceinline__ void load_rows_packed(const NarrowView &nv, uint64_t first, int lane, uint64_t (&c)[R / 6]) {
+__device__ __forceinline__ void load_rows_packed(const void *codes, uint64_t at, uint32_t nbytes, int lane, uint64_t (&c)[R / 6]) {
     static_assert(R % 6 == 0, "packed codes: three pairs per word");
-    constexpr uint64_t WAVE_BYTES = 512u * (R / 6);
-    const uint64_t at = first / 384u * 512u;
-    const uint64_t left = nv.bytes > at ? nv.bytes - at : 0;
-    const uint32_t nbytes = uniform32(static_cast<uint32_t>(left < WAVE_BYTES ? left : WAVE_BYTES));
-    const uint64_t base = uniform64(reinterpret_cast<uint64_t>(nv.codes) + at);
+    const uint64_t base = reinterpret_cast<uint64_t>(codes) + at;
     const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void *>(base), 0, nbytes, 0x00020000);
 #pragma unroll
     for (int t = 0; t < R / 6; ++t) {
