@@ -419,6 +419,22 @@ inline ArrayRef Array::adopt(const ContextRef &ctx, rv_dcolumn *h) {
         default: rv_free(ctx->raw(), h); throw Error(RV_ERR_UNSUPPORTED, "unsupported device array type");
     }
 }
+// the handles a C-ABI call returned, adopted in their order
+inline std::vector<ArrayRef> adopt_columns(const ContextRef &ctx, const std::vector<rv_dcolumn *> &out) {
+    std::vector<ArrayRef> res;
+    for (auto *h : out) res.push_back(Array::adopt(ctx, h));
+    return res;
+}
+// ... and the handles a C-ABI call takes: those of `columns`, in their order.  A column off the device is refused with `off_device`.
+inline std::vector<const rv_dcolumn *> column_handles(const std::vector<ArrayRef> &columns,
+                                                      const std::string &off_device = "columns off the device are outside the device path") {
+    std::vector<const rv_dcolumn *> h;
+    for (auto &c : columns) {
+        if (!c->on_device()) throw Error(RV_ERR_UNSUPPORTED, off_device);
+        h.push_back(c->handle());
+    }
+    return h;
+}
 
 // ---------------------------------------------------------------------------------------
 // RecordBatch -- record_batch.rs:8-422
@@ -551,17 +567,10 @@ class RecordBatch {
   private:
     RecordBatch(SchemaRef s, std::vector<ArrayRef> c, size_t n) : schema_(std::move(s)), columns_(std::move(c)), num_rows_(n) {}
     std::vector<const rv_dcolumn *> device_handles(const char *what) const {
-        std::vector<const rv_dcolumn *> h;
-        for (auto &c : columns_) {
-            if (!c->on_device()) throw Error(RV_ERR_UNSUPPORTED, std::string(what) + ": String columns are outside the device path");
-            h.push_back(c->handle());
-        }
-        return h;
+        return column_handles(columns_, std::string(what) + ": String columns are outside the device path");
     }
     RecordBatch adopt_all(const ContextRef &ctx, const std::vector<rv_dcolumn *> &out, size_t rows) const {
-        std::vector<ArrayRef> cols;
-        for (auto *h : out) cols.push_back(Array::adopt(ctx, h));
-        return RecordBatch(schema_, std::move(cols), rows);
+        return RecordBatch(schema_, adopt_columns(ctx, out), rows);
     }
     SchemaRef schema_;
     std::vector<ArrayRef> columns_;
@@ -1581,19 +1590,21 @@ inline void restore_build_key(std::vector<ArrayRef> &out, size_t n_probe, size_t
     out.pop_back();
 }
 
-// One side of a streaming join: a stream, or a resident frame (a DataFrameSource: its columns after dataframe_to_batches' null
-// fill, cut into batch_size-row batches).
+// The schema of a frame of named columns: every field nullable, as dataframe_to_batches declares them.
+inline SchemaRef nullable_schema(const std::vector<std::string> &names, const std::vector<ArrayRef> &columns) {
+    std::vector<Field> f;
+    for (size_t c = 0; c < columns.size(); ++c) f.push_back(Field{names[c], columns[c]->data_type(), true});
+    return std::make_shared<const Schema>(f);
+}
+
+// One side of a streaming join, or the input of a pipeline breaker (StreamingPhysicalPlan::as_input): a stream, or a resident frame
+// (a DataFrameSource: its columns after dataframe_to_batches' null fill, cut into batch_size-row batches).
 struct JoinSide {
     DataStreamRef stream;
     std::vector<std::string> names;
     std::vector<ArrayRef> columns;
     size_t batch_size = 0;
-    SchemaRef schema() const {
-        if (stream) return stream->schema();
-        std::vector<Field> f;
-        for (size_t c = 0; c < columns.size(); ++c) f.push_back(Field{names[c], columns[c]->data_type(), true});
-        return std::make_shared<const Schema>(f);
-    }
+    SchemaRef schema() const { return stream ? stream->schema() : nullable_schema(names, columns); }
 };
 
 // GpuHashJoinStream -- StreamingPhysicalPlan::HashJoin (the reference's arm is todo!(), streaming.rs:128-131), for the inner join and
@@ -1696,8 +1707,7 @@ class GpuHashJoinStream : public DataStream {
             check_stream(rv_hash_join_chunked_kind(ctx->raw(), table_, build_handles_.data(), static_cast<uint32_t>(build_handles_.size()), bki_, p.cols.data(),
                                                    static_cast<uint32_t>(p.cols.size()), p.key, kind_, chunk, max_pairs_, raw.data(), rows.data(), nb,
                                                    nulls.data(), &pairs, &taken));
-        out.clear();
-        for (auto *h : raw) out.push_back(Array::adopt(ctx, h));
+        out = adopt_columns(ctx, raw);
         rows.resize(taken);
         without_key_helper(p, out, &nulls, taken);
         return taken;
@@ -1777,6 +1787,51 @@ class GpuHashJoinStream : public DataStream {
     LimitWindow limit_;
 };
 
+// A PIPELINE BREAKER (group_by, sort, window, top_k): it drains its input and emits EXACTLY ONE batch.  This is the drain -- a resident
+// frame is taken as it is, the batches of any other stream are concatenated (RecordBatch::concat), one batch alone is taken as it is --
+// and run() is the operator's own step over the whole input.  An input that yields no batch at all gives one zero-row batch with the
+// output schema.
+class GpuBreakerStream : public DataStream {
+  public:
+    SchemaRef schema() const override { return schema_; }
+    std::optional<RecordBatch> next_batch() override {
+        if (done_) return std::nullopt;
+        done_ = true;
+        std::vector<ArrayRef> columns = input_.columns;
+        if (input_.stream) {
+            std::vector<RecordBatch> all;
+            while (auto b = input_.stream->next_batch()) all.push_back(std::move(*b));
+            if (all.empty()) return no_batch();
+            RecordBatch whole = all.size() == 1 ? all[0] : stream_call([&] { return RecordBatch::concat(all); });
+            columns = whole.columns();
+        }
+        return stream_call([&] { return run(ctx_of(columns), columns); });
+    }
+
+  protected:
+    // `op`: the operator's name in the errors; `fallback_ctx`: where the zero-row batch of an input that yields no batch at all is
+    // created.  The constructor of the operator sets schema_, which is where its planning errors come from.
+    GpuBreakerStream(const char *op, JoinSide input, ContextRef fallback_ctx)
+        : op_(op), input_(std::move(input)), ctx_(std::move(fallback_ctx)), input_schema_(input_.schema()) {}
+    // the operator over the whole input (`columns` in the order of input_schema_), as its one batch
+    virtual RecordBatch run(const ContextRef &ctx, const std::vector<ArrayRef> &columns) = 0;
+    RecordBatch batch_of(std::vector<ArrayRef> out) const {
+        const size_t rows = out[0]->len();
+        return RecordBatch::new_unchecked(schema_, std::move(out), rows);
+    }
+    RecordBatch no_batch() const {
+        if (!ctx_) throw StreamError::execution(std::string(op_) + ": the input yielded no batch and the plan holds no device context");
+        return RecordBatch::empty(ctx_, schema_);
+    }
+    ContextRef ctx_of(const std::vector<ArrayRef> &columns) const { return columns.empty() ? ctx_ : columns[0]->context(); }
+
+    const char *op_;
+    JoinSide input_;
+    ContextRef ctx_;
+    SchemaRef input_schema_, schema_;
+    bool done_ = false;
+};
+
 // ---------------------------------------------------------------------------------------
 // group_by(key).agg([...]) -- the reference has no aggregate operator: include/rivulus_gpu.h, rv_hash_aggregate
 // ---------------------------------------------------------------------------------------
@@ -1850,66 +1905,32 @@ inline SchemaRef group_by_schema(const Schema &in, const std::vector<std::string
     return group_by_agg_fields(in, std::move(out), aggs);
 }
 
-// One rv_hash_aggregate over the named columns of one frame (`columns` in the order of `schema`); the output columns in the order of
-// group_by_schema.  A String key goes through the string dictionary: the ids of the key (null strings are null ids: the null group;
-// "" is a value) are grouped, and the key cells are gathered from the String column itself at the groups' first rows.
-inline std::vector<ArrayRef> group_by_columns(const ContextRef &ctx, const Schema &schema, const std::vector<ArrayRef> &columns, const std::string &key,
-                                              const std::vector<AggSpec> &aggs) {
-    (void)group_by_schema(schema, key, aggs);
-    auto handle_of = [&](const std::string &n) {
-        const ArrayRef &c = columns[*schema.index_of(n)];
-        if (!c->on_device()) throw Error(RV_ERR_UNSUPPORTED, "columns off the device are outside the device path");
-        return c->handle();
-    };
-    std::vector<const rv_dcolumn *> values;
-    std::vector<rv_agg_spec> specs;
-    for (auto &a : aggs) {
-        rv_agg_spec s{static_cast<uint32_t>(a.op), 0};
-        if (a.op != AggOp::CountRows) {
-            const rv_dcolumn *h = handle_of(a.column);
-            const auto at = std::find(values.begin(), values.end(), h);
-            s.col = static_cast<uint32_t>(at - values.begin());
-            if (at == values.end()) values.push_back(h);
-        }
-        specs.push_back(s);
-    }
-    const rv_dcolumn *key_col = handle_of(key);
-    const bool string_key = schema.field_by_name(key)->data_type() == DataType::String;
-    ArrayRef ids;
-    if (string_key) {
-        rv_string_dict *dict = nullptr;
-        rv_dcolumn *h = nullptr;
-        check(rv_string_dict_build(ctx->raw(), key_col, &dict, &h));
-        ids = Array::adopt(ctx, h);
-        check(rv_string_dict_free(ctx->raw(), dict));  // only the ids are needed: equal strings share an id
-    }
-    std::vector<rv_dcolumn *> out(specs.size() + 1, nullptr);
-    rv_dcolumn *first_row = nullptr;
-    uint64_t groups = 0;
-    check(rv_hash_aggregate(ctx->raw(), string_key ? ids->handle() : key_col, values.data(), static_cast<uint32_t>(values.size()), specs.data(),
-                            static_cast<uint32_t>(specs.size()), out.data(), &first_row, &groups));
-    std::vector<ArrayRef> res;
-    for (auto *h : out) res.push_back(Array::adopt(ctx, h));
-    const ArrayRef first = Array::adopt(ctx, first_row);
-    if (string_key) {  // the strings at the first rows in place of their ids
-        rv_dcolumn *cells = nullptr;
-        check(rv_take_device(ctx->raw(), &key_col, 1, first->handle(), &cells));
-        res[0] = Array::adopt(ctx, cells);
-    }
-    return res;
+// The single-key form as the list form sees it: `by_list` false is group_by(keys[0]), with that form's refusals.
+inline SchemaRef group_by_schema(const Schema &in, const std::vector<std::string> &keys, const std::vector<AggSpec> &aggs, bool by_list) {
+    return by_list ? group_by_schema(in, keys, aggs) : group_by_schema(in, keys.at(0), aggs);
 }
 
-// One rv_hash_aggregate_keys over the named columns of one frame; the output columns in the order of group_by_schema(keys).  Every
-// String key goes through the string dictionary on its own: its ids (a null string is a null id; "" is a value) stand in the tuple,
-// and its key cells are gathered from the String column itself at the groups' first rows.
+// The Int64 ids of a String key column, through the string dictionary: equal strings share an id, a null string is a null id, "" is a value.
+// Only the ids are needed, so the dictionary is freed at once.
+inline ArrayRef string_key_ids(const ContextRef &ctx, const rv_dcolumn *strings) {
+    rv_string_dict *dict = nullptr;
+    rv_dcolumn *h = nullptr;
+    check(rv_string_dict_build(ctx->raw(), strings, &dict, &h));
+    const ArrayRef ids = Array::adopt(ctx, h);
+    check(rv_string_dict_free(ctx->raw(), dict));
+    return ids;
+}
+
+// One aggregation over the named columns of one frame (`columns` in the order of `schema`); the output columns in the order of
+// group_by_schema: the keys, then the aggregates.  `by_list`: one rv_hash_aggregate_keys over the key tuple; else the single-key form,
+// one rv_hash_aggregate over keys[0].  Every String key goes through the string dictionary on its own: its ids (null strings are null
+// ids: the null group; "" is a value) stand in for it, and its key cells are gathered from the String column itself at the groups'
+// first rows.
 inline std::vector<ArrayRef> group_by_columns(const ContextRef &ctx, const Schema &schema, const std::vector<ArrayRef> &columns,
-                                              const std::vector<std::string> &keys, const std::vector<AggSpec> &aggs) {
-    (void)group_by_schema(schema, keys, aggs);
-    auto handle_of = [&](const std::string &n) {
-        const ArrayRef &c = columns[*schema.index_of(n)];
-        if (!c->on_device()) throw Error(RV_ERR_UNSUPPORTED, "columns off the device are outside the device path");
-        return c->handle();
-    };
+                                              const std::vector<std::string> &keys, const std::vector<AggSpec> &aggs, bool by_list) {
+    (void)group_by_schema(schema, keys, aggs, by_list);
+    const std::vector<const rv_dcolumn *> handles = column_handles(columns);
+    auto handle_of = [&](const std::string &n) { return handles[*schema.index_of(n)]; };
     std::vector<const rv_dcolumn *> values;
     std::vector<rv_agg_spec> specs;
     for (auto &a : aggs) {
@@ -1927,11 +1948,7 @@ inline std::vector<ArrayRef> group_by_columns(const ContextRef &ctx, const Schem
     for (size_t k = 0; k < keys.size(); ++k) {
         const rv_dcolumn *col = handle_of(keys[k]);
         if (schema.field_by_name(keys[k])->data_type() == DataType::String) {
-            rv_string_dict *dict = nullptr;
-            rv_dcolumn *h = nullptr;
-            check(rv_string_dict_build(ctx->raw(), col, &dict, &h));
-            ids.push_back(Array::adopt(ctx, h));
-            check(rv_string_dict_free(ctx->raw(), dict));  // only the ids are needed: equal strings share an id
+            ids.push_back(string_key_ids(ctx, col));
             strings[k] = col;
             col = ids.back()->handle();
         }
@@ -1940,10 +1957,13 @@ inline std::vector<ArrayRef> group_by_columns(const ContextRef &ctx, const Schem
     std::vector<rv_dcolumn *> out(keys.size() + specs.size(), nullptr);
     rv_dcolumn *first_row = nullptr;
     uint64_t groups = 0;
-    check(rv_hash_aggregate_keys(ctx->raw(), key_cols.data(), static_cast<uint32_t>(key_cols.size()), values.data(), static_cast<uint32_t>(values.size()),
-                                 specs.data(), static_cast<uint32_t>(specs.size()), out.data(), &first_row, &groups));
-    std::vector<ArrayRef> res;
-    for (auto *h : out) res.push_back(Array::adopt(ctx, h));
+    if (by_list)
+        check(rv_hash_aggregate_keys(ctx->raw(), key_cols.data(), static_cast<uint32_t>(key_cols.size()), values.data(), static_cast<uint32_t>(values.size()),
+                                     specs.data(), static_cast<uint32_t>(specs.size()), out.data(), &first_row, &groups));
+    else
+        check(rv_hash_aggregate(ctx->raw(), key_cols[0], values.data(), static_cast<uint32_t>(values.size()), specs.data(),
+                                static_cast<uint32_t>(specs.size()), out.data(), &first_row, &groups));
+    std::vector<ArrayRef> res = adopt_columns(ctx, out);
     const ArrayRef first = Array::adopt(ctx, first_row);
     for (size_t k = 0; k < keys.size(); ++k) {
         if (!strings[k]) continue;  // the strings at the first rows in place of their ids
@@ -1953,58 +1973,38 @@ inline std::vector<ArrayRef> group_by_columns(const ContextRef &ctx, const Schem
     }
     return res;
 }
+inline std::vector<ArrayRef> group_by_columns(const ContextRef &ctx, const Schema &schema, const std::vector<ArrayRef> &columns, const std::string &key,
+                                              const std::vector<AggSpec> &aggs) {
+    return group_by_columns(ctx, schema, columns, {key}, aggs, false);
+}
+inline std::vector<ArrayRef> group_by_columns(const ContextRef &ctx, const Schema &schema, const std::vector<ArrayRef> &columns,
+                                              const std::vector<std::string> &keys, const std::vector<AggSpec> &aggs) {
+    return group_by_columns(ctx, schema, columns, keys, aggs, true);
+}
 
-// group_by as a stream: a PIPELINE BREAKER.  It drains its input -- a resident frame is taken as it is, the batches of any other
-// stream are concatenated (RecordBatch::concat) -- and emits EXACTLY ONE batch: the groups in first-row order.  An input without rows
-// gives one zero-row batch with the output schema.  (Aggregating batch by batch without the concatenation -- a begin / update /
-// finish handle -- is not built.)
-class GpuGroupByStream : public DataStream {
+// group_by as a stream (a GpuBreakerStream): its one batch is the groups in first-row order.  An input without rows gives one zero-row
+// batch with the output schema.  (Aggregating batch by batch without the concatenation -- a begin / update / finish handle -- is not
+// built.)
+class GpuGroupByStream : public GpuBreakerStream {
   public:
-    // `fallback_ctx`: where the zero-row batch of an input that yields no batch at all is created
     GpuGroupByStream(JoinSide input, std::string key, std::vector<AggSpec> aggs, ContextRef fallback_ctx)
-        : input_(std::move(input)), key_(std::move(key)), aggs_(std::move(aggs)), ctx_(std::move(fallback_ctx)) {
-        input_schema_ = input_.schema();
-        schema_ = group_by_schema(*input_schema_, key_, aggs_);
-    }
+        : GpuGroupByStream(std::move(input), std::vector<std::string>{std::move(key)}, std::move(aggs), std::move(fallback_ctx), false) {}
     // the same over a list of key columns (group_by_schema(keys)): one batch, the keys first
     GpuGroupByStream(JoinSide input, std::vector<std::string> keys, std::vector<AggSpec> aggs, ContextRef fallback_ctx)
-        : input_(std::move(input)), keys_(std::move(keys)), by_list_(true), aggs_(std::move(aggs)), ctx_(std::move(fallback_ctx)) {
-        input_schema_ = input_.schema();
-        schema_ = group_by_schema(*input_schema_, keys_, aggs_);
-    }
-    SchemaRef schema() const override { return schema_; }
-    std::optional<RecordBatch> next_batch() override {
-        if (done_) return std::nullopt;
-        done_ = true;
-        std::vector<ArrayRef> columns = input_.columns;
-        if (input_.stream) {
-            std::vector<RecordBatch> all;
-            while (auto b = input_.stream->next_batch()) all.push_back(std::move(*b));
-            if (all.empty()) {
-                if (!ctx_) throw StreamError::execution("group_by: the input yielded no batch and the plan holds no device context");
-                return RecordBatch::empty(ctx_, schema_);
-            }
-            RecordBatch whole = all.size() == 1 ? all[0] : stream_call([&] { return RecordBatch::concat(all); });
-            columns = whole.columns();
-        }
-        return stream_call([&] {
-            const ContextRef ctx = columns.empty() ? ctx_ : columns[0]->context();
-            std::vector<ArrayRef> out = by_list_ ? group_by_columns(ctx, *input_schema_, columns, keys_, aggs_)
-                                                 : group_by_columns(ctx, *input_schema_, columns, key_, aggs_);
-            const size_t rows = out[0]->len();
-            return RecordBatch::new_unchecked(schema_, std::move(out), rows);
-        });
+        : GpuGroupByStream(std::move(input), std::move(keys), std::move(aggs), std::move(fallback_ctx), true) {}
+    // either form, as the plans hold it: `by_list` false is the single-key form over keys[0]
+    GpuGroupByStream(JoinSide input, std::vector<std::string> keys, std::vector<AggSpec> aggs, ContextRef fallback_ctx, bool by_list)
+        : GpuBreakerStream("group_by", std::move(input), std::move(fallback_ctx)), keys_(std::move(keys)), by_list_(by_list), aggs_(std::move(aggs)) {
+        schema_ = group_by_schema(*input_schema_, keys_, aggs_, by_list_);
     }
 
   private:
-    JoinSide input_;
-    std::string key_;
-    std::vector<std::string> keys_;  // by_list_: the key-list form
-    bool by_list_ = false;
+    RecordBatch run(const ContextRef &ctx, const std::vector<ArrayRef> &columns) override {
+        return batch_of(group_by_columns(ctx, *input_schema_, columns, keys_, aggs_, by_list_));
+    }
+    std::vector<std::string> keys_;  // one name and !by_list_: the single-key form
+    bool by_list_;
     std::vector<AggSpec> aggs_;
-    ContextRef ctx_;
-    SchemaRef input_schema_, schema_;
-    bool done_ = false;
 };
 
 // ---------------------------------------------------------------------------------------
@@ -2038,22 +2038,13 @@ inline SchemaRef sort_schema(const Schema &in, const std::vector<SortKey> &keys)
 struct SortCall {
     std::vector<const rv_dcolumn *> handles;
     std::vector<uint32_t> key_cols, key_flags;
-    SortCall(const Schema &schema, const std::vector<ArrayRef> &columns, const std::vector<SortKey> &keys) {
-        for (auto &c : columns) {
-            if (!c->on_device()) throw Error(RV_ERR_UNSUPPORTED, "columns off the device are outside the device path");
-            handles.push_back(c->handle());
-        }
+    SortCall(const Schema &schema, const std::vector<ArrayRef> &columns, const std::vector<SortKey> &keys) : handles(column_handles(columns)) {
         for (auto &k : keys) {
             key_cols.push_back(static_cast<uint32_t>(*schema.index_of(k.column)));
             key_flags.push_back((k.descending ? RV_SORT_DESCENDING : 0u) | (k.nulls_last ? RV_SORT_NULLS_LAST : 0u));
         }
     }
 };
-inline std::vector<ArrayRef> adopt_columns(const ContextRef &ctx, const std::vector<rv_dcolumn *> &out) {
-    std::vector<ArrayRef> res;
-    for (auto *h : out) res.push_back(Array::adopt(ctx, h));
-    return res;
-}
 
 // One rv_sort over one frame (`columns` in the order of `schema`): every column reordered, the first key the most significant.  Columns
 // that are no key ride along whatever their dtype.
@@ -2066,45 +2057,21 @@ inline std::vector<ArrayRef> sort_columns(const ContextRef &ctx, const Schema &s
     return adopt_columns(ctx, out);
 }
 
-// sort as a stream: a PIPELINE BREAKER like GpuGroupByStream.  It drains its input the same way -- a resident frame is taken as it is,
-// the batches of any other stream are concatenated (RecordBatch::concat) -- and emits EXACTLY ONE batch: every row, in order.  An input
-// without rows gives one zero-row batch with the schema.  (Merging sorted runs in place of the concatenation is not built.)
-class GpuSortStream : public DataStream {
+// sort as a stream (a GpuBreakerStream): its one batch is every row, in order.  An input without rows gives one zero-row batch with the
+// schema.  (Merging sorted runs in place of the concatenation is not built.)
+class GpuSortStream : public GpuBreakerStream {
   public:
-    // `fallback_ctx`: where the zero-row batch of an input that yields no batch at all is created
-    GpuSortStream(JoinSide input, std::vector<SortKey> keys, ContextRef fallback_ctx) : input_(std::move(input)), keys_(std::move(keys)), ctx_(std::move(fallback_ctx)) {
-        schema_ = sort_schema(*input_.schema(), keys_);
-    }
-    SchemaRef schema() const override { return schema_; }
-    std::optional<RecordBatch> next_batch() override {
-        if (done_) return std::nullopt;
-        done_ = true;
-        std::vector<ArrayRef> columns = input_.columns;
-        if (input_.stream) {
-            std::vector<RecordBatch> all;
-            while (auto b = input_.stream->next_batch()) all.push_back(std::move(*b));
-            if (all.empty()) {
-                if (!ctx_) throw StreamError::execution("sort: the input yielded no batch and the plan holds no device context");
-                return RecordBatch::empty(ctx_, schema_);
-            }
-            RecordBatch whole = all.size() == 1 ? all[0] : stream_call([&] { return RecordBatch::concat(all); });
-            columns = whole.columns();
-        }
-        return stream_call([&] {
-            const ContextRef ctx = columns.empty() ? ctx_ : columns[0]->context();
-            if (columns.empty() || columns[0]->len() == 0) return RecordBatch::empty(ctx, schema_);
-            std::vector<ArrayRef> out = sort_columns(ctx, *schema_, columns, keys_);
-            const size_t rows = out[0]->len();
-            return RecordBatch::new_unchecked(schema_, std::move(out), rows);
-        });
+    GpuSortStream(JoinSide input, std::vector<SortKey> keys, ContextRef fallback_ctx)
+        : GpuBreakerStream("sort", std::move(input), std::move(fallback_ctx)), keys_(std::move(keys)) {
+        schema_ = sort_schema(*input_schema_, keys_);
     }
 
   private:
-    JoinSide input_;
+    RecordBatch run(const ContextRef &ctx, const std::vector<ArrayRef> &columns) override {
+        if (columns.empty() || columns[0]->len() == 0) return RecordBatch::empty(ctx, schema_);
+        return batch_of(sort_columns(ctx, *schema_, columns, keys_));
+    }
     std::vector<SortKey> keys_;
-    ContextRef ctx_;
-    SchemaRef schema_;
-    bool done_ = false;
 };
 
 // ---------------------------------------------------------------------------------------
@@ -2195,7 +2162,7 @@ inline SchemaRef window_schema(const Schema &in, const std::vector<std::string> 
 }
 
 // One rv_window_frames over one frame (`columns` in the order of `schema`): the NEW columns, one per expression, in the frame's row order.
-// Every String partition key goes through the string dictionary on its own, as group_by's do: its ids (a null string is a null id; "" is
+// Every String partition key goes through the string dictionary on its own (string_key_ids): its ids (a null string is a null id; "" is
 // a value) stand in the tuple.
 inline std::vector<ArrayRef> window_columns(const ContextRef &ctx, const Schema &schema, const std::vector<ArrayRef> &columns,
                                             const std::vector<std::string> &partition_by, const std::vector<SortKey> &order_by,
@@ -2211,11 +2178,7 @@ inline std::vector<ArrayRef> window_columns(const ContextRef &ctx, const Schema 
             part_cols.push_back(static_cast<uint32_t>(at));
             continue;
         }
-        rv_string_dict *dict = nullptr;
-        rv_dcolumn *h = nullptr;
-        check(rv_string_dict_build(ctx->raw(), call.handles[at], &dict, &h));
-        ids.push_back(Array::adopt(ctx, h));
-        check(rv_string_dict_free(ctx->raw(), dict));  // only the ids are needed: equal strings share an id
+        ids.push_back(string_key_ids(ctx, call.handles[at]));
         part_cols.push_back(static_cast<uint32_t>(handles.size()));
         handles.push_back(ids.back()->handle());
     }
@@ -2230,50 +2193,26 @@ inline std::vector<ArrayRef> window_columns(const ContextRef &ctx, const Schema 
     return adopt_columns(ctx, out);
 }
 
-// window as a stream: a PIPELINE BREAKER like GpuSortStream.  It drains its input the same way -- a resident frame is taken as it is, the
-// batches of any other stream are concatenated (RecordBatch::concat) -- and emits EXACTLY ONE batch: every row in input order, the new
-// columns appended.  An input without rows gives one zero-row batch with the schema.  (Windows over input that arrives partitioned,
-// batch by batch, are not built.)
-class GpuWindowStream : public DataStream {
+// window as a stream (a GpuBreakerStream): its one batch is every row in input order, the new columns appended.  An input without rows
+// gives one zero-row batch with the schema.  (Windows over input that arrives partitioned, batch by batch, are not built.)
+class GpuWindowStream : public GpuBreakerStream {
   public:
-    // `fallback_ctx`: where the zero-row batch of an input that yields no batch at all is created
     GpuWindowStream(JoinSide input, std::vector<std::string> partition_by, std::vector<SortKey> order_by, std::vector<WindowExpr> exprs, ContextRef fallback_ctx)
-        : input_(std::move(input)), partition_by_(std::move(partition_by)), order_by_(std::move(order_by)), exprs_(std::move(exprs)), ctx_(std::move(fallback_ctx)) {
-        input_schema_ = input_.schema();
+        : GpuBreakerStream("window", std::move(input), std::move(fallback_ctx)), partition_by_(std::move(partition_by)), order_by_(std::move(order_by)),
+          exprs_(std::move(exprs)) {
         schema_ = window_schema(*input_schema_, partition_by_, order_by_, exprs_);
-    }
-    SchemaRef schema() const override { return schema_; }
-    std::optional<RecordBatch> next_batch() override {
-        if (done_) return std::nullopt;
-        done_ = true;
-        std::vector<ArrayRef> columns = input_.columns;
-        if (input_.stream) {
-            std::vector<RecordBatch> all;
-            while (auto b = input_.stream->next_batch()) all.push_back(std::move(*b));
-            if (all.empty()) {
-                if (!ctx_) throw StreamError::execution("window: the input yielded no batch and the plan holds no device context");
-                return RecordBatch::empty(ctx_, schema_);
-            }
-            RecordBatch whole = all.size() == 1 ? all[0] : stream_call([&] { return RecordBatch::concat(all); });
-            columns = whole.columns();
-        }
-        return stream_call([&] {
-            const ContextRef ctx = columns.empty() ? ctx_ : columns[0]->context();
-            if (columns.empty() || columns[0]->len() == 0) return RecordBatch::empty(ctx, schema_);
-            const size_t rows = columns[0]->len();
-            for (auto &c : window_columns(ctx, *input_schema_, columns, partition_by_, order_by_, exprs_)) columns.push_back(c);
-            return RecordBatch::new_unchecked(schema_, std::move(columns), rows);
-        });
     }
 
   private:
-    JoinSide input_;
+    RecordBatch run(const ContextRef &ctx, const std::vector<ArrayRef> &columns) override {
+        if (columns.empty() || columns[0]->len() == 0) return RecordBatch::empty(ctx, schema_);
+        std::vector<ArrayRef> out = columns;
+        for (auto &c : window_columns(ctx, *input_schema_, columns, partition_by_, order_by_, exprs_)) out.push_back(c);
+        return batch_of(std::move(out));
+    }
     std::vector<std::string> partition_by_;
     std::vector<SortKey> order_by_;
     std::vector<WindowExpr> exprs_;
-    ContextRef ctx_;
-    SchemaRef input_schema_, schema_;
-    bool done_ = false;
 };
 
 // ---------------------------------------------------------------------------------------
@@ -2304,19 +2243,18 @@ constexpr size_t kTopKFoldRows = size_t{1} << 22;
 // so no more than fold_rows + k rows (and the batch that crossed the line) are held at once.  The fold is exact: `best` comes before
 // the later rows in the concatenation and the sort is stable, so rows with equal keys come out in input order, whatever batches they
 // arrived in.  An input without rows gives one zero-row batch with the schema.
-class GpuTopKStream : public DataStream {
+class GpuTopKStream : public GpuBreakerStream {
   public:
-    // `fallback_ctx`: where the zero-row batch of an input that yields no batch at all is created
     GpuTopKStream(JoinSide input, std::vector<SortKey> keys, size_t k, ContextRef fallback_ctx, size_t fold_rows = kTopKFoldRows)
-        : input_(std::move(input)), keys_(std::move(keys)), k_(k), fold_rows_(std::max<size_t>(fold_rows, 1)), ctx_(std::move(fallback_ctx)) {
-        schema_ = top_k_schema(*input_.schema(), keys_, k_);
+        : GpuBreakerStream("top_k", std::move(input), std::move(fallback_ctx)), keys_(std::move(keys)), k_(k), fold_rows_(std::max<size_t>(fold_rows, 1)) {
+        schema_ = top_k_schema(*input_schema_, keys_, k_);
     }
-    SchemaRef schema() const override { return schema_; }
     size_t folds() const { return folds_; }  // rv_top_k calls so far (tests)
-    std::optional<RecordBatch> next_batch() override {
+    std::optional<RecordBatch> next_batch() override {  // the fold in place of the drain
         if (done_) return std::nullopt;
         done_ = true;
-        if (!input_.stream) return stream_call([&] { return best_of(input_.columns); });
+        auto best_of = [&](const std::vector<ArrayRef> &columns) { return stream_call([&] { return run(ctx_of(columns), columns); }); };
+        if (!input_.stream) return best_of(input_.columns);
         std::optional<RecordBatch> best;
         std::vector<RecordBatch> gathered;
         size_t gathered_rows = 0;
@@ -2326,7 +2264,7 @@ class GpuTopKStream : public DataStream {
             for (auto &b : gathered) all.push_back(std::move(b));
             gathered.clear();
             gathered_rows = 0;
-            best = stream_call([&] { return best_of((all.size() == 1 ? all[0] : RecordBatch::concat(all)).columns()); });
+            best = all.size() == 1 ? best_of(all[0].columns()) : best_of(stream_call([&] { return RecordBatch::concat(all); }).columns());
         };
         while (auto b = input_.stream->next_batch()) {
             if (!ctx_ && b->num_columns() > 0) ctx_ = b->column(0)->context();
@@ -2337,25 +2275,17 @@ class GpuTopKStream : public DataStream {
         }
         if (!gathered.empty()) fold();
         if (best) return best;
-        if (!ctx_) throw StreamError::execution("top_k: the input yielded no batch and the plan holds no device context");
-        return RecordBatch::empty(ctx_, schema_);
+        return no_batch();
     }
 
   private:
-    RecordBatch best_of(const std::vector<ArrayRef> &columns) {
-        const ContextRef ctx = columns.empty() ? ctx_ : columns[0]->context();
+    RecordBatch run(const ContextRef &ctx, const std::vector<ArrayRef> &columns) override {
         if (columns.empty() || columns[0]->len() == 0) return RecordBatch::empty(ctx, schema_);
         ++folds_;
-        std::vector<ArrayRef> out = top_k_columns(ctx, *schema_, columns, keys_, k_);
-        const size_t rows = out[0]->len();
-        return RecordBatch::new_unchecked(schema_, std::move(out), rows);
+        return batch_of(top_k_columns(ctx, *schema_, columns, keys_, k_));
     }
-    JoinSide input_;
     std::vector<SortKey> keys_;
     size_t k_, fold_rows_, folds_ = 0;
-    ContextRef ctx_;
-    SchemaRef schema_;
-    bool done_ = false;
 };
 
 }  // namespace execution
@@ -2665,18 +2595,18 @@ struct DeviceFrame {  // the typed-column stand-in for datatypes::DataFrame
     std::vector<execution::ArrayRef> columns;
     size_t height() const { return columns.empty() ? 0 : columns[0]->len(); }
     size_t width() const { return columns.size(); }
-    const execution::ArrayRef *column(const std::string &n) const {
+    std::optional<size_t> index_of(const std::string &n) const {
         for (size_t i = 0; i < names.size(); ++i)
-            if (names[i] == n) return &columns[i];
-        return nullptr;
+            if (names[i] == n) return i;
+        return std::nullopt;
+    }
+    const execution::ArrayRef *column(const std::string &n) const {
+        const auto i = index_of(n);
+        return i ? &columns[*i] : nullptr;
     }
 };
 
-inline execution::Schema frame_schema(const DeviceFrame &df) {  // every field nullable, as dataframe_to_batches declares them
-    std::vector<execution::Field> f;
-    for (size_t c = 0; c < df.columns.size(); ++c) f.push_back(execution::Field{df.names[c], df.columns[c]->data_type(), true});
-    return execution::Schema(f);
-}
+inline execution::Schema frame_schema(const DeviceFrame &df) { return *execution::nullable_schema(df.names, df.columns); }
 
 // dataframe_to_batches -- streaming.rs:135-233: batch_size-row chunks (zero-copy slices); the null cells of
 // Int64 / Float64 / Boolean columns become 0 / 0.0 / false and the column loses its bitmap (the reference
@@ -2686,9 +2616,7 @@ inline std::vector<execution::RecordBatch> dataframe_to_batches(const DeviceFram
     std::vector<RecordBatch> batches;
     if (df.columns.empty() || df.height() == 0) return batches;  // df.is_empty()
     if (batch_size == 0) throw Panic("attempt to divide by zero");
-    std::vector<Field> fields;
-    for (size_t c = 0; c < df.columns.size(); ++c) fields.push_back(Field{df.names[c], df.columns[c]->data_type(), true});
-    auto schema = std::make_shared<Schema>(fields);
+    const SchemaRef schema = nullable_schema(df.names, df.columns);
     const size_t rows = df.height();
     for (size_t start = 0; start < rows; start += batch_size) {
         const size_t len = std::min(batch_size, rows - start);
@@ -2731,9 +2659,8 @@ class StreamingPhysicalPlan {
     StreamingPlanPtr build_side;  // HashJoin { build_side, probe_side = input, build_key, probe_key, join_kind }: the sides as joined
     rv_join_kind join_kind = RV_JOIN_INNER;
     std::string build_key, probe_key;
-    std::string group_key;  // GroupBy { input, group_key, aggs }
-    std::vector<std::string> group_keys;  // GroupBy { input, group_keys, aggs } when group_by_list: the key-list form
-    bool group_by_list = false;
+    std::vector<std::string> group_keys;  // GroupBy { input, group_keys, aggs }: the key list, or the one key of the single-key form
+    bool group_by_list = false;           // ... which of the two forms
     std::vector<execution::AggSpec> aggs;
     std::vector<execution::SortKey> sort_keys;  // Sort { input, sort_keys }, TopK { input, sort_keys, top_k_rows, top_k_fold_rows }
     size_t top_k_rows = 0, top_k_fold_rows = execution::kTopKFoldRows;
@@ -2741,14 +2668,12 @@ class StreamingPhysicalPlan {
     std::vector<execution::WindowExpr> window_exprs;
 
     static StreamingPlanPtr memory_source(std::vector<execution::RecordBatch> b) {
-        auto p = std::make_shared<StreamingPhysicalPlan>();
-        p->kind = MemorySource;
+        auto p = node(MemorySource);
         p->batches = std::move(b);
         return p;
     }
     static StreamingPlanPtr dataframe_source(DeviceFrame df, size_t batch_size) {
-        auto p = std::make_shared<StreamingPhysicalPlan>();
-        p->kind = DataFrameSource;
+        auto p = node(DataFrameSource);
         p->df = std::move(df);
         p->df_batch_size = batch_size;
         return p;
@@ -2756,8 +2681,7 @@ class StreamingPhysicalPlan {
     static StreamingPlanPtr csv_file_source(ContextRef ctx, std::string path, execution::SchemaRef schema, std::optional<size_t> batch_size = std::nullopt,
                                             std::optional<char> delimiter = std::nullopt, execution::CsvNulls nulls = execution::CsvNulls::AsReference,
                                             execution::CsvScan scan = execution::CsvScan::Host) {
-        auto p = std::make_shared<StreamingPhysicalPlan>();
-        p->kind = CsvFileSource;
+        auto p = node(CsvFileSource);
         p->csv_ctx = std::move(ctx);
         p->csv_path = std::move(path);
         p->csv_schema = std::move(schema);
@@ -2768,50 +2692,38 @@ class StreamingPhysicalPlan {
         return p;
     }
     static StreamingPlanPtr filter(StreamingPlanPtr in, std::string predicate_column) {
-        auto p = std::make_shared<StreamingPhysicalPlan>();
-        p->kind = Filter;
-        p->input = std::move(in);
+        auto p = node(Filter, std::move(in));
         p->predicate_column = std::move(predicate_column);
         return p;
     }
     // Filter(expr) followed by Select(columns): one fused operator
     static StreamingPlanPtr gpu_filter_project(StreamingPlanPtr in, execution::LoweredPredicate predicate, std::vector<std::string> columns) {
-        auto p = std::make_shared<StreamingPhysicalPlan>();
-        p->kind = GpuFilterProject;
-        p->input = std::move(in);
+        auto p = node(GpuFilterProject, std::move(in));
         p->predicate = std::move(predicate);
         p->columns = std::move(columns);
         return p;
     }
     static StreamingPlanPtr select(StreamingPlanPtr in, std::vector<std::string> columns) {
-        auto p = std::make_shared<StreamingPhysicalPlan>();
-        p->kind = Select;
-        p->input = std::move(in);
+        auto p = node(Select, std::move(in));
         p->columns = std::move(columns);
         return p;
     }
     // select([...]) whose expressions may be arithmetic (lower_select_exprs): GpuProjectStream
     static StreamingPlanPtr project(StreamingPlanPtr in, std::vector<Expr> exprs) {
-        auto p = std::make_shared<StreamingPhysicalPlan>();
-        p->kind = Project;
-        p->input = std::move(in);
+        auto p = node(Project, std::move(in));
         p->exprs = std::move(exprs);
         return p;
     }
     // Filter(expr) with computed terms (lower_computed_predicate) followed by Select(columns): the helper columns are appended by a
     // GpuProjectStream and dropped again by the fused operator's projection
     static StreamingPlanPtr computed_filter_project(StreamingPlanPtr in, Expr predicate, std::vector<std::string> columns) {
-        auto p = std::make_shared<StreamingPhysicalPlan>();
-        p->kind = ComputedFilterProject;
-        p->input = std::move(in);
+        auto p = node(ComputedFilterProject, std::move(in));
         p->predicate_expr = std::move(predicate);
         p->columns = std::move(columns);
         return p;
     }
     static StreamingPlanPtr limit(StreamingPlanPtr in, size_t n) {
-        auto p = std::make_shared<StreamingPhysicalPlan>();
-        p->kind = Limit;
-        p->input = std::move(in);
+        auto p = node(Limit, std::move(in));
         p->n = n;
         return p;
     }
@@ -2830,10 +2742,8 @@ class StreamingPhysicalPlan {
             std::swap(build, probe);
             std::swap(build_key, probe_key);
         }
-        auto p = std::make_shared<StreamingPhysicalPlan>();
-        p->kind = HashJoin;
+        auto p = node(HashJoin, std::move(probe));
         p->build_side = std::move(build);
-        p->input = std::move(probe);
         p->build_key = std::move(build_key);
         p->probe_key = std::move(probe_key);
         p->join_kind = shape.kind;
@@ -2842,19 +2752,15 @@ class StreamingPhysicalPlan {
 
     // group_by(key).agg(aggs): a pipeline breaker that emits exactly one batch (GpuGroupByStream); the reference has no such operator
     static StreamingPlanPtr group_by(StreamingPlanPtr in, std::string key, std::vector<execution::AggSpec> aggs) {
-        auto p = std::make_shared<StreamingPhysicalPlan>();
-        p->kind = GroupBy;
-        p->input = std::move(in);
-        p->group_key = std::move(key);
+        auto p = node(GroupBy, std::move(in));
+        p->group_keys = {std::move(key)};
         p->aggs = std::move(aggs);
         return p;
     }
     // group_by([k0, k1, ...]).agg(aggs): the same over tuples of up to 8 key columns of any dtype (group_by_schema(keys)); the keys come
     // first in the batch
     static StreamingPlanPtr group_by(StreamingPlanPtr in, std::vector<std::string> keys, std::vector<execution::AggSpec> aggs) {
-        auto p = std::make_shared<StreamingPhysicalPlan>();
-        p->kind = GroupBy;
-        p->input = std::move(in);
+        auto p = node(GroupBy, std::move(in));
         p->group_keys = std::move(keys);
         p->group_by_list = true;
         p->aggs = std::move(aggs);
@@ -2862,18 +2768,14 @@ class StreamingPhysicalPlan {
     }
     // sort(keys): a pipeline breaker that emits exactly one batch (GpuSortStream); the reference has no such operator
     static StreamingPlanPtr sort(StreamingPlanPtr in, std::vector<execution::SortKey> keys) {
-        auto p = std::make_shared<StreamingPhysicalPlan>();
-        p->kind = Sort;
-        p->input = std::move(in);
+        auto p = node(Sort, std::move(in));
         p->sort_keys = std::move(keys);
         return p;
     }
     // top_k(keys, k): the first k rows of sort(keys) without sorting the input; a pipeline breaker that emits exactly one batch
     // (GpuTopKStream, which folds the input every `fold_rows` rows).  What a planner makes of Limit(Sort(x)).
     static StreamingPlanPtr top_k(StreamingPlanPtr in, std::vector<execution::SortKey> keys, size_t k, size_t fold_rows = execution::kTopKFoldRows) {
-        auto p = std::make_shared<StreamingPhysicalPlan>();
-        p->kind = TopK;
-        p->input = std::move(in);
+        auto p = node(TopK, std::move(in));
         p->sort_keys = std::move(keys);
         p->top_k_rows = k;
         p->top_k_fold_rows = fold_rows;
@@ -2883,9 +2785,7 @@ class StreamingPhysicalPlan {
     // emits exactly one batch (GpuWindowStream); the reference has no such operator
     static StreamingPlanPtr window(StreamingPlanPtr in, std::vector<std::string> partition_by, std::vector<execution::SortKey> order_by,
                                    std::vector<execution::WindowExpr> exprs) {
-        auto p = std::make_shared<StreamingPhysicalPlan>();
-        p->kind = Window;
-        p->input = std::move(in);
+        auto p = node(Window, std::move(in));
         p->partition_keys = std::move(partition_by);
         p->sort_keys = std::move(order_by);
         p->window_exprs = std::move(exprs);
@@ -2943,50 +2843,13 @@ class StreamingPhysicalPlan {
                     auto widened = std::make_unique<GpuProjectStream>(std::move(in), with_arith_helpers(*schema, lowered.helpers));
                     return std::make_unique<GpuFilterProjectStream>(std::move(widened), std::move(lowered.predicate), columns);
                 }
-                case HashJoin: {
-                    // a resident frame is taken whole, after the null fill: windows of the probe frame, the build frame as it is (an
-                    // empty frame too: it still has its columns' names and dtypes)
-                    auto side = [](const StreamingPhysicalPlan &p) {
-                        JoinSide s;
-                        if (p.kind == DataFrameSource && !p.df.columns.empty() && p.df_batch_size > 0) {
-                            s.names = p.df.names;
-                            s.columns = p.filled_columns();
-                            s.batch_size = p.df_batch_size;
-                        } else {
-                            s.stream = p.execute();
-                        }
-                        return s;
-                    };
-                    return std::make_unique<GpuHashJoinStream>(side(*build_side), side(*input), build_key, probe_key, size_t(1) << 28, uint64_t(1) << 28,
-                                                               join_kind);
-                }
-                case GroupBy: {  // a resident frame is taken whole, after the null fill, as the join takes it
-                    JoinSide s;
-                    if (input->kind == DataFrameSource && !input->df.columns.empty() && input->df_batch_size > 0) {
-                        s.names = input->df.names;
-                        s.columns = input->filled_columns();
-                        s.batch_size = input->df_batch_size;
-                    } else {
-                        s.stream = input->execute();
-                    }
-                    if (group_by_list) return std::make_unique<GpuGroupByStream>(std::move(s), group_keys, aggs, any_context());
-                    return std::make_unique<GpuGroupByStream>(std::move(s), group_key, aggs, any_context());
-                }
-                case Sort:
-                case Window:
-                case TopK: {  // drain their input as GroupBy does
-                    JoinSide s;
-                    if (input->kind == DataFrameSource && !input->df.columns.empty() && input->df_batch_size > 0) {
-                        s.names = input->df.names;
-                        s.columns = input->filled_columns();
-                        s.batch_size = input->df_batch_size;
-                    } else {
-                        s.stream = input->execute();
-                    }
-                    if (kind == TopK) return std::make_unique<GpuTopKStream>(std::move(s), sort_keys, top_k_rows, any_context(), top_k_fold_rows);
-                    if (kind == Window) return std::make_unique<GpuWindowStream>(std::move(s), partition_keys, sort_keys, window_exprs, any_context());
-                    return std::make_unique<GpuSortStream>(std::move(s), sort_keys, any_context());
-                }
+                case HashJoin:  // windows of a resident probe frame, a resident build frame as it is
+                    return std::make_unique<GpuHashJoinStream>(build_side->as_input(), input->as_input(), build_key, probe_key, size_t(1) << 28,
+                                                               uint64_t(1) << 28, join_kind);
+                case GroupBy: return std::make_unique<GpuGroupByStream>(input->as_input(), group_keys, aggs, any_context(), group_by_list);
+                case Sort: return std::make_unique<GpuSortStream>(input->as_input(), sort_keys, any_context());
+                case Window: return std::make_unique<GpuWindowStream>(input->as_input(), partition_keys, sort_keys, window_exprs, any_context());
+                case TopK: return std::make_unique<GpuTopKStream>(input->as_input(), sort_keys, top_k_rows, any_context(), top_k_fold_rows);
             }
         } catch (const StreamError &e) {
             throw StreamingExecutionError(std::string("Stream error: ") + e.what());
@@ -3002,6 +2865,19 @@ class StreamingPhysicalPlan {
             filled.push_back(execution::Array::adopt(col->context(), f));
         }
         return filled;
+    }
+    // This node as the input of a join or of a pipeline breaker: a resident frame (a DataFrameSource with a batch size) is taken whole,
+    // after the null fill -- an empty frame too: it still has its columns' names and dtypes --, anything else is its stream.
+    execution::JoinSide as_input() const {
+        execution::JoinSide s;
+        if (kind == DataFrameSource && !df.columns.empty() && df_batch_size > 0) {
+            s.names = df.names;
+            s.columns = filled_columns();
+            s.batch_size = df_batch_size;
+        } else {
+            s.stream = execute();
+        }
+        return s;
     }
     std::vector<execution::RecordBatch> collect_batches() const {
         auto s = execute();
@@ -3027,6 +2903,14 @@ class StreamingPhysicalPlan {
             throw StreamingExecutionError(std::string("Stream error: ") + e.what());
         }
     }
+
+  private:
+    static std::shared_ptr<StreamingPhysicalPlan> node(Kind kind, StreamingPlanPtr input = nullptr) {  // what every factory starts from
+        auto p = std::make_shared<StreamingPhysicalPlan>();
+        p->kind = kind;
+        p->input = std::move(input);
+        return p;
+    }
 };
 
 // Eager PhysicalPlan (plan.rs:8-150) over a frame of named, typed device columns.  Filter keeps
@@ -3049,9 +2933,8 @@ class PhysicalPlan {
     PhysicalPlanPtr build_side;          // HashJoin { build_side, probe_side = input, build_key, probe_key, join_kind }: the sides as joined
     rv_join_kind join_kind = RV_JOIN_INNER;
     std::string build_key, probe_key;
-    std::string group_key;  // GroupBy { input, group_key, aggs }
-    std::vector<std::string> group_keys;  // GroupBy { input, group_keys, aggs } when group_by_list: the key-list form
-    bool group_by_list = false;
+    std::vector<std::string> group_keys;  // GroupBy { input, group_keys, aggs }: the key list, or the one key of the single-key form
+    bool group_by_list = false;           // ... which of the two forms
     std::vector<execution::AggSpec> aggs;
     std::vector<execution::SortKey> sort_keys;  // Sort { input, sort_keys }, TopK { input, sort_keys, top_k_rows }
     size_t top_k_rows = 0;
@@ -3059,21 +2942,17 @@ class PhysicalPlan {
     std::vector<execution::WindowExpr> window_exprs;
 
     static PhysicalPlanPtr source(DeviceFrame f) {
-        auto p = std::make_shared<PhysicalPlan>();
+        auto p = node(DataFrameSource);
         p->df = std::move(f);
         return p;
     }
     static PhysicalPlanPtr filter(PhysicalPlanPtr in, CompareTerm t) {
-        auto p = std::make_shared<PhysicalPlan>();
-        p->kind = Filter;
-        p->input = std::move(in);
+        auto p = node(Filter, std::move(in));
         p->term = std::move(t);
         return p;
     }
     static PhysicalPlanPtr select(PhysicalPlanPtr in, std::vector<std::string> cols, std::vector<std::string> finals) {
-        auto p = std::make_shared<PhysicalPlan>();
-        p->kind = Select;
-        p->input = std::move(in);
+        auto p = node(Select, std::move(in));
         p->columns = std::move(cols);
         p->final_names = std::move(finals);
         return p;
@@ -3081,18 +2960,14 @@ class PhysicalPlan {
     // Select whose expressions may be arithmetic (lower_select_exprs): plain columns pass through as Select passes them, computed
     // ones are one rv_eval_arith each
     static PhysicalPlanPtr project(PhysicalPlanPtr in, std::vector<Expr> exprs) {
-        auto p = std::make_shared<PhysicalPlan>();
-        p->kind = Project;
-        p->input = std::move(in);
+        auto p = node(Project, std::move(in));
         p->exprs = std::move(exprs);
         return p;
     }
     // Filter over computed terms (lower_computed_predicate): every column kept, AnyValue ordering for nulls -- on the helper
     // columns as on any other
     static PhysicalPlanPtr computed_filter(PhysicalPlanPtr in, Expr predicate) {
-        auto p = std::make_shared<PhysicalPlan>();
-        p->kind = ComputedFilter;
-        p->input = std::move(in);
+        auto p = node(ComputedFilter, std::move(in));
         p->predicate_expr = std::move(predicate);
         return p;
     }
@@ -3105,10 +2980,8 @@ class PhysicalPlan {
             std::swap(build, probe);
             std::swap(build_key, probe_key);
         }
-        auto p = std::make_shared<PhysicalPlan>();
-        p->kind = HashJoin;
+        auto p = node(HashJoin, std::move(probe));
         p->build_side = std::move(build);
-        p->input = std::move(probe);
         p->build_key = std::move(build_key);
         p->probe_key = std::move(probe_key);
         p->join_kind = shape.kind;
@@ -3117,10 +2990,8 @@ class PhysicalPlan {
     // group_by(key).agg(aggs), eager: one rv_hash_aggregate; the key under its own name, then every aggregate under its name, the
     // groups in the order of their first rows.  The nulls of the frame stay nulls (no fill: this is not a stream).
     static PhysicalPlanPtr group_by(PhysicalPlanPtr in, std::string key, std::vector<execution::AggSpec> aggs) {
-        auto p = std::make_shared<PhysicalPlan>();
-        p->kind = GroupBy;
-        p->input = std::move(in);
-        p->group_key = std::move(key);
+        auto p = node(GroupBy, std::move(in));
+        p->group_keys = {std::move(key)};
         p->aggs = std::move(aggs);
         return p;
     }
@@ -3128,9 +2999,7 @@ class PhysicalPlan {
     // String or Null, each with its nulls; the keys under their own names in the order given, then the aggregates.  The list with one
     // name is how a Float64 or Boolean key is grouped.
     static PhysicalPlanPtr group_by(PhysicalPlanPtr in, std::vector<std::string> keys, std::vector<execution::AggSpec> aggs) {
-        auto p = std::make_shared<PhysicalPlan>();
-        p->kind = GroupBy;
-        p->input = std::move(in);
+        auto p = node(GroupBy, std::move(in));
         p->group_keys = std::move(keys);
         p->group_by_list = true;
         p->aggs = std::move(aggs);
@@ -3139,17 +3008,13 @@ class PhysicalPlan {
     // sort(keys), eager: one rv_sort; names and dtypes unchanged, the first key the most significant, equal rows in input order.  The nulls
     // of the frame stay nulls (no fill: this is not a stream).
     static PhysicalPlanPtr sort(PhysicalPlanPtr in, std::vector<execution::SortKey> keys) {
-        auto p = std::make_shared<PhysicalPlan>();
-        p->kind = Sort;
-        p->input = std::move(in);
+        auto p = node(Sort, std::move(in));
         p->sort_keys = std::move(keys);
         return p;
     }
     // top_k(keys, k), eager: one rv_top_k -- the first min(k, rows) rows of sort(keys), without sorting the frame
     static PhysicalPlanPtr top_k(PhysicalPlanPtr in, std::vector<execution::SortKey> keys, size_t k) {
-        auto p = std::make_shared<PhysicalPlan>();
-        p->kind = TopK;
-        p->input = std::move(in);
+        auto p = node(TopK, std::move(in));
         p->sort_keys = std::move(keys);
         p->top_k_rows = k;
         return p;
@@ -3158,9 +3023,7 @@ class PhysicalPlan {
     // appended under its alias.  The nulls of the frame stay nulls (no fill: this is not a stream).
     static PhysicalPlanPtr window(PhysicalPlanPtr in, std::vector<std::string> partition_by, std::vector<execution::SortKey> order_by,
                                   std::vector<execution::WindowExpr> exprs) {
-        auto p = std::make_shared<PhysicalPlan>();
-        p->kind = Window;
-        p->input = std::move(in);
+        auto p = node(Window, std::move(in));
         p->partition_keys = std::move(partition_by);
         p->sort_keys = std::move(order_by);
         p->window_exprs = std::move(exprs);
@@ -3203,11 +3066,9 @@ class PhysicalPlan {
             case GroupBy: {
                 DeviceFrame in = input->execute();
                 const execution::Schema schema = frame_schema(in);
-                const execution::SchemaRef out_schema =
-                    group_by_list ? execution::group_by_schema(schema, group_keys, aggs) : execution::group_by_schema(schema, group_key, aggs);  // the planning errors
+                const execution::SchemaRef out_schema = execution::group_by_schema(schema, group_keys, aggs, group_by_list);  // the planning errors
                 DeviceFrame out;
-                if (group_by_list) out.columns = execution::group_by_columns((*in.column(group_keys[0]))->context(), schema, in.columns, group_keys, aggs);
-                else out.columns = execution::group_by_columns((*in.column(group_key))->context(), schema, in.columns, group_key, aggs);
+                out.columns = execution::group_by_columns((*in.column(group_keys[0]))->context(), schema, in.columns, group_keys, aggs, group_by_list);
                 for (auto &f : out_schema->fields()) out.names.push_back(f.name());
                 return out;
             }
@@ -3224,28 +3085,19 @@ class PhysicalPlan {
             }
             case Filter: {  // plan.rs:97-150: mask over one column, every column kept
                 DeviceFrame in = input->execute();
-                const execution::ArrayRef *fc = in.column(term.column);
-                if (!fc) throw ExecutionError(ExecutionError::ColumnNotFound, "Column not found: '" + term.column + "'");
-                std::vector<const rv_dcolumn *> cols;
+                const auto pred_col = in.index_of(term.column);
+                if (!pred_col) throw ExecutionError(ExecutionError::ColumnNotFound, "Column not found: '" + term.column + "'");
+                const std::vector<const rv_dcolumn *> cols = execution::column_handles(in.columns, "String columns are outside the device path");
                 std::vector<uint32_t> proj;
-                uint32_t pred_col = 0;
-                for (size_t i = 0; i < in.columns.size(); ++i) {
-                    if (!in.columns[i]->on_device()) throw Error(RV_ERR_UNSUPPORTED, "String columns are outside the device path");
-                    if (&in.columns[i] == fc) pred_col = static_cast<uint32_t>(i);
-                    cols.push_back(in.columns[i]->handle());
-                    proj.push_back(static_cast<uint32_t>(i));
-                }
-                rv_term t = execution::to_rv_term(term, pred_col);
+                for (uint32_t i = 0; i < cols.size(); ++i) proj.push_back(i);
+                rv_term t = execution::to_rv_term(term, static_cast<uint32_t>(*pred_col));
                 rv_predicate pred{&t, 1, RV_NULL_IS_LEAST, nullptr, 0};
                 std::vector<rv_dcolumn *> out(cols.size(), nullptr);
                 uint64_t rows = 0;
-                const ContextRef ctx = (*fc)->context();
+                const ContextRef ctx = in.columns[*pred_col]->context();
                 check(rv_filter_project(ctx->raw(), cols.data(), static_cast<uint32_t>(cols.size()), &pred, proj.data(),
                                         static_cast<uint32_t>(proj.size()), out.data(), &rows, nullptr));
-                DeviceFrame res;
-                res.names = in.names;
-                for (auto *h : out) res.columns.push_back(execution::Array::adopt(ctx, h));
-                return res;
+                return DeviceFrame{in.names, execution::adopt_columns(ctx, out)};
             }
             case Project: {
                 DeviceFrame in = input->execute();
@@ -3276,13 +3128,9 @@ class PhysicalPlan {
                     helpers.push_back(execution::eval_arith(h.program, column, missing));
                     names.push_back(h.name);
                 }
-                std::vector<const rv_dcolumn *> cols;
+                std::vector<const rv_dcolumn *> cols = execution::column_handles(in.columns);
                 std::vector<uint32_t> proj;
-                for (size_t i = 0; i < in.columns.size(); ++i) {
-                    if (!in.columns[i]->on_device()) throw Error(RV_ERR_UNSUPPORTED, "columns off the device are outside the device path");
-                    cols.push_back(in.columns[i]->handle());
-                    proj.push_back(static_cast<uint32_t>(i));
-                }
+                for (uint32_t i = 0; i < in.columns.size(); ++i) proj.push_back(i);
                 for (auto &h : helpers) cols.push_back(h->handle());
                 std::vector<rv_term> terms;
                 for (auto &t : lowered.predicate.terms) {
@@ -3298,38 +3146,26 @@ class PhysicalPlan {
                 uint64_t rows = 0;
                 check(rv_filter_project(ctx->raw(), cols.data(), static_cast<uint32_t>(cols.size()), &pred, proj.data(), static_cast<uint32_t>(proj.size()),
                                         out.data(), &rows, nullptr));
-                DeviceFrame res;
-                res.names = in.names;
-                for (auto *h : out) res.columns.push_back(execution::Array::adopt(ctx, h));
-                return res;
+                return DeviceFrame{in.names, execution::adopt_columns(ctx, out)};
             }
             case HashJoin: {  // plan.rs:174-207 (JoinType::Inner), one rv_hash_join; the other kinds one rv_hash_join_kind
                 DeviceFrame b = build_side->execute();
-                const execution::ArrayRef *bk = b.column(build_key);
-                if (!bk) throw Panic("called `Option::unwrap()` on a `None` value");  // plan.rs:184: build_df.column(..).unwrap()
+                const auto build_at = b.index_of(build_key);
+                if (!build_at) throw Panic("called `Option::unwrap()` on a `None` value");  // plan.rs:184: build_df.column(..).unwrap()
                 DeviceFrame p = input->execute();
-                const execution::ArrayRef *pk = p.column(probe_key);
-                if (!pk) throw Panic("called `Option::unwrap()` on a `None` value");  // plan.rs:195
-                std::vector<const rv_dcolumn *> bcols, pcols;
-                uint32_t bki = 0, pki = 0;
-                for (size_t i = 0; i < b.columns.size(); ++i) {
-                    if (!b.columns[i]->on_device()) throw Error(RV_ERR_UNSUPPORTED, "columns off the device are outside the device path");
-                    if (&b.columns[i] == bk) bki = static_cast<uint32_t>(i);
-                    bcols.push_back(b.columns[i]->handle());
-                }
-                for (size_t i = 0; i < p.columns.size(); ++i) {
-                    if (!p.columns[i]->on_device()) throw Error(RV_ERR_UNSUPPORTED, "columns off the device are outside the device path");
-                    if (&p.columns[i] == pk) pki = static_cast<uint32_t>(i);
-                    pcols.push_back(p.columns[i]->handle());
-                }
+                const auto probe_at = p.index_of(probe_key);
+                if (!probe_at) throw Panic("called `Option::unwrap()` on a `None` value");  // plan.rs:195
+                const uint32_t bki = static_cast<uint32_t>(*build_at), pki = static_cast<uint32_t>(*probe_at);
+                const execution::ArrayRef &bk = b.columns[bki], &pk = p.columns[pki];
+                std::vector<const rv_dcolumn *> bcols = execution::column_handles(b.columns), pcols = execution::column_handles(p.columns);
                 // String keys go through the string dictionary: ids in place of the build key, a helper column as the probe key
-                const ContextRef ctx = (*pk)->context();
-                execution::StringKeyEncoder string_keys((*bk)->data_type(), (*pk)->data_type());
-                const execution::ArrayRef build_ids = string_keys.build_key(*bk), helper = string_keys.probe_key(ctx, *pk);
+                const ContextRef ctx = pk->context();
+                execution::StringKeyEncoder string_keys(bk->data_type(), pk->data_type());
+                const execution::ArrayRef build_ids = string_keys.build_key(bk), helper = string_keys.probe_key(ctx, pk);
                 if (build_ids) bcols[bki] = build_ids->handle();
                 // a full outer join returns the build key: the strings, carried as one more build column, not their ids
                 const bool carried_key = build_ids && join_kind == RV_JOIN_FULL_OUTER;
-                if (carried_key) bcols.push_back((*bk)->handle());
+                if (carried_key) bcols.push_back(bk->handle());
                 const execution::ProbeColumns probe = execution::with_key_helper(std::move(pcols), pki, helper);
                 const bool probe_only = join_kind == RV_JOIN_PROBE_SEMI || join_kind == RV_JOIN_PROBE_ANTI;
                 const size_t nout = probe_only ? probe.cols.size() : probe.cols.size() + bcols.size() - (join_kind == RV_JOIN_FULL_OUTER ? 0 : 1);
@@ -3341,16 +3177,22 @@ class PhysicalPlan {
                 else
                     check(rv_hash_join_kind(ctx->raw(), bcols.data(), static_cast<uint32_t>(bcols.size()), bki, probe.cols.data(),
                                             static_cast<uint32_t>(probe.cols.size()), probe.key, join_kind, out.data(), &rows));
-                DeviceFrame res;
-                for (auto *h : out) res.columns.push_back(execution::Array::adopt(ctx, h));
+                DeviceFrame res{{}, execution::adopt_columns(ctx, out)};
                 if (carried_key) execution::restore_build_key(res.columns, probe.cols.size(), bki);
                 execution::without_key_helper(probe, res.columns);  // the helper column's pairs: not part of the frame
-                const execution::JoinSide bs{nullptr, b.names, b.columns, 0}, ps{nullptr, p.names, p.columns, 0};
-                for (auto &f : execution::join_output_fields(*ps.schema(), *bs.schema(), bki, join_kind)) res.names.push_back(f.name());
+                for (auto &f : execution::join_output_fields(frame_schema(p), frame_schema(b), bki, join_kind)) res.names.push_back(f.name());
                 return res;
             }
         }
         throw Panic("unreachable");
+    }
+
+  private:
+    static std::shared_ptr<PhysicalPlan> node(Kind kind, PhysicalPlanPtr input = nullptr) {  // what every factory starts from
+        auto p = std::make_shared<PhysicalPlan>();
+        p->kind = kind;
+        p->input = std::move(input);
+        return p;
     }
 };
 
