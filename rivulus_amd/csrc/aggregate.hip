@@ -1,7 +1,7 @@
 // Filter + SUM/COUNT (rv_filter_agg), row-range shards, one-rank-per-process RCCL communicator (rv_comm_*).
 // One unit of the backend library behind include/rivulus_gpu.h (gfx950 only; compiled with hipcc).  Shared helpers and the
 // functions the units call across each other are declared in launch.hpp (namespace rvl).
-#include "launch.hpp"
+#include "breaker_steps.hpp"
 #include "rccl_loader.hpp"
 
 using namespace rvh;
@@ -155,10 +155,12 @@ rv_status rv_filter_agg(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t nco
         p.partials = static_cast<rvk::AggPartial *>(partials->ptr);
         p.ntiles = static_cast<uint32_t>(ntiles);
         ctx->last_kernel = fmt("filter_agg_kernel<%d,%d,%d,%d,%d>", e->ncols, e->r, e->vec, e->waves, e->flags);
-        if (ctx->opt_profile) RV_HIP(hipEventRecord(ctx->evk0, ctx->stream));
+        PassTimer timer(ctx);  // round the pass itself: the fold behind it is not counted
+        timer.start();
+        timer.launches = 1;
         hipLaunchKernelGGL(e->fn, dim3(static_cast<uint32_t>(grid)), dim3(e->waves * 64), 0, ctx->stream, p);
         RV_HIP(hipGetLastError());
-        if (ctx->opt_profile) RV_HIP(hipEventRecord(ctx->evk1, ctx->stream));
+        timer.stop();
         if (grid > 16384) {  // two levels: 1024-partial chunks first
             const uint32_t chunk = 1024, nchunks = static_cast<uint32_t>((grid + chunk - 1) / chunk);
             DevBufRef level1 = pool_alloc(ctx, static_cast<size_t>(nchunks) * sizeof(rvk::AggPartial));
@@ -174,12 +176,7 @@ rv_status rv_filter_agg(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t nco
             RV_HIP(hipGetLastError());
         }
         const Ctrl *h = fetch_ctrl(ctx);
-        if (ctx->opt_profile) {
-            float ms = 0.f;
-            RV_HIP(hipEventElapsedTime(&ms, ctx->evk0, ctx->evk1));
-            ctx->kernel_ms += ms;
-            ctx->kernel_launches += 1;
-        }
+        timer.add();
         if (sum_i) *sum_i = h->agg.sum_i;
         if (sum_f) *sum_f = h->agg.sum_f;
         if (count) *count = h->agg.count;

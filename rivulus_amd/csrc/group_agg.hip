@@ -1,13 +1,13 @@
 // Grouped aggregation on the device: group_by(key).agg(count / sum / min / max) -- rv_group_ids and rv_hash_aggregate over one key
 // column, rv_group_ids_keys and rv_hash_aggregate_keys over a tuple of them.
 // One unit of the backend library behind include/rivulus_gpu.h (gfx950 only; compiled with hipcc).  Shared helpers are declared in
-// launch.hpp (namespace rvl); the kernels and the layout of the group table are in group_agg_kernel.hpp, the passes over tuples in
-// group_keys_kernel.hpp.
+// launch.hpp (namespace rvl), the steps every breaker's unit takes in breaker_steps.hpp; the kernels and the layout of the group table
+// are in group_agg_kernel.hpp, the passes over tuples in group_keys_kernel.hpp.
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "group_agg_kernel.hpp"
 #include "group_keys_kernel.hpp"
-#include "launch.hpp"
+#include "breaker_steps.hpp"
 
 using namespace rvh;
 using namespace rvl;
@@ -142,11 +142,7 @@ GroupIds group_ids_of(rv_ctx *ctx, const KeyCols &keys, const char *what, bool w
     hipLaunchKernelGGL(rvk::group_mark_first, dim3(grid_for_words(ctx, nslots + 1, rvk::kGroupAggThreads)), dim3(rvk::kGroupAggThreads), 0, ctx->stream, t, nslots,
                        static_cast<unsigned long long *>(marks->ptr));
     RV_HIP(hipGetLastError());
-    rv_dcolumn sel;
-    sel.dtype = RV_BOOLEAN;
-    sel.values = marks;
-    sel.length = n;
-    sel.null_count = 0;
+    const rv_dcolumn sel = plain_view(RV_BOOLEAN, marks, n);
     DevBufRef excl = selection_prefix(ctx, &sel, r.groups);
     r.first_row = selection_to_indices(ctx, &sel, r.groups, excl);
 
@@ -165,15 +161,6 @@ GroupIds group_ids_of(rv_ctx *ctx, const KeyCols &keys, const char *what, bool w
     RV_HIP(hipGetLastError());
     ctx->last_kernel = keys.tuple ? "group_ids<keys>" : "group_ids";
     return r;  // (the table, the marks and the scan go back to the pool; their next user runs behind these kernels on the stream)
-}
-
-rv_dcolumn *int64_column(const DevBufRef &buf, uint64_t rows) {
-    auto o = std::make_unique<rv_dcolumn>();
-    o->dtype = RV_INT64;
-    o->length = rows;
-    o->null_count = 0;
-    o->values = buf;
-    return o.release();
 }
 
 // one accumulator of the integer pass
@@ -308,27 +295,6 @@ KeyCols key_cols(const rv_dcolumn *const *keys, uint32_t nkeys) {
     return KeyCols{keys, nkeys, !(nkeys == 1 && (keys[0]->dtype == RV_INT64 || keys[0]->dtype == RV_NULL))};
 }
 
-// events around the accumulate stage (option profile_kernels)
-struct StageTimer {
-    rv_ctx *ctx;
-    bool started = false;
-    explicit StageTimer(rv_ctx *c) : ctx(c) {}
-    void start() {
-        if (ctx->opt_profile && !started) RV_HIP(hipEventRecord(ctx->evk0, ctx->stream));
-        started = true;
-    }
-    void stop() {
-        if (ctx->opt_profile && started) RV_HIP(hipEventRecord(ctx->evk1, ctx->stream));
-    }
-    void add(uint64_t launches) {  // after a wait
-        if (!ctx->opt_profile || !started) return;
-        float ms = 0.f;
-        RV_HIP(hipEventElapsedTime(&ms, ctx->evk0, ctx->evk1));
-        ctx->kernel_ms += ms;
-        ctx->kernel_launches += launches;
-    }
-};
-
 // everything behind the group ids; out: the key cells of every key column, then the aggregates
 void hash_aggregate(rv_ctx *ctx, const KeyCols &keys, const char *what, const rv_dcolumn *const *value_cols, const rv_agg_spec *specs, uint32_t n_specs,
                     rv_dcolumn **out, rv_dcolumn **out_first_row, uint64_t *out_groups) {
@@ -337,11 +303,7 @@ void hash_aggregate(rv_ctx *ctx, const KeyCols &keys, const char *what, const rv
     const uint64_t G = ids.groups;
     std::vector<std::unique_ptr<rv_dcolumn>> outs(n_specs);
     std::vector<Acc> accs;
-    struct MinMax {
-        uint32_t j;
-        DevBufRef counts;
-    };
-    std::vector<MinMax> minmax;
+    std::vector<std::pair<uint32_t, DevBufRef>> minmax;  // (output, its non-null counts)
     std::vector<uint32_t> fsums;
     for (uint32_t j = 0; j < n_specs; ++j) {
         const uint32_t op = specs[j].op;
@@ -355,8 +317,8 @@ void hash_aggregate(rv_ctx *ctx, const KeyCols &keys, const char *what, const rv
         else {
             accs.push_back(Acc{op, col, o->values});  // rv_agg_op and the AK_ kinds share their values
             if (op == RV_AGG_MIN || op == RV_AGG_MAX) {
-                minmax.push_back(MinMax{j, new_acc(ctx, G, false)});
-                accs.push_back(Acc{rvk::AK_COUNT, col, minmax.back().counts});
+                minmax.emplace_back(j, new_acc(ctx, G, false));
+                accs.push_back(Acc{rvk::AK_COUNT, col, minmax.back().second});
             }
         }
         outs[j] = std::move(o);
@@ -364,14 +326,21 @@ void hash_aggregate(rv_ctx *ctx, const KeyCols &keys, const char *what, const rv
     static_assert(int(RV_AGG_COUNT_ROWS) == int(rvk::AK_COUNT_ROWS) && int(RV_AGG_COUNT) == int(rvk::AK_COUNT) && int(RV_AGG_SUM) == int(rvk::AK_SUM_I64) &&
                       int(RV_AGG_MIN) == int(rvk::AK_MIN) && int(RV_AGG_MAX) == int(rvk::AK_MAX), "rv_agg_op and the accumulator kinds");
     if (G) {
-        // group_ids_of left its id pass queued with a fresh control block: ctrl->err is that pass's flag
-        Ctrl *ctrl = static_cast<Ctrl *>(ctx->d_ctrl);
-        StageTimer timer(ctx);
+        // group_ids_of left its id pass queued with a fresh control block: ctrl->err is that pass's flag, read with the first read-back
+        NullCounts nulls(ctx, outs, static_cast<Ctrl *>(ctx->d_ctrl));
+        bool ids_checked = false;
+        auto settle = [&] {
+            const Ctrl *h = nulls.settle();
+            if (ids_checked) return;
+            if (!h) h = fetch_ctrl(ctx);  // no MIN / MAX: the read-back is the flag's alone
+            require(h->err == 0, RV_ERR_INTERNAL, fmt("%s: a row's key was not found in the group table", what));
+            ids_checked = true;
+        };
+        PassTimer timer(ctx);
         std::string name;
-        uint64_t launches = 0;
         if (!accs.empty()) {
             timer.start();
-            launches += launch_accumulate(ctx, accs, ids, n, name);
+            timer.launches += launch_accumulate(ctx, accs, ids, n, name);
         }
         if (!fsums.empty()) {
             timer.start();
@@ -381,36 +350,24 @@ void hash_aggregate(rv_ctx *ctx, const KeyCols &keys, const char *what, const rv
                                    dev_view(value_cols[specs[j].col]), static_cast<const uint32_t *>(L.rows->ptr), static_cast<const uint64_t *>(L.starts->ptr),
                                    static_cast<uint32_t>(G), rvt::kGroupAggWaveListMost, static_cast<double *>(outs[j]->values->ptr));
                 RV_HIP(hipGetLastError());
-                ++launches;
+                ++timer.launches;
             }
             name += name.empty() ? "group_f64_sum" : "+group_f64_sum";
         }
         timer.stop();
         ctx->last_kernel = name;
-        // MIN / MAX: the winning bits in place, the validity, the nulls -- eight striped counters per read-back
-        size_t done = 0;
-        do {
-            const size_t upto = std::min(minmax.size(), done + 8);
-            for (size_t k = done; k < upto; ++k) {
-                rv_dcolumn *o = outs[minmax[k].j].get();
-                o->validity = pool_alloc(ctx, zeroed_bitmap_bytes(G));
-                RV_HIP(hipMemsetAsync(o->validity->ptr, 0, zeroed_bitmap_bytes(G), ctx->stream));
-                hipLaunchKernelGGL(rvk::group_minmax_finish, row_grid(G), dim3(rvk::kGroupAggThreads), 0, ctx->stream, static_cast<unsigned long long *>(o->values->ptr),
-                                   static_cast<const unsigned long long *>(minmax[k].counts->ptr), G, o->dtype == RV_FLOAT64 ? 1 : 0,
-                                   static_cast<uint64_t *>(o->validity->ptr), striped(ctx, &ctrl->valid_pop[k - done]));
-                RV_HIP(hipGetLastError());
-            }
-            const Ctrl *h = fetch_ctrl(ctx);
-            require(h->err == 0, RV_ERR_INTERNAL, fmt("%s: a row's key was not found in the group table", what));
-            for (size_t k = done; k < upto; ++k) {
-                rv_dcolumn *o = outs[minmax[k].j].get();
-                o->null_count = static_cast<int64_t>(h->valid_pop[k - done]);
-                if (o->null_count == 0) o->validity.reset();  // attached iff some cell is null
-            }
-            done = upto;
-            if (done < minmax.size()) ctrl = prepare_ctrl(ctx, 0);
-        } while (done < minmax.size());
-        timer.add(launches);
+        // MIN / MAX: the winning bits in place, the validity, the nulls
+        for (const auto &[j, counts] : minmax) {
+            if (nulls.pending.size() == 8) settle();
+            rv_dcolumn *o = outs[j].get();
+            unsigned long long *null_cells = nulls.attach(j, G);
+            hipLaunchKernelGGL(rvk::group_minmax_finish, row_grid(G), dim3(rvk::kGroupAggThreads), 0, ctx->stream, static_cast<unsigned long long *>(o->values->ptr),
+                               static_cast<const unsigned long long *>(counts->ptr), G, o->dtype == RV_FLOAT64 ? 1 : 0, static_cast<uint64_t *>(o->validity->ptr),
+                               null_cells);
+            RV_HIP(hipGetLastError());
+        }
+        settle();
+        timer.add();
     }
     // out[0 .. nkeys): the key cells at the first rows (a gather with read-backs of its own: after this call's control block has been read)
     rv_dcolumn *key_cells[rvk::kGroupKeysMost] = {};
@@ -418,10 +375,32 @@ void hash_aggregate(rv_ctx *ctx, const KeyCols &keys, const char *what, const rv
     std::vector<std::unique_ptr<rv_dcolumn>> cells(keys.nkeys);
     for (uint32_t k = 0; k < keys.nkeys; ++k) cells[k].reset(key_cells[k]);
     RV_HIP(hipStreamSynchronize(ctx->stream));  // the ids, the lists and the count accumulators go back to the pool
+    if (out_first_row) *out_first_row = index_column(ids.first_row, G);  // (the last step that can fail: before the outputs are handed over)
     for (uint32_t k = 0; k < keys.nkeys; ++k) out[k] = cells[k].release();
     for (uint32_t j = 0; j < n_specs; ++j) out[keys.nkeys + j] = outs[j].release();
-    if (out_first_row) *out_first_row = int64_column(ids.first_row, G);
     if (out_groups) *out_groups = G;
+}
+
+// rv_group_ids and rv_group_ids_keys behind their checks
+void group_ids_call(rv_ctx *ctx, const KeyCols &keys, const char *what, rv_dcolumn **out_gids, rv_dcolumn **out_first_row, uint64_t *out_groups) {
+    set_device(ctx);
+    breaker_call(ctx, nullptr, 0, [&] {  // both outputs are handed over by the last step, which cannot fail
+        GroupIds ids = group_ids_of(ctx, keys, what, true);
+        require(fetch_ctrl(ctx)->err == 0, RV_ERR_INTERNAL, fmt("%s: a row's key was not found in the group table", what));
+        std::unique_ptr<rv_dcolumn> a(index_column(ids.gids, keys.rows())), b(index_column(ids.first_row, ids.groups));
+        *out_gids = a.release();
+        *out_first_row = b.release();
+        if (out_groups) *out_groups = ids.groups;
+    });
+}
+
+// rv_hash_aggregate and rv_hash_aggregate_keys behind their checks
+void hash_aggregate_call(rv_ctx *ctx, const KeyCols &keys, const char *what, const rv_dcolumn *const *value_cols, const rv_agg_spec *specs, uint32_t n_specs,
+                         rv_dcolumn **out, rv_dcolumn **out_first_row, uint64_t *out_groups) {
+    for (uint32_t j = 0; j < keys.nkeys + n_specs; ++j) out[j] = nullptr;
+    if (out_first_row) *out_first_row = nullptr;
+    set_device(ctx);
+    breaker_call(ctx, out, keys.nkeys + n_specs, [&] { hash_aggregate(ctx, keys, what, value_cols, specs, n_specs, out, out_first_row, out_groups); });
 }
 
 }  // namespace
@@ -442,18 +421,7 @@ rv_status rv_group_ids(rv_ctx *ctx, const rv_dcolumn *key, rv_dcolumn **out_gids
         require(ctx && key && out_gids && out_first_row, RV_ERR_INVALID_ARG, "rv_group_ids: NULL argument");
         *out_gids = *out_first_row = nullptr;
         check_group_key(key, "rv_group_ids");
-        set_device(ctx);
-        try {
-            GroupIds ids = group_ids_of(ctx, KeyCols{&key, 1, false}, "rv_group_ids", true);
-            require(fetch_ctrl(ctx)->err == 0, RV_ERR_INTERNAL, "rv_group_ids: a row's key was not found in the group table");
-            std::unique_ptr<rv_dcolumn> a(int64_column(ids.gids, key->length)), b(int64_column(ids.first_row, ids.groups));
-            *out_gids = a.release();
-            *out_first_row = b.release();
-            if (out_groups) *out_groups = ids.groups;
-        } catch (...) {
-            (void)hipStreamSynchronize(ctx->stream);  // whatever was queued has run before its buffers go back to the pool
-            throw;
-        }
+        group_ids_call(ctx, KeyCols{&key, 1, false}, "rv_group_ids", out_gids, out_first_row, out_groups);
     });
 }
 
@@ -463,15 +431,7 @@ rv_status rv_hash_aggregate(rv_ctx *ctx, const rv_dcolumn *key, const rv_dcolumn
         require(ctx && key && specs && out && (value_cols || n_values == 0), RV_ERR_INVALID_ARG, "rv_hash_aggregate: NULL argument");
         check_specs("rv_hash_aggregate", key->length, value_cols, n_values, specs, n_specs);
         check_group_key(key, "rv_hash_aggregate");
-        for (uint32_t j = 0; j <= n_specs; ++j) out[j] = nullptr;
-        if (out_first_row) *out_first_row = nullptr;
-        set_device(ctx);
-        try {
-            hash_aggregate(ctx, KeyCols{&key, 1, false}, "rv_hash_aggregate", value_cols, specs, n_specs, out, out_first_row, out_groups);
-        } catch (...) {
-            (void)hipStreamSynchronize(ctx->stream);
-            throw;
-        }
+        hash_aggregate_call(ctx, KeyCols{&key, 1, false}, "rv_hash_aggregate", value_cols, specs, n_specs, out, out_first_row, out_groups);
     });
 }
 
@@ -480,18 +440,7 @@ rv_status rv_group_ids_keys(rv_ctx *ctx, const rv_dcolumn *const *keys, uint32_t
         require(ctx && keys && out_gids && out_first_row, RV_ERR_INVALID_ARG, "rv_group_ids_keys: NULL argument");
         *out_gids = *out_first_row = nullptr;
         check_group_keys(keys, nkeys, "rv_group_ids_keys");
-        set_device(ctx);
-        try {
-            GroupIds ids = group_ids_of(ctx, key_cols(keys, nkeys), "rv_group_ids_keys", true);
-            require(fetch_ctrl(ctx)->err == 0, RV_ERR_INTERNAL, "rv_group_ids_keys: a row's key was not found in the group table");
-            std::unique_ptr<rv_dcolumn> a(int64_column(ids.gids, keys[0]->length)), b(int64_column(ids.first_row, ids.groups));
-            *out_gids = a.release();
-            *out_first_row = b.release();
-            if (out_groups) *out_groups = ids.groups;
-        } catch (...) {
-            (void)hipStreamSynchronize(ctx->stream);  // whatever was queued has run before its buffers go back to the pool
-            throw;
-        }
+        group_ids_call(ctx, key_cols(keys, nkeys), "rv_group_ids_keys", out_gids, out_first_row, out_groups);
     });
 }
 
@@ -501,15 +450,7 @@ rv_status rv_hash_aggregate_keys(rv_ctx *ctx, const rv_dcolumn *const *keys, uin
         require(ctx && keys && specs && out && (value_cols || n_values == 0), RV_ERR_INVALID_ARG, "rv_hash_aggregate_keys: NULL argument");
         check_group_keys(keys, nkeys, "rv_hash_aggregate_keys");
         check_specs("rv_hash_aggregate_keys", keys[0]->length, value_cols, n_values, specs, n_specs);
-        for (uint32_t j = 0; j < nkeys + n_specs; ++j) out[j] = nullptr;
-        if (out_first_row) *out_first_row = nullptr;
-        set_device(ctx);
-        try {
-            hash_aggregate(ctx, key_cols(keys, nkeys), "rv_hash_aggregate_keys", value_cols, specs, n_specs, out, out_first_row, out_groups);
-        } catch (...) {
-            (void)hipStreamSynchronize(ctx->stream);
-            throw;
-        }
+        hash_aggregate_call(ctx, key_cols(keys, nkeys), "rv_hash_aggregate_keys", value_cols, specs, n_specs, out, out_first_row, out_groups);
     });
 }
 

@@ -4,8 +4,8 @@
 // functions the units call across each other are declared in launch.hpp (namespace rvl); the kernels are in join_kernel.hpp.
 #include <rocprim/device/device_radix_sort.hpp>
 
+#include "breaker_steps.hpp"
 #include "join_kernel.hpp"
-#include "launch.hpp"
 
 using namespace rvh;
 using namespace rvl;
@@ -49,11 +49,7 @@ void check_key(const rv_dcolumn *key, const char *what) {
 
 // a bitmap of n rows at offset 0 as the BooleanArray selection_prefix / selection_to_indices read
 DevBufRef ascending_rows(rv_ctx *ctx, const DevBufRef &bitmap, uint64_t n, uint64_t count) {
-    rv_dcolumn sel;
-    sel.dtype = RV_BOOLEAN;
-    sel.values = bitmap;
-    sel.length = n;
-    sel.null_count = 0;
+    const rv_dcolumn sel = plain_view(RV_BOOLEAN, bitmap, n);
     DevBufRef excl = selection_prefix(ctx, &sel, count);
     return selection_to_indices(ctx, &sel, count, excl);
 }
@@ -125,15 +121,6 @@ std::unique_ptr<rv_join_table> build_table(rv_ctx *ctx, const rv_dcolumn *key) {
     return t;
 }
 
-rv_dcolumn *index_column(const DevBufRef &buf, uint64_t rows) {
-    auto o = std::make_unique<rv_dcolumn>();
-    o->dtype = RV_INT64;
-    o->length = rows;
-    o->null_count = 0;
-    o->values = buf;
-    return o.release();
-}
-
 // JoinProbeParams of `key` against `t`, without the tile counts and the outputs; longest = the longest list a probe row of this key
 // column can meet
 rvk::JoinProbeParams probe_params(const rv_join_table *t, const rv_dcolumn *key, uint64_t &longest) {
@@ -149,10 +136,6 @@ rvk::JoinProbeParams probe_params(const rv_join_table *t, const rv_dcolumn *key,
 // pairs the device can hold: two 8-byte indices each
 uint64_t device_pair_cap(const rv_ctx *ctx) { return static_cast<uint64_t>(ctx->props.totalGlobalMem) / 16; }
 
-// the emit pass over the first p.n rows, into fresh index buffers of `pairs` pairs: by lists of at most one row, of at most a lane's
-// share, or longer
-// `kind` other than RV_JOIN_INNER: the kind's instantiation, named with the kind appended.  `pairs` are the rows the emit pass writes,
-// `room` >= pairs the rows the buffers hold (the full outer join's tail goes behind); semi and anti joins get no build buffer.
 bool kind_has_pairs(rv_join_kind kind) { return kind != RV_JOIN_PROBE_SEMI && kind != RV_JOIN_PROBE_ANTI; }
 const char *kind_name(rv_join_kind kind) {
     switch (kind) {
@@ -166,11 +149,11 @@ const char *kind_name(rv_join_kind kind) {
 void check_kind(const char *what, int kind) {
     require(kind >= RV_JOIN_INNER && kind <= RV_JOIN_PROBE_ANTI, RV_ERR_INVALID_ARG, fmt("%s: unknown join kind %d", what, kind));
 }
-// f(std::integral_constant<int, KIND>) for the kernel kind of a kind other than RV_JOIN_INNER: the one place a run-time kind becomes
-// a template argument
+// f(std::integral_constant<int, KIND>) for the kernel kind of a join kind: the one place a run-time kind becomes a template argument
 template <class F>
 void with_kind(rv_join_kind kind, F f) {
     switch (kind) {
+        case RV_JOIN_INNER: return f(std::integral_constant<int, rvk::JOIN_INNER>{});
         case RV_JOIN_PROBE_OUTER: return f(std::integral_constant<int, rvk::JOIN_OUTER>{});
         case RV_JOIN_FULL_OUTER: return f(std::integral_constant<int, rvk::JOIN_FULL>{});
         case RV_JOIN_PROBE_SEMI: return f(std::integral_constant<int, rvk::JOIN_SEMI>{});
@@ -178,6 +161,9 @@ void with_kind(rv_join_kind kind, F f) {
         default: throw Error(RV_ERR_INTERNAL, "join: no kernel kind for this join kind");
     }
 }
+// the emit pass over the first p.n rows, into fresh index buffers: by lists of at most one row, of at most a lane's share, or longer, in
+// the kind's instantiation (named with the kind appended, but for the inner join).  `pairs` are the rows the emit pass writes, `room` >=
+// pairs the rows the buffers hold (the full outer join's tail goes behind); semi and anti joins get no build buffer.
 void emit_pairs(rv_ctx *ctx, rvk::JoinProbeParams &p, uint64_t longest, uint64_t pairs, DevBufRef &out_probe, DevBufRef &out_build,
                 rv_join_kind kind = RV_JOIN_INNER, uint64_t room = 0) {
     room = std::max(room, pairs);
@@ -188,72 +174,39 @@ void emit_pairs(rv_ctx *ctx, rvk::JoinProbeParams &p, uint64_t longest, uint64_t
     p.out_build = out_build ? static_cast<int64_t *>(out_build->ptr) : nullptr;
     const dim3 grid(static_cast<uint32_t>((p.n + rvk::kJoinTileRows - 1) / rvk::kJoinTileRows)), block(rvk::kJoinThreads);
     const int mode = !kind_has_pairs(kind) || longest <= 1 ? 0 : longest <= rvt::kJoinLaneListMost ? 1 : 2;
-    if (kind == RV_JOIN_INNER) {
-        if (mode == 0) hipLaunchKernelGGL(rvk::join_probe_emit<0>, grid, block, 0, ctx->stream, p);
-        else if (mode == 1) hipLaunchKernelGGL(rvk::join_probe_emit<1>, grid, block, 0, ctx->stream, p);
-        else hipLaunchKernelGGL(rvk::join_probe_emit<2>, grid, block, 0, ctx->stream, p);
-        RV_HIP(hipGetLastError());
-        ctx->last_kernel = fmt("join_probe_emit<%d>", mode);
-        return;
-    }
     with_kind(kind, [&](auto k) {
         constexpr int K = decltype(k)::value;
         if constexpr (K == rvk::JOIN_SEMI || K == rvk::JOIN_ANTI) {
-            hipLaunchKernelGGL((rvk::join_probe_emit_kind<0, K>), grid, block, 0, ctx->stream, p);
+            hipLaunchKernelGGL((rvk::join_probe_emit<0, K>), grid, block, 0, ctx->stream, p);
         } else {
-            if (mode == 0) hipLaunchKernelGGL((rvk::join_probe_emit_kind<0, K>), grid, block, 0, ctx->stream, p);
-            else if (mode == 1) hipLaunchKernelGGL((rvk::join_probe_emit_kind<1, K>), grid, block, 0, ctx->stream, p);
-            else hipLaunchKernelGGL((rvk::join_probe_emit_kind<2, K>), grid, block, 0, ctx->stream, p);
+            if (mode == 0) hipLaunchKernelGGL((rvk::join_probe_emit<0, K>), grid, block, 0, ctx->stream, p);
+            else if (mode == 1) hipLaunchKernelGGL((rvk::join_probe_emit<1, K>), grid, block, 0, ctx->stream, p);
+            else hipLaunchKernelGGL((rvk::join_probe_emit<2, K>), grid, block, 0, ctx->stream, p);
         }
     });
     RV_HIP(hipGetLastError());
-    ctx->last_kernel = fmt("join_probe_emit<%d,%s>", mode, kind_name(kind));
+    ctx->last_kernel = kind == RV_JOIN_INNER ? fmt("join_probe_emit<%d>", mode) : fmt("join_probe_emit<%d,%s>", mode, kind_name(kind));
 }
 
-// result_pairs of plan.rs:196-204 as two Int64 index buffers: count pass, scan of the tile counts, one read-back of the total,
-// the size check, then the emit pass
-uint64_t probe_table(rv_ctx *ctx, const rv_join_table *t, const rv_dcolumn *key, DevBufRef &out_probe, DevBufRef &out_build) {
-    check_key(key, "rv_join_probe");
+// result_pairs of plan.rs:196-204 as two Int64 index buffers, for every kind (rv_join_probe: RV_JOIN_INNER; rv_join_probe_kind): the count
+// pass with the kind's row rule, the scan of the tile counts, one read-back of the total, the size check, then the emit pass.  A cell
+// without a partner is kJoinNone in the buffers.
+//   RV_JOIN_INNER: a probe without rows, or against a table without a single list, has nothing to count: no count pass, no read-back.
+//   The other kinds count every probe row -- against such a table every one of them is unmatched -- and always read the block back.
+//   RV_JOIN_FULL_OUTER: the count pass marks the groups it meets; the build rows of the unmarked groups and of no group are counted before
+//   the size check and written behind the probe rows, ascending.  That check comes before any OUTPUT is allocated; the marks and the two
+//   build-row bitmaps -- a bit per slot and two bits per build row -- are scratch of the count pass and are there before it.
+// The inner join reports under rv_join_probe's name whichever entry point it came through.
+uint64_t probe_table(rv_ctx *ctx, const rv_join_table *t, const rv_dcolumn *key, rv_join_kind kind, DevBufRef &out_probe, DevBufRef &out_build) {
+    const bool inner = kind == RV_JOIN_INNER, full = kind == RV_JOIN_FULL_OUTER;
+    check_key(key, inner ? "rv_join_probe" : "rv_join_probe_kind");
     uint64_t longest = 0;
     rvk::JoinProbeParams p = probe_params(t, key, longest);
-    uint64_t total = 0;
-    DevBufRef tiles;
     const uint64_t ntiles = (p.n + rvk::kJoinTileRows - 1) / rvk::kJoinTileRows;
-    if (p.n && longest) {
-        tiles = pool_alloc(ctx, ntiles * 8 + 16);
-        p.tile_counts = static_cast<uint64_t *>(tiles->ptr);
-        Ctrl *ctrl = prepare_ctrl(ctx, 0);
-        hipLaunchKernelGGL(rvk::join_probe_count, dim3(static_cast<uint32_t>(ntiles)), dim3(rvk::kJoinThreads), 0, ctx->stream, p);
-        hipLaunchKernelGGL(rvk::scan_sums_inplace, dim3(1), dim3(1024), 0, ctx->stream, p.tile_counts, ntiles, &ctrl->pops[0]);
-        RV_HIP(hipGetLastError());
-        ctx->last_kernel = "join_probe_count";
-        total = fetch_ctrl(ctx)->pops[0];
-    }
-    // refuse what the device cannot hold before anything is allocated (n_probe x n_build pairs can exceed 2^64 bytes)
-    require(total <= device_pair_cap(ctx), RV_ERR_OOM,
-            fmt("rv_join_probe: %llu pairs need %llu x 16 bytes of output, more than the device's %llu bytes", static_cast<unsigned long long>(total),
-                static_cast<unsigned long long>(total), static_cast<unsigned long long>(ctx->props.totalGlobalMem)));
-    emit_pairs(ctx, p, longest, total, out_probe, out_build);
-    RV_HIP(hipStreamSynchronize(ctx->stream));  // `tiles` goes back to the pool
-    return total;
-}
-
-// (The size check of a full outer join comes before any OUTPUT is allocated; its marks and the two build-row bitmaps -- a bit per slot
-// and two bits per build row -- are scratch of the count pass and are there before it.)
-// The probe of the other kinds (rv_join_probe_kind): the count pass with the kind's row rule -- run even against a table without a
-// single list, where every probe row is unmatched -- the scan, one read-back of the total, the size check, the emit pass.  A cell
-// without a partner is kJoinNone in the buffers.  RV_JOIN_FULL_OUTER: the count pass marks the groups it meets; the build rows of
-// the unmarked groups and of no group are counted before the size check and written behind the probe rows, ascending.
-uint64_t probe_table_kind(rv_ctx *ctx, const rv_join_table *t, const rv_dcolumn *key, rv_join_kind kind, DevBufRef &out_probe, DevBufRef &out_build) {
-    if (kind == RV_JOIN_INNER) return probe_table(ctx, t, key, out_probe, out_build);
-    check_key(key, "rv_join_probe_kind");
-    uint64_t longest = 0;
-    rvk::JoinProbeParams p = probe_params(t, key, longest);
-    const bool full = kind == RV_JOIN_FULL_OUTER;
-    const uint64_t ntiles = (p.n + rvk::kJoinTileRows - 1) / rvk::kJoinTileRows;
+    const bool counted = p.n && (longest || !inner), fetched = counted || !inner;
     uint64_t total = 0, tail = 0;
     DevBufRef tiles, marks, matched, unmatched, tail_rows;
-    Ctrl *ctrl = prepare_ctrl(ctx, 0);
+    Ctrl *ctrl = fetched ? prepare_ctrl(ctx, 0) : nullptr;
     if (full) {
         const size_t mark_bytes = ((t->nslots + 1 + 31) / 32) * 4, row_bytes = ((t->n_build + 63) / 64) * 8;
         marks = pool_alloc(ctx, mark_bytes + 16);
@@ -262,12 +215,12 @@ uint64_t probe_table_kind(rv_ctx *ctx, const rv_join_table *t, const rv_dcolumn 
         RV_HIP(hipMemsetAsync(marks->ptr, 0, mark_bytes, ctx->stream));
         RV_HIP(hipMemsetAsync(matched->ptr, 0, row_bytes + 16, ctx->stream));
     }
-    if (p.n) {
+    if (counted) {
         tiles = pool_alloc(ctx, ntiles * 8 + 16);
         p.tile_counts = static_cast<uint64_t *>(tiles->ptr);
         const dim3 grid(static_cast<uint32_t>(ntiles)), block(rvk::kJoinThreads);
         uint32_t *m = full ? static_cast<uint32_t *>(marks->ptr) : nullptr;
-        with_kind(kind, [&](auto k) { hipLaunchKernelGGL(rvk::join_probe_count_kind<decltype(k)::value>, grid, block, 0, ctx->stream, p, m); });
+        with_kind(kind, [&](auto k) { hipLaunchKernelGGL(rvk::join_probe_count<decltype(k)::value>, grid, block, 0, ctx->stream, p, m); });
         hipLaunchKernelGGL(rvk::scan_sums_inplace, dim3(1), dim3(1024), 0, ctx->stream, p.tile_counts, ntiles, &ctrl->pops[0]);
         RV_HIP(hipGetLastError());
     }
@@ -280,18 +233,22 @@ uint64_t probe_table_kind(rv_ctx *ctx, const rv_join_table *t, const rv_dcolumn 
                            static_cast<const unsigned long long *>(matched->ptr), t->n_build, static_cast<uint64_t *>(unmatched->ptr), &ctrl->pops[1]);
         RV_HIP(hipGetLastError());
     }
-    ctx->last_kernel = "join_probe_count";
-    {
+    if (fetched) {
+        ctx->last_kernel = "join_probe_count";
         const Ctrl *h = fetch_ctrl(ctx);
-        total = p.n ? h->pops[0] : 0;
+        total = counted ? h->pops[0] : 0;
         tail = h->pops[1];
     }
-    // refuse what the device cannot hold before anything is allocated
+    // refuse what the device cannot hold before anything is allocated (n_probe x n_build pairs can exceed 2^64 bytes)
     require(total <= device_pair_cap(ctx) && tail <= device_pair_cap(ctx) - total, RV_ERR_OOM,
-            fmt("rv_join_probe_kind: %llu rows need %llu x 16 bytes of output, more than the device's %llu bytes", static_cast<unsigned long long>(total + tail),
-                static_cast<unsigned long long>(total + tail), static_cast<unsigned long long>(ctx->props.totalGlobalMem)));
-    if (tail) tail_rows = ascending_rows(ctx, unmatched, t->n_build, tail);  // before the outputs: its scratch is freed first
-    ctx->last_kernel = "join_probe_count";
+            fmt(inner ? "rv_join_probe: %llu pairs need %llu x 16 bytes of output, more than the device's %llu bytes"
+                      : "rv_join_probe_kind: %llu rows need %llu x 16 bytes of output, more than the device's %llu bytes",
+                static_cast<unsigned long long>(total + tail), static_cast<unsigned long long>(total + tail),
+                static_cast<unsigned long long>(ctx->props.totalGlobalMem)));
+    if (tail) {
+        tail_rows = ascending_rows(ctx, unmatched, t->n_build, tail);  // before the outputs: its scratch is freed first
+        ctx->last_kernel = "join_probe_count";
+    }
     emit_pairs(ctx, p, longest, total, out_probe, out_build, kind, total + tail);
     if (tail) {
         hipLaunchKernelGGL(rvk::join_unmatched_tail, dim3(grid_for_words(ctx, tail, 256)), dim3(256), 0, ctx->stream, static_cast<const uint64_t *>(tail_rows->ptr),
@@ -344,18 +301,13 @@ uint64_t probe_table_batched(rv_ctx *ctx, const char *what, rv_join_kind kind, c
         if (!fast) RV_HIP(hipMemsetAsync(counts->ptr, 0, nb * 8, ctx->stream));
         Ctrl *ctrl = prepare_ctrl(ctx, 0);
         const dim3 grid(static_cast<uint32_t>(ntiles)), block(rvk::kJoinThreads);
-        if (kind == RV_JOIN_INNER) {
-            if (fast) hipLaunchKernelGGL(rvk::join_probe_count_batched<true>, grid, block, 0, ctx->stream, p, b);
-            else hipLaunchKernelGGL(rvk::join_probe_count_batched<false>, grid, block, 0, ctx->stream, p, b);
-        } else {
-            with_kind(kind, [&](auto k) {
-                constexpr int K = decltype(k)::value;
-                if constexpr (K != rvk::JOIN_FULL) {  // a full outer join has no batched form: refused by the entry point
-                    if (fast) hipLaunchKernelGGL((rvk::join_probe_count_batched_kind<true, K>), grid, block, 0, ctx->stream, p, b);
-                    else hipLaunchKernelGGL((rvk::join_probe_count_batched_kind<false, K>), grid, block, 0, ctx->stream, p, b);
-                }
-            });
-        }
+        with_kind(kind, [&](auto k) {
+            constexpr int K = decltype(k)::value;
+            if constexpr (K != rvk::JOIN_FULL) {  // a full outer join has no batched form: refused by the entry point
+                if (fast) hipLaunchKernelGGL((rvk::join_probe_count_batched<true, K>), grid, block, 0, ctx->stream, p, b);
+                else hipLaunchKernelGGL((rvk::join_probe_count_batched<false, K>), grid, block, 0, ctx->stream, p, b);
+            }
+        });
         hipLaunchKernelGGL(rvk::scan_sums_inplace, dim3(1), dim3(1024), 0, ctx->stream, p.tile_counts, ntiles, &ctrl->pops[0]);
         RV_HIP(hipGetLastError());
         void *hs = ctx->stage(nb * 8);
@@ -413,17 +365,13 @@ void gather_pairs(rv_ctx *ctx, const rv_dcolumn *const *build_cols, uint32_t n_b
     const IndexNulls none{};  // kJoinNone is the null index
     const uint64_t *p_idx = static_cast<const uint64_t *>(pi->ptr), *b_idx = bi ? static_cast<const uint64_t *>(bi->ptr) : nullptr;
     const uint32_t n_rest = static_cast<uint32_t>(build_rest.size());
-    try {
+    breaker_call(ctx, out, nout, [&] {
         if (kind == RV_JOIN_FULL_OUTER) take_nullable_on_device(ctx, probe_cols, n_probe, p_idx, rows, out, false, none);
         else take_on_device(ctx, probe_cols, n_probe, p_idx, rows, out, false);
         if (kind == RV_JOIN_FULL_OUTER || kind == RV_JOIN_PROBE_OUTER) take_nullable_on_device(ctx, build_rest.data(), n_rest, b_idx, rows, out + n_probe, false, none);
         else if (kind_has_pairs(kind)) take_on_device(ctx, build_rest.data(), n_rest, b_idx, rows, out + n_probe, false);
         RV_HIP(hipStreamSynchronize(ctx->stream));  // the index buffers go back to the pool
-    } catch (...) {
-        (void)hipStreamSynchronize(ctx->stream);
-        drop_outputs(out, nout);
-        throw;
-    }
+    });
 }
 
 }  // namespace
@@ -447,7 +395,7 @@ rv_status rv_join_probe(rv_ctx *ctx, const rv_join_table *table, const rv_dcolum
         *out_probe_idx = *out_build_idx = nullptr;
         set_device(ctx);
         DevBufRef pi, bi;
-        const uint64_t rows = probe_table(ctx, table, probe_key, pi, bi);
+        const uint64_t rows = probe_table(ctx, table, probe_key, RV_JOIN_INNER, pi, bi);
         std::unique_ptr<rv_dcolumn> a(index_column(pi, rows)), b(index_column(bi, rows));
         *out_probe_idx = a.release();
         *out_build_idx = b.release();
@@ -464,7 +412,7 @@ rv_status rv_join_probe_kind(rv_ctx *ctx, const rv_join_table *table, const rv_d
         *out_probe_idx = *out_build_idx = nullptr;
         set_device(ctx);
         DevBufRef pi, bi;
-        const uint64_t rows = probe_table_kind(ctx, table, probe_key, kind, pi, bi);
+        const uint64_t rows = probe_table(ctx, table, probe_key, kind, pi, bi);
         std::unique_ptr<rv_dcolumn> a, b;
         a.reset(kind == RV_JOIN_FULL_OUTER ? nullable_index_column(ctx, pi, rows) : index_column(pi, rows));
         if (kind == RV_JOIN_FULL_OUTER || kind == RV_JOIN_PROBE_OUTER) b.reset(nullable_index_column(ctx, bi, rows));
@@ -505,7 +453,7 @@ rv_status rv_hash_join(rv_ctx *ctx, const rv_dcolumn *const *build_cols, uint32_
         for (uint32_t c = 0; c < nout; ++c) out[c] = nullptr;
         std::unique_ptr<rv_join_table> t = build_table(ctx, build_cols[build_key]);
         DevBufRef pi, bi;
-        const uint64_t rows = probe_table(ctx, t.get(), probe_cols[probe_key], pi, bi);
+        const uint64_t rows = probe_table(ctx, t.get(), probe_cols[probe_key], RV_JOIN_INNER, pi, bi);
         gather_pairs(ctx, build_cols, n_build, build_key, probe_cols, n_probe, pi, bi, rows, out);
         if (out_rows) *out_rows = rows;
     });
@@ -523,7 +471,7 @@ rv_status rv_hash_join_kind(rv_ctx *ctx, const rv_dcolumn *const *build_cols, ui
         for (uint32_t c = 0; c < nout; ++c) out[c] = nullptr;
         std::unique_ptr<rv_join_table> t = build_table(ctx, build_cols[build_key]);
         DevBufRef pi, bi;
-        const uint64_t rows = probe_table_kind(ctx, t.get(), probe_cols[probe_key], kind, pi, bi);
+        const uint64_t rows = probe_table(ctx, t.get(), probe_cols[probe_key], kind, pi, bi);
         gather_pairs(ctx, build_cols, n_build, build_key, probe_cols, n_probe, pi, bi, rows, out, kind);
         if (out_rows) *out_rows = rows;
     });
@@ -554,12 +502,9 @@ static void hash_join_chunked(rv_ctx *ctx, const char *what, rv_join_kind kind, 
         DevBufRef pi, bi;
         const uint64_t rows = probe_table_batched(ctx, what, kind, table, probe_cols[probe_key], chunk_rows, max_pairs, counts.data(), taken, pi, bi);
         gather_pairs(ctx, build_cols, n_build, build_key, probe_cols, n_probe, pi, bi, rows, out, kind);
-        try {
+        breaker_call(ctx, out, nout, [&] {
             if (out_nulls) batch_null_counts(ctx, what, out, nout, counts.data(), taken, out_nulls);
-        } catch (...) {
-            drop_outputs(out, nout);
-            throw;
-        }
+        });
         if (nb) std::memcpy(out_rows, counts.data(), nb * 8);
         if (out_total) *out_total = rows;
         *out_batches = taken;

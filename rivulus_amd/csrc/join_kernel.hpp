@@ -72,9 +72,12 @@ struct JoinTableView {
     int32_t pad;
 };
 
-// (start, count) of the matches of one probe cell
-__device__ __forceinline__ uint32_t join_lookup(const JoinTableView &t, uint32_t cls, uint64_t bits, uint32_t &start) {
+// (start, count) of the matches of one probe cell.  `group` (the full outer join's count pass; nullptr everywhere else, and nothing of it
+// is left in those inlined copies): the group met, for the marks -- the slot of a key group, the table's slot count for the null group
+// (bit `slots` of the marks).  Meaningful only where the returned count is not 0.
+__device__ __forceinline__ uint32_t join_lookup(const JoinTableView &t, uint32_t cls, uint64_t bits, uint32_t &start, uint64_t *group = nullptr) {
     start = 0;
+    if (group) *group = t.slot_mask + 1;
     if (cls == JK_NULL) {
         start = t.null_start;
         return t.null_count;
@@ -86,6 +89,7 @@ __device__ __forceinline__ uint32_t join_lookup(const JoinTableView &t, uint32_t
         if (e.y == 0) return 0;
         if (e.x == bits) {
             start = static_cast<uint32_t>(e.y);
+            if (group) *group = s;
             return static_cast<uint32_t>(e.y >> 32);
         }
         s = (s + 1) & t.slot_mask;
@@ -93,8 +97,8 @@ __device__ __forceinline__ uint32_t join_lookup(const JoinTableView &t, uint32_t
 }
 
 // ---- join kinds -----------------------------------------------------------------------------------------------------------------
-// rv_join_kind as a compile-time constant of the probe kernels.  The inner join is the kernels below under their old names; every
-// other kind is the same body with another row rule.
+// rv_join_kind as a compile-time constant of the probe kernels: one body and one __global__ wrapper per pass, the inner join one of the
+// kinds -- the row rule below is all that tells them apart.
 enum : int { JOIN_INNER = 0, JOIN_OUTER = 1, JOIN_FULL = 2, JOIN_SEMI = 3, JOIN_ANTI = 4 };
 constexpr uint64_t kJoinNone = ~0ull;  // "no partner" inside the index buffers; the public columns get a null cell for it
 
@@ -105,29 +109,6 @@ __device__ __forceinline__ uint32_t join_rows(uint32_t c) {
     if (KIND == JOIN_SEMI) return c != 0;
     if (KIND == JOIN_ANTI) return c == 0;
     return c;
-}
-
-// join_lookup that also names the group it met, for the marks of the full outer join: the slot of a key group, the table's slot
-// count for the null group (bit `slots` of the marks).  Meaningful only where the returned count is not 0.
-__device__ __forceinline__ uint32_t join_lookup_at(const JoinTableView &t, uint32_t cls, uint64_t bits, uint32_t &start, uint64_t &group) {
-    start = 0;
-    group = t.slot_mask + 1;
-    if (cls == JK_NULL) {
-        start = t.null_start;
-        return t.null_count;
-    }
-    if (cls != JK_VALUE || !t.match_values) return 0;
-    uint64_t s = join_hash(bits) & t.hash_mask & t.slot_mask;
-    for (;;) {
-        const ulonglong2 e = *reinterpret_cast<const ulonglong2 *>(&t.slots[2 * s]);
-        if (e.y == 0) return 0;
-        if (e.x == bits) {
-            start = static_cast<uint32_t>(e.y);
-            group = s;
-            return static_cast<uint32_t>(e.y >> 32);
-        }
-        s = (s + 1) & t.slot_mask;
-    }
 }
 
 // One bit per group a probe row met (JOIN_FULL's count pass): a plain load first, the atomic only while the bit is clear, so a hot
@@ -238,7 +219,7 @@ __device__ __forceinline__ void join_count_body(const JoinProbeParams p, uint32_
             uint32_t start;
             if (KIND == JOIN_FULL) {
                 uint64_t group;
-                const uint32_t c = join_lookup_at(p.table, cls, bits, start, group);
+                const uint32_t c = join_lookup(p.table, cls, bits, start, &group);
                 if (c) join_mark(marks, group);
                 mine += join_rows<KIND>(c);
             } else {
@@ -256,9 +237,8 @@ __device__ __forceinline__ void join_count_body(const JoinProbeParams p, uint32_
         p.tile_counts[blockIdx.x] = t;
     }
 }
-static __global__ __launch_bounds__(kJoinThreads) void join_probe_count(JoinProbeParams p) { join_count_body<JOIN_INNER>(p, nullptr); }
 template <int KIND>
-static __global__ __launch_bounds__(kJoinThreads) void join_probe_count_kind(JoinProbeParams p, uint32_t *marks) { join_count_body<KIND>(p, marks); }
+static __global__ __launch_bounds__(kJoinThreads) void join_probe_count(JoinProbeParams p, uint32_t *marks) { join_count_body<KIND>(p, marks); }
 
 // Pass 1 of a probe cut into batches of chunk_rows rows (rv_hash_join_chunked): the tile counts of join_probe_count and, in the
 // same pass, the pairs of every batch -- batch b is probe rows [b * chunk_rows, min((b + 1) * chunk_rows, n)).
@@ -376,12 +356,8 @@ __device__ __forceinline__ void join_count_batched_body(const JoinProbeParams p,
         else if (s_batch[t]) atomicAdd(&b.batch_counts[bi], s_batch[t]);
     }
 }
-template <bool FAST>
-static __global__ __launch_bounds__(kJoinThreads) void join_probe_count_batched(JoinProbeParams p, JoinBatchParams b) {
-    join_count_batched_body<FAST, JOIN_INNER>(p, b);
-}
 template <bool FAST, int KIND>
-static __global__ __launch_bounds__(kJoinThreads) void join_probe_count_batched_kind(JoinProbeParams p, JoinBatchParams b) {
+static __global__ __launch_bounds__(kJoinThreads) void join_probe_count_batched(JoinProbeParams p, JoinBatchParams b) {
     join_count_batched_body<FAST, KIND>(p, b);
 }
 
@@ -492,10 +468,8 @@ __device__ __forceinline__ void join_emit_body(const JoinProbeParams p) {
         }
     }
 }
-template <int MODE>
-static __global__ __launch_bounds__(kJoinThreads) void join_probe_emit(JoinProbeParams p) { join_emit_body<MODE, JOIN_INNER>(p); }
 template <int MODE, int KIND>
-static __global__ __launch_bounds__(kJoinThreads) void join_probe_emit_kind(JoinProbeParams p) { join_emit_body<MODE, KIND>(p); }
+static __global__ __launch_bounds__(kJoinThreads) void join_probe_emit(JoinProbeParams p) { join_emit_body<MODE, KIND>(p); }
 
 // ---- full outer join: the build rows no probe row met ----------------------------------------------------------------------------
 // marks (one bit per slot, bit `slots` for the null group) -> a bitmap of the build rows of the marked groups.  A wave takes 64 slots:

@@ -1,6 +1,7 @@
 // Internal interface between the translation units of librivulus_gpu.so (core / fused_launch / narrow / strings / predicate / arrays /
-// query / take_concat / host_table / aggregate / join / string_dict / csv / group / group_agg / sort / topk / window / window_frame .hip): the control block, the request / launch
-// records that travel with a fused pass, and the functions the units call across each other.  Nothing here is part of the C ABI.
+// query / take_concat / take_nullable / host_table / aggregate / arith / join / string_dict / csv / group / group_agg / sort / topk / window /
+// window_frame .hip): the control block, the request / launch records that travel with a fused pass, and the functions the units call across
+// each other.  The host-side steps the breakers' units share are in breaker_steps.hpp.  Nothing here is part of the C ABI.
 #pragma once
 
 #include <algorithm>
@@ -278,8 +279,9 @@ void take_on_device(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, 
 void check_sort_key(const rv_dcolumn *key, uint32_t flags, const char *what);
 // the stable permutation of `key` (of `prior`, n device-resident indices, reordered by it) as key->length Int64 rows
 DevBufRef sort_indices(rv_ctx *ctx, const rv_dcolumn *key, uint32_t flags, const uint64_t *prior);
-// an Int64 column without nulls over the first `rows` rows of `buf`
-rv_dcolumn *sort_index_column(const DevBufRef &buf, uint64_t rows);
+// the chain of stable sorts from the last key to the first, over `prior` (null: the identity): the permutation by (keys[0], keys[1], ...);
+// ctx->last_kernel and ctx->sort_last_passes are those of the last link run, the first key's
+DevBufRef sort_chain(rv_ctx *ctx, const rv_dcolumn *const *keys, const uint32_t *flags, uint32_t nkeys, DevBufRef prior = nullptr);
 
 // ---- group_agg.hip -----------------------------------------------------------------------------------------
 // what rv_group_ids_keys checks of its key list, under the caller's name `what`, and the dense Int64 group id of every row (n cells, no

@@ -1,9 +1,11 @@
 // Sort on the device: rv_sort_indices (the stable permutation of a key column) and rv_sort (that permutation, chained over the keys,
 // followed by the gather of take_concat.hip).  One unit of the backend library behind include/rivulus_gpu.h (gfx950 only; compiled with
-// hipcc).  Shared helpers are declared in launch.hpp (namespace rvl); the kernels and the shape of the passes are in sort_kernel.hpp.
+// hipcc).  Shared helpers are declared in launch.hpp (namespace rvl), the steps every breaker's unit takes in breaker_steps.hpp; the
+// kernels and the shape of the passes are in sort_kernel.hpp.  sort_chain is the chain for every unit that orders rows by several keys
+// (topk.hip, window.hip).
 #include <rocprim/device/device_radix_sort.hpp>
 
-#include "launch.hpp"
+#include "breaker_steps.hpp"
 #include "sort_kernel.hpp"
 
 using namespace rvh;
@@ -58,7 +60,8 @@ DevBufRef sort_indices(rv_ctx *ctx, const rv_dcolumn *key, uint32_t flags, const
     RV_HIP(hipMemsetAsync(hist->ptr, 0, kHistBytes, ctx->stream));
     Ctrl *ctrl = prepare_ctrl(ctx, 0);
     RV_HIP(hipMemsetAsync(&ctrl->pops[0], 0xFF, 8, ctx->stream));
-    if (ctx->opt_profile) RV_HIP(hipEventRecord(ctx->evk0, ctx->stream));
+    PassTimer timer(ctx);
+    timer.start();
 
     rvk::SortMapParams m{};
     m.key = dev_view(key);
@@ -83,7 +86,8 @@ DevBufRef sort_indices(rv_ctx *ctx, const rv_dcolumn *key, uint32_t flags, const
     const uint64_t value_passes = h->pops[1], valid_rows = h->pops[2];
     const bool null_pass = valid_rows > 0 && valid_rows < n;
 
-    uint64_t launches = 2, scatters = 0;
+    timer.launches = 2;  // the map and the plan
+    uint64_t scatters = 0;
     int cur = 0;
     std::string name;
     rvk::SortPassParams p{};
@@ -107,7 +111,7 @@ DevBufRef sort_indices(rv_ctx *ctx, const rv_dcolumn *key, uint32_t flags, const
         DevBufRef temp = pool_alloc(ctx, std::max<size_t>(temp_bytes, 16));
         RV_HIP(rocprim::radix_sort_pairs(temp->ptr, temp_bytes, p.keys_in, p.keys_out, p.rows_in, p.rows_out, static_cast<size_t>(n), 0u, 64u, ctx->stream));
         cur ^= 1;
-        ++launches;
+        ++timer.launches;
         name = "rocprim::radix_sort_pairs";
     } else {
         for (uint32_t pos = 0; pos < static_cast<uint32_t>(rvk::kSortPositions); ++pos) {
@@ -133,18 +137,13 @@ DevBufRef sort_indices(rv_ctx *ctx, const rv_dcolumn *key, uint32_t flags, const
         hipLaunchKernelGGL(rvk::sort_widen, dim3(grid_for_words(ctx, n, rvk::kSortThreads)), dim3(rvk::kSortThreads), 0, ctx->stream,
                            static_cast<const uint32_t *>(rows[cur]->ptr), n, static_cast<int64_t *>(out->ptr));
         RV_HIP(hipGetLastError());
-        ++launches;
+        ++timer.launches;
         name += name.empty() ? "sort_widen" : "+sort_widen";
     }
-    launches += scatters * 5;  // tile counts, the scan's three, the scatter
-    if (ctx->opt_profile) RV_HIP(hipEventRecord(ctx->evk1, ctx->stream));
+    timer.launches += scatters * 5;  // tile counts, the scan's three, the scatter
+    timer.stop();
     RV_HIP(hipStreamSynchronize(ctx->stream));  // the working buffers go back to the pool
-    if (ctx->opt_profile) {
-        float ms = 0.f;
-        RV_HIP(hipEventElapsedTime(&ms, ctx->evk0, ctx->evk1));
-        ctx->kernel_ms += ms;
-        ctx->kernel_launches += launches;
-    }
+    timer.add();
     ctx->sort_last_passes = scatters;
     ctx->last_kernel = name;
     return out;
@@ -167,13 +166,10 @@ const uint64_t *check_prior(rv_ctx *ctx, const rv_dcolumn *key, const rv_dcolumn
 
 }  // namespace
 
-rv_dcolumn *sort_index_column(const DevBufRef &buf, uint64_t rows) {
-    auto o = std::make_unique<rv_dcolumn>();
-    o->dtype = RV_INT64;
-    o->length = rows;
-    o->null_count = 0;
-    o->values = buf;
-    return o.release();
+// (k0, k1, ...) is the chain from the last key to the first: each stable sort reorders what the keys after it left
+DevBufRef sort_chain(rv_ctx *ctx, const rv_dcolumn *const *keys, const uint32_t *flags, uint32_t nkeys, DevBufRef prior) {
+    for (uint32_t k = nkeys; k-- > 0;) prior = sort_indices(ctx, keys[k], flags[k], prior ? static_cast<const uint64_t *>(prior->ptr) : nullptr);
+    return prior;
 }
 
 }  // namespace rvl
@@ -187,13 +183,7 @@ rv_status rv_sort_indices(rv_ctx *ctx, const rv_dcolumn *key, uint32_t flags, co
         check_sort_key(key, flags, "rv_sort_indices");
         set_device(ctx);
         const uint64_t *d_prior = check_prior(ctx, key, prior);
-        try {
-            DevBufRef idx = sort_indices(ctx, key, flags, d_prior);
-            *out_indices = sort_index_column(idx, key->length);
-        } catch (...) {
-            (void)hipStreamSynchronize(ctx->stream);  // whatever was queued has run before its buffers go back to the pool
-            throw;
-        }
+        breaker_call(ctx, out_indices, 1, [&] { *out_indices = index_column(sort_indices(ctx, key, flags, d_prior), key->length); });
     });
 }
 
@@ -203,26 +193,21 @@ rv_status rv_sort(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, co
         require(ctx && cols && out && (nkeys == 0 || (key_cols && key_flags)), RV_ERR_INVALID_ARG, "rv_sort: NULL argument");
         require(nkeys >= 1, RV_ERR_INVALID_ARG, "rv_sort: no sort keys");
         check_batch(cols, ncols);
-        for (uint32_t k = 0; k < nkeys; ++k)
-            require(key_cols[k] < ncols, RV_ERR_INVALID_ARG, fmt("rv_sort: key %u is column %u of %u", k, key_cols[k], ncols));
+        check_key_columns("rv_sort", "", key_cols, nkeys, ncols);
         for (uint32_t k = 0; k < nkeys; ++k) check_sort_key(cols[key_cols[k]], key_flags[k], "rv_sort");
         for (uint32_t c = 0; c < ncols; ++c) out[c] = nullptr;
         set_device(ctx);
-        try {
-            // (k0, k1, ...) is the chain from the last key to the first: each stable sort reorders what the keys after it left
-            DevBufRef idx;
-            for (uint32_t k = nkeys; k-- > 0;)
-                idx = sort_indices(ctx, cols[key_cols[k]], key_flags[k], idx ? static_cast<const uint64_t *>(idx->ptr) : nullptr);
+        breaker_call(ctx, out, ncols, [&] {
+            std::vector<const rv_dcolumn *> keys(nkeys);
+            for (uint32_t k = 0; k < nkeys; ++k) keys[k] = cols[key_cols[k]];
+            DevBufRef idx = sort_chain(ctx, keys.data(), key_flags, nkeys);
             const std::string name = ctx->last_kernel;
             const uint64_t passes = ctx->sort_last_passes;
             take_on_device(ctx, cols, ncols, static_cast<const uint64_t *>(idx->ptr), cols[0]->length, out, false);
             RV_HIP(hipStreamSynchronize(ctx->stream));  // the index list goes back to the pool
             ctx->last_kernel = name;
             ctx->sort_last_passes = passes;
-        } catch (...) {
-            (void)hipStreamSynchronize(ctx->stream);
-            throw;
-        }
+        });
     });
 }
 

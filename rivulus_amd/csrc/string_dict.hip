@@ -2,7 +2,7 @@
 // One unit of the backend library behind include/rivulus_gpu.h (gfx950 only; compiled with hipcc).  Shared helpers are declared in
 // launch.hpp (namespace rvl); the kernels are in string_dict_kernel.hpp, the hash in string_hash.hpp.
 #include "string_dict_kernel.hpp"
-#include "launch.hpp"
+#include "breaker_steps.hpp"
 
 using namespace rvh;
 using namespace rvl;
@@ -95,24 +95,6 @@ rv_dcolumn *finish_ids(IdsLaunch &L, const Ctrl *fetched) {
     return L.ids.release();
 }
 
-// events around a call's kernels (option profile_kernels)
-struct KernelTimer {
-    rv_ctx *ctx;
-    explicit KernelTimer(rv_ctx *c) : ctx(c) {
-        if (ctx->opt_profile) RV_HIP(hipEventRecord(ctx->evk0, ctx->stream));
-    }
-    void stop() {
-        if (ctx->opt_profile) RV_HIP(hipEventRecord(ctx->evk1, ctx->stream));
-    }
-    void add(uint64_t launches) {  // after the call's wait
-        if (!ctx->opt_profile) return;
-        float ms = 0.f;
-        RV_HIP(hipEventElapsedTime(&ms, ctx->evk0, ctx->evk1));
-        ctx->kernel_ms += ms;
-        ctx->kernel_launches += launches;
-    }
-};
-
 }  // namespace
 }  // namespace rvl
 
@@ -139,7 +121,8 @@ rv_status rv_string_dict_build(rv_ctx *ctx, const rv_dcolumn *col, rv_string_dic
         d->slots = pool_alloc(ctx, nslots * 8);
         RV_HIP(hipMemsetAsync(d->slots->ptr, 0, nslots * 8, ctx->stream));
         Ctrl *ctrl = prepare_ctrl(ctx, 0);
-        KernelTimer timer(ctx);
+        PassTimer timer(ctx);
+        timer.start();
         const bool insert = n && col->dtype == RV_STRING;
         if (insert) {
             rvk::StrDictParams q = dict_params(d.get(), col, ctrl);
@@ -152,7 +135,8 @@ rv_status rv_string_dict_build(rv_ctx *ctx, const rv_dcolumn *col, rv_string_dic
         if (out_ids) L = queue_encode(ctx, d.get(), col, ctrl);
         timer.stop();
         const Ctrl *h = fetch_ctrl(ctx);  // the call's one read-back: distinct strings, non-null rows, the error flag
-        timer.add((insert ? 1 : 0) + (out_ids && insert ? 1 : 0));
+        timer.launches = (insert ? 1 : 0) + (out_ids && insert ? 1 : 0);
+        timer.add();
         require(h->err == 0, RV_ERR_INTERNAL, "rv_string_dict_build: a chain walk exhausted the table");
         d->distinct = h->pops[0];
         if (out_ids) *out_ids = finish_ids(L, h);
@@ -167,11 +151,13 @@ rv_status rv_string_dict_encode(rv_ctx *ctx, const rv_string_dict *dict, const r
         check_column(col, "rv_string_dict_encode");
         set_device(ctx);
         Ctrl *ctrl = prepare_ctrl(ctx, 0);
-        KernelTimer timer(ctx);
+        PassTimer timer(ctx);
+        timer.start();
         IdsLaunch L = queue_encode(ctx, dict, col, ctrl);
         timer.stop();
         const Ctrl *h = fetch_ctrl(ctx);
-        timer.add(col->length && col->dtype == RV_STRING ? 1 : 0);
+        timer.launches = col->length && col->dtype == RV_STRING ? 1 : 0;
+        timer.add();
         require(h->err == 0, RV_ERR_INTERNAL, "rv_string_dict_encode: a chain walk exhausted the table");
         *out_ids = finish_ids(L, h);
     });

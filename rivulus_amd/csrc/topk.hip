@@ -1,8 +1,9 @@
 // Top-k on the device: rv_top_k_indices (the first k rows of rv_sort_indices) and rv_top_k (the first k rows of rv_sort) without sorting
 // the column: a radix select over the first key finds a small set of candidate rows that holds the answer, and the existing sort and
 // gather settle the rest.  One unit of the backend library behind include/rivulus_gpu.h (gfx950 only; compiled with hipcc).  Shared helpers
-// are declared in launch.hpp (namespace rvl); the kernels and the shape of the passes are in topk_kernel.hpp, the decisions in topk_rule.hpp.
-#include "launch.hpp"
+// are declared in launch.hpp (namespace rvl), the steps every breaker's unit takes in breaker_steps.hpp; the kernels and the shape of the
+// passes are in topk_kernel.hpp, the decisions in topk_rule.hpp.  Both sorts here, of the whole column and of the candidates, are sort_chain.
+#include "breaker_steps.hpp"
 #include "topk_kernel.hpp"
 
 using namespace rvh;
@@ -32,9 +33,9 @@ Candidates select_candidates(rv_ctx *ctx, const rv_dcolumn *key, uint32_t flags,
     DevBufRef hist = pool_alloc(ctx, kHistBytes), pass_hist = pool_alloc(ctx, rvk::kSortDigits * 8), scan_total = pool_alloc(ctx, 16);
     RV_HIP(hipMemsetAsync(hist->ptr, 0, kHistBytes, ctx->stream));
     Ctrl *ctrl = prepare_ctrl(ctx, 0);
-    if (ctx->opt_profile) RV_HIP(hipEventRecord(ctx->evk0, ctx->stream));
+    PassTimer timer(ctx);
+    timer.start();
     const dim3 grid(grid_for_words(ctx, n, rvk::kTopKThreads)), block(rvk::kTopKThreads);
-    uint64_t launches = 0;
 
     rvk::TopKHistParams hp{};
     hp.key = dev_view(key);
@@ -51,7 +52,7 @@ Candidates select_candidates(rv_ctx *ctx, const rv_dcolumn *key, uint32_t flags,
     pp.out = &ctrl->valid_pop[0];
     hipLaunchKernelGGL(rvk::topk_plan<true>, dim3(1), block, 0, ctx->stream, pp);
     RV_HIP(hipGetLastError());
-    launches += 2;
+    timer.launches += 2;
     const Ctrl *h = fetch_ctrl(ctx);
     res.passes = 1;
     const uint64_t valid_rows = h->valid_pop[rvk::TOPK_OUT_VALID], mask = h->valid_pop[rvk::TOPK_OUT_MASK];
@@ -93,7 +94,7 @@ Candidates select_candidates(rv_ctx *ctx, const rv_dcolumn *key, uint32_t flags,
             qp.out = &ctrl->valid_pop[0];
             hipLaunchKernelGGL(rvk::topk_plan<false>, dim3(1), block, 0, ctx->stream, qp);
             RV_HIP(hipGetLastError());
-            launches += 2;
+            timer.launches += 2;
             h = fetch_ctrl(ctx);
             ++res.passes;
             prefix = h->valid_pop[rvk::TOPK_OUT_PREFIX];
@@ -124,17 +125,12 @@ Candidates select_candidates(rv_ctx *ctx, const rv_dcolumn *key, uint32_t flags,
     cp.bases = static_cast<const uint64_t *>(bases->ptr);
     hipLaunchKernelGGL(rvk::topk_collect, dim3(ntiles), block, 0, ctx->stream, cp);
     RV_HIP(hipGetLastError());
-    launches += 5;
-    if (ctx->opt_profile) RV_HIP(hipEventRecord(ctx->evk1, ctx->stream));
+    timer.launches += 5;
+    timer.stop();
     uint64_t collected = 0;
     RV_HIP(hipMemcpyAsync(&collected, scan_total->ptr, 8, hipMemcpyDeviceToHost, ctx->stream));
     RV_HIP(hipStreamSynchronize(ctx->stream));  // the working buffers go back to the pool
-    if (ctx->opt_profile) {
-        float ms = 0.f;
-        RV_HIP(hipEventElapsedTime(&ms, ctx->evk0, ctx->evk1));
-        ctx->kernel_ms += ms;
-        ctx->kernel_launches += launches;
-    }
+    timer.add();
     require(collected == count, RV_ERR_INTERNAL,
             fmt("top-k: the collect found %llu candidates, the plan %llu", static_cast<unsigned long long>(collected), static_cast<unsigned long long>(count)));
     res.count = count;
@@ -154,26 +150,20 @@ DevBufRef top_k_rows(rv_ctx *ctx, const rv_dcolumn *const *keys, const uint32_t 
     Candidates cand;
     if (n >= select_from && kk < n - kk) cand = select_candidates(ctx, keys[0], flags[0], kk, divisor);
     if (!cand.selected) {  // the whole sort; the caller keeps the first kk rows of it
-        DevBufRef idx;
-        for (uint32_t j = nkeys; j-- > 0;) idx = sort_indices(ctx, keys[j], flags[j], idx ? static_cast<const uint64_t *>(idx->ptr) : nullptr);
         ctx->top_k_last_candidates = n;
-        return idx;
+        return sort_chain(ctx, keys, flags, nkeys);
     }
     // every key at the candidates, the chain of stable sorts from the last key to the first over those few rows, and the candidates' row
     // ids through the permutation: ties of the first key that straddle the cut are all candidates, so the later keys decide them
     const uint64_t *d_cand = static_cast<const uint64_t *>(cand.rows->ptr);
-    DevBufRef perm;
-    for (uint32_t j = nkeys; j-- > 0;) {
-        rv_dcolumn *g = nullptr;
-        take_on_device(ctx, &keys[j], 1, d_cand, cand.count, &g, false);
-        std::unique_ptr<rv_dcolumn> gathered(g);
-        perm = sort_indices(ctx, gathered.get(), flags[j], perm ? static_cast<const uint64_t *>(perm->ptr) : nullptr);
+    std::vector<rv_dcolumn *> at_cand(nkeys, nullptr);
+    std::vector<std::unique_ptr<rv_dcolumn>> gathered(nkeys);
+    for (uint32_t j = 0; j < nkeys; ++j) {
+        take_on_device(ctx, &keys[j], 1, d_cand, cand.count, &at_cand[j], false);
+        gathered[j].reset(at_cand[j]);
     }
-    rv_dcolumn ids;
-    ids.dtype = RV_INT64;
-    ids.values = cand.rows;
-    ids.length = cand.count;
-    ids.null_count = 0;
+    DevBufRef perm = sort_chain(ctx, at_cand.data(), flags, nkeys);
+    const rv_dcolumn ids = plain_view(RV_INT64, cand.rows, cand.count);
     const rv_dcolumn *ids_ptr = &ids;
     rv_dcolumn *first = nullptr;
     take_on_device(ctx, &ids_ptr, 1, static_cast<const uint64_t *>(perm->ptr), kk, &first, false);
@@ -196,14 +186,11 @@ rv_status rv_top_k_indices(rv_ctx *ctx, const rv_dcolumn *key, uint32_t flags, u
         *out_indices = nullptr;
         check_sort_key(key, flags, "rv_top_k_indices");
         set_device(ctx);
-        try {
+        breaker_call(ctx, out_indices, 1, [&] {
             uint64_t rows = 0;
             DevBufRef idx = top_k_rows(ctx, &key, &flags, 1, k, &rows);
-            *out_indices = sort_index_column(idx, rows);
-        } catch (...) {
-            (void)hipStreamSynchronize(ctx->stream);  // whatever was queued has run before its buffers go back to the pool
-            throw;
-        }
+            *out_indices = index_column(idx, rows);
+        });
     });
 }
 
@@ -213,12 +200,11 @@ rv_status rv_top_k(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, c
         require(ctx && cols && out && (nkeys == 0 || (key_cols && key_flags)), RV_ERR_INVALID_ARG, "rv_top_k: NULL argument");
         require(nkeys >= 1, RV_ERR_INVALID_ARG, "rv_top_k: no sort keys");
         check_batch(cols, ncols);
-        for (uint32_t j = 0; j < nkeys; ++j)
-            require(key_cols[j] < ncols, RV_ERR_INVALID_ARG, fmt("rv_top_k: key %u is column %u of %u", j, key_cols[j], ncols));
+        check_key_columns("rv_top_k", "", key_cols, nkeys, ncols);
         for (uint32_t j = 0; j < nkeys; ++j) check_sort_key(cols[key_cols[j]], key_flags[j], "rv_top_k");
         for (uint32_t c = 0; c < ncols; ++c) out[c] = nullptr;
         set_device(ctx);
-        try {
+        breaker_call(ctx, out, ncols, [&] {
             std::vector<const rv_dcolumn *> keys(nkeys);
             for (uint32_t j = 0; j < nkeys; ++j) keys[j] = cols[key_cols[j]];
             uint64_t rows = 0;
@@ -227,11 +213,7 @@ rv_status rv_top_k(rv_ctx *ctx, const rv_dcolumn *const *cols, uint32_t ncols, c
             take_on_device(ctx, cols, ncols, static_cast<const uint64_t *>(idx->ptr), rows, out, false);
             RV_HIP(hipStreamSynchronize(ctx->stream));  // the index list goes back to the pool
             ctx->last_kernel = name;
-        } catch (...) {
-            (void)hipStreamSynchronize(ctx->stream);
-            drop_outputs(out, ncols);
-            throw;
-        }
+        });
     });
 }
 

@@ -1,7 +1,8 @@
 // Window functions on the device: rv_window -- rank, running aggregates and lag / lead over PARTITION BY ... ORDER BY.  One unit of the
 // backend library behind include/rivulus_gpu.h (gfx950 only; compiled with hipcc).  Shared helpers are declared in launch.hpp (namespace
 // rvl); the kernels, the shape of the passes and the bracketing of the scan are in window_kernel.hpp, the combine in window_combine.hpp.
-// The partition ids are rv_group_ids_keys' (group_agg.hip), the sequence is the sort's chain (sort.hip), LAG / LEAD gather through
+// The partition ids are rv_group_ids_keys' (group_agg.hip), the sequence is sort_chain (sort.hip) over the ids and the order keys, the
+// timer and the null counts are breaker_steps.hpp's, LAG / LEAD gather through
 // take_nullable_on_device (take_nullable.hip): what is new here is the heads pass, the segmented scan and the shift.
 #include "window_passes.hpp"
 
@@ -56,14 +57,13 @@ void window(const char *who, rv_ctx *ctx, const rv_dcolumn *const *cols, const u
         for (uint32_t k = 0; k < npart; ++k) keys[k] = cols[partition_cols[k]];
         q.ids = partition_ids(ctx, keys.data(), npart, who);
     }
-    for (uint32_t k = norder; k-- > 0;) q.perm = sort_indices(ctx, cols[order_cols[k]], order_flags[k], q.d_perm());
-    if (npart) {
-        rv_dcolumn id_col;
-        id_col.dtype = RV_INT64;
-        id_col.values = q.ids;
-        id_col.length = n;
-        id_col.null_count = 0;
-        q.perm = sort_indices(ctx, &id_col, 0, q.d_perm());
+    {
+        const rv_dcolumn id_col = plain_view(RV_INT64, q.ids, n);
+        std::vector<const rv_dcolumn *> keys;
+        std::vector<uint32_t> flags;
+        if (npart) keys.push_back(&id_col), flags.push_back(0);
+        for (uint32_t k = 0; k < norder; ++k) keys.push_back(cols[order_cols[k]]), flags.push_back(order_flags[k]);
+        q.perm = sort_chain(ctx, keys.data(), flags.data(), static_cast<uint32_t>(keys.size()));
     }
 
     PassTimer timer(ctx);
@@ -153,7 +153,7 @@ void window(const char *who, rv_ctx *ctx, const rv_dcolumn *const *cols, const u
     // 5. the frames, first / last value and ntile, over the same sequence
     for (uint32_t j = 0; j < nspecs; ++j) framed = framed || is_window_frame_op(specs[j].op);
     if (framed) window_frame_passes(ctx, q, cols, specs, nspecs, outs, nulls, shifts, timer);
-    timer.stop_after_wait_for(ctx->stream);
+    timer.stop_and_wait();
     nulls.settle();
     for (const IndexGather &s : shifts) {
         const rv_dcolumn *col = cols[specs[s.j].col];
@@ -177,10 +177,8 @@ void window_call(const char *who, uint32_t op_most, rv_ctx *ctx, const rv_dcolum
     require(ncols >= 1, RV_ERR_INVALID_ARG, w + ": no columns");
     require(nspecs >= 1, RV_ERR_INVALID_ARG, w + ": no window expressions");
     check_batch(cols, ncols);
-    for (uint32_t k = 0; k < npart; ++k)
-        require(partition_cols[k] < ncols, RV_ERR_INVALID_ARG, fmt("%s: partition key %u is column %u of %u", who, k, partition_cols[k], ncols));
-    for (uint32_t k = 0; k < norder; ++k)
-        require(order_cols[k] < ncols, RV_ERR_INVALID_ARG, fmt("%s: order key %u is column %u of %u", who, k, order_cols[k], ncols));
+    check_key_columns(who, "partition ", partition_cols, npart, ncols);
+    check_key_columns(who, "order ", order_cols, norder, ncols);
     require(norder <= static_cast<uint32_t>(rvk::kWinOrderKeysMost), RV_ERR_INVALID_ARG,
             fmt("%s: %u order keys; at most %d are taken", who, norder, rvk::kWinOrderKeysMost));
     for (uint32_t j = 0; j < nspecs; ++j) {
@@ -210,12 +208,7 @@ void window_call(const char *who, uint32_t op_most, rv_ctx *ctx, const rv_dcolum
     }
     for (uint32_t j = 0; j < nspecs; ++j) out[j] = nullptr;
     set_device(ctx);
-    try {
-        window(who, ctx, cols, partition_cols, npart, order_cols, order_flags, norder, specs, nspecs, out);
-    } catch (...) {
-        (void)hipStreamSynchronize(ctx->stream);  // whatever was queued has run before its buffers go back to the pool
-        throw;
-    }
+    breaker_call(ctx, out, nspecs, [&] { window(who, ctx, cols, partition_cols, npart, order_cols, order_flags, norder, specs, nspecs, out); });
 }
 
 }  // namespace rvl
