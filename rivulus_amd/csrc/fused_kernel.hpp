@@ -29,6 +29,7 @@
 #pragma once
 
 #include "lookback.hpp"
+#include "narrow_sides.hpp"
 #include "scan_frontend.hpp"
 #include "tile_addr.hpp"
 
@@ -175,6 +176,8 @@ constexpr int kLdsHeader = 256;
 // per-wave dump area behind the slots: 64 x 8 bytes + 64 bytes.  The generic staging loop is branch-free:
 // lanes without a survivor store to their own dump cell instead of being masked off (see stage_slot).
 constexpr int kLdsDumpBytes = 576;
+// behind every slot of a pass over packed codes: one spare 2-byte cell (fused_filter_compact, the whole-tile staging's one clamp)
+constexpr uint32_t kPackedSpareBytes = 2;
 
 __device__ __forceinline__ unsigned long long stamp_now() {
     unsigned long long t;
@@ -352,7 +355,10 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
             if constexpr (kXs)
                 if (s < p.nxs) cur += (VEC == 1 && cap < (R + 2) * 8u) ? (R + 2) * 8u : cap;  // VEC == 1: R + 1 words of bits
         }
-        slot_bytes = (cur + 15u) & ~15u;
+        // (a pass over packed codes: one spare 2-byte cell behind the slot's `cap`, what the whole-tile staging's one clamp per pair may
+        //  write in a wave that outgrew the slot -- see there; fused_launch.hip, size_staged, sizes the launch's LDS with it)
+        if constexpr (kPack10) slot_bytes = (cur + (cur ? kPackedSpareBytes : 0u) + 15u) & ~15u;
+        else slot_bytes = (cur + 15u) & ~15u;
     }
     auto slot_of = [&](uint32_t stage) { return kLdsHeader + (stage * WAVES + wave) * slot_bytes; };
 
@@ -372,6 +378,20 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
                 using Code = typename std::conditional<kNarrow == 2, uint16_t, uint32_t>::type;
                 const Code *sc = reinterpret_cast<const Code *>(smem + sb + off_v[c]);
                 const uint64_t base = kLeanTile ? own.narrow_base : static_cast<uint64_t>(p.narrow.base);
+                if constexpr (kLeanTile) {
+                    // A pass over packed codes writes WHOLE LINES: store instruction i covers the output rows [A + 64 i, A + 64 i + 64)
+                    // from the line-aligned row A = g0 & ~15 (out_values[0] of these launches is line-aligned, and out_bias keeps
+                    // "row % 16 == 0 means line-aligned address" true for a launch that appends), lane l taking the staged cell
+                    // 64 i + l - (g0 & 15) when it lies in [0, cnt).  The same rows at the same addresses as the loop below writes,
+                    // cut at line boundaries: a run that starts at any 8-byte address leaves a split 128-byte line behind every
+                    // store instruction, five per ~307-survivor run.  At most one more iteration per run.
+                    const uint32_t head = static_cast<uint32_t>(g0) & 15u;
+                    uint64_t *const dst_a = dst - head;
+                    if (!(kStamp && (p.debug & 1)))
+                        for (uint32_t k = fl; k < cnt + head; k += 64)
+                            if (k >= head) __builtin_nontemporal_store(base + sc[k - head], &dst_a[k]);
+                    continue;
+                }
                 if (!(kStamp && (p.debug & 1)))
                     for (uint32_t k = fl; k < cnt; k += 64) __builtin_nontemporal_store(base + sc[k], &dst[k]);
                 continue;
@@ -540,6 +560,11 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
         TSPAN = static_cast<uint32_t>(static_cast<uint64_t>(ct.lit) >> 32);
         negated = ct.packed != 0;
     }
+    // A pass over packed codes also hears which ends of the interval a code of the companion can fall outside of (narrow_sides.hpp, in
+    // the same slot's `pad`): a single `<`, `<=`, `>` or `>=` is one-sided in code space, and its whole tiles run a form without the
+    // subtraction.  Tested once per tile, like `negated`.
+    uint32_t sides = 0;
+    if constexpr (kPack10) sides = own_scalar(p.in.terms[1].pad);
     // (the stamped instantiations carry the interval in VECTOR registers across the tile loop and read it once per tile, like the terms
     // above: with the stamps beside the staging loop's masks and bases the scalar file is full, and one of them got a stack frame)
     uint32_t tlo_v = 0, tspan_v = 0;
@@ -643,7 +668,59 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
                     else unpack_pair<kNarrow>(codes[j], c0, c1);
                 };
                 if constexpr (kStamp) TLO = uniform32(tlo_v), TSPAN = uniform32(tspan_v);
-                if (full && project && !negated) {
+                // ---- packed codes, whole tile: one raw word (three pairs) at a time.  Six unpacks, six ballots, three rank chains (v_mbcnt
+                //      from 0, then one v_lshl_add onto the address of the pair's first cell) and six branch-free stores.  The three pairs
+                //      of a word share no temporary, so nothing orders pair j + 1 behind pair j but that address, `at`: a wave-uniform
+                //      scalar moved by two bit counts, one addition and one shift-and-add per pair.  (Kept as a COUNT of cells and seeded
+                //      into the pair's first v_mbcnt_lo it is the same four scalar instructions, but the seed, a second scalar operand
+                //      beside the mask, costs a v_mov per pair in front of the rank chain: 0.380 against 0.372 ms on one box)
+                //      ONE clamp per pair: a0 is clamped to the slot's last cell and a1 = a0 + (p0 ? 2 : 0).  In a wave that does not
+                //      outgrow its slot every survivor's rank is below `cap`, so neither of the two clamps this replaces ever acted; a
+                //      wave that does is discarded to the redo kernel, and its a1 reaches at most ONE cell past the slot: the spare
+                //      cell every packed slot has (slot_bytes above), never a neighbour's.
+                //      `keep` is the compare.  A one-sided interval (narrow_sides.hpp) is `code >= lo` or `code <= hi` alone; whole
+                //      tiles hold only real rows, so no padding code 0 ever meets these forms -- and code 0 is a code of the range the
+                //      class was formed for in any case.  The two-sided form remains for `==`, `!=` and wrapped intervals.
+                if constexpr (kPack10) {
+                    const uint32_t slot0c = opaque_uniform(slot0);
+                    auto stage_words = [&](auto keep) __attribute__((always_inline)) {
+                        uint32_t at = slot0c;  // LDS address of the cell the pair's first survivor takes, wave-uniform
+#pragma unroll
+                        for (int w = 0; w < NRAW; ++w) {
+                            uint32_t c[6];
+                            uint64_t m[6];
+#pragma unroll
+                            for (int s = 0; s < 3; ++s) unpack_packed_pair(codes[w], s, c[2 * s], c[2 * s + 1]);
+#pragma unroll
+                            for (int k = 0; k < 6; ++k) m[k] = ballot64(keep(c[k]));
+#pragma unroll
+                            for (int s = 0; s < 3; ++s) {
+                                const uint64_t ma = m[2 * s], mb = m[2 * s + 1];
+                                const uint32_t ra = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(ma >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(ma), 0u));
+                                const uint32_t rank = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(mb >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(mb), ra));
+                                uint32_t a0 = at + rank * kNarrow;
+                                a0 = a0 < top ? a0 : top;
+                                const uint32_t a1 = a0 + (lane_of(ma) ? static_cast<uint32_t>(kNarrow) : 0u);
+                                put(lane_of(ma) ? a0 : cell, c[2 * s]);
+                                put(lane_of(mb) ? a1 : cell, c[2 * s + 1]);
+                                // at += 2 * (the pair's survivors): ONE scalar instruction, which the compiler does not form by itself
+                                asm("s_lshl1_add_u32 %0, %1, %0" : "+s"(at) : "s"(static_cast<uint32_t>(__popcll(ma) + __popcll(mb))) : "scc");
+                            }
+                        }
+                        next = slot0 + (at - slot0c);
+                    };
+                    if (full && project && !negated) {
+                        if (sides == rvn::kSidesLowerOnly) stage_words([&](uint32_t code) { return code >= TLO; });
+                        else if (sides == rvn::kSidesUpperOnly) stage_words([&](uint32_t code) { return code <= TSPAN; });
+                        else stage_words([&](uint32_t code) { return code - TLO <= TSPAN; });
+                    }
+                }
+                // The two arms every other pass over codes has.  `!kPack10` is a constant: without packed codes the conditions read
+                // `if (whole tile) ... else ...`, as before; with them the first arm is gone (the word forms above took the whole tiles) and
+                // the second runs for exactly the tiles they did not take.  Written this way, not as `if constexpr` around the arms with
+                // the second arm in a lambda for both: that form moved the register allocation of the 2- and 4-byte code kernels (14 of
+                // them compiled to other instructions), and they must stay the parent's.
+                if (!kPack10 && full && project && !negated) {
                     // ---- every tile but a launch's last: no test in the loop that comes out the same for every row of the tile ----
 #pragma unroll
                     for (int j = 0; j < R / 2; ++j) {
@@ -654,7 +731,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
                         put(lane_of(m0) ? a0 : cell, c0);
                         put(lane_of(m1) ? a1 : cell, c1);
                     }
-                } else {
+                } else if (!kPack10 || !(full && project && !negated)) {
                     // ---- the ragged last tile, a launch that projects nothing and the one term that kept its `negate` (the empty
                     //      set over 4-byte codes): the same with the tests and the flip in the loop ----
                     const uint64_t TNEG = negated ? ~0ull : 0;

@@ -3,6 +3,7 @@
 // functions the units call across each other are declared in launch.hpp (namespace rvl).
 #include "fused_rule.hpp"
 #include "launch.hpp"
+#include "narrow_sides.hpp"
 #include "narrow_term.hpp"
 #include "tile_addr.hpp"
 
@@ -494,6 +495,11 @@ static void size_staged(rv_ctx *ctx, LaunchChoice &c, const rvk::FusedEntry &e, 
     c.stages_plain = plain_stages(c.stages);
     c.lds = c.lds_plain = lds_for(c.stages_plain, c.cap);
     if (code_bytes && c.stage_row_bytes == 8) c.lds = lds_at(c.stages, c.cap, code_bytes);
+    // (a pass over packed codes: one spare 2-byte cell behind every slot's `cap`, rvk::kPackedSpareBytes, 16 bytes after rounding -- what
+    //  its whole-tile staging's one clamp per pair may write in a wave that outgrew its slot, fused_kernel.hpp.  `cap`, the plain twin's
+    //  slots and lds_plain stay)
+    if (packed && code_bytes && c.stage_row_bytes == 8)
+        c.lds = rvk::kLdsHeader + c.stages * e.waves * ((static_cast<size_t>(c.cap) * code_bytes + rvk::kPackedSpareBytes + 15) & ~size_t(15)) + static_cast<size_t>(e.waves) * rvk::kLdsDumpBytes;
 }
 
 // Survivors that come in RUNS (a table sorted or clustered on the predicate's column: ids, timestamps): a wave of the staged
@@ -690,7 +696,9 @@ static void launch_pass(rv_ctx *ctx, FusedLaunch &L, const LaunchChoice &c, int 
         // ((code - lo) as uint32 <= span) != negate, fused_kernel.hpp)
         p.in.terms[1].lit = static_cast<int64_t>(static_cast<uint64_t>(ct.lo) | (static_cast<uint64_t>(ct.span) << 32));
         p.in.terms[1].packed = ct.negate ? 1u : 0u;
-        p.in.terms[1].pad = 0;
+        // (a pass over packed codes: which ends of the interval a code 0 .. range can fall outside of, narrow_sides.hpp -- its whole tiles
+        //  run `code >= lo` or `code <= hi` alone for a one-sided interval.  In the same slot's `pad`: the block stays what it is)
+        p.in.terms[1].pad = (packed && interval) ? static_cast<uint32_t>(rvn::classify_sides(ct.lo, ct.span, c.narrow->range)) : 0u;
         L.plain = {c.staged->fn_plain, c.lds_plain, static_cast<int32_t>(c.stages_plain) - 1};
         ctx->narrow_passes += 1;
     }

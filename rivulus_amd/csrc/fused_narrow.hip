@@ -27,6 +27,10 @@ namespace rvk {
 // of slots: with two (what the plain form's LDS rule gives 3072-row wave ranges) the look-back is exposed, 15 280 cycles per tile and
 // 0.57 ms -- so its slots are sized as the plain form sizes two stages, and its plain re-run runs two-staged (fused_launch.hip,
 // size_staged).
+// Their whole tiles are staged a raw word (three pairs) at a time, by one of three forms chosen per tile from the class of the code
+// interval (narrow_sides.hpp: `code >= lo`, `code <= hi`, or subtract-and-compare), with one clamp per pair and a spare cell behind every
+// slot, and written out in whole 128-byte lines (fused_kernel.hpp, kPack10): 21 listed instructions per pair where the form above has 25,
+// 0.396 -> 0.369 ms for the headline kernel (profiles/narrow6_steps.txt).
 // The pass is bound by the vector instructions of its waves, not by HBM latency (tools/narrow_stamp.py, profiles/narrow2_stamps_*.txt:
 // a wave waits ~50 of 11 000-15 000 cycles per tile for its codes; evaluating them and waiting at the barrier for the other waves on the
 // SIMD to evaluate theirs is 80-87 %).  Tried on top of the above and taken out again: THREE sets of pairs per lane, the tile two
